@@ -306,6 +306,16 @@ def side_config(pkg, dev, name, curve, digits, log2n, depth, threads, steps, exp
     return out, expect == result
 
 
+def dump_outputs(d, result):
+    """what the caller of the timed path receives from its last step -- the affine result x || y, little-endian -- as exact
+    float64 arrays of 16-bit limbs, least significant first (16 per coordinate; 24 for BLS12-377 G1)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    half = len(result) // 2
+    for name, coord in (("result_x", result[:half]), ("result_y", result[half:])):
+        np.save(os.path.join(d, name + ".npy"), np.frombuffer(coord, dtype="<u2").astype(np.float64))
+
+
 def launch_ranks(n, cmd, timeout=None, env=None):
     """`python bench.py --gpus N` WITHOUT a launcher: starts N fresh child processes of `cmd` (one rank per GPU) with RANK /
     LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set -- plain subprocess.Popen from a process that has not imported
@@ -412,7 +422,10 @@ def main():
                          "resident inputs and says so: input_distribution_error); resident = every rank synthesises the full inputs on its GPU (untimed)")
     ap.add_argument("--no-pipeline", action="store_true", help="N=1: await every MSM before submitting the next (latency mode)")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--repeats", type=int, default=3, help="timed passes of --steps steps each; value = the median pass")
+    ap.add_argument("--repeats", type=int, default=1, help="timed passes of --steps steps each; value = the median pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the MSM result of the last timed step to DIR/result_x.npy and DIR/result_y.npy "
+                         "(float64, 16-bit limbs of the affine coordinate, least significant first: exact)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("TE_BENCH_FORCE_DIST") != "1":
@@ -665,9 +678,18 @@ def main():
             el = float(t.item())
         return el, res, 1
 
-    # The timed region runs args.repeats (3) times, each EXACTLY args.steps steps; `value` / `ms_per_step` are the MEDIAN pass
-    # (the driver's 20 steps are 20 ms of GPU time: one pass alone carries the box's clock wobble straight into `value`); all
-    # passes are in "passes_ms_per_step".
+    # one untimed pass of the timed form and length first: after the synchronous latency steps above the GPU needs some tens of
+    # milliseconds of steady work before its step time settles (a first pass of 20 steps ran 2-3 % slower than the next ones)
+    if pipelined and sharded:
+        sharded_pass(batch_inputs)
+    elif pipelined:
+        pipelined_pass(ctx, d_pts.data_ptr(), d_sc.data_ptr(), n, args.steps, depth)
+    else:
+        for _ in range(args.steps):
+            step()
+    # The timed region is then ONE pass of EXACTLY args.steps steps by default; with --repeats R it runs R such passes and `value` /
+    # `ms_per_step` are the MEDIAN pass (a short pass alone carries the box's clock wobble straight into `value`); all passes
+    # are in "passes_ms_per_step".
     passes = []
     for _ in range(max(1, args.repeats)):
         el, result, last = timed_pass()
@@ -675,6 +697,8 @@ def main():
     if pipelined and sharded:
         note_stage()                                   # events of the last launch sequence (`last` MSMs): a sample, not the mean
     elapsed = sorted(passes)[len(passes) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
     if pipelined and sharded and batch > 1 and len(base_copies) == 1:
         # the same again with a point buffer of its own per MSM of a batch (same bytes at distinct addresses): a shared
         # buffer is converted once per launch sequence, distinct ones once each -- both figures belong in the line
