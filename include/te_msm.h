@@ -35,6 +35,12 @@ typedef struct te_ctx te_ctx;
 #define TE_MSM_ESCALAR     (-3)   /* a scalar left a final carry: the reference's "final carry is 1"
                                      (submission/miscellaneous/utils.ts:80-83) */
 #define TE_MSM_ESTATE      (-4)   /* call order / capacity */
+#define TE_MSM_EPOINT      (-5)   /* an input point failed the check selected by option `check_points` */
+
+/* Why a point failed (option "bad_point_reason", te_msm_check_points*):  */
+#define TE_MSM_POINT_NONCANONICAL     1   /* a coordinate >= p (Twisted-Edwards) / q (BLS12-377) */
+#define TE_MSM_POINT_OFF_CURVE        2   /* the curve equation fails; BLS12-377: or the map to the twisted-Edwards form is undefined */
+#define TE_MSM_POINT_NOT_IN_SUBGROUP  3   /* on the curve, outside the subgroup of prime order */
 
 /* Groups (option "curve").  0: the Twisted-Edwards BLS12 curve of the competition (default; everything above).
  * 1: BLS12-377 G1, y^2 = x^3 + 1 over the 377-bit base field (README.md:57-73, BASELINE config 5): points are
@@ -157,6 +163,8 @@ int te_msm_ticket_device(te_ctx* ctx, uint64_t ticket, int* device_index, int* d
  *   released only when no ticket that uses it is in flight (TE_MSM_ESTATE).  The caller's point buffer is not retained.
  * te_msm_bind_points_device: the same from points already resident on a device of the context. */
 typedef struct te_bases te_bases;
+/* With option "check_points" != 0 the points are checked once, here, at the level in force now (TE_MSM_EPOINT: no handle, no
+ * set bound, "bases_bound" unchanged); MSMs over the set never check them again. */
 int te_msm_bind_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, te_bases** out);
 int te_msm_bind_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, te_bases** out);
 int te_msm_release_points(te_ctx* ctx, te_bases* bases);
@@ -176,6 +184,26 @@ int te_msm_run_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_scalar
  * PCIe (0.6 ms at n = 2^20) under the device work of the others (1.0 ms): the boundary stops being the link. */
 int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_le, uint64_t* ticket);
 int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_scalars_le, uint64_t* ticket);
+
+/* ---- input-point validation ------------------------------------------------------------------------------------------------
+ * The engine trusts its points unless asked: the wire format above says what a caller must pass, and a point that breaks it gives a
+ * wrong result, not an error.  Level 1, FORM: both coordinates canonical (below p / q), the curve equation holds
+ * (-x^2 + y^2 = 1 + d x^2 y^2, resp. y^2 = x^3 + 1), and for BLS12-377 the map to the engine's twisted-Edwards form is defined
+ * (y != 0 and s x + s + 1 != 0: the points of order 2 and 4).  Level 2, FORM + SUBGROUP: also [order] P = O -- the prime-order
+ * subgroup of the Twisted-Edwards curve (cofactor 4), resp. G1.  On BLS12-377 only level 2 makes the engine's addition law safe:
+ * it is complete on G1 alone.
+ * The BLS12-377 point at infinity as an INPUT (96 zero bytes) is rejected as off the curve (0 != 0^3 + 1): the engine's map sends
+ * (0, 0) to a record with Z = 0, which is not the neutral element, so it never stood for "nothing" in an MSM.
+ * COST: level 1 is a few field products per point -- cheap beside any MSM.  Level 2 is a double-and-add chain over the 251 / 253-bit
+ * order, about 3 000 field products per point: meant for te_msm_bind_points (once per point set) and the stand-alone check below;
+ * per-call use is allowed and costly (DESIGN.md section "Input-point validation" has the measured times).
+ *
+ * te_msm_check_points / _device: checks n points (host memory / memory of a device of the context) at `level` (1 or 2) and runs no
+ * MSM.  Returns 0 when every point passes (*first_bad = -1, *reason = 0), TE_MSM_EPOINT with *first_bad = the LOWEST failing index
+ * and *reason = TE_MSM_POINT_* otherwise.  The curve is option "curve".  Host memory is uploaded in pieces through a buffer of the
+ * first device; device memory is checked where it lies. */
+int te_msm_check_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason);
+int te_msm_check_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason);
 
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "window_bits"   c in [4,16]; 0 = choose from n (default)
@@ -252,6 +280,17 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
  *                   "fixed_base_fallbacks" (fixed-base MSMs answered by the ordinary windows after a row overflow),
  *                   "in_flight" (tickets not collected, all devices), "streams_final" (te_msm_workset_stream's handles will not change any
  *                   more), "device_bytes" (device memory held in work-set buffers, see te_msm_trim)
+ *   "check_points"  0 (default) = points are not checked (the launch sequence of every call is exactly the unchecked one);
+ *                   1 = form, 2 = form + subgroup (see "input-point validation" above), read when a call starts: te_msm_run, te_msm_run_device,
+ *                   te_msm_submit, te_msm_submit_async, te_msm_submit_device, te_msm_bind_points[_device].  The points are checked
+ *                   BEFORE the MSM is enqueued -- host buffers in pieces through a buffer of their own (one more pass over PCIe), device
+ *                   buffers where they lie (multi-device te_msm_run_device: on the device that holds them, before the scatter).  On a
+ *                   failure the call returns TE_MSM_EPOINT and leaves out_xy_le untouched; tickets: te_msm_submit* still hands out the
+ *                   ticket and ITS te_msm_collect returns TE_MSM_EPOINT (other tickets are not affected; te_msm_submit_async checks on
+ *                   its upload lane).  MSMs over a bound set are not checked again.  te_msm_partial_device[_batch] refuse to run with
+ *                   the option set (TE_MSM_EINVAL): use te_msm_check_points_device in front of them.  The context stays usable.
+ *   read-only:      "bad_point_index" (the lowest failing index -- into the caller's whole buffer -- of the last call that returned
+ *                   TE_MSM_EPOINT, -1 before any), "bad_point_reason" (its TE_MSM_POINT_* code, 0 before any)
  *   "prezero"       1 (default) = a work set's block of counters is cleared BEHIND an MSM's read-back, for its next MSM
  *                   (the next MSM starts with its first kernel instead of a fill); 0 = cleared in front of every MSM --
  *                   te_msm_debug_read of "bucket_count" / "num_segments" / "partials" needs 0 (it refuses otherwise)

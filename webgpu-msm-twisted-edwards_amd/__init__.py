@@ -31,5 +31,9 @@ from .binding import (  # noqa: F401
     CURVE_BLS12_377_G1,
     WORKSETS,
     MAX_BATCH,
+    EPOINT,
+    POINT_NONCANONICAL,
+    POINT_OFF_CURVE,
+    POINT_NOT_IN_SUBGROUP,
 )
 from .sharding import ShardedPipeline, compute_msm_sharded, distribute_inputs, exchange_partials, merge_partials, rows_of_batched_msm, window_shard_for_rank  # noqa: F401

@@ -17,12 +17,19 @@ PARTIAL_BYTES_BLS12_377 = 1120          # TE_MSM_PARTIAL_BYTES_BLS12_377
 CURVE_TE_BLS12, CURVE_BLS12_377_G1 = 0, 1        # option "curve" (TE_MSM_CURVE_*)
 WORKSETS = 8            # TE_MSM_WORKSETS: MSMs one context can have in flight
 MAX_BATCH = 8           # TE_MSM_MAX_BATCH: MSMs one te_msm_partial_device_batch call takes
+EPOINT = -5             # TE_MSM_EPOINT: an input point failed the check of option "check_points"
+# why a point failed (TE_MSM_POINT_*): MsmError.reason, the second item of MsmContext.check_points' answer
+POINT_NONCANONICAL, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = 1, 2, 3
 
 
 class MsmError(RuntimeError):
-    def __init__(self, code: int, msg: str):
+    """code: the TE_MSM_E* value.  index / reason: the lowest failing point and TE_MSM_POINT_* when code is EPOINT, else None."""
+
+    def __init__(self, code: int, msg: str, index: int | None = None, reason: int | None = None):
         super().__init__(f"te_msm error {code}: {msg}")
         self.code = code
+        self.index = index
+        self.reason = reason
 
 
 def library_path() -> str:
@@ -160,6 +167,10 @@ def _lib() -> ctypes.CDLL:
         L.te_msm_stage_ms.restype = ci
         L.te_msm_debug_read.argtypes = [vp, cp, vp, u64]
         L.te_msm_debug_read.restype = ctypes.c_int64
+        L.te_msm_check_points.argtypes = [vp, cp, u64, ci, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci)]
+        L.te_msm_check_points.restype = ci
+        L.te_msm_check_points_device.argtypes = [vp, vp, u64, ci, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci)]
+        L.te_msm_check_points_device.restype = ci
         _LIB = L
     return _LIB
 
@@ -196,8 +207,34 @@ class MsmContext:
 
     def _check(self, rc: int):
         if rc < 0:
-            raise MsmError(rc, self._L.te_msm_last_error(self._h).decode())
+            msg = self._L.te_msm_last_error(self._h).decode()
+            if rc == EPOINT:
+                raise MsmError(rc, msg, self.get_option("bad_point_index"), self.get_option("bad_point_reason"))
+            raise MsmError(rc, msg)
         return rc
+
+    # ---- input-point validation (include/te_msm.h: option "check_points" makes the calls below check; these run no MSM)
+    def _verdict(self, rc: int, bad, why):
+        if rc == EPOINT:
+            return bad.value, why.value
+        self._check(rc)
+        return None
+
+    def check_points(self, points: bytes, level: int = 1):
+        """te_msm_check_points: None when every point passes, else (lowest failing index, POINT_* reason).  level 1: canonical
+        and on the curve; 2: also in the prime-order subgroup (costly: meant for a point set that is used many times)."""
+        pb = self._sizes[0]
+        if len(points) % pb:
+            raise MsmError(-1, f"points must be {pb}*n bytes")
+        bad, why = ctypes.c_int64(), ctypes.c_int()
+        rc = self._L.te_msm_check_points(self._h, bytes(points), len(points) // pb, int(level), ctypes.byref(bad), ctypes.byref(why))
+        return self._verdict(rc, bad, why)
+
+    def check_points_device(self, d_points: int, n: int, level: int = 1):
+        """te_msm_check_points_device: the same for n points in the memory of a device of the context"""
+        bad, why = ctypes.c_int64(), ctypes.c_int()
+        rc = self._L.te_msm_check_points_device(self._h, d_points, n, int(level), ctypes.byref(bad), ctypes.byref(why))
+        return self._verdict(rc, bad, why)
 
     # ---- options
     def set_option(self, key: str, value: int):

@@ -31,6 +31,7 @@
 #include "host_tail.hpp"
 #include "synth.hpp"
 #include "kernels.hip.hpp"
+#include "check.hip.hpp"
 #include "probe.hip.hpp"
 #include "host_tail377.hpp"
 #include "host_sched.hpp"
@@ -132,6 +133,8 @@ struct workset_t {
   int slab = -1;                      // shared record slab the MSM in flight on this set uses (-1: its own d_recs, or a bound point set)
   const uint8_t* recs_last = nullptr; // where the records of the set's last MSM are (te_msm_debug_read "records"): d_recs or a shared slab
   te_bases* bound = nullptr;          // the bound point set the set's ticket in flight gathers from (te_msm_submit_scalars*): released only after the collect
+  // a ticket whose points failed the check (option "check_points"): nothing was enqueued for it, its te_msm_collect reports TE_MSM_EPOINT
+  int pt_rc = 0; int64_t pt_index = -1; int pt_reason = 0;
 };
 constexpr int TE_MAX_WINDOWS = 64;    // window_bits >= 4
 // words [Z_CLOCK, Z_ROWS): k_accumulate's profiling words, 4 x TE_CLK_SLOTS 64-bit values (first wave in / last wave out on the
@@ -168,6 +171,11 @@ struct gpu_t {
   // MSMs in flight instead of two at half speed
   std::unique_ptr<std::mutex> acc_mu{new std::mutex};
   hipEvent_t acc_ev[16] = {}; uint32_t acc_next = 0; hipEvent_t acc_prev = nullptr; hipStream_t acc_prev_stream = nullptr;
+  // input-point validation (option "check_points", te_msm_check_points*): a stream, a piece buffer for host points and the report word
+  // of its own, shared by every thread that checks on this device (upload lanes of asynchronous tickets included) under chk_mu
+  std::unique_ptr<std::mutex> chk_mu{new std::mutex};
+  hipStream_t chk_stream = nullptr; uint8_t* chk_pts = nullptr; size_t chk_cap = 0;
+  unsigned long long *chk_word = nullptr, *chk_host = nullptr;
   bool streams_exported = false;         // te_msm_workset_stream handed a handle out: te_msm_destroy parks the streams instead of destroying them
   bool streams_final = false;            // ... and the work sets' streams will not be re-dealt any more
 };
@@ -206,6 +214,8 @@ struct te_ctx {
   int opt_fold_pairs = 1;      // first fold level of small MSMs with two lanes per output (k_sum_groups<N, true>)
   int opt_packed = 1;          // level-1 sort entries as one 32-bit word where n <= 2^23 (make_plan)
   int opt_prezero = 1;         // clear a work set's zeroed block behind an MSM's read-back instead of in front of the next MSM's first kernel
+  int opt_check_points = 0;    // validate input points before an MSM / a bind: 0 off, 1 form, 2 form + subgroup (include/te_msm.h)
+  int64_t bad_point_index = -1; int bad_point_reason = 0;   // the last TE_MSM_EPOINT (get_option "bad_point_index" / "bad_point_reason")
   float stage_ms[ST_COUNT + 2] = {};
   bool have_stage_ms = false;
   int64_t stat_peer_copies = 0;  // hipMemcpyPeerAsync calls issued so far (multi-device contexts fed from device 0's memory; get_option "peer_copies")
@@ -1100,6 +1110,11 @@ void free_dev(gpu_t& d) {
   d.slabs.clear();
   for (hipEvent_t& e : d.acc_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   d.acc_prev = nullptr; d.acc_prev_stream = nullptr;
+  if (d.chk_stream) (void)hipStreamDestroy(d.chk_stream);
+  if (d.chk_pts) (void)hipFree(d.chk_pts);
+  if (d.chk_word) (void)hipFree(d.chk_word);
+  if (d.chk_host) (void)hipHostFree(d.chk_host);
+  d.chk_stream = nullptr; d.chk_pts = nullptr; d.chk_cap = 0; d.chk_word = d.chk_host = nullptr;
   for (workset_t& ws : d.ws) {
     free_workset_buffers(ws);
     if (ws.h_err) (void)hipHostFree(ws.h_err);
@@ -1783,6 +1798,74 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
   return 0;
 }
 
+// ---- input-point validation (option "check_points", te_msm_check_points*; kernels in check.hip.hpp) ----------------------------
+// Runs on device devs[di] in front of whatever the call does with the points, and waits for its verdict: a point that fails must
+// stop the call before an MSM result exists.  Device-resident points are checked where they lie (one launch per check); host points
+// cross PCIe in pieces of kCheckPiece through the device's own buffer -- the same bytes the MSM uploads again afterwards: checking is
+// opt-in and priced in the header.  The report word takes the lowest failing index of a launch (check_code); pieces run in order,
+// so the first piece that reports holds the lowest index of the whole buffer.
+constexpr uint64_t kCheckPiece = 1ull << 18;
+
+int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason) {
+  *bad = -1; *reason = 0;
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  std::lock_guard<std::mutex> lk(*d.chk_mu);
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
+  if (!d.chk_word) HIP_TRY(ctx, hipMalloc(&d.chk_word, sizeof(unsigned long long)));
+  if (!d.chk_host) HIP_TRY(ctx, hipHostMalloc(&d.chk_host, sizeof(unsigned long long), hipHostMallocDefault));
+  const size_t pb = sizes_of(curve).point_in;
+  const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
+  if (src_is_host && d.chk_cap < piece * pb) {
+    if (d.chk_pts) { HIP_TRY(ctx, hipFree(d.chk_pts)); d.chk_pts = nullptr; d.chk_cap = 0; }
+    HIP_TRY(ctx, hipMalloc(&d.chk_pts, piece * pb));
+    d.chk_cap = piece * pb;
+  }
+  hipStream_t st = d.chk_stream;
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint8_t* at = static_cast<const uint8_t*>(src) + off * pb;
+    if (src_is_host) { HIP_TRY(ctx, hipMemcpyAsync(d.chk_pts, at, (size_t)m * pb, hipMemcpyHostToDevice, st)); at = d.chk_pts; }
+    const uint4* p4 = reinterpret_cast<const uint4*>(at);
+    HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
+    const dim3 grid((m + 255u) / 256u), block(256);
+    if (curve == TE_MSM_CURVE_BLS12_377_G1) {
+      hipLaunchKernelGGL(te::k_check_form<1>, grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<1>, grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
+    } else {
+      hipLaunchKernelGGL(te::k_check_form<0>, grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<0>, grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(d.chk_host, d.chk_word, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (*d.chk_host) {
+      int64_t i = -1;
+      te::check_decode(*d.chk_host, m, &i, reason);
+      *bad = (int64_t)off + i;
+      return TE_MSM_EPOINT;
+    }
+  }
+  return 0;
+}
+// the verdict as the outcome of a call: the failure is remembered for get_option and described in the error text
+int note_bad_point(te_ctx* ctx, int64_t index, int reason) {
+  ctx->bad_point_index = index; ctx->bad_point_reason = reason;
+  char buf[256];
+  snprintf(buf, sizeof buf, "input point %lld failed the check of option \"check_points\": %s", (long long)index,
+           reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical coordinate" : reason == TE_MSM_POINT_OFF_CURVE ? "not on the curve (or map undefined)" : "not in the prime-order subgroup");
+  return set_err(ctx, TE_MSM_EPOINT, buf);
+}
+// option "check_points" in front of a call: 0 = go on, TE_MSM_EPOINT (noted) or a device error
+int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n) {
+  if (!ctx->opt_check_points) return 0;
+  int64_t bad = -1; int reason = 0;
+  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points, &bad, &reason);
+  if (rc == TE_MSM_EPOINT) return note_bad_point(ctx, bad, reason);
+  return rc;
+}
+
 int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, bool src_is_host, uint64_t n, uint8_t out[64]) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
@@ -1792,6 +1875,8 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
     return 0;
   }
   if (!src_points || !src_scalars) return set_err(ctx, TE_MSM_EINVAL, "null input buffer");
+  // (device-resident inputs live on the first device: a multi-device call checks them there, before the scatter)
+  if (int rc = check_call(ctx, 0, src_points, src_is_host, n)) return rc;
   const size_t nd = ctx->devs.size();
   // several devices: host buffers -> slices of the points, one upload thread per device; device-resident inputs -> window shards
   if (nd > 1) {
@@ -2009,6 +2094,11 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
   const int wi = take_free_workset(ctx, d, true);
   if (wi < 0) return wi;
   workset_t& ws = d.ws[wi];
+  if (ctx->opt_check_points) {                        // checked where the inputs lie; a failure is the ticket's outcome (te_msm_collect)
+    ws.pt_rc = check_points_on(ctx, (size_t)owner, d_points_xy_le, false, n, ctx->opt_curve, ctx->opt_check_points, &ws.pt_index, &ws.pt_reason);
+    if (ws.pt_rc == TE_MSM_EPOINT) { hand_out_ticket(ctx, di, ws, ticket); return 0; }
+    if (const int rc = ws.pt_rc) { ws.pt_rc = 0; return rc; }
+  }
   const bool stage = multi && (d.device != ctx->devs[(size_t)owner].device || ctx->opt_stage_device_inputs);
   const int src_dev = ctx->devs[(size_t)owner].device;
   if (stage) { const curve_sizes sz = sizes_of(ctx->opt_curve); ctx->stat_peer_copies += 2; ctx->stat_peer_bytes += (int64_t)(n * (sz.point_in + sz.scalar_in)); }
@@ -2106,7 +2196,13 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
   workset_t& ws = d.ws[wi];
   plan_t pf; make_plan(ctx, d, n, pf, 0, 1, 0, true);
   const int c = pf.c, K = host_pieces(ctx, n);
+  const int level = ctx->opt_check_points, curve = ctx->opt_curve;
   if (!async) {
+    if (level) {                                      // a failure is the ticket's outcome (te_msm_collect)
+      ws.pt_rc = check_points_on(ctx, (size_t)di, points_xy_le, true, n, curve, level, &ws.pt_index, &ws.pt_reason);
+      if (ws.pt_rc == TE_MSM_EPOINT) { hand_out_ticket(ctx, di, ws, ticket); return 0; }
+      if (const int rc = ws.pt_rc) { ws.pt_rc = 0; return rc; }
+    }
     if (int rc = enqueue_host_slice(ctx, d, ws, points_xy_le, scalars_le, n, c, K, true)) return rc;
     hand_out_ticket(ctx, di, ws, ticket);
     return 0;
@@ -2117,7 +2213,14 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
   ws.job_err.clear();
   workset_t* wsp = &ws; gpu_t* dp = &d;
   warm_upload_lanes(ctx);                            // (once per process and device: all of the context's devices together)
-  te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, points_xy_le, scalars_le, n, c, K]() -> int {
+  te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, points_xy_le, scalars_le, n, c, K, di, level, curve]() -> int {
+    if (level) {                                      // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
+      wsp->pt_rc = check_points_on(ctx, (size_t)di, points_xy_le, true, n, curve, level, &wsp->pt_index, &wsp->pt_reason);
+      if (const int prc = wsp->pt_rc) {
+        if (prc != TE_MSM_EPOINT) { std::lock_guard<std::mutex> lk(ctx->err_mu); wsp->job_err = ctx->err; }
+        return prc;
+      }
+    }
     const int rc = enqueue_host_slice(ctx, *dp, *wsp, points_xy_le, scalars_le, n, c, K, false);
     if (rc) { std::lock_guard<std::mutex> lk(ctx->err_mu); wsp->job_err = ctx->err; }
     return rc;
@@ -2171,7 +2274,19 @@ int te_msm_collect(te_ctx* ctx, uint64_t ticket, uint8_t out_xy_le[64]) {
   workset_t* wsp = workset_of_ticket(ctx, ticket, &dp);
   if (!wsp) return set_err(ctx, TE_MSM_ESTATE, kNoTicket);
   workset_t& ws = *wsp; gpu_t& d = *dp;
+  if (!ws.slot.job && ws.pt_rc == TE_MSM_EPOINT) {    // its points failed the check in te_msm_submit[_device]: nothing was enqueued
+    const int64_t bad = ws.pt_index; const int reason = ws.pt_reason;
+    ws.pt_rc = 0;
+    retire_ticket(ctx, d, ws);
+    return note_bad_point(ctx, bad, reason);
+  }
   if (const int jrc = await_job(ctx, d, ws)) {
+    if (jrc == TE_MSM_EPOINT) {                       // te_msm_submit_async: the lane's check failed, nothing was enqueued
+      const int64_t bad = ws.pt_index; const int reason = ws.pt_reason;
+      ws.pt_rc = 0;
+      retire_ticket(ctx, d, ws);
+      return note_bad_point(ctx, bad, reason);
+    }
     // the upload / enqueue failed on the device's host thread: the ticket is over, the set must not keep half an MSM
     (void)hipSetDevice(d.device);
     (void)hipStreamSynchronize(ws.stream); if (ws.copy_stream) (void)hipStreamSynchronize(ws.copy_stream);
@@ -2268,6 +2383,11 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
     const int owner = nd > 1 ? device_index_of_pointer(ctx, src) : 0;
     if (owner < 0) return set_err(ctx, TE_MSM_EINVAL, "te_msm_bind_points_device: the points must be resident on a device of the context");
     src_dev = ctx->devs[(size_t)owner].device;
+  }
+  if (n > 0) {                                        // option "check_points": once, here (MSMs over the set never check again)
+    size_t ci = 0;
+    if (!src_is_host) while (ctx->devs[ci].device != src_dev) ci++;
+    if (int rc = check_call(ctx, ci, src, src_is_host, n)) return rc;
   }
   te_bases* b = new te_bases();
   b->ctx = ctx; b->n = n; b->curve = ctx->opt_curve;
@@ -2603,6 +2723,7 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
   if (!strcmp(key, "profile")) { ctx->opt_profile = value < 0 ? 0 : (value > 2 ? 2 : (int)value); ctx->have_stage_ms = false; return 0; }
   if (!strcmp(key, "graph")) { ctx->opt_graph = value ? 1 : 0; return 0; }
   if (!strcmp(key, "prezero")) { ctx->opt_prezero = value ? 1 : 0; return 0; }
+  if (!strcmp(key, "check_points")) { if (value < 0 || value > 2) return set_err(ctx, TE_MSM_EINVAL, "check_points must be 0, 1 or 2"); ctx->opt_check_points = (int)value; return 0; }
   if (!strcmp(key, "fuse_prep")) { ctx->opt_fuse_prep = value ? 1 : 0; return 0; }
   if (!strcmp(key, "host_chunks")) { if (value < 0 || value > 64) return set_err(ctx, TE_MSM_EINVAL, "host_chunks out of range"); ctx->opt_host_chunks = (int)value; return 0; }
   if (!strcmp(key, "workset")) { if (value < 0 || value >= TE_MSM_WORKSETS) return set_err(ctx, TE_MSM_EINVAL, "workset out of range"); ctx->opt_workset = (int)value; return 0; }
@@ -2642,6 +2763,9 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "workset")) { *value = ctx->opt_workset; return 0; }
   if (!strcmp(key, "graph")) { *value = ctx->opt_graph; return 0; }
   if (!strcmp(key, "prezero")) { *value = ctx->opt_prezero; return 0; }
+  if (!strcmp(key, "check_points")) { *value = ctx->opt_check_points; return 0; }
+  if (!strcmp(key, "bad_point_index")) { *value = ctx->bad_point_index; return 0; }
+  if (!strcmp(key, "bad_point_reason")) { *value = ctx->bad_point_reason; return 0; }
   if (!strcmp(key, "fuse_prep")) { *value = ctx->opt_fuse_prep; return 0; }
   if (!strcmp(key, "host_chunks")) { *value = ctx->opt_host_chunks; return 0; }
   if (!strcmp(key, "host_shard_min")) { *value = ctx->opt_host_shard_min; return 0; }
@@ -2670,6 +2794,37 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   return set_err(ctx, TE_MSM_EINVAL, "unknown option");
 }
 
+namespace {
+int check_standalone(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, int level, int64_t* first_bad, int* reason) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  int64_t bad = -1; int why = 0;
+  if (first_bad) *first_bad = -1;
+  if (reason) *reason = 0;
+  if (level != 1 && level != 2) return set_err(ctx, TE_MSM_EINVAL, "te_msm_check_points: level must be 1 or 2");
+  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
+  if (n > 0 && !src) return set_err(ctx, TE_MSM_EINVAL, "null point buffer");
+  size_t di = 0;
+  if (!src_is_host && n > 0 && ctx->devs.size() > 1) {
+    const int owner = device_index_of_pointer(ctx, src);
+    if (owner < 0) return set_err(ctx, TE_MSM_EINVAL, "te_msm_check_points_device: the points must be resident on a device of the context");
+    di = (size_t)owner;
+  }
+  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why);
+  if (rc != TE_MSM_EPOINT) return rc;
+  if (first_bad) *first_bad = bad;
+  if (reason) *reason = why;
+  return note_bad_point(ctx, bad, why);
+}
+}  // namespace
+
+int te_msm_check_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason) {
+  return check_standalone(ctx, points_xy_le, true, n, level, first_bad, reason);
+}
+int te_msm_check_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason) {
+  return check_standalone(ctx, d_points_xy_le, false, n, level, first_bad, reason);
+}
+
 int te_msm_set_window_shard(te_ctx* ctx, int first, int step) {
   if (!ctx) return TE_MSM_EINVAL;
   if (ctx->devs.size() != 1) return set_err(ctx, TE_MSM_ESTATE, "window shards are set automatically for multi-device contexts");
@@ -2687,10 +2842,14 @@ int te_msm_plan(te_ctx* ctx, uint64_t n, int* window_bits, int* num_windows) {
   return 0;
 }
 
+static const char* const kPartialNoCheck =
+    "option \"check_points\" is not supported by the te_msm_partial_device building blocks (they report nothing per point): "
+    "check the points with te_msm_check_points_device, then set \"check_points\" to 0";
 int te_msm_partial_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_scalars_le, uint64_t n, void* d_partials, void* stream) {
   device_guard restore_callers_device;
   if (!ctx) return TE_MSM_EINVAL;
   if (ctx->devs.size() != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_partial_device needs a single-device context");
+  if (ctx->opt_check_points) return set_err(ctx, TE_MSM_EINVAL, kPartialNoCheck);
   if (!d_points_xy_le || !d_scalars_le || !d_partials || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
   gpu_t& d = ctx->devs[0];
   workset_t& ws = d.ws[ctx->opt_workset];
@@ -2705,6 +2864,7 @@ int te_msm_partial_device_batch(te_ctx* ctx, const void* const* d_points_xy_le, 
   device_guard restore_callers_device;
   if (!ctx) return TE_MSM_EINVAL;
   if (ctx->devs.size() != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_partial_device_batch needs a single-device context");
+  if (ctx->opt_check_points) return set_err(ctx, TE_MSM_EINVAL, kPartialNoCheck);
   if (!d_points_xy_le || !d_scalars_le || !d_partials || n == 0 || n >= (1ull << 31) || count < 1 || count > TE_MSM_MAX_BATCH)
     return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
   for (int m = 0; m < count; m++) if (!d_points_xy_le[m] || !d_scalars_le[m]) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");

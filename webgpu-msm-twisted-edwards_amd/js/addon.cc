@@ -22,6 +22,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -29,6 +30,8 @@
 #include "promise_protocol.hpp"
 
 namespace {
+
+std::atomic<int> g_check_points{0};    // setCheckPoints(level): option "check_points" of every context created from now on
 
 // the engine behind te_promise::protocol (js/promise_protocol.hpp holds the lock protocol itself)
 struct EngineApi {
@@ -45,7 +48,14 @@ struct EngineApi {
     if (ids.empty()) ids.push_back(0);
     return ids;
   }
-  static int init(const int* ids, int n, te_ctx** out) { return te_msm_init(ids, n, out); }
+  static int init(const int* ids, int n, te_ctx** out) {
+    const int rc = te_msm_init(ids, n, out);
+    if (rc == 0 && g_check_points.load()) {
+      const int orc = te_msm_set_option(*out, "check_points", g_check_points.load());
+      if (orc) { te_msm_destroy(*out); *out = nullptr; return orc; }
+    }
+    return rc;
+  }
   static void destroy(te_ctx* c) { te_msm_destroy(c); }
   static const char* last_error(te_ctx* c) { return te_msm_last_error(c); }
   static int run(te_ctx* c, const uint8_t* p, const uint8_t* s, uint64_t n, uint8_t* out) { return te_msm_run(c, p, s, n, out); }
@@ -182,6 +192,24 @@ napi_value SetBases(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+// setCheckPoints(level): opt-in validation of the input points (include/te_msm.h, option "check_points"): 0 = none (default),
+// 1 = canonical and on the curve, 2 = also in the prime-order subgroup (costly: about 3 000 field products per point).  A call whose
+// points fail rejects its promise with an Error that names the lowest failing index and the reason; setBases then throws for a bad
+// set.  Takes effect for the next call: the cached context is dropped once no promise is pending (like resetContext), so call it
+// before setBases.
+napi_value SetCheckPoints(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  int32_t level = -1;
+  if (argc < 1 || napi_get_value_int32(env, argv[0], &level) != napi_ok || level < 0 || level > 2) {
+    napi_throw_range_error(env, nullptr, "setCheckPoints(level: 0 | 1 | 2)");
+    return nullptr;
+  }
+  g_proto.reset();
+  g_check_points.store(level);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
 // getStats(): how the promises so far were mapped onto the engine -- tickets submitted from the JavaScript thread / from pool
 // threads, lone calls, jobs over bound bases, and the largest number of tickets seen in flight at a submit
 napi_value GetStats(napi_env env, napi_callback_info) {
@@ -204,7 +232,7 @@ napi_value GetDevices(napi_env env, napi_callback_info) {
 napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
-      {"setBases", SetBases}, {"getStats", GetStats}};
+      {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -53,5 +53,9 @@ const getDevices = () => native.getDevices();
 // point buffer to six calls per size (submission/miscellaneous/full_benchmarks.ts:63-68,100-105).  setBases(null) unbinds.
 const setBases = (bufferPoints) => native.setBases(bufferPoints === undefined ? null : bufferPoints);
 const getStats = () => native.getStats();
+// Opt-in as well: setCheckPoints(level) validates the input points of later calls (0 = none, default; 1 = canonical and on the
+// curve; 2 = also in the prime-order subgroup, costly -- best paired with setBases, which then checks the set once).  A call with
+// a bad point rejects with an Error naming the lowest failing index and the reason; setBases throws for a bad set.
+const setCheckPoints = (level) => native.setCheckPoints(level);
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints };

@@ -15,3 +15,6 @@ export declare const getDevices: () => number[];
 // one point buffer to six calls per size).  setBases(null) unbinds.
 export declare const setBases: (bufferPoints: Buffer | null) => void;
 export declare const getStats: () => { submittedInEnter: number; submittedInExecute: number; loneRuns: number; boundJobs: number; maxInFlight: number };
+// Not in the reference: opt-in validation of input points (0 none, 1 canonical + on the curve, 2 + prime-order subgroup); a bad
+// point rejects the call's promise (the message names the index and the reason), setBases throws for a bad set.
+export declare const setCheckPoints: (level: 0 | 1 | 2) => void;
