@@ -56,6 +56,8 @@ typedef struct te_ctx te_ctx;
 
 #define TE_MSM_POINT_BYTES   64
 #define TE_MSM_SCALAR_BYTES  32
+#define TE_MSM_X_BYTES              32   /* one x-only point (te_msm_points_from_x): x, little-endian */
+#define TE_MSM_X_BYTES_BLS12_377    48   /* the same for BLS12-377 G1: x with two flag bits in byte 47 */
 #define TE_MSM_WORKSETS      8    /* MSMs one context can have in flight (submit/collect, partial_device) */
 #define TE_MSM_PARTIAL_BYTES 720  /* per window: 5 extended points x 144 B (see te_msm_partial_device) */
 #define TE_MSM_PARTIAL_BYTES_BLS12_377 1120   /* the same row for BLS12-377 G1: 5 points x 224 B (14 limbs per coordinate) */
@@ -204,6 +206,39 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
  * first device; device memory is checked where it lies. */
 int te_msm_check_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason);
 int te_msm_check_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason);
+
+/* ---- x-only points -----------------------------------------------------------------------------------------------------------
+ * The reference passes its CPU MSM x-coordinates only (Address.msm takes "<x>group" strings): an Aleo group value IS its
+ * x-coordinate, and the point is the one with that x in the prime-order subgroup.  These entry points recover y on the device.
+ * Curve 0 (Twisted-Edwards BLS12): n x TE_MSM_X_BYTES little-endian x.  y^2 = (a x^2 - 1) / (d x^2 - 1), a = -1, d = 3021; of the two
+ *   roots the one whose point lies in the subgroup of order L (one [L] chain decides).  x = 0 gives (0, 1).
+ *   Reasons: x >= p TE_MSM_POINT_NONCANONICAL; no root TE_MSM_POINT_OFF_CURVE; neither root in the subgroup (x = +-sqrt(-1), and every
+ *   x of the order-4 cosets) TE_MSM_POINT_NOT_IN_SUBGROUP.  The reference's getPointFromX returns (x, -y) in that last case; Address.msm
+ *   cannot build such a group, and neither does the engine.
+ * Curve 1 (BLS12-377 G1): n x TE_MSM_X_BYTES_BLS12_377 little-endian x with flags in byte 47: bit 7 = y is the larger root
+ *   (y > q - y), bit 6 = the point at infinity (rejected, TE_MSM_POINT_OFF_CURVE, as in the uncompressed form); bits 377..381 must be 0
+ *   (else TE_MSM_POINT_NONCANONICAL, as x >= q).  y = sqrt(x^3 + 1); no root, y = 0, or s x + s + 1 = 0 (the engine's map to the
+ *   twisted-Edwards form undefined): TE_MSM_POINT_OFF_CURVE -- a recovered point always passes check_points level 1.  Recovery does not
+ *   decide membership in G1 (both roots share it): option "check_points" = 2 still applies.  The flag layout is meant to be the one
+ *   arkworks / snarkVM use for compressed short-Weierstrass points; that could not be verified against them -- pinned as written here.
+ * Output: canonical x || y, the wire format above (64 / 96 bytes per point), ready for every other entry point.
+ * All four: the curve is option "curve"; on a failure TE_MSM_EPOINT with the LOWEST failing index and its reason (*first_bad / *reason,
+ *   and the read-only options "bad_point_index" / "bad_point_reason"), outputs untouched, no MSM run, the context still usable.  Host
+ *   x-coordinates are uploaded in pieces through a buffer of the first device; the temporary device memory is freed before the call
+ *   returns.  The calling thread's current device is left as it was.
+ * te_msm_points_from_x / _device: n points into out (host memory / memory of the device that holds d_x_le: both buffers on one device
+ *   of the context, else TE_MSM_EINVAL).  Returns 0 (*first_bad = -1, *reason = 0) when every x has its point.
+ * te_msm_bind_points_x: recovers on the first device, then proceeds as te_msm_bind_points_device (conversion on every device, option
+ *   "check_points" applied as there).
+ * te_msm_run_x: Address.msm's counterpart: uploads x and the scalars to the first device, recovers there, then proceeds as
+ *   te_msm_run_device on the recovered points (window shards over several devices, "check_points", TE_MSM_ESCALAR, a 64 / 96-byte
+ *   result; its x half is Address.msm's output).
+ * COST: recovery is a square root (an exponentiation of ~1 600 field products) plus, for curve 0, the [L] chain of check_points level 2
+ *   (~3 000): correct per call, and slower than the MSM itself -- x-only input belongs at bind time. */
+int te_msm_points_from_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_points_xy_le, int64_t* first_bad, int* reason);
+int te_msm_points_from_x_device(te_ctx* ctx, const void* d_x_le, uint64_t n, void* d_out_points_xy_le, int64_t* first_bad, int* reason);
+int te_msm_bind_points_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, te_bases** out);
+int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, uint8_t* out_xy_le);
 
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "window_bits"   c in [4,16]; 0 = choose from n (default)

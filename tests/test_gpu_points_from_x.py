@@ -1,0 +1,240 @@
+"""x-only points on the GPU (te_msm_points_from_x[_device], te_msm_bind_points_x, te_msm_run_x; include/te_msm.h): recovery gives
+back the synthesized points byte for byte on both curves, run_x over the x-coordinates of every WASM golden equals the reference's
+own CPU MSM (Address.msm took x-coordinates only), bind_points_x + run_scalars equals run on x || y, and a buffer with bad x at
+several indices across the host pieces reports the lowest index and its reason through every entry point, outputs untouched."""
+import ctypes
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import model as m
+from oracle import model377 as b
+from oracle import oracle, oracle377
+from oracle.gen_golden import make_inputs
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PIECE = 1 << 18                      # host x-coordinates cross the link in pieces of 2^18 (te_msm.hip, kCheckPiece)
+
+
+def _dev(buf):
+    import torch
+    return torch.frombuffer(bytearray(buf), dtype=torch.uint8).cuda()
+
+
+def _sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+def xs_of(pts: bytes, curve: int) -> bytes:
+    """the x-only form of points x || y: TE the 32-byte x; BLS12-377 the 48-byte x with bit 7 of byte 47 set for the larger root"""
+    pb, xb = (96, 48) if curve == 1 else (64, 32)
+    a = np.frombuffer(pts, dtype=np.uint8).reshape(-1, pb)
+    xs = a[:, :xb].copy()
+    if curve == 1:
+        half = (b.Q - 1) // 2
+        ys = a[:, 48:].tobytes()
+        larger = np.fromiter((int.from_bytes(ys[48 * i:48 * i + 48], "little") > half for i in range(len(a))), dtype=bool, count=len(a))
+        xs[larger, 47] |= 0x80
+    return xs.tobytes()
+
+
+def _ctx(pkg, curve, level=0, ids=(0,)):
+    c = pkg.MsmContext(ids)
+    c.set_option("curve", curve)
+    c.set_option("check_points", level)
+    return c
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_points_from_x_gives_back_the_points(pkg, curve):
+    with _ctx(pkg, curve) as c:
+        for n in (1, 3, 300, PIECE + 1, 1 << 20):
+            pts, _ = pkg.synth_inputs(0xA11CE + n, n, scalars=False, curve=curve)
+            xs = xs_of(pts, curve)
+            assert c.points_from_x(xs) == pts, n
+            import torch
+            dx, dout = _dev(xs), torch.zeros(len(pts), dtype=torch.uint8, device="cuda")
+            _sync()
+            c.points_from_x_device(dx.data_ptr(), n, dout.data_ptr())
+            assert bytes(dout.cpu().numpy()) == pts, n
+        assert c.points_from_x(b"") == b""
+
+
+def test_run_x_equals_every_wasm_golden(pkg, wasm_golden, model):
+    """Address.msm got x-coordinates only (oracle/gen_golden.py): run_x on the same x-coordinates gives its (x, y), up to 2^20"""
+    seen = set()
+    with _ctx(pkg, 0) as c:
+        for g in wasm_golden:
+            pts, sc = make_inputs(g["seed"], g["n"], g["mode"])
+            got = c.run_x(xs_of(pts, 0), sc)
+            assert model.xy_from_bytes(got) == (int(g["x"]), int(g["y"])), g["name"]
+            seen.add(g["n"])
+    assert len(wasm_golden) == 24 and max(seen) == 1 << 20
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+@pytest.mark.parametrize("ids", [(0,), (0, 0, 0, 0)])
+@pytest.mark.parametrize("level", [0, 2])
+def test_bind_points_x_then_run_scalars_equals_run(pkg, curve, ids, level):
+    n = 5000
+    pts, sc = pkg.synth_inputs(0xB1D + curve, n, curve=curve)
+    with _ctx(pkg, curve, level, ids) as c:
+        want = c.run(pts, sc)
+        bs = c.bind_points_x(xs_of(pts, curve))
+        try:
+            assert bs.n == n
+            assert c.run_scalars(bs, sc) == want
+        finally:
+            c.release_points(bs)
+        assert c.run_x(xs_of(pts, curve), sc) == want
+    want_o = oracle377.msm(pts, sc, threads=8) if curve == 1 else oracle.msm(pts, sc, threads=8)
+    assert want == want_o
+
+
+def _bad_te():
+    P = m.xy_from_bytes(oracle.gen_points(21, 1))
+    i4 = m.sqrt_mod_p(m.P - 1)
+    PT4 = m.add(P, (i4, 0))
+    x2 = 5
+    while m.sqrt_mod_p((1 + x2 * x2) * pow(1 - m.D * x2 * x2, -1, m.P)) is not None:
+        x2 += 1
+    return {1: m.P.to_bytes(32, "little"), 2: x2.to_bytes(32, "little"), 3: PT4[0].to_bytes(32, "little")}
+
+
+def _bad_377():
+    x2 = 5
+    while pow(x2 ** 3 + 1, (b.Q - 1) // 2, b.Q) == 1:
+        x2 += 1
+    return {1: (b.GX | (1 << 379)).to_bytes(48, "little"), 2: (b.GX | (1 << 382)).to_bytes(48, "little"),
+            -2: x2.to_bytes(48, "little")}
+
+
+def _with_bad(xs, xb, placed):
+    a = bytearray(xs)
+    for at, x in placed:
+        a[xb * at:xb * at + xb] = x
+    return bytes(a)
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_bad_x_lowest_index_through_every_entry_point(pkg, curve):
+    import torch
+    n = PIECE + 3000
+    pb, xb, sb = (96, 48, 48) if curve == 1 else (64, 32, 32)
+    pts, sc = pkg.synth_inputs(0xBAD + curve, n, curve=curve)
+    xs = xs_of(pts, curve)
+    bad = _bad_377() if curve == 1 else _bad_te()
+    r1, r2 = bad[1], bad[2]
+    r3 = bad[-2] if curve == 1 else bad[3]
+    want3 = 2 if curve == 1 else 3
+    cases = [  # (placed bad x, lowest index, its reason)
+        ([(PIECE + 900, r1), (PIECE + 7, r3), (n - 1, r2)], PIECE + 7, want3),              # the second piece only
+        ([(PIECE + 2, r1), (PIECE - 1, r2), (17 + PIECE // 2, r3), (n - 5, r1)], 17 + PIECE // 2, want3),
+        ([(PIECE - 1, r2), (PIECE, r1), (n - 1, r3)], PIECE - 1, 2),                        # across the boundary
+    ]
+    L = pkg.binding._lib()
+    with _ctx(pkg, curve) as c:
+        want_run = c.run(pts, sc)
+        for placed, idx, reason in cases:
+            bx = _with_bad(xs, xb, placed)
+            # te_msm_points_from_x: the caller's buffer stays as it was
+            out = ctypes.create_string_buffer(b"\x5a" * (pb * n), pb * n)
+            fb, why = ctypes.c_int64(), ctypes.c_int()
+            assert L.te_msm_points_from_x(c._h, bx, n, out, ctypes.byref(fb), ctypes.byref(why)) == -5
+            assert (fb.value, why.value) == (idx, reason)
+            assert out.raw == b"\x5a" * (pb * n)
+            with pytest.raises(pkg.MsmError) as e:
+                c.points_from_x(bx)
+            assert (e.value.code, e.value.index, e.value.reason) == (-5, idx, reason)
+            # te_msm_points_from_x_device: the output buffer stays as it was
+            dx = _dev(bx)
+            dout = torch.full((pb * n,), 0x5a, dtype=torch.uint8, device="cuda")
+            _sync()
+            assert L.te_msm_points_from_x_device(c._h, dx.data_ptr(), n, dout.data_ptr(), ctypes.byref(fb), ctypes.byref(why)) == -5
+            assert (fb.value, why.value) == (idx, reason)
+            assert bool((dout == 0x5a).all())
+            # te_msm_run_x: the result buffer stays as it was, the options name the point
+            res = ctypes.create_string_buffer(b"\x5a" * 96, 96)
+            assert L.te_msm_run_x(c._h, bx, sc, n, res) == -5
+            assert res.raw == b"\x5a" * 96
+            assert (c.get_option("bad_point_index"), c.get_option("bad_point_reason")) == (idx, reason)
+            # te_msm_bind_points_x: no handle
+            h = ctypes.c_void_p(1234)
+            assert L.te_msm_bind_points_x(c._h, bx, n, ctypes.byref(h)) == -5
+            assert not h.value
+            with pytest.raises(pkg.MsmError) as e:
+                c.bind_points_x(bx)
+            assert (e.value.index, e.value.reason) == (idx, reason)
+            # the same context then runs good calls correctly
+            assert c.run_x(xs, sc) == want_run
+        assert c.points_from_x(xs) == pts
+        bs = c.bind_points_x(xs)
+        assert c.run_scalars(bs, sc) == want_run
+        c.release_points(bs)
+        assert c.get_option("bases_bound") == 0
+
+
+def test_device_form_needs_both_buffers_on_a_device_of_the_context(pkg):
+    import torch
+    pts, _ = pkg.synth_inputs(3, 64, scalars=False)
+    xs = xs_of(pts, 0)
+    with _ctx(pkg, 0) as c:
+        dx = _dev(xs)
+        _sync()
+        host_out = ctypes.create_string_buffer(64 * 64)
+        fb, why = ctypes.c_int64(), ctypes.c_int()
+        L = pkg.binding._lib()
+        assert L.te_msm_points_from_x_device(c._h, dx.data_ptr(), 64, host_out, ctypes.byref(fb), ctypes.byref(why)) == -1
+        dout = torch.zeros(64 * 64, dtype=torch.uint8, device="cuda")
+        c.points_from_x_device(dx.data_ptr(), 64, dout.data_ptr())
+        assert bytes(dout.cpu().numpy()) == pts
+
+
+def test_node_points_from_x_round_trip(pkg, tmp_path):
+    node = shutil.which("node")
+    if not node:
+        pytest.skip("node is not installed on this box")
+    js = os.path.join(ROOT, "webgpu-msm-twisted-edwards_amd", "js")
+    if not os.path.exists("/usr/include/node/node_api.h") and not os.path.exists(os.path.join(js, "te_msm_napi.node")):
+        pytest.skip("no N-API addon and no node headers to build it")
+    if not os.path.exists(os.path.join(js, "te_msm_napi.node")):
+        subprocess.check_call(["make", "-C", js, "-s"])
+    n = 3000
+    pts, sc = oracle.gen_points(14, n), oracle.gen_scalars(14, n)
+    xs = xs_of(pts, 0)
+    bad = _with_bad(xs, 32, [(2999, _bad_te()[2]), (1234, _bad_te()[3])])
+    for name, data in (("x.bin", xs), ("bad.bin", bad), ("s.bin", sc), ("p.bin", pts)):
+        (tmp_path / name).write_bytes(data)
+    script = r"""
+const fs = require('fs');
+const m = require(process.argv[1] + '/compute_msm.js');
+const [xs, bad, sc, pts] = process.argv.slice(2).map((f) => fs.readFileSync(f));
+(async () => {
+  const out = {};
+  const p = m.pointsFromX(xs);
+  out.same = Buffer.compare(p, pts) === 0;
+  const r = await m.compute_msm(p, sc, false);
+  out.x = r.x.toString(); out.y = r.y.toString();
+  m.setBases(p);
+  const r2 = await m.compute_msm(p, sc, false);
+  out.bx = r2.x.toString();
+  m.setBases(null);
+  try { m.pointsFromX(bad); out.bad = 'returned'; } catch (e) { out.bad = String(e.message); out.index = e.index; out.reason = e.reason; }
+  console.log(JSON.stringify(out));
+})().catch((e) => { console.log(JSON.stringify({ fatal: String(e) })); });
+"""
+    r = subprocess.run([node, "-e", script, js] + [str(tmp_path / f) for f in ("x.bin", "bad.bin", "s.bin", "p.bin")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    out = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    want = m.xy_from_bytes(oracle.msm(pts, sc, threads=8))
+    assert out.get("same") is True, out
+    assert (int(out["x"]), int(out["y"])) == want and int(out["bx"]) == want[0], out
+    assert "te_msm error -5" in out["bad"] and "x-coordinate 1234" in out["bad"] and "reason 3" in out["bad"], out
+    assert (out["index"], out["reason"]) == (1234, 3), out

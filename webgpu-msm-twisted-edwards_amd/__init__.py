@@ -35,5 +35,7 @@ from .binding import (  # noqa: F401
     POINT_NONCANONICAL,
     POINT_OFF_CURVE,
     POINT_NOT_IN_SUBGROUP,
+    X_BYTES,
+    X_BYTES_BLS12_377,
 )
 from .sharding import ShardedPipeline, compute_msm_sharded, distribute_inputs, exchange_partials, merge_partials, rows_of_batched_msm, window_shard_for_rank  # noqa: F401

@@ -20,6 +20,7 @@ MAX_BATCH = 8           # TE_MSM_MAX_BATCH: MSMs one te_msm_partial_device_batch
 EPOINT = -5             # TE_MSM_EPOINT: an input point failed the check of option "check_points"
 # why a point failed (TE_MSM_POINT_*): MsmError.reason, the second item of MsmContext.check_points' answer
 POINT_NONCANONICAL, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = 1, 2, 3
+X_BYTES, X_BYTES_BLS12_377 = 32, 48      # TE_MSM_X_BYTES*: one x-only point (points_from_x, bind_points_x, run_x)
 
 
 class MsmError(RuntimeError):
@@ -171,6 +172,14 @@ def _lib() -> ctypes.CDLL:
         L.te_msm_check_points.restype = ci
         L.te_msm_check_points_device.argtypes = [vp, vp, u64, ci, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci)]
         L.te_msm_check_points_device.restype = ci
+        L.te_msm_points_from_x.argtypes = [vp, cp, u64, cp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci)]
+        L.te_msm_points_from_x.restype = ci
+        L.te_msm_points_from_x_device.argtypes = [vp, vp, u64, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci)]
+        L.te_msm_points_from_x_device.restype = ci
+        L.te_msm_bind_points_x.argtypes = [vp, cp, u64, ctypes.POINTER(vp)]
+        L.te_msm_bind_points_x.restype = ci
+        L.te_msm_run_x.argtypes = [vp, cp, cp, u64, cp]
+        L.te_msm_run_x.restype = ci
         _LIB = L
     return _LIB
 
@@ -337,6 +346,45 @@ class MsmContext:
         h = ctypes.c_void_p()
         self._check(self._L.te_msm_bind_points_device(self._h, d_points, n, ctypes.byref(h)))
         return Bases(self, h, n, self.curve)
+
+    # ---- x-only points (include/te_msm.h "x-only points"): y recovered on the device; a bad x raises MsmError(EPOINT) with .index / .reason
+    def _x_count(self, xs) -> int:
+        xb = X_BYTES_BLS12_377 if self.curve == CURVE_BLS12_377_G1 else X_BYTES
+        n = len(xs) // xb
+        if len(xs) != xb * n:
+            raise MsmError(-1, f"x-coordinates must be {xb}*n bytes")
+        return n
+
+    def points_from_x(self, xs: bytes) -> bytes:
+        """te_msm_points_from_x: n x-coordinates (32 bytes; BLS12-377: 48 with the flag bits) -> n points x || y (64 / 96 bytes)"""
+        n = self._x_count(xs)
+        out = ctypes.create_string_buffer(max(1, self._sizes[0] * n))
+        bad, why = ctypes.c_int64(), ctypes.c_int()
+        self._check(self._L.te_msm_points_from_x(self._h, bytes(xs), n, out, ctypes.byref(bad), ctypes.byref(why)))
+        return out.raw[:self._sizes[0] * n]
+
+    def points_from_x_device(self, d_x: int, n: int, d_out: int):
+        """te_msm_points_from_x_device: the same between two buffers on one device of the context"""
+        bad, why = ctypes.c_int64(), ctypes.c_int()
+        self._check(self._L.te_msm_points_from_x_device(self._h, d_x, n, d_out, ctypes.byref(bad), ctypes.byref(why)))
+
+    def bind_points_x(self, xs: bytes) -> "Bases":
+        """te_msm_bind_points_x: recovers the points on the first device and binds them (as bind_points_device)"""
+        n = self._x_count(xs)
+        h = ctypes.c_void_p()
+        self._check(self._L.te_msm_bind_points_x(self._h, bytes(xs), n, ctypes.byref(h)))
+        return Bases(self, h, n, self.curve)
+
+    def run_x(self, xs: bytes, scalars: bytes) -> bytes:
+        """te_msm_run_x, Address.msm's counterpart: x-only points and scalars -> the affine result x || y (64 / 96 bytes).
+        Correct per call, and slower than the MSM itself: bind_points_x is where x-only input belongs."""
+        n = self._x_count(xs)
+        sb = self._sizes[1]
+        if len(scalars) != sb * n:
+            raise MsmError(-1, f"scalars must be {sb}*n bytes")
+        out = ctypes.create_string_buffer(96)
+        self._check(self._L.te_msm_run_x(self._h, bytes(xs), bytes(scalars), n, out))
+        return out.raw[:self._sizes[2]]
 
     def bases_read(self, bases: "Bases", first: int, count: int, device_index: int = 0):
         """(record bytes, raw records [first, first + count) of the bound set on one device) -- te_msm_bases_read"""

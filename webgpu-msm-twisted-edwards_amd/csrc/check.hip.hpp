@@ -100,10 +100,8 @@ TE_HD int check_form_te(const uint32_t (&w)[16]) {
   const bool on = fe_is_zero(fp_sub<4>(lhs, rhs));
   return !canon ? 1 : (!on ? 2 : 0);
 }
-// [L] P = O on the whole curve (ete_add is complete there: a square, d not)
-TE_HD bool in_subgroup_te(const uint32_t (&w)[16], const naf_t& k) {
-  fp X, Y;
-  te_coords(w, X, Y);
+// [k] (X, Y) in extended coordinates, X and Y in Montgomery form (product outputs); also the root choice of from_x.hip.hpp
+TE_HD ete mul_order_te(const fp& X, const fp& Y, const naf_t& k) {
   ete P;
   P.x = X; P.y = Y; P.z = fp_R1(); P.t = mont_mul(X, Y);
   ete N = P;                                                       // -P = (-x, y, 1, -t), reduced to class N below 1.1 p
@@ -120,6 +118,13 @@ TE_HD bool in_subgroup_te(const uint32_t (&w)[16], const naf_t& k) {
     const int dg = naf_digit(k, i);
     if (dg) acc = ete_add<9>(acc, dg > 0 ? P : N);
   }
+  return acc;
+}
+// [L] P = O on the whole curve (ete_add is complete there: a square, d not)
+TE_HD bool in_subgroup_te(const uint32_t (&w)[16], const naf_t& k) {
+  fp X, Y;
+  te_coords(w, X, Y);
+  const ete acc = mul_order_te(X, Y, k);
   // the neutral element (0 : Z : Z : 0), Z != 0
   return fe_is_zero(acc.x) && fe_is_zero(fp_sub<2>(acc.y, acc.z)) && !fe_is_zero(acc.z);
 }

@@ -32,6 +32,7 @@
 #include "synth.hpp"
 #include "kernels.hip.hpp"
 #include "check.hip.hpp"
+#include "from_x.hip.hpp"
 #include "probe.hip.hpp"
 #include "host_tail377.hpp"
 #include "host_sched.hpp"
@@ -2823,6 +2824,161 @@ int te_msm_check_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, in
 }
 int te_msm_check_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason) {
   return check_standalone(ctx, d_points_xy_le, false, n, level, first_bad, reason);
+}
+
+// ---- x-only points (te_msm_points_from_x[_device], te_msm_bind_points_x, te_msm_run_x; kernels in from_x.hip.hpp) ----------------
+// Recovery runs on device devs[di] into a buffer of the call's own, and the call waits for the verdict: on a failure nothing reaches
+// the caller's output and no MSM runs.  Host x-coordinates cross PCIe in pieces of kCheckPiece through a staging buffer, on the
+// check stream of the device (one stream: a piece's copy waits for the previous piece's kernel); every piece reports into one word
+// over the whole buffer, so the lowest failing index wins without a wait per piece.  The temporary buffers are freed before the call
+// returns (dev_tmp): nothing is cached, nothing counts in "device_bytes".
+namespace {
+struct dev_tmp {
+  int dev = -1; void* p = nullptr;
+  dev_tmp() = default;
+  dev_tmp(const dev_tmp&) = delete;
+  dev_tmp& operator=(const dev_tmp&) = delete;
+  ~dev_tmp() { if (p) { (void)hipSetDevice(dev); (void)hipFree(p); } }
+};
+int tmp_alloc(te_ctx* ctx, gpu_t& d, dev_tmp& t, size_t bytes) {
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  HIP_TRY(ctx, hipMalloc(&t.p, bytes ? bytes : 16));
+  t.dev = d.device;
+  return 0;
+}
+inline size_t x_bytes_of(int curve) { return curve == TE_MSM_CURVE_BLS12_377_G1 ? TE_MSM_X_BYTES_BLS12_377 : TE_MSM_X_BYTES; }
+
+// n x-coordinates at src (host, or memory of devs[di]) -> n points in d_pts (memory of devs[di]); then, when dst is given and every x
+// passed, the points are copied to dst (host or device memory) before the lock is released
+int recover_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, void* d_pts, void* dst, bool dst_is_host,
+               int64_t* bad, int* reason) {
+  *bad = -1; *reason = 0;
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const int curve = ctx->opt_curve;
+  const size_t xb = x_bytes_of(curve), pb = sizes_of(curve).point_in;
+  std::lock_guard<std::mutex> lk(*d.chk_mu);
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
+  if (!d.chk_word) HIP_TRY(ctx, hipMalloc(&d.chk_word, sizeof(unsigned long long)));
+  if (!d.chk_host) HIP_TRY(ctx, hipHostMalloc(&d.chk_host, sizeof(unsigned long long), hipHostMallocDefault));
+  const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
+  dev_tmp stage;
+  if (src_is_host) { if (int rc = tmp_alloc(ctx, d, stage, piece * xb)) return rc; }
+  hipStream_t st = d.chk_stream;
+  HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint8_t* at = static_cast<const uint8_t*>(src) + off * xb;
+    if (src_is_host) { HIP_TRY(ctx, hipMemcpyAsync(stage.p, at, (size_t)m * xb, hipMemcpyHostToDevice, st)); at = static_cast<const uint8_t*>(stage.p); }
+    const uint4* x4 = reinterpret_cast<const uint4*>(at);
+    uint4* o4 = reinterpret_cast<uint4*>(static_cast<uint8_t*>(d_pts) + off * pb);
+    const dim3 grid((m + 255u) / 256u), block(256);
+    if (curve == TE_MSM_CURVE_BLS12_377_G1) hipLaunchKernelGGL(te::k_points_from_x<1>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::kRootExp377, te::kNaf377Order);
+    else hipLaunchKernelGGL(te::k_points_from_x<0>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::kRootExpTe, te::kNafTeOrder);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(d.chk_host, d.chk_word, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (*d.chk_host) {
+    te::check_decode(*d.chk_host, n, bad, reason);
+    return TE_MSM_EPOINT;
+  }
+  if (dst) {
+    HIP_TRY(ctx, hipMemcpyAsync(dst, d_pts, n * pb, dst_is_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+  }
+  return 0;
+}
+// a failed recovery as the outcome of a call: "bad_point_index" / "bad_point_reason" and the error text
+int note_bad_x(te_ctx* ctx, int64_t index, int reason) {
+  ctx->bad_point_index = index; ctx->bad_point_reason = reason;
+  char buf[256];
+  snprintf(buf, sizeof buf, "x-coordinate %lld has no point (reason %d): %s", (long long)index, reason,
+           reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical (x >= modulus, or reserved flag bits set)"
+           : reason == TE_MSM_POINT_OFF_CURVE ? "no point on the curve has this x (or the point at infinity / map undefined)"
+                                              : "no point of the prime-order subgroup has this x");
+  return set_err(ctx, TE_MSM_EPOINT, buf);
+}
+// host x -> points of the first device in t (allocated here): 0, TE_MSM_EPOINT (noted) or a device error
+int recover_host_to_first(te_ctx* ctx, const uint8_t* x_le, uint64_t n, dev_tmp& t) {
+  if (int rc = tmp_alloc(ctx, ctx->devs[0], t, n * sizes_of(ctx->opt_curve).point_in)) return rc;
+  int64_t bad = -1; int why = 0;
+  const int rc = recover_on(ctx, 0, x_le, true, n, t.p, nullptr, false, &bad, &why);
+  if (rc == TE_MSM_EPOINT) return note_bad_x(ctx, bad, why);
+  return rc;
+}
+int from_x_args(te_ctx* ctx, const void* x, uint64_t n, const void* out) {
+  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
+  if (n > 0 && (!x || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  return 0;
+}
+}  // namespace
+
+int te_msm_points_from_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_points_xy_le, int64_t* first_bad, int* reason) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (first_bad) *first_bad = -1;
+  if (reason) *reason = 0;
+  if (int rc = from_x_args(ctx, x_le, n, out_points_xy_le)) return rc;
+  if (n == 0) return 0;
+  dev_tmp pts;
+  if (int rc = tmp_alloc(ctx, ctx->devs[0], pts, n * sizes_of(ctx->opt_curve).point_in)) return rc;
+  int64_t bad = -1; int why = 0;
+  const int rc = recover_on(ctx, 0, x_le, true, n, pts.p, out_points_xy_le, true, &bad, &why);
+  if (rc != TE_MSM_EPOINT) return rc;
+  if (first_bad) *first_bad = bad;
+  if (reason) *reason = why;
+  return note_bad_x(ctx, bad, why);
+}
+
+int te_msm_points_from_x_device(te_ctx* ctx, const void* d_x_le, uint64_t n, void* d_out_points_xy_le, int64_t* first_bad, int* reason) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (first_bad) *first_bad = -1;
+  if (reason) *reason = 0;
+  if (int rc = from_x_args(ctx, d_x_le, n, d_out_points_xy_le)) return rc;
+  if (n == 0) return 0;
+  const int owner = device_index_of_pointer(ctx, d_x_le);
+  if (owner < 0 || device_index_of_pointer(ctx, d_out_points_xy_le) != owner)
+    return set_err(ctx, TE_MSM_EINVAL, "te_msm_points_from_x_device: x and the output must be resident on one device of the context");
+  dev_tmp pts;
+  if (int rc = tmp_alloc(ctx, ctx->devs[(size_t)owner], pts, n * sizes_of(ctx->opt_curve).point_in)) return rc;
+  int64_t bad = -1; int why = 0;
+  const int rc = recover_on(ctx, (size_t)owner, d_x_le, false, n, pts.p, d_out_points_xy_le, false, &bad, &why);
+  if (rc != TE_MSM_EPOINT) return rc;
+  if (first_bad) *first_bad = bad;
+  if (reason) *reason = why;
+  return note_bad_x(ctx, bad, why);
+}
+
+int te_msm_bind_points_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, te_bases** out) {
+  device_guard restore_callers_device;
+  if (!ctx || !out) return TE_MSM_EINVAL;
+  *out = nullptr;
+  if (int rc = from_x_args(ctx, x_le, n, out)) return rc;
+  if (n == 0) return bind_common(ctx, x_le, true, 0, out);
+  dev_tmp pts;
+  if (int rc = recover_host_to_first(ctx, x_le, n, pts)) return rc;
+  return bind_common(ctx, pts.p, false, n, out);                 // as te_msm_bind_points_device (conversion on every device, check_points)
+}
+
+int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx || !out_xy_le) return TE_MSM_EINVAL;
+  if (int rc = from_x_args(ctx, x_le, n, scalars_le)) return rc;
+  if (n == 0) return run_common(ctx, x_le, scalars_le, true, 0, out_xy_le);
+  dev_tmp pts, sc;
+  if (int rc = recover_host_to_first(ctx, x_le, n, pts)) return rc;
+  gpu_t& d = ctx->devs[0];
+  const size_t sbytes = n * sizes_of(ctx->opt_curve).scalar_in;
+  if (int rc = tmp_alloc(ctx, d, sc, sbytes)) return rc;
+  {
+    std::lock_guard<std::mutex> lk(*d.chk_mu);                  // (recover_on made the stream)
+    HIP_TRY(ctx, hipMemcpyAsync(sc.p, scalars_le, sbytes, hipMemcpyHostToDevice, d.chk_stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d.chk_stream));
+  }
+  return run_common(ctx, pts.p, sc.p, false, n, out_xy_le);      // as te_msm_run_device (window shards, check_points, TE_MSM_ESCALAR)
 }
 
 int te_msm_set_window_shard(te_ctx* ctx, int first, int step) {

@@ -192,6 +192,45 @@ napi_value SetBases(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+// pointsFromX(xs: Buffer): Buffer -- x-only points (include/te_msm.h, te_msm_points_from_x): n x 32-byte little-endian x-coordinates
+// (Aleo group values, the form Address.msm takes) -> n x 64-byte x || y with y recovered on the device, ready for compute_msm or
+// setBases.  Twisted-Edwards curve only, like the rest of the addon.  Runs on the addon's context under its lock once no promise is
+// pending (like setBases).  A bad x throws an Error that names the lowest failing index and the reason (TE_MSM_POINT_*); the Error
+// also carries them as .index / .reason.
+napi_value PointsFromX(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool is_buf = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &is_buf);
+  if (!is_buf) { napi_throw_type_error(env, nullptr, "pointsFromX(xs: Buffer)"); return nullptr; }
+  void* p = nullptr; size_t pl = 0;
+  napi_get_buffer_info(env, argv[0], &p, &pl);
+  if (pl % TE_MSM_X_BYTES != 0) { napi_throw_range_error(env, nullptr, "pointsFromX: x-coordinates must be 32*n bytes"); return nullptr; }
+  const uint64_t n = pl / TE_MSM_X_BYTES;
+  std::vector<uint8_t> out((size_t)n * TE_MSM_POINT_BYTES);
+  int64_t bad = -1; int reason = 0;
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    return te_msm_points_from_x(c, static_cast<const uint8_t*>(p), n, out.data(), &bad, &reason);
+  }, err);
+  if (rc) {
+    const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_value msg, errv;
+    napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+    napi_create_error(env, nullptr, msg, &errv);
+    if (rc == TE_MSM_EPOINT) {
+      napi_value iv, rv;
+      napi_create_int64(env, bad, &iv); napi_create_int32(env, reason, &rv);
+      napi_set_named_property(env, errv, "index", iv); napi_set_named_property(env, errv, "reason", rv);
+    }
+    napi_throw(env, errv);
+    return nullptr;
+  }
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
+  return buf;
+}
+
 // setCheckPoints(level): opt-in validation of the input points (include/te_msm.h, option "check_points"): 0 = none (default),
 // 1 = canonical and on the curve, 2 = also in the prime-order subgroup (costly: about 3 000 field products per point).  A call whose
 // points fail rejects its promise with an Error that names the lowest failing index and the reason; setBases then throws for a bad
@@ -232,7 +271,8 @@ napi_value GetDevices(napi_env env, napi_callback_info) {
 napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
-      {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints}};
+      {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints},
+      {"pointsFromX", PointsFromX}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -57,5 +57,9 @@ const getStats = () => native.getStats();
 // curve; 2 = also in the prime-order subgroup, costly -- best paired with setBases, which then checks the set once).  A call with
 // a bad point rejects with an Error naming the lowest failing index and the reason; setBases throws for a bad set.
 const setCheckPoints = (level) => native.setCheckPoints(level);
+// Outside the reference's interface: pointsFromX(xs) turns n x 32-byte little-endian x-coordinates (Aleo group values, what
+// Address.msm takes) into the 64n-byte points buffer of compute_msm / setBases, y recovered on the GPU.  A bad x throws an Error
+// naming the lowest failing index and the reason (also as .index / .reason).
+const pointsFromX = (xs) => native.pointsFromX(xs);
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX };

@@ -146,6 +146,17 @@ template <class Api> class protocol {
     return rc;
   }
   bool has_bases() { std::lock_guard<std::mutex> lk(mu_); return bases_points_ != nullptr; }
+  // Runs f(ctx) on the context (created if need be) once no promise is pending, under the context's lock, like set_bases.  Returns
+  // f's engine code; err receives its text.
+  template <class F> int with_context(F&& f, std::string& err) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [this] { return pending() == 0; });
+    int rc = ensure_context(err);
+    if (rc) return rc;
+    rc = f(ctx_);
+    if (rc) err = Api::last_error(ctx_);
+    return rc;
+  }
 
  private:
   static bool lone_in_enter() { static const bool on = [] { const char* e = getenv("TE_MSM_LONE_IN_ENTER"); return !(e && e[0] == '0'); }(); return on; }

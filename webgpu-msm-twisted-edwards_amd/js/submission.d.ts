@@ -18,3 +18,6 @@ export declare const getStats: () => { submittedInEnter: number; submittedInExec
 // Not in the reference: opt-in validation of input points (0 none, 1 canonical + on the curve, 2 + prime-order subgroup); a bad
 // point rejects the call's promise (the message names the index and the reason), setBases throws for a bad set.
 export declare const setCheckPoints: (level: 0 | 1 | 2) => void;
+// Not in the reference: x-only points (Aleo group values, Address.msm's input) -> the 64n-byte points buffer of compute_msm /
+// setBases, y recovered on the GPU; a bad x throws (the message names the index and the reason; also error.index / error.reason).
+export declare const pointsFromX: (xs: Buffer) => Buffer;
