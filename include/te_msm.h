@@ -240,6 +240,31 @@ int te_msm_points_from_x_device(te_ctx* ctx, const void* d_x_le, uint64_t n, voi
 int te_msm_bind_points_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, te_bases** out);
 int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, uint8_t* out_xy_le);
 
+/* ---- batch scalar multiplication ----------------------------------------------------------------------------------------------
+ * out[i] = [k_i] P_i for every i, no sum: the reference's bulkGroupScalarMul / groupScalarMul (utils/wasmFunctions.ts:127-138, Aleo's
+ * Address.group_scalar_mul) and FieldMath.multiply (utils/FieldMath.ts:71-84).  The curve is option "curve".
+ * Points: the wire format above (64 / 96 bytes); te_msm_mul_x takes x-only points in te_msm_points_from_x's format and recovers them
+ *   first (on the device, no host round trip).  Scalars: the MSM's format -- 32-byte little-endian (Twisted-Edwards), 48-byte records
+ *   holding values below 2^256 (BLS12-377; bytes 32..47 are not read).  shared_scalar != 0: scalars_le holds ONE scalar, used for all
+ *   n points (one account scalar applied to many group values).
+ * The result is exactly [k] P for every k below 2^256, with no reduction of k that could be wrong for the input:
+ *   Twisted-Edwards: any point of the curve, cofactor part included (the group law is complete on the whole curve; a shared scalar is
+ *   reduced mod 4 L, the exponent of the group).  BLS12-377: inputs must lie in G1, as for the MSM (a shared scalar is reduced mod r).
+ * Output: canonical affine x || y, 64 / 96 bytes a point.  The Twisted-Edwards identity is (0, 1); the BLS12-377 point at infinity
+ *   is 96 zero bytes, as the MSM result encodes it.  n = 0 is a no-op.
+ * Bad points: option "check_points" (1, 2) applies to te_msm_mul[_device] as to te_msm_run; te_msm_mul_x reports recovery failures as
+ *   te_msm_points_from_x does (and applies "check_points" to the recovered points).  A failure is TE_MSM_EPOINT with the LOWEST failing
+ *   index and its reason in the read-only options "bad_point_index" / "bad_point_reason"; the output is untouched.
+ * Host buffers: contiguous slices over the context's devices, one host thread per device; each slice is staged on its device (inputs
+ *   and results) and copied out only after every slice passed.  Temporary device memory is freed before the call returns.
+ * te_msm_mul_device: the points, the scalars and the output on one device of the context (else TE_MSM_EINVAL); returns with the result
+ *   complete in d_out.  The calling thread's current device is left as it was.
+ * COST: a chain of 256 doublings and 129 additions a point (signed 2-bit windows), about 1.2 / 1.8 x option "check_points" = 2
+ *   (Twisted-Edwards / BLS12-377); a shared scalar runs the NAF chain of the subgroup check, about 1.0 / 1.2 x. */
+int te_msm_mul(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le);
+int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_scalars_le, uint64_t n, int shared_scalar, void* d_out_points_xy_le);
+int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le);
+
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "window_bits"   c in [4,16]; 0 = choose from n (default)
  *   "signed_digits" 1 = signed window digits, 2^(c-1) buckets per window (default; the reference's shipped behaviour,

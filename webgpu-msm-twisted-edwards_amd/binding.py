@@ -180,6 +180,12 @@ def _lib() -> ctypes.CDLL:
         L.te_msm_bind_points_x.restype = ci
         L.te_msm_run_x.argtypes = [vp, cp, cp, u64, cp]
         L.te_msm_run_x.restype = ci
+        L.te_msm_mul.argtypes = [vp, cp, cp, u64, ci, cp]
+        L.te_msm_mul.restype = ci
+        L.te_msm_mul_device.argtypes = [vp, vp, vp, u64, ci, vp]
+        L.te_msm_mul_device.restype = ci
+        L.te_msm_mul_x.argtypes = [vp, cp, cp, u64, ci, cp]
+        L.te_msm_mul_x.restype = ci
         _LIB = L
     return _LIB
 
@@ -385,6 +391,41 @@ class MsmContext:
         out = ctypes.create_string_buffer(96)
         self._check(self._L.te_msm_run_x(self._h, bytes(xs), bytes(scalars), n, out))
         return out.raw[:self._sizes[2]]
+
+    # ---- batch scalar multiplication (include/te_msm.h): out[i] = [k_i] P_i, no sum
+    def _mul_scalars(self, scalars: bytes, n: int) -> bool:
+        """True for a shared scalar (one scalar's bytes), False for one scalar per point"""
+        sb = self._sizes[1]
+        if len(scalars) == sb:
+            return True
+        if len(scalars) != sb * n:
+            raise MsmError(-1, f"scalars must be {sb} bytes (one shared scalar) or {sb}*n bytes")
+        return False
+
+    def mul(self, points: bytes, scalars: bytes) -> bytes:
+        """te_msm_mul: n points (64 / 96 bytes) and n scalars (32 / 48 bytes), or ONE scalar for all of them -> n points [k_i] P_i,
+        canonical affine x || y (the Twisted-Edwards identity as (0, 1), the BLS12-377 point at infinity as 96 zero bytes)"""
+        pb = self._sizes[0]
+        if len(points) % pb:
+            raise MsmError(-1, f"points must be {pb}*n bytes")
+        n = len(points) // pb
+        shared = self._mul_scalars(scalars, n)
+        out = ctypes.create_string_buffer(max(1, pb * n))
+        self._check(self._L.te_msm_mul(self._h, bytes(points), bytes(scalars), n, int(shared), out))
+        return out.raw[:pb * n]
+
+    def mul_device(self, d_points: int, d_scalars: int, n: int, d_out: int, shared: bool = False):
+        """te_msm_mul_device: the same between buffers on one device of the context; shared: d_scalars holds one scalar"""
+        self._check(self._L.te_msm_mul_device(self._h, d_points, d_scalars, n, int(bool(shared)), d_out))
+
+    def mul_x(self, xs: bytes, scalars: bytes) -> bytes:
+        """te_msm_mul_x, bulkGroupScalarMul's counterpart: n x-only points (32 / 48 bytes, points_from_x's format) and n scalars, or
+        one -> n points x || y"""
+        n = self._x_count(xs)
+        shared = self._mul_scalars(scalars, n)
+        out = ctypes.create_string_buffer(max(1, self._sizes[0] * n))
+        self._check(self._L.te_msm_mul_x(self._h, bytes(xs), bytes(scalars), n, int(shared), out))
+        return out.raw[:self._sizes[0] * n]
 
     def bases_read(self, bases: "Bases", first: int, count: int, device_index: int = 0):
         """(record bytes, raw records [first, first + count) of the bound set on one device) -- te_msm_bases_read"""

@@ -33,6 +33,7 @@
 #include "kernels.hip.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
+#include "scalar_mul.hip.hpp"
 #include "probe.hip.hpp"
 #include "host_tail377.hpp"
 #include "host_sched.hpp"
@@ -2979,6 +2980,153 @@ int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
     HIP_TRY(ctx, hipStreamSynchronize(d.chk_stream));
   }
   return run_common(ctx, pts.p, sc.p, false, n, out_xy_le);      // as te_msm_run_device (window shards, check_points, TE_MSM_ESCALAR)
+}
+
+// ---- batch scalar multiplication (te_msm_mul[_device], te_msm_mul_x; kernels in scalar_mul.hip.hpp) ------------------------------
+// Host buffers: contiguous slices over the context's devices, one host thread per device (worker_of), as te_msm_run's point slices.
+// Every slice is staged whole on its device -- points (or x), scalars and results -- checked (recovery, option "check_points"),
+// multiplied, and copied out only when no slice reported a bad point: on a failure `out` is untouched.  The chain writes projective
+// results of a piece of kMulPiece points into a buffer of the call's own; the affine pass turns them into the wire format.  Every
+// temporary is freed before the call returns (dev_tmp).
+namespace {
+constexpr uint64_t kMulPiece = 1ull << 18;
+
+inline te::naf_t shared_naf_of(const uint8_t* k32, int curve) {
+  uint32_t k[8];
+  memcpy(k, k32, 32);
+  return te::sm_shared_naf(k, curve);
+}
+// n points and scalars (memory of devs[di]) -> n affine results at d_out (memory of devs[di]); returns when they are there
+int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t n, bool shared, const te::naf_t& kn, void* d_out) {
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const int curve = ctx->opt_curve;
+  const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1;
+  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in;
+  const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
+  std::lock_guard<std::mutex> lk(*d.chk_mu);
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
+  const uint64_t piece = std::min(n, kMulPiece);
+  dev_tmp proj;
+  if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
+  hipStream_t st = d.chk_stream;
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint4* p4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_pts) + off * pb);
+    const uint4* s4 = shared ? nullptr : reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_sc) + off * sb);
+    uint4* j4 = static_cast<uint4*>(proj.p);
+    uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
+    const dim3 grid((m + 255u) / 256u), block(256), agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP));
+    if (bls) {
+      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<1, true>), grid, block, 0, st, p4, s4, m, j4, kn);
+      else hipLaunchKernelGGL((te::k_scalar_mul<1, false>), grid, block, 0, st, p4, s4, m, j4, kn);
+      hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExp377);
+    } else {
+      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<0, true>), grid, block, 0, st, p4, s4, m, j4, kn);
+      else hipLaunchKernelGGL((te::k_scalar_mul<0, false>), grid, block, 0, st, p4, s4, m, j4, kn);
+      hipLaunchKernelGGL(te::k_scalar_mul_affine<0>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExpTe);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+int mul_args(te_ctx* ctx, const void* pts, const void* sc, uint64_t n, const void* out) {
+  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
+  if (n > 0 && (!pts || !sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  return 0;
+}
+// te_msm_mul (x_only = false) and te_msm_mul_x (true): host buffers, sliced over the devices
+int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalars_le, uint64_t n, bool shared, uint8_t* out) {
+  if (int rc = mul_args(ctx, src, scalars_le, n, out)) return rc;
+  if (n == 0) return 0;
+  const int curve = ctx->opt_curve, level = ctx->opt_check_points;
+  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in, ib = x_only ? x_bytes_of(curve) : pb;
+  const te::naf_t kn = shared ? shared_naf_of(scalars_le, curve) : te::naf_t{};
+  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
+  const uint64_t per = (n + D - 1) / D;
+  struct slice_t { dev_tmp pts, sc, res; int64_t bad = -1; int why = 0; bool from_x = false; };
+  std::vector<slice_t> sl(D);
+  auto stage = [&](size_t i) -> int {                             // upload, recover, check, multiply: everything but the copy out
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    gpu_t& d = ctx->devs[i];
+    slice_t& s = sl[i];
+    if (int rc = tmp_alloc(ctx, d, s.pts, m * pb)) return rc;
+    if (int rc = tmp_alloc(ctx, d, s.res, m * pb)) return rc;
+    if (!shared) {
+      if (int rc = tmp_alloc(ctx, d, s.sc, m * sb)) return rc;
+      HIP_TRY(ctx, hipMemcpy(s.sc.p, scalars_le + lo * sb, m * sb, hipMemcpyHostToDevice));
+    }
+    if (x_only) {
+      const int rc = recover_on(ctx, i, src + lo * ib, true, m, s.pts.p, nullptr, false, &s.bad, &s.why);
+      if (rc == TE_MSM_EPOINT) { s.from_x = true; return 0; }
+      if (rc) return rc;
+    } else {
+      HIP_TRY(ctx, hipMemcpy(s.pts.p, src + lo * ib, m * pb, hipMemcpyHostToDevice));
+    }
+    if (level) {
+      const int rc = check_points_on(ctx, i, s.pts.p, false, m, curve, level, &s.bad, &s.why);
+      if (rc == TE_MSM_EPOINT) return 0;
+      if (rc) return rc;
+    }
+    return mul_on(ctx, i, s.pts.p, s.sc.p, m, shared, kn, s.res.p);
+  };
+  auto copy_out = [&](size_t i) -> int {
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
+    HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].res.p, m * pb, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  auto on_all = [&](const std::function<int(size_t)>& f) -> int {
+    std::vector<te_sched::job_ref> jobs(D);
+    for (size_t i = 1; i < D; i++) jobs[i] = worker_of(ctx, i).post([&f, i] { return f(i); });
+    int rc = f(0);
+    for (size_t i = 1; i < D; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
+    return rc;
+  };
+  if (int rc = on_all(stage)) return rc;
+  for (size_t i = 0; i < D; i++) {                                // slices in order: the first that reports holds the lowest index
+    if (sl[i].bad < 0) continue;
+    const int64_t index = (int64_t)(per * i) + sl[i].bad;
+    return sl[i].from_x ? note_bad_x(ctx, index, sl[i].why) : note_bad_point(ctx, index, sl[i].why);
+  }
+  return on_all(copy_out);
+}
+}  // namespace
+
+int te_msm_mul(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  return mul_host(ctx, points_xy_le, false, scalars_le, n, shared_scalar != 0, out_points_xy_le);
+}
+
+int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  return mul_host(ctx, x_le, true, scalars_le, n, shared_scalar != 0, out_points_xy_le);
+}
+
+int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_scalars_le, uint64_t n, int shared_scalar, void* d_out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = mul_args(ctx, d_points_xy_le, d_scalars_le, n, d_out_points_xy_le)) return rc;
+  if (n == 0) return 0;
+  const int owner = device_index_of_pointer(ctx, d_points_xy_le);
+  if (owner < 0 || device_index_of_pointer(ctx, d_scalars_le) != owner || device_index_of_pointer(ctx, d_out_points_xy_le) != owner)
+    return set_err(ctx, TE_MSM_EINVAL, "te_msm_mul_device: the points, the scalars and the output must be resident on one device of the context");
+  gpu_t& d = ctx->devs[(size_t)owner];
+  te::naf_t kn = {};
+  if (shared_scalar) {                                            // the NAF is built here: the scalar's first 32 bytes come back
+    uint8_t k[32];
+    HIP_TRY(ctx, hipSetDevice(d.device));
+    HIP_TRY(ctx, hipMemcpy(k, d_scalars_le, 32, hipMemcpyDeviceToHost));
+    kn = shared_naf_of(k, ctx->opt_curve);
+  }
+  if (int rc = check_call(ctx, (size_t)owner, d_points_xy_le, false, n)) return rc;
+  return mul_on(ctx, (size_t)owner, d_points_xy_le, d_scalars_le, n, shared_scalar != 0, kn, d_out_points_xy_le);
 }
 
 int te_msm_set_window_shard(te_ctx* ctx, int first, int step) {

@@ -231,6 +231,58 @@ napi_value PointsFromX(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+// scalarMul(points: Buffer, scalars: Buffer): Buffer -- batch scalar multiplication (include/te_msm.h, te_msm_mul): n x 64-byte points
+// and n x 32-byte little-endian scalars, or ONE 32-byte scalar for all of them -> n x 64-byte points [k_i] P_i (the identity as
+// (0, 1)).  scalarMulX(xs, scalars) takes x-only points (pointsFromX's format) instead: bulkGroupScalarMul's counterpart
+// (te_msm_mul_x).  Twisted-Edwards curve only, like the rest of the addon; run like pointsFromX.  A bad point (setCheckPoints) or a
+// bad x throws an Error naming the lowest failing index and the reason, also as .index / .reason.
+napi_value MulCommon(napi_env env, napi_callback_info info, bool x_only) {
+  const char* const sig = x_only ? "scalarMulX(xs: Buffer, scalars: Buffer)" : "scalarMul(points: Buffer, scalars: Buffer)";
+  size_t argc = 2; napi_value argv[2];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool b0 = false, b1 = false;
+  if (argc >= 2) { napi_is_buffer(env, argv[0], &b0); napi_is_buffer(env, argv[1], &b1); }
+  if (!b0 || !b1) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  void *p = nullptr, *s = nullptr; size_t pl = 0, sl = 0;
+  napi_get_buffer_info(env, argv[0], &p, &pl);
+  napi_get_buffer_info(env, argv[1], &s, &sl);
+  const size_t in_bytes = x_only ? TE_MSM_X_BYTES : TE_MSM_POINT_BYTES;
+  const uint64_t n = pl / in_bytes;
+  if (pl % in_bytes != 0 || (sl != TE_MSM_SCALAR_BYTES && sl != n * TE_MSM_SCALAR_BYTES)) {
+    napi_throw_range_error(env, nullptr, x_only ? "scalarMulX: xs must be 32*n bytes, scalars 32 (shared) or 32*n bytes"
+                                                : "scalarMul: points must be 64*n bytes, scalars 32 (shared) or 32*n bytes");
+    return nullptr;
+  }
+  const int shared = sl == TE_MSM_SCALAR_BYTES ? 1 : 0;
+  std::vector<uint8_t> out((size_t)n * TE_MSM_POINT_BYTES);
+  int64_t bad = -1, reason = 0;
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    const int r = x_only ? te_msm_mul_x(c, static_cast<const uint8_t*>(p), static_cast<const uint8_t*>(s), n, shared, out.data())
+                         : te_msm_mul(c, static_cast<const uint8_t*>(p), static_cast<const uint8_t*>(s), n, shared, out.data());
+    if (r == TE_MSM_EPOINT) { (void)te_msm_get_option(c, "bad_point_index", &bad); (void)te_msm_get_option(c, "bad_point_reason", &reason); }
+    return r;
+  }, err);
+  if (rc) {
+    const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_value msg, errv;
+    napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+    napi_create_error(env, nullptr, msg, &errv);
+    if (rc == TE_MSM_EPOINT) {
+      napi_value iv, rv;
+      napi_create_int64(env, bad, &iv); napi_create_int32(env, (int32_t)reason, &rv);
+      napi_set_named_property(env, errv, "index", iv); napi_set_named_property(env, errv, "reason", rv);
+    }
+    napi_throw(env, errv);
+    return nullptr;
+  }
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
+  return buf;
+}
+napi_value ScalarMul(napi_env env, napi_callback_info info) { return MulCommon(env, info, false); }
+napi_value ScalarMulX(napi_env env, napi_callback_info info) { return MulCommon(env, info, true); }
+
 // setCheckPoints(level): opt-in validation of the input points (include/te_msm.h, option "check_points"): 0 = none (default),
 // 1 = canonical and on the curve, 2 = also in the prime-order subgroup (costly: about 3 000 field products per point).  A call whose
 // points fail rejects its promise with an Error that names the lowest failing index and the reason; setBases then throws for a bad
@@ -272,7 +324,7 @@ napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
       {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints},
-      {"pointsFromX", PointsFromX}};
+      {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -61,5 +61,10 @@ const setCheckPoints = (level) => native.setCheckPoints(level);
 // Address.msm takes) into the 64n-byte points buffer of compute_msm / setBases, y recovered on the GPU.  A bad x throws an Error
 // naming the lowest failing index and the reason (also as .index / .reason).
 const pointsFromX = (xs) => native.pointsFromX(xs);
+// Outside the reference's interface too: scalarMul(points, scalars) returns the n points [k_i] P_i (no sum) as a 64n-byte Buffer;
+// scalarMulX(xs, scalars) takes x-only points (bulkGroupScalarMul's counterpart).  One 32-byte scalar is shared by every point.  A
+// bad point or x throws an Error naming the lowest failing index and the reason (also as .index / .reason).
+const scalarMul = (points, scalars) => native.scalarMul(points, scalars);
+const scalarMulX = (xs, scalars) => native.scalarMulX(xs, scalars);
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX, scalarMul, scalarMulX };

@@ -21,3 +21,7 @@ export declare const setCheckPoints: (level: 0 | 1 | 2) => void;
 // Not in the reference: x-only points (Aleo group values, Address.msm's input) -> the 64n-byte points buffer of compute_msm /
 // setBases, y recovered on the GPU; a bad x throws (the message names the index and the reason; also error.index / error.reason).
 export declare const pointsFromX: (xs: Buffer) => Buffer;
+// Not in the reference: batch scalar multiplication, [k_i] P_i for every i (no sum) as a 64n-byte points Buffer; scalarMulX takes
+// x-only points (bulkGroupScalarMul).  One 32-byte scalar is shared by all points; a bad point or x throws (error.index / error.reason).
+export declare const scalarMul: (points: Buffer, scalars: Buffer) => Buffer;
+export declare const scalarMulX: (xs: Buffer, scalars: Buffer) => Buffer;
