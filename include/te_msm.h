@@ -7,7 +7,9 @@
  * `compute_msm(bufferPoints, bufferScalars)` (submission/submission.ts:73-78) intact.
  *
  * Wire format (README.md:297-299; encoder reference/webgpu/utils.ts:90-99):
- *   points : n x (x[32 B little-endian] || y[32 B little-endian]), canonical affine, NOT Montgomery
+ *   points : n x (x[32 B little-endian] || y[32 B little-endian]), canonical affine, NOT Montgomery.  With option
+ *            "check_points" = 0 a coordinate may be any 256-bit value: it stands for its residue mod p (x + k p gives the
+ *            result of x)
  *   scalars: n x 32 B little-endian integers (< p < 2^253; signed digits accept anything below 2^254 - 2^240 at every
  *            window size -- TE_MSM_ESCALAR above --, unsigned digits any 256-bit value)
  *   result : x[32 B LE] || y[32 B LE], canonical affine  ( == result.toAffine(), submission.ts:412 )
@@ -48,7 +50,9 @@ typedef struct te_ctx te_ctx;
  * values below 2^256 (README.md:325-331), the result is x || y in 96 bytes (the point at infinity as 96 zero bytes) --
  * `out_xy_le` of te_msm_run / run_device / collect must then hold TE_MSM_RESULT_BYTES_MAX bytes.  Inputs must lie in G1 (the
  * subgroup of prime order r, as the harness generates them): the engine works in the curve's twisted-Edwards form, whose
- * map from y^2 = x^3 + 1 is undefined at the points of order 2 and 4.  Every entry point serves both curves; partial
+ * map from y^2 = x^3 + 1 is undefined at the points of order 2 and 4.  As on the other curve, with "check_points" = 0 a
+ * coordinate may be any 48-byte value below 2^384 and stands for its residue mod q (x + k q, y + k q for every k that stays
+ * below 2^384: 151 for a typical coordinate), bound sets included.  Every entry point serves both curves; partial
  * rows of this curve are TE_MSM_PARTIAL_BYTES_BLS12_377 bytes per window (te_msm_partial_device, te_msm_finalize*). */
 #define TE_MSM_CURVE_TE_BLS12      0
 #define TE_MSM_CURVE_BLS12_377_G1  1

@@ -35,6 +35,16 @@ void f377_madd(const uint8_t acc[224], const uint8_t rec[224], int neg, uint8_t 
   ete_t<14> a; pnt_t<14> b; memcpy(&a, acc, 224); memcpy(&b, rec, 224);
   const ete_t<14> r = ete_madd(a, pnt_cneg(b, neg != 0)); memcpy(out, &r, 224);
 }
+// the AFFINE record of a bound point set (pnt_aff377, 168 bytes: hm | hp | dt, z = 1): the 7-product mixed addition, and the
+// conversion every segment of k_accumulate starts with -- both after the same conditional negation as on the device
+void f377_madd_aff(const uint8_t acc[224], const uint8_t rec[168], int neg, uint8_t out[224]) {
+  ete_t<14> a; pnt_aff377 b; memcpy(&a, acc, 224); memcpy(&b, rec, 168);
+  const ete_t<14> r = ete_madd(a, pnt_cneg(b, neg != 0)); memcpy(out, &r, 224);
+}
+void f377_from_aff(const uint8_t rec[168], int neg, uint8_t out[224]) {
+  pnt_aff377 b; memcpy(&b, rec, 168);
+  const ete_t<14> r = ete_from_pnt(pnt_cneg(b, neg != 0)); memcpy(out, &r, 224);
+}
 void f377_add(const uint8_t a_[224], const uint8_t b_[224], uint8_t out[224]) {
   ete_t<14> a, b; memcpy(&a, a_, 224); memcpy(&b, b_, 224); const ete_t<14> r = ete_add<14>(a, b); memcpy(out, &r, 224);
 }

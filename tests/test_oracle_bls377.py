@@ -220,6 +220,69 @@ def test_device_group_law_377_on_the_host(fq377check):
     assert L.f377_overflow_and_reset() == 0
 
 
+def test_device_affine_mixed_addition_377_on_the_host(fq377check):
+    """csrc/curve.hpp, the AFFINE record of a bound point set (pnt_aff377): the 7-product mixed addition, pnt_cneg and the
+    first-entry conversion ete_from_pnt, against the affine short-Weierstrass model -- the neutral element, doubling through the
+    mixed law, P - P, (-P) + (-P), a long signed chain; every column stays below 2^64"""
+    import ctypes
+    NL, LB, LM, limbs, val = _limb_helpers()
+    Q, L = m.Q, fq377check
+    R = 1 << (NL * LB)
+    rinv = pow(R, -1, Q)
+    s_, f_, d_ = _edwards_consts(L)
+
+    def aff(b):                                       # extended point x | y | z | t -> Weierstrass affine
+        X, Y, Z, T = (sum(int.from_bytes(b[56 * k + 4 * i:56 * k + 4 * i + 4], "little") << (LB * i) for i in range(NL)) * rinv % Q
+                      for k in range(4))
+        for k in range(4):
+            assert all(int.from_bytes(b[56 * k + 4 * i:56 * k + 4 * i + 4], "little") <= LM for i in range(NL - 1)), "limb class N"
+        zi = pow(Z, -1, Q)
+        xa, ya = X * zi % Q, Y * zi % Q
+        assert (-xa * xa + ya * ya - 1 - d_ * xa * xa * ya * ya) % Q == 0, "not on the Edwards curve"
+        assert xa * ya % Q == T * zi % Q, "T = XY/Z"
+        return edwards_to_weierstrass(xa, ya, s_, f_)
+
+    def rec(pt):                                      # ((Y - X)/2, (Y + X)/2, -d X Y) of the Edwards point, times R
+        x, y = pt
+        u, v = s_ * (x + 1) % Q, s_ * y % Q
+        X, Y = f_ * u * pow(v, -1, Q) % Q, (u - 1) * pow(u + 1, -1, Q) % Q
+        assert edwards_to_weierstrass(X, Y, s_, f_) == pt
+        h = pow(2, -1, Q)
+        return b"".join(bytes(limbs(c * R % Q)) for c in ((Y - X) * h, (Y + X) * h, -d_ * X * Y))
+
+    def madd(acc, pt, neg):
+        o = ctypes.create_string_buffer(224)
+        L.f377_madd_aff(acc, rec(pt), 1 if neg else 0, o)
+        return o.raw
+
+    def first(pt, neg):
+        o = ctypes.create_string_buffer(224)
+        L.f377_from_aff(rec(pt), 1 if neg else 0, o)
+        return o.raw
+    ib = ctypes.create_string_buffer(224)
+    L.f377_identity(ib)
+    ident = ib.raw
+    pts = m.gen_points(11, 16)
+    for p in pts[:4]:
+        assert aff(madd(ident, p, False)) == p                                    # O + P
+        assert aff(madd(ident, p, True)) == m.neg(p)                              # O + (-P)
+        assert aff(first(p, False)) == p and aff(first(p, True)) == m.neg(p)      # the first entry of a segment
+        assert aff(madd(first(p, False), p, False)) == m.add(p, p)                # P + P: doubling through the mixed law
+        assert aff(madd(madd(ident, p, False), p, False)) == m.add(p, p)
+        assert aff(madd(first(p, False), p, True)) is None                        # P + (-P)
+        assert aff(madd(first(p, True), p, False)) is None                        # (-P) + P
+        assert aff(madd(first(p, True), p, True)) == m.neg(m.add(p, p))           # (-P) + (-P)
+        assert aff(madd(madd(first(p, True), p, False), p, True)) == m.neg(p)      # through the neutral element and on
+    rnd = random.Random(12)
+    acc, exp = first(pts[0], False), pts[0]
+    for r in range(64):                                                           # a signed chain: repeats, inverses, doublings
+        p, neg = pts[rnd.randrange(len(pts))], rnd.random() < 0.5
+        acc = madd(acc, p, neg)
+        exp = m.add(exp, m.neg(p) if neg else p)
+        assert aff(acc) == exp, r
+    assert L.f377_overflow_and_reset() == 0
+
+
 def test_emulated_stages_plus_host_tail_377(fq377check):
     """digits -> buckets -> marginals -> weighted sums with the device arithmetic on the host, then the PRODUCT's host tail
     (Horner in the Edwards form + the map back to y^2 = x^3 + 1, te_msm_finalize_host_curve / _gathered_curve): the oracle's
