@@ -191,6 +191,35 @@ int te_msm_run_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_scalar
 int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_le, uint64_t* ticket);
 int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_scalars_le, uint64_t* ticket);
 
+/* ---- batched MSMs over prefixes of a bound point set -------------------------------------------------------------------------
+ * A prover commits to many polynomials of different degrees against ONE SRS: every commitment is an MSM over a PREFIX of the same point
+ * set.  te_msm_run_scalars* needs a scalar for every point of the set (a shorter polynomial pays for zero padding), and every MSM is a
+ * launch sequence of its own with a latency-bound reduction tail.  These two calls take the whole list:
+ *   MSM m = sum_{i < lens[m]} k_{m,i} P_i over the bound set's points.  scalars_le is PACKED: MSM m's lens[m] scalar records start at
+ *   record sum_{j<m} lens[j]; the record format is the MSM's own (32 bytes Twisted-Edwards, 48-byte records for BLS12-377).  out receives
+ *   `count` results in input order, each encoded as te_msm_run_scalars encodes its result (64 / 96 bytes; the Twisted-Edwards identity as
+ *   (0, 1), the BLS12-377 point at infinity as zeros).  lens[m] == 0 gives the identity; count == 0 does nothing.
+ *   TE_MSM_EINVAL, out untouched: lens[m] > te_msm_bases_count(bases); a null pointer (lens, out, or the scalars while some lens[m] > 0);
+ *   a bases handle of another curve or one already released; a context with a window shard set (te_msm_set_window_shard, step > 1).
+ *   TE_MSM_ESCALAR, out untouched: a scalar anywhere in the batch trips the final-carry check (the rule of te_msm_partial_device_batch).
+ *   A set bound with "bind_fixed_base" is served from its table 0 (the ordinary records) with the ordinary windows: the same results as
+ *   an ordinary set.
+ *   How it runs (csrc/batch_plan.hpp): MSMs of at most option "batch_small_max" points (default 2^15) are grouped by
+ *   length class (the largest length of a group below twice its smallest) and packed, up to TE_MSM_BATCH_SEQ_MAX of them and within a
+ *   scratch budget of 1 GB, into SHARED launch sequences -- one digit launch over all of them (a ragged form of the digit kernel: MSM m
+ *   reads its own slice of the packed scalars, entries past its length are digit 0), one sort, one accumulation, one reduction.  Window
+ *   bits, digit form and segment length follow the options, with the sequence's largest length standing for n.  Longer MSMs run as
+ *   whole-MSM sequences of their own.  The sequences of a device are dealt over its free work sets, up to TE_MSM_WORKSETS in flight (the
+ *   call returns TE_MSM_ESTATE when tickets own every set).  The host tails (one fold per MSM) run on up to 8 host threads.
+ *   Host form: with several devices, whole MSMs are spread over them, longest first to the least loaded (sum of lengths), and every
+ *   device gathers from its own copy of the records.  Device form: the packed scalars lie on one device of the context and the whole
+ *   batch runs there.
+ *   Synchronous; the calling thread's current device is left as it was.  Read-only option "batch_sequences": the launch sequences the
+ *   last batch call ran.  Option "profile" does not apply (no stage times). */
+#define TE_MSM_BATCH_SEQ_MAX 64   /* MSMs one shared launch sequence of te_msm_run_scalars_batch holds at most */
+int te_msm_run_scalars_batch(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const uint8_t* scalars_le, uint8_t* out);
+int te_msm_run_scalars_batch_device(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const void* d_scalars_le, uint8_t* out);
+
 /* ---- input-point validation ------------------------------------------------------------------------------------------------
  * The engine trusts its points unless asked: the wire format above says what a caller must pass, and a point that breaks it gives a
  * wrong result, not an error.  Level 1, FORM: both coordinates canonical (below p / q), the curve equation holds
@@ -336,6 +365,8 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *                   chains the accumulations of the MSMs in flight (slower: profiles/r06_serial_accumulate_experiment.txt).
  *   "scalar_chunks" te_msm_run_scalars / te_msm_submit_scalars: pieces the scalars of a bound point set are uploaded and processed
  *                   in; 0 = from n (default), 1 = whole.  The result does not depend on it.
+ *   "batch_small_max" te_msm_run_scalars_batch*: MSMs of at most this many points share launch sequences, longer ones run alone
+ *                   (default 32768; 0 = every MSM alone).  The result does not depend on it.  Read-only "batch_sequences": see there.
  *   read-only:      "num_devices", "segment_len_used", "peer_copies" / "peer_bytes" (hipMemcpyPeerAsync calls a multi-device
  *                   context issued, and the bytes they moved), "entries_accumulated" (non-zero window digits of the MSM whose
  *                   result was fetched last, counted on the device: the points k_accumulate gathered -- all windows of this

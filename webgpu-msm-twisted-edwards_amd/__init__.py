@@ -31,6 +31,7 @@ from .binding import (  # noqa: F401
     CURVE_BLS12_377_G1,
     WORKSETS,
     MAX_BATCH,
+    BATCH_SEQ_MAX,
     EPOINT,
     POINT_NONCANONICAL,
     POINT_OFF_CURVE,

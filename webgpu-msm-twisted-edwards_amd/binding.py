@@ -17,6 +17,7 @@ PARTIAL_BYTES_BLS12_377 = 1120          # TE_MSM_PARTIAL_BYTES_BLS12_377
 CURVE_TE_BLS12, CURVE_BLS12_377_G1 = 0, 1        # option "curve" (TE_MSM_CURVE_*)
 WORKSETS = 8            # TE_MSM_WORKSETS: MSMs one context can have in flight
 MAX_BATCH = 8           # TE_MSM_MAX_BATCH: MSMs one te_msm_partial_device_batch call takes
+BATCH_SEQ_MAX = 64      # TE_MSM_BATCH_SEQ_MAX: MSMs one shared launch sequence of te_msm_run_scalars_batch holds
 EPOINT = -5             # TE_MSM_EPOINT: an input point failed the check of option "check_points"
 # why a point failed (TE_MSM_POINT_*): MsmError.reason, the second item of MsmContext.check_points' answer
 POINT_NONCANONICAL, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = 1, 2, 3
@@ -118,6 +119,10 @@ def _lib() -> ctypes.CDLL:
         L.te_msm_run_scalars.restype = ci
         L.te_msm_run_scalars_device.argtypes = [vp, vp, vp, cp]
         L.te_msm_run_scalars_device.restype = ci
+        L.te_msm_run_scalars_batch.argtypes = [vp, vp, ci, ctypes.POINTER(u64), cp, cp]
+        L.te_msm_run_scalars_batch.restype = ci
+        L.te_msm_run_scalars_batch_device.argtypes = [vp, vp, ci, ctypes.POINTER(u64), vp, cp]
+        L.te_msm_run_scalars_batch_device.restype = ci
         L.te_msm_submit_scalars.argtypes = [vp, vp, cp, ctypes.POINTER(u64)]
         L.te_msm_submit_scalars.restype = ci
         L.te_msm_submit_scalars_device.argtypes = [vp, vp, vp, ctypes.POINTER(u64)]
@@ -456,6 +461,35 @@ class MsmContext:
         out = ctypes.create_string_buffer(96)
         self._check(self._L.te_msm_run_scalars_device(self._h, bases._h, d_scalars, out))
         return out.raw[:self._sizes[2]]
+
+    def run_scalars_batch(self, bases: "Bases", scalar_list) -> list:
+        """Batched MSMs over prefixes of a bound point set (te_msm_run_scalars_batch): scalar_list holds one scalar buffer per MSM
+        (bytes or a numpy array of the curve's scalar records); MSM m runs over the first len(scalar_list[m]) // scalar_bytes points.
+        Returns the results in input order."""
+        if bases._h is None or bases._ctx is not self:
+            raise MsmError(-1, "not a bound point set of this context")
+        sb = self._sizes[1]
+        bufs = [bytes(memoryview(s).cast("B")) if not isinstance(s, (bytes, bytearray)) else bytes(s) for s in scalar_list]
+        for b in bufs:
+            if len(b) % sb:
+                raise MsmError(-1, f"every scalar buffer must hold whole {sb}-byte records")
+        lens = [len(b) // sb for b in bufs]
+        return self._run_batch(bases, lens, b"".join(bufs), False)
+
+    def run_scalars_batch_device(self, bases: "Bases", d_scalars: int, lens) -> list:
+        """te_msm_run_scalars_batch_device: the packed scalars of all MSMs (MSM m's lens[m] records behind MSM m-1's) in the memory of
+        a device of the context."""
+        if bases._h is None or bases._ctx is not self:
+            raise MsmError(-1, "not a bound point set of this context")
+        return self._run_batch(bases, [int(x) for x in lens], d_scalars, True)
+
+    def _run_batch(self, bases: "Bases", lens, scalars, device: bool) -> list:
+        count, rb = len(lens), self._sizes[2]
+        lv = (ctypes.c_uint64 * max(1, count))(*lens)
+        out = ctypes.create_string_buffer(max(1, count * rb))
+        fn = self._L.te_msm_run_scalars_batch_device if device else self._L.te_msm_run_scalars_batch
+        self._check(fn(self._h, bases._h, count, lv, scalars, out))
+        return [out.raw[rb * m:rb * (m + 1)] for m in range(count)]
 
     def submit_scalars(self, bases: "Bases", scalars: bytes) -> int:
         """te_msm_submit_scalars: asynchronous ticket over a bound point set (this object holds the scalars until the ticket

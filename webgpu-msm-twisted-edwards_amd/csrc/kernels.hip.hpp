@@ -120,12 +120,12 @@ __device__ __forceinline__ bool digit_bucket(uint32_t stored, uint32_t half, uin
 #ifndef TE_L2_WAVES
 #define TE_L2_WAVES 3
 #endif
+// The body of k_digits and k_digits_ragged: the block's entries of MSM blockIdx.y, whose n scalars start at `scalars`; entries i >= n
+// (up to the row stride nst) are padding and get digit 0.  hist: the block's LDS histogram.
 template <int C>
-__global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_ptrs in, uint16_t* __restrict__ digits,
-                                                digits_params prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
-  __shared__ uint32_t hist[4096];                        // [local window][partition]: nw_local * P <= 4096 for every plan
-  // MSM blockIdx.y of the launch sequence: its scalars, its digit rows and level-1 counts [y * nw_local, (y + 1) * nw_local)
-  const uint4* __restrict__ scalars = in.p[blockIdx.y];
+__device__ __forceinline__ void digits_block(const uint4* __restrict__ scalars, const uint32_t n, uint32_t* __restrict__ hist, uint16_t* __restrict__ digits,
+                                             const digits_params& prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
+  // MSM blockIdx.y of the launch sequence: its digit rows and level-1 counts [y * nw_local, (y + 1) * nw_local)
   digits += (size_t)blockIdx.y * prm.nw_local * prm.nst;
   counts1 += (size_t)blockIdx.y * prm.nw_local * prm.CH * prm.P;
   const uint32_t hn = (uint32_t)prm.nw_local * prm.P;
@@ -142,7 +142,7 @@ __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_p
 #pragma unroll
   for (uint32_t step = 0; step < STEPS; step++) {
     const uint32_t i0 = 2u * ((blockIdx.x * STEPS + step) * TE_DIG_THREADS + threadIdx.x);
-    const size_t ia = min(i0, prm.n - 1u), ib = min(i0 + 1u, prm.n - 1u);        // clamped: unconditional loads
+    const size_t ia = min(i0, n - 1u), ib = min(i0 + 1u, n - 1u);        // clamped: unconditional loads
     ld[step][0] = scalars[st * ia]; ld[step][1] = scalars[st * ia + 1]; ld[step][2] = scalars[st * ib]; ld[step][3] = scalars[st * ib + 1];
     ld[step][4] = ld[step][5] = make_uint4(0u, 0u, 0u, 0u);
     if (st == 3) { ld[step][4] = scalars[st * ia + 2]; ld[step][5] = scalars[st * ib + 2]; }
@@ -151,11 +151,11 @@ __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_p
   for (uint32_t step = 0; step < STEPS; step++) {
     const uint32_t pair = (blockIdx.x * STEPS + step) * TE_DIG_THREADS + threadIdx.x, i0 = 2u * pair;
     if (i0 >= prm.nst) break;
-    if (i0 >= prm.n) {                                   // padding entries: digit 0
+    if (i0 >= n) {                                   // padding entries: digit 0
       for (int k = 0; k < prm.nw_local; k++) out[(size_t)k * half_stride + pair] = ZERO_DIGIT | (ZERO_DIGIT << 16);
       continue;
     }
-    const bool second = i0 + 1u < prm.n;
+    const bool second = i0 + 1u < n;
     const uint4 a0 = ld[step][0], a1 = ld[step][1], b0 = ld[step][2], b1 = ld[step][3];
     {                                                     // 48-byte records hold values below 2^256
       const uint4 a2 = ld[step][4], b2 = ld[step][5];
@@ -208,6 +208,28 @@ __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_p
     const uint32_t v = hist[j];
     if (v) { const uint32_t k = j / prm.P, p = j - k * prm.P; atomicAdd(&counts1[((size_t)k * prm.CH + ch) * prm.P + p], v); }
   }
+}
+
+template <int C>
+__global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_ptrs in, uint16_t* __restrict__ digits,
+                                                digits_params prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
+  __shared__ uint32_t hist[4096];                        // [local window][partition]: nw_local * P <= 4096 for every plan
+  digits_block<C>(in.p[blockIdx.y], prm.n, hist, digits, prm, err, counts1);      // every MSM of the sequence has prm.n scalars
+}
+
+// RAGGED SEQUENCES (te_msm_run_scalars_batch): up to TE_RAGGED_MAX MSMs of DIFFERENT lengths over prefixes of one bound point set.
+// MSM m (blockIdx.y) has len[m] >= 1 scalars starting off[m] records into ONE packed buffer; its digit rows keep the sequence's stride
+// prm.nst (from the largest length) and entries i >= len[m] are padding (digit 0, the scalar is not read) -- so the sort, the
+// accumulation and the reduction see a batch of equal-length MSMs, and entry i of every MSM gathers bound record i.  The table rides in
+// the kernel arguments (TE_RAGGED_MAX x 12 bytes): a separate kernel, so that k_digits (the headline path) keeps its code.
+#define TE_RAGGED_MAX 64
+struct ragged_tab { uint64_t off[TE_RAGGED_MAX]; uint32_t len[TE_RAGGED_MAX]; };
+template <int C>
+__global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits_ragged(const uint4* __restrict__ scalars, ragged_tab tab, uint16_t* __restrict__ digits,
+                                                       digits_params prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
+  __shared__ uint32_t hist[4096];
+  const uint32_t m = blockIdx.y;
+  digits_block<C>(scalars + tab.off[m] * prm.sc_stride, tab.len[m], hist, digits, prm, err, counts1);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -37,6 +37,7 @@
 #include "probe.hip.hpp"
 #include "host_tail377.hpp"
 #include "host_sched.hpp"
+#include "batch_plan.hpp"
 
 namespace {
 
@@ -137,6 +138,7 @@ struct workset_t {
   te_bases* bound = nullptr;          // the bound point set the set's ticket in flight gathers from (te_msm_submit_scalars*): released only after the collect
   // a ticket whose points failed the check (option "check_points"): nothing was enqueued for it, its te_msm_collect reports TE_MSM_EPOINT
   int pt_rc = 0; int64_t pt_index = -1; int pt_reason = 0;
+  uint8_t* d_batch_rows = nullptr;    // te_msm_run_scalars_batch: the rows of a ragged sequence (all its MSMs; cap[28])
 };
 constexpr int TE_MAX_WINDOWS = 64;    // window_bits >= 4
 // words [Z_CLOCK, Z_ROWS): k_accumulate's profiling words, 4 x TE_CLK_SLOTS 64-bit values (first wave in / last wave out on the
@@ -180,6 +182,7 @@ struct gpu_t {
   unsigned long long *chk_word = nullptr, *chk_host = nullptr;
   bool streams_exported = false;         // te_msm_workset_stream handed a handle out: te_msm_destroy parks the streams instead of destroying them
   bool streams_final = false;            // ... and the work sets' streams will not be re-dealt any more
+  uint8_t* h_batch_rows = nullptr; size_t h_batch_cap = 0;   // te_msm_run_scalars_batch: pinned landing area of every sequence's rows (grown on use)
 };
 
 }  // namespace
@@ -231,6 +234,8 @@ struct te_ctx {
                                  // it, instead of putting a stream wait in front of them (see lane_wait; A/B: option "lane_host_waits", env TE_MSM_LANE_HOST_WAITS)
   int opt_exp_table_replicas = 1; // EXPERIMENT (profiles/r06_fixed_base_windows.txt): te_msm_bind_points keeps this many copies of the records and
                                  // the windows of a device-scalar MSM gather from different copies -- the gather footprint of a per-window table
+  int64_t opt_batch_small_max = 1ll << 15;   // te_msm_run_scalars_batch: MSMs up to this length share launch sequences (option "batch_small_max")
+  int64_t stat_batch_sequences = 0;          // launch sequences the last batch call ran (get_option "batch_sequences")
 };
 
 // A bound point set (include/te_msm.h, "resident bases"): the records of n points on EVERY device of its context, converted
@@ -415,6 +420,10 @@ template <int C> void launch_digits(const te::batch_ptrs& sc, int batch, uint16_
   hipLaunchKernelGGL(te::k_digits<C>, dim3((prm.nst + TE_DIG_BLOCK - 1u) / TE_DIG_BLOCK, batch), dim3(TE_DIG_THREADS), 0, s, sc, dg, prm, err, counts1);
 }
 static_assert(TE_BATCH_MAX == TE_MSM_MAX_BATCH, "batch tables");
+template <int C> void launch_digits_ragged(const void* sc, const te::ragged_tab& tab, int batch, uint16_t* dg, const te::digits_params& prm, uint32_t* err, uint32_t* counts1, hipStream_t s) {
+  hipLaunchKernelGGL(te::k_digits_ragged<C>, dim3((prm.nst + TE_DIG_BLOCK - 1u) / TE_DIG_BLOCK, batch), dim3(TE_DIG_THREADS), 0, s, static_cast<const uint4*>(sc), tab, dg, prm, err, counts1);
+}
+static_assert(TE_RAGGED_MAX == TE_BATCH_SEQ_MAX && TE_BATCH_SEQ_MAX == TE_MSM_BATCH_SEQ_MAX, "ragged tables");
 
 // One MSM's device work in three parts, so that the parts before and after the dominant kernel can be replayed as HIP
 // graphs (one launch each instead of ~30: the host-side enqueue cost, ~0.35 ms, is what bounds small MSMs and the
@@ -433,6 +442,8 @@ struct msm_launch {
   int table_replicas = 1;         // experiment "exp_table_replicas": window k gathers from copy k / ceil(windows / copies) of the bound records
   const uint8_t* bound = nullptr; // records of a bound point set (te_msm_bind_points), already offset to this launch's first point: no conversion,
                                   // k_accumulate gathers from here instead of ws.d_recs (p.rec_kind tells which record form)
+  const te::ragged_tab* ragged = nullptr;   // a ragged sequence (te_msm_run_scalars_batch): d_scalars is ONE packed buffer, MSM m's scalars at
+                                  // ragged->off[m] with ragged->len[m] of them (k_digits_ragged); every window gathers from `bound` itself
   // Own rows of a context that computes ALL windows can be written to host memory by the tail kernel (every row slot is
   // rewritten by every MSM).  Not with window shards (rows of foreign windows must read as zero: they come from the cleared
   // device block), not with captured graphs (fixed pointers), not with "prezero" = 0 (stage verifiers read the device rows).
@@ -511,10 +522,26 @@ struct msm_launch {
       prm.half_code = sg.half; prm.logS = p.logS; prm.P = p.P; prm.CH = p.CH; prm.chunk_len = p.chunk_len;
       // one launch over the MSMs of the sequence: MSM m (blockIdx.y) fills digit rows and level-1 counts [m * nw1, (m + 1) * nw1)
       te::batch_ptrs sc; memset(&sc, 0, sizeof sc);
-      for (int m = 0; m < p.batch; m++) sc.p[m] = (const uint4*)scalars_of(m);
+      if (!ragged) for (int m = 0; m < p.batch; m++) sc.p[m] = (const uint4*)scalars_of(m);
       uint16_t* dg = ws.d_digits;
       uint32_t* c1 = ws.d_counts1;
-      switch (p.c) {
+      if (ragged) {
+        switch (p.c) {
+          case 4: launch_digits_ragged<4>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 5: launch_digits_ragged<5>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 6: launch_digits_ragged<6>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 7: launch_digits_ragged<7>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 8: launch_digits_ragged<8>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 9: launch_digits_ragged<9>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 10: launch_digits_ragged<10>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 11: launch_digits_ragged<11>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 12: launch_digits_ragged<12>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 13: launch_digits_ragged<13>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 14: launch_digits_ragged<14>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          case 15: launch_digits_ragged<15>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+          default: launch_digits_ragged<16>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
+        }
+      } else switch (p.c) {
         case 4: launch_digits<4>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
         case 5: launch_digits<5>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
         case 6: launch_digits<6>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
@@ -605,7 +632,9 @@ struct msm_launch {
       hipLaunchKernelGGL((te::k_accumulate<N, RK>), dim3((smax + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const slot_t*>(bound ? bound : recs_out()), ws.d_sorted,
                          ws.d_bucket_start, ws.d_bucket_count, ws.d_seg_base, ws.d_seg_bucket, ws.d_seg_lenv, order, ws.d_num_seg,
                          reinterpret_cast<te::ete_t<N>*>(ws.d_buckets), reinterpret_cast<te::ete_t<N>*>(ws.d_seg_out), n32, p.logB, p.seg_len, smax, onto ? 1u : 0u,
-                         table_replicas > 1 ? (uint32_t)((p.nw1 + table_replicas - 1) / table_replicas) : (uint32_t)p.nw1, table_replicas > 1 ? replica_slabs() : slabs(),
+                         // (a ragged sequence: every window's k / nw is 0 -- record slab 0, the bound set itself, for any number of MSMs)
+                         ragged ? (uint32_t)p.nw : table_replicas > 1 ? (uint32_t)((p.nw1 + table_replicas - 1) / table_replicas) : (uint32_t)p.nw1,
+                         ragged ? te::batch_slabs{} : table_replicas > 1 ? replica_slabs() : slabs(),
                          prof ? reinterpret_cast<unsigned long long*>(ws.d_zero + Z_CLOCK) : nullptr);
       if (chain.owns_lock()) {
         hipEvent_t& ev = d.acc_ev[d.acc_next++ % 16u];
@@ -1095,7 +1124,7 @@ void free_workset_buffers(workset_t& ws) {      // the big device buffers of a w
                    (void**)&ws.d_part_idx, (void**)&ws.d_seg_part_base, (void**)&ws.d_bucket_start, (void**)&ws.d_bucket_cursor, (void**)&ws.d_sorted,
                    (void**)&ws.d_seg_base, (void**)&ws.d_seg_bucket, (void**)&ws.d_seg_lenv, (void**)&ws.d_order, (void**)&ws.d_split_list,
                    (void**)&ws.d_chunk_list, (void**)&ws.d_seg_out, (void**)&ws.d_buckets, (void**)&ws.d_red[0], (void**)&ws.d_red[1],
-                   (void**)&ws.d_red[2], (void**)&ws.d_red[3], &ws.d_in_points, &ws.d_in_scalars, (void**)&ws.d_fb_remap};
+                   (void**)&ws.d_red[2], (void**)&ws.d_red[3], &ws.d_in_points, &ws.d_in_scalars, (void**)&ws.d_fb_remap, (void**)&ws.d_batch_rows};
   for (void** q : ptrs) if (*q) { (void)hipFree(*q); *q = nullptr; }
   if (ws.h_ring) { (void)hipHostFree(ws.h_ring); ws.h_ring = nullptr; }       // the pinned ring of option "host_staging" (its events stay)
   memset(ws.cap, 0, sizeof ws.cap); ws.cap_in_points = ws.cap_in_scalars = 0;
@@ -1117,6 +1146,8 @@ void free_dev(gpu_t& d) {
   if (d.chk_word) (void)hipFree(d.chk_word);
   if (d.chk_host) (void)hipHostFree(d.chk_host);
   d.chk_stream = nullptr; d.chk_pts = nullptr; d.chk_cap = 0; d.chk_word = d.chk_host = nullptr;
+  if (d.h_batch_rows) (void)hipHostFree(d.h_batch_rows);
+  d.h_batch_rows = nullptr; d.h_batch_cap = 0;
   for (workset_t& ws : d.ws) {
     free_workset_buffers(ws);
     if (ws.h_err) (void)hipHostFree(ws.h_err);
@@ -2743,6 +2774,7 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
   if (!strcmp(key, "bind_fixed_base")) { if (value != 0 && (value < 16 || value > 21)) return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base must be 0 or in [16, 21]"); ctx->opt_bind_fixed_base = (int)value; return 0; }
   if (!strcmp(key, "exp_table_replicas")) { if (value < 1 || value > TE_BATCH_MAX) return set_err(ctx, TE_MSM_EINVAL, "exp_table_replicas must be in [1, 8]"); ctx->opt_exp_table_replicas = (int)value; return 0; }
   if (!strcmp(key, "scalar_chunks")) { if (value < 0 || value > 64) return set_err(ctx, TE_MSM_EINVAL, "scalar_chunks out of range"); ctx->opt_scalar_chunks = (int)value; return 0; }
+  if (!strcmp(key, "batch_small_max")) { if (value < 0 || value > (1ll << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch_small_max must be in [0, 2^31]"); ctx->opt_batch_small_max = value; return 0; }
   return set_err(ctx, TE_MSM_EINVAL, "unknown option");
 }
 
@@ -2780,6 +2812,8 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "share_records")) { *value = ctx->opt_share_records; return 0; }
   if (!strcmp(key, "record_slabs")) { int64_t t = 0; for (const gpu_t& d : ctx->devs) for (const auto& sl : d.slabs) if (sl.d) t++; *value = t; return 0; }
   if (!strcmp(key, "scalar_chunks")) { *value = ctx->opt_scalar_chunks; return 0; }
+  if (!strcmp(key, "batch_small_max")) { *value = ctx->opt_batch_small_max; return 0; }
+  if (!strcmp(key, "batch_sequences")) { *value = ctx->stat_batch_sequences; return 0; }
   if (!strcmp(key, "bind_fixed_base")) { *value = ctx->opt_bind_fixed_base; return 0; }
   if (!strcmp(key, "fixed_base_fallbacks")) { *value = ctx->stat_fb_fallbacks; return 0; }
   if (!strcmp(key, "bases_bound")) { *value = (int64_t)ctx->bases.size(); return 0; }
@@ -3127,6 +3161,222 @@ int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_sca
   }
   if (int rc = check_call(ctx, (size_t)owner, d_points_xy_le, false, n)) return rc;
   return mul_on(ctx, (size_t)owner, d_points_xy_le, d_scalars_le, n, shared_scalar != 0, kn, d_out_points_xy_le);
+}
+
+// ---- batched MSMs over prefixes of a bound point set (te_msm_run_scalars_batch[_device]) -------------------------------------------
+namespace {
+// what one MSM adds to a ragged sequence whose largest length is n (ensure_buffers' sizes, per MSM; te_batch::make_plan's budget)
+void batch_cost(const te_ctx* ctx, uint64_t n, te_batch::msm_cost& c) {
+  plan_t p; make_plan(ctx, ctx->devs[0], n, p, 0, 1, 0, true);
+  const curve_sizes sz = sizes_of(p.curve);
+  c.windows = (uint64_t)p.W; c.stride = p.nst;
+  const uint64_t cells = c.windows * c.stride, wb = c.windows * p.B, segs = wb + c.windows * (n / p.seg_len);
+  c.segments = segs;
+  // digits 2 + sorted 4 + level-1 index 4 (+ key 2) bytes a cell; buckets, two fold chains (1.5 x) and bucket tables; segment tables and
+  // sums; the rows
+  c.bytes = cells * (p.packed ? 10 : 12) + wb * (sz.acc * 5 / 2 + 28) + segs * (sz.acc + 20) + c.windows * sz.row;
+}
+
+struct batch_seq_run {              // one sequence of the plan, as the engine runs it
+  const te_batch::sequence* s = nullptr;
+  plan_t p;                         // the plan of its launch sequence (n = its largest length, batch = its MSMs)
+  size_t rows_at = 0;               // offset of its rows in its device's pinned landing area
+};
+
+// One ragged sequence on work set ws: the scalar stages over the packed buffer, the accumulation from the bound records, the reduction
+// into the set's batch rows, their read-back to h_rows, and the clearing of the zeroed block (finish_sequence)
+int enqueue_ragged(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const void* d_scalars, const te::ragged_tab& tab, const plan_t& p,
+                   uint8_t* h_rows) {
+  if ((uint64_t)p.nw * p.nst >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch sequence too large: windows x points must stay below 2^31");
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  const uint64_t n_max = [&] { uint64_t m = 0; for (int j = 0; j < p.batch; j++) m = std::max<uint64_t>(m, tab.len[j]); return m; }();
+  if ((uint64_t)p.nw * p.B + (uint64_t)p.nw * (n_max / p.seg_len) + 1024u >= (1ull << 32))
+    return set_err(ctx, TE_MSM_EINVAL, "segment_len is too small for this batch: more than 2^32 segments");
+  if (int rc = ensure_buffers(ctx, d, ws, n_max, p, false)) return rc;
+  const size_t row_bytes = (size_t)p.batch * p.W * sizes_of(p.curve).row;
+  if (int rc = ensure(ctx, ws, ws.d_batch_rows, ws.cap[28], row_bytes)) return rc;
+  release_shared_recs(d, ws, false);
+  hipStream_t stream = ws.stream;
+  if (ws.used && ws.last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ws.ev_done, 0));
+  ws.plan = p; ws.n = n_max; ws.used = true; ws.last_stream = stream; __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
+  ws.prof_level = 0; ws.rows_on_host = false; ws.recs_last = nullptr;
+  msm_launch L{ctx, d, ws, p, nullptr, d_scalars, n_max, ws.d_batch_rows, 0, stream, false};
+  L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];      // (a fixed-base set: table 0, the ordinary records)
+  L.ragged = &tab;
+  if (int rc = L.front_scalars()) return rc;
+  if (int rc = L.accumulate()) return rc;
+  if (int rc = L.back()) return rc;                             // ... ends with the flag words' read-back into ws.h_err
+  HIP_TRY(ctx, hipMemcpyAsync(h_rows, ws.d_batch_rows, row_bytes, hipMemcpyDeviceToHost, stream));
+  if (int rc = finish_sequence(ctx, ws, stream)) return rc;
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+// The sequences of one device, dealt over its free work sets in plan order (up to TE_MSM_WORKSETS in flight: a set is reused once its
+// previous sequence is over).  d_sc: the packed scalars on this device, off[m]: where MSM m's start (records).
+int run_batch_on_device(te_ctx* ctx, size_t di, const te_bases* bases, const void* d_sc, const std::vector<uint64_t>& off, const uint64_t* lens,
+                        std::vector<batch_seq_run>& runs, bool* carry, int64_t* entries) {
+  gpu_t& d = ctx->devs[di];
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  std::vector<int> sets;
+  for (int wi = 0; wi < TE_MSM_WORKSETS; wi++) if (!te_sched::slot_ticket(d.ws[wi].slot)) sets.push_back(wi);
+  if (sets.empty()) return set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned);
+  size_t total = 0;
+  for (batch_seq_run& r : runs) { r.rows_at = total; total += (size_t)r.p.batch * r.p.W * sizes_of(r.p.curve).row; }
+  if (total > d.h_batch_cap) {
+    if (d.h_batch_rows) HIP_TRY(ctx, hipHostFree(d.h_batch_rows));
+    d.h_batch_rows = nullptr; d.h_batch_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void**)&d.h_batch_rows, total ? total : 16, hipHostMallocDefault));
+    d.h_batch_cap = total;
+  }
+  std::vector<int> busy(sets.size(), 0);
+  auto settle = [&](size_t slot) -> int {
+    workset_t& ws = d.ws[sets[slot]];
+    HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
+    *carry = *carry || *ws.h_err != 0;
+    *entries += entries_of(ws);
+    busy[slot] = 0;
+    return 0;
+  };
+  int rc = 0;
+  for (size_t k = 0; k < runs.size() && !rc; k++) {
+    const size_t slot = k % sets.size();
+    if (busy[slot] && (rc = settle(slot))) break;
+    te::ragged_tab tab; memset(&tab, 0, sizeof tab);
+    const std::vector<uint32_t>& ms = runs[k].s->msms;
+    for (size_t j = 0; j < ms.size(); j++) { tab.off[j] = off[ms[j]]; tab.len[j] = (uint32_t)lens[ms[j]]; }
+    rc = enqueue_ragged(ctx, d, d.ws[sets[slot]], bases, d_sc, tab, runs[k].p, d.h_batch_rows + runs[k].rows_at);
+    busy[slot] = 1;
+  }
+  for (size_t slot = 0; slot < sets.size(); slot++) {
+    if (!busy[slot]) continue;
+    if (rc) { (void)hipStreamSynchronize(d.ws[sets[slot]].stream); continue; }
+    rc = settle(slot);
+  }
+  return rc;
+}
+
+int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const void* src, bool src_is_host, uint8_t* out) {
+  if (!ctx) return TE_MSM_EINVAL;
+  drain_workers(ctx);
+  if (!valid_bases(ctx, bases)) return set_err(ctx, TE_MSM_EINVAL, kBadBases);
+  if (bases->curve != ctx->opt_curve) return set_err(ctx, TE_MSM_EINVAL, kBasesCurve);
+  // (the window shards of a multi-device context are the engine's own, for its lone calls: a batch runs whole MSMs on every device)
+  if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_EINVAL, "batched MSMs compute whole MSMs: reset the window shard first");
+  if (count < 0) return set_err(ctx, TE_MSM_EINVAL, "count must be >= 0");
+  if (count == 0) return 0;
+  if (!lens || !out) return set_err(ctx, TE_MSM_EINVAL, "null lens or out");
+  uint64_t total = 0;
+  std::vector<uint64_t> off((size_t)count);
+  for (int m = 0; m < count; m++) {
+    if (lens[m] > bases->n) return set_err(ctx, TE_MSM_EINVAL, "an MSM of the batch is longer than the bound point set");
+    off[(size_t)m] = total; total += lens[m];
+  }
+  if (total && !src) return set_err(ctx, TE_MSM_EINVAL, "null scalar buffer");
+  const curve_sizes sz = sizes_of(ctx->opt_curve);
+  size_t holder = 0;
+  if (!src_is_host && total) {
+    const int owner = device_index_of_pointer(ctx, src);
+    if (owner < 0 && ctx->devs.size() > 1) return set_err(ctx, TE_MSM_EINVAL, "te_msm_run_scalars_batch_device: the scalars must be resident on a device of the context");
+    holder = owner < 0 ? 0 : (size_t)owner;
+  }
+  const size_t nd = src_is_host ? ctx->devs.size() : 1;
+  te_batch::limits lim;
+  lim.small_max = (uint64_t)ctx->opt_batch_small_max;
+  const te_batch::plan P = te_batch::make_plan(lens, (uint32_t)count, (int)nd, lim, [ctx](uint64_t n) { te_batch::msm_cost c; batch_cost(ctx, n, c); return c; });
+  ctx->stat_batch_sequences = (int64_t)P.seqs.size();
+  // per device: its sequences with their launch plans
+  std::vector<std::vector<batch_seq_run>> runs(nd);
+  for (const te_batch::sequence& s : P.seqs) {
+    batch_seq_run r; r.s = &s;
+    const size_t di = src_is_host ? (size_t)s.device : holder;
+    make_plan(ctx, ctx->devs[di], s.n_max, r.p, 0, (int)s.msms.size(), 0, true);
+    r.p.rec_kind = bases->rec_kind;
+    runs[(size_t)s.device].push_back(r);
+  }
+  // the scalars on each device that runs sequences: device form -- in place; host form -- one device: the caller's packed buffer,
+  // uploaded whole; several: each device's MSMs packed (input order) into a buffer of its own
+  std::vector<dev_tmp> tmp(nd);
+  std::vector<std::vector<uint64_t>> offs(nd);
+  std::vector<const void*> dsc(nd, src);
+  for (size_t i = 0; i < nd; i++) {
+    if (runs[i].empty()) continue;
+    if (!src_is_host) { offs[i] = off; continue; }
+    gpu_t& d = ctx->devs[i];
+    if (nd == 1) {
+      offs[i] = off;
+      if (int rc = tmp_alloc(ctx, d, tmp[i], total * sz.scalar_in)) return rc;
+      HIP_TRY(ctx, hipMemcpy(tmp[i].p, src, total * sz.scalar_in, hipMemcpyHostToDevice));
+    } else {
+      offs[i].assign((size_t)count, 0);
+      std::vector<uint32_t> mine;
+      for (const batch_seq_run& r : runs[i]) mine.insert(mine.end(), r.s->msms.begin(), r.s->msms.end());
+      std::sort(mine.begin(), mine.end());
+      uint64_t here = 0;
+      for (uint32_t m : mine) { offs[i][m] = here; here += lens[m]; }
+      std::vector<uint8_t> pack((size_t)(here * sz.scalar_in));
+      for (uint32_t m : mine) memcpy(&pack[(size_t)(offs[i][m] * sz.scalar_in)], static_cast<const uint8_t*>(src) + off[m] * sz.scalar_in, (size_t)(lens[m] * sz.scalar_in));
+      if (int rc = tmp_alloc(ctx, d, tmp[i], pack.size())) return rc;
+      HIP_TRY(ctx, hipMemcpy(tmp[i].p, pack.data(), pack.size(), hipMemcpyHostToDevice));
+    }
+    dsc[i] = tmp[i].p;
+  }
+  std::vector<char> carry(nd, 0);
+  std::vector<int64_t> entries(nd, 0);
+  auto on = [&](size_t i) -> int {
+    if (runs[i].empty()) return 0;
+    bool c = false;
+    const int r = run_batch_on_device(ctx, src_is_host ? i : holder, bases, dsc[i], offs[i], lens, runs[i], &c, &entries[i]);
+    carry[i] = c;
+    return r;
+  };
+  int rc = 0;
+  if (nd == 1) rc = on(0);
+  else {
+    std::vector<te_sched::job_ref> jobs(nd);
+    for (size_t i = 1; i < nd; i++) jobs[i] = worker_of(ctx, i).post([&on, i] { return on(i); });
+    rc = on(0);
+    for (size_t i = 1; i < nd; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
+  }
+  if (rc) return rc;
+  int64_t ent = 0; bool any_carry = false;
+  for (size_t i = 0; i < nd; i++) { ent += entries[i]; any_carry = any_carry || carry[i]; }
+  ctx->stat_entries = ent;
+  if (any_carry) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  // host tails: one fold per MSM with its sequence's plan, on up to 8 threads
+  struct fold_job { const plan_t* p; const uint8_t* rows; uint32_t m; };
+  std::vector<fold_job> jobs;
+  for (size_t i = 0; i < nd; i++) {
+    const gpu_t& d = ctx->devs[src_is_host ? i : holder];
+    for (const batch_seq_run& r : runs[i]) {
+      const size_t rb = (size_t)r.p.W * sizes_of(r.p.curve).row;
+      for (size_t j = 0; j < r.s->msms.size(); j++) jobs.push_back({&r.p, d.h_batch_rows + r.rows_at + j * rb, r.s->msms[j]});
+    }
+  }
+  std::vector<uint8_t> res((size_t)count * sz.result, 0);
+  const size_t nthreads = std::min<size_t>(8, (jobs.size() + 7) / 8);
+  auto fold_part = [&](size_t t) { for (size_t j = t; j < jobs.size(); j += nthreads) fold_rows(*jobs[j].p, jobs[j].rows, &res[(size_t)jobs[j].m * sz.result]); };
+  if (nthreads <= 1) { if (!jobs.empty()) fold_part(0); }
+  else {
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < nthreads; t++) th.emplace_back(fold_part, t);
+    fold_part(0);
+    for (std::thread& t : th) t.join();
+  }
+  for (uint32_t m : P.empty) if (ctx->opt_curve == TE_MSM_CURVE_TE_BLS12) res[(size_t)m * sz.result + 32] = 1;     // the identity: (0, 1) / zeros
+  memcpy(out, res.data(), res.size());
+  return 0;
+}
+}  // namespace
+
+int te_msm_run_scalars_batch(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const uint8_t* scalars_le, uint8_t* out) {
+  device_guard restore_callers_device;
+  return run_batch_common(ctx, bases, count, lens, scalars_le, true, out);
+}
+
+int te_msm_run_scalars_batch_device(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const void* d_scalars_le, uint8_t* out) {
+  device_guard restore_callers_device;
+  return run_batch_common(ctx, bases, count, lens, d_scalars_le, false, out);
 }
 
 int te_msm_set_window_shard(te_ctx* ctx, int first, int step) {

@@ -280,6 +280,46 @@ napi_value MulCommon(napi_env env, napi_callback_info info, bool x_only) {
   napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
   return buf;
 }
+// msmBatch(scalarBuffers: Buffer[]): Buffer -- batched MSMs over prefixes of the set bound by setBases (include/te_msm.h,
+// te_msm_run_scalars_batch): MSM m runs over the first scalarBuffers[m].length / 32 points of that set.  Returns count x 64 bytes, the
+// results in input order (the identity as (0, 1)); compute_msm.js turns them into {x, y}.  Run like pointsFromX; without setBases, with a
+// buffer longer than the set, or with a scalar out of range it throws.
+napi_value MsmBatch(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool is_arr = false;
+  if (argc >= 1) napi_is_array(env, argv[0], &is_arr);
+  if (!is_arr) { napi_throw_type_error(env, nullptr, "msmBatch(scalarBuffers: Buffer[])"); return nullptr; }
+  uint32_t count = 0;
+  napi_get_array_length(env, argv[0], &count);
+  std::vector<uint64_t> lens(count);
+  std::vector<uint8_t> packed;
+  for (uint32_t m = 0; m < count; m++) {
+    napi_value e; bool is_buf = false;
+    napi_get_element(env, argv[0], m, &e);
+    napi_is_buffer(env, e, &is_buf);
+    if (!is_buf) { napi_throw_type_error(env, nullptr, "msmBatch(scalarBuffers: Buffer[])"); return nullptr; }
+    void* p = nullptr; size_t pl = 0;
+    napi_get_buffer_info(env, e, &p, &pl);
+    if (pl % TE_MSM_SCALAR_BYTES != 0) { napi_throw_range_error(env, nullptr, "msmBatch: every scalar buffer must be 32*n bytes"); return nullptr; }
+    lens[m] = pl / TE_MSM_SCALAR_BYTES;
+    packed.insert(packed.end(), static_cast<const uint8_t*>(p), static_cast<const uint8_t*>(p) + pl);
+  }
+  std::vector<uint8_t> out((size_t)count * TE_MSM_POINT_BYTES);
+  std::string err;
+  const int rc = g_proto.with_bases([&](te_ctx* c, te_bases* b) {
+    return te_msm_run_scalars_batch(c, b, (int)count, lens.data(), packed.data(), out.data());
+  }, TE_MSM_ESTATE, err);
+  if (rc) {
+    const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_throw_error(env, nullptr, m.c_str());
+    return nullptr;
+  }
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
+  return buf;
+}
+
 napi_value ScalarMul(napi_env env, napi_callback_info info) { return MulCommon(env, info, false); }
 napi_value ScalarMulX(napi_env env, napi_callback_info info) { return MulCommon(env, info, true); }
 
@@ -324,7 +364,7 @@ napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
       {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints},
-      {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}};
+      {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -67,4 +67,14 @@ const pointsFromX = (xs) => native.pointsFromX(xs);
 const scalarMul = (points, scalars) => native.scalarMul(points, scalars);
 const scalarMulX = (xs, scalars) => native.scalarMulX(xs, scalars);
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX, scalarMul, scalarMulX };
+// Outside the reference's interface too: msmBatch(scalarBuffers) runs one MSM per Buffer over the set bound by setBases -- MSM m over
+// its first scalarBuffers[m].length / 32 points (a prover's commitments to polynomials of different degrees against one SRS) -- and
+// returns their results as [{x, y}, ...] in compute_msm's form, in input order.  Small MSMs share launch sequences on the GPU.
+const msmBatch = (scalarBuffers) => {
+  const out = native.msmBatch(scalarBuffers);
+  const res = [];
+  for (let m = 0; m < scalarBuffers.length; m++) res.push({ x: fromLE32(out, 64 * m), y: fromLE32(out, 64 * m + 32) });
+  return res;
+};
+
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX, scalarMul, scalarMulX, msmBatch };

@@ -157,6 +157,18 @@ template <class Api> class protocol {
     if (rc) err = Api::last_error(ctx_);
     return rc;
   }
+  // Runs f(ctx, bases) on the context and its bound point set (bound again on a new context) like with_context; no set bound: returns
+  // `none` with err = "no point set bound (setBases)".
+  template <class F> int with_bases(F&& f, int none, std::string& err) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [this] { return pending() == 0; });
+    int rc = ensure_context(err);
+    if (rc) return rc;
+    if (!bases_) { err = "no point set bound (setBases)"; return none; }
+    rc = f(ctx_, bases_);
+    if (rc) err = Api::last_error(ctx_);
+    return rc;
+  }
 
  private:
   static bool lone_in_enter() { static const bool on = [] { const char* e = getenv("TE_MSM_LONE_IN_ENTER"); return !(e && e[0] == '0'); }(); return on; }
