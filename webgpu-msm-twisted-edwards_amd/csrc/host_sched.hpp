@@ -14,6 +14,7 @@
 #include <mutex>
 #include <thread>
 #include <utility>
+#include <vector>
 
 namespace te_sched {
 
@@ -163,6 +164,16 @@ template <class Ctx> worker_t& worker_of(Ctx& ctx, size_t i) {
   if (ctx.workers.size() < ctx.devs.size()) ctx.workers.resize(ctx.devs.size());
   if (!ctx.workers[i]) ctx.workers[i].reset(new worker_t());
   return *ctx.workers[i];
+}
+// f(i) for the first D devices: f(0) on the calling thread (device 0's pageable uploads and HIP thread state stay there), f(i) on
+// device i's host thread.  Waits for every job, also after a failure; f(0)'s status if non-zero, else the first non-zero one in
+// device order.
+template <class Ctx, class F> int on_devices(Ctx& ctx, size_t D, F&& f) {
+  std::vector<job_ref> jobs(D);
+  for (size_t i = 1; i < D; i++) jobs[i] = worker_of(ctx, i).post([&f, i] { return f(i); });
+  int rc = f(0);
+  for (size_t i = 1; i < D; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
+  return rc;
 }
 // Upload lanes: the host threads that take ASYNCHRONOUS tickets (upload + enqueue of one whole MSM each), `lanes` per device.
 // One pageable upload keeps its thread inside the runtime while the data is staged; a second thread preparing the next

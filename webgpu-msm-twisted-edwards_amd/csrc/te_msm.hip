@@ -1635,9 +1635,12 @@ void fold_rows(const plan_t& p, const uint8_t* rows, uint8_t* out) {
   else if (p.curve == TE_MSM_CURVE_BLS12_377_G1) te377_host::horner_to_affine(rows, p.c, (int)p.logB, p.W, out);
   else te_host::horner_to_affine(rows, p.c, (int)p.logB, p.W, out);
 }
+// the result of an empty MSM: the identity, (0, 1) on the Twisted-Edwards curve, infinity (all zero) on BLS12-377
+void write_identity(int curve, uint8_t* out) {
+  memset(out, 0, sizes_of(curve).result);
+  if (curve == TE_MSM_CURVE_TE_BLS12) out[32] = 1;
+}
 
-// the host thread of device i of the context (host_sched.hpp), created on first use
-te_sched::worker_t& worker_of(te_ctx* ctx, size_t i) { return te_sched::worker_of(*ctx, i); }
 // every job posted to the context's host threads has run (asynchronous submits touch work sets, options and the error
 // string: calls that change or read those beside them wait first)
 void drain_workers(te_ctx* ctx) { te_sched::drain_workers(*ctx); }
@@ -1645,6 +1648,19 @@ void drain_workers(te_ctx* ctx) { te_sched::drain_workers(*ctx); }
 // the lowest-numbered work set of a device that no ticket owns (-1: none)
 int free_workset_index(const gpu_t& d) { return te_sched::free_set_index(d, TE_MSM_WORKSETS); }
 const char* const kAllSetsOwned = "every work set holds a submitted MSM that has not been collected: te_msm_collect one first";
+// a work set no ticket owns on each of the first D devices, for a lone call over several devices (tickets and lone calls may be mixed)
+int free_sets(te_ctx* ctx, size_t D, std::vector<int>& wsel) {
+  wsel.assign(D, 0);
+  for (size_t i = 0; i < D; i++) { wsel[i] = free_workset_index(ctx->devs[i]); if (wsel[i] < 0) return set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned); }
+  return 0;
+}
+// the work set a lone call on one device runs on: the selected one, unless a submitted MSM still owns it -- then any free one; with
+// every set owned by a ticket the call is refused
+int lone_set(te_ctx* ctx, const gpu_t& d, int selected) {
+  if (!te_sched::slot_ticket(d.ws[selected].slot)) return selected;
+  const int wi = free_workset_index(d);
+  return wi < 0 ? set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned) : wi;
+}
 
 // the non-zero window digits the device counted for the MSM whose flag words are in the set's pinned block (word 1)
 int64_t entries_of(const workset_t& ws) { uint64_t v; memcpy(&v, ws.h_err + Z_ENTRIES, sizeof v); return (int64_t)v; }
@@ -1659,8 +1675,7 @@ int run_host_chunked(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
   note_entries(ctx, ws);
   if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
-  if (pf.curve == TE_MSM_CURVE_BLS12_377_G1) te377_host::horner_to_affine(ws.h_partials, pf.c, (int)pf.logB, pf.W, out);
-  else te_host::horner_to_affine(ws.h_partials, pf.c, (int)pf.logB, pf.W, out);
+  fold_rows(pf, ws.h_partials, out);
   return 0;
 }
 
@@ -1684,9 +1699,8 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
   plan_t p0; make_plan(ctx, ctx->devs[0], per, p0, 0, 1, 0, true);     // geometry of every slice's rows (window bits from the slice size)
   const curve_sizes sz = sizes_of(p0.curve);
   const int K = bases ? scalar_pieces(ctx, per) : host_pieces(ctx, per);
-  // a work set per device that no ticket owns (tickets and lone calls may be mixed)
-  std::vector<int> wsel(D, 0);
-  for (size_t i = 0; i < D; i++) { wsel[i] = free_workset_index(ctx->devs[i]); if (wsel[i] < 0) return set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned); }
+  std::vector<int> wsel;
+  if (int rc = free_sets(ctx, D, wsel)) return rc;
   auto slice = [&](size_t i) -> int {
     const uint64_t lo = std::min<uint64_t>(n, per * i), hi = std::min<uint64_t>(n, lo + per);
     gpu_t& d = ctx->devs[i];
@@ -1700,11 +1714,7 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
     HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
     return 0;
   };
-  std::vector<te_sched::job_ref> jobs(D);
-  for (size_t i = 1; i < D; i++) jobs[i] = worker_of(ctx, i).post([&slice, i] { return slice(i); });
-  int rc = slice(0);
-  for (size_t i = 1; i < D; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
-  if (rc) return rc;
+  if (int rc = te_sched::on_devices(*ctx, D, slice)) return rc;
   std::vector<const uint8_t*> sets;
   int64_t entries = 0;
   for (size_t i = 0; i < D; i++) {
@@ -1735,11 +1745,34 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
     }
     return 0;
   };
-  for (size_t i = 1; i < D; i++) jobs[i] = worker_of(ctx, i).post([&merge, i] { return merge(i); });
-  (void)merge(0);
-  for (size_t i = 1; i < D; i++) (void)worker_of(ctx, i).wait(jobs[i]);
+  (void)te_sched::on_devices(*ctx, D, merge);
   if (bls) te377_host::horner_to_affine_points(m14.data(), present.data(), p0.c, (int)p0.logB, p0.W, out);
   else te_host::horner_to_affine_points(m9.data(), present.data(), p0.c, (int)p0.logB, p0.W, out);
+  return 0;
+}
+
+// The end of a lone call over window shards (wsel: each device's work set; rc: the status of their enqueues): every device's MSM
+// complete, each device's windows merged into one set of rows, the entries summed and the final carry checked, then one fold.
+// stage_ms: the first device's stage times are collected (option "profile").
+int settle_window_shards(te_ctx* ctx, const std::vector<int>& wsel, const plan_t& p0, int rc, bool stage_ms, uint8_t* out) {
+  const size_t row = sizes_of(p0.curve).row;
+  std::vector<uint8_t> merged((size_t)p0.W * row, 0);
+  int64_t entries = 0; bool carry = false;
+  for (size_t i = 0; i < wsel.size(); i++) {
+    gpu_t& d = ctx->devs[i];
+    workset_t& ws = d.ws[wsel[i]];
+    if (rc) { (void)hipSetDevice(d.device); (void)hipStreamSynchronize(ws.stream); continue; }      // leave nothing of a failed call in flight
+    HIP_TRY(ctx, hipSetDevice(d.device));
+    HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
+    carry = carry || *ws.h_err != 0;
+    entries += entries_of(ws);
+    for (int w = d.w_first; w < p0.W; w += d.w_step) memcpy(&merged[(size_t)w * row], ws.h_partials + (size_t)w * row, row);
+  }
+  if (rc) return rc;
+  ctx->stat_entries = entries;
+  if (carry) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  if (stage_ms) (void)collect_stage_ms(ctx, ctx->devs[0], ctx->devs[0].ws[wsel[0]]);
+  fold_rows(p0, merged.data(), out);
   return 0;
 }
 
@@ -1758,8 +1791,8 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
   const size_t nd = ctx->devs.size();
   plan_t p0; make_plan(ctx, ctx->devs[0], n, p0);
   const curve_sizes sz = sizes_of(p0.curve);
-  std::vector<int> wsel(nd, 0);
-  for (size_t i = 0; i < nd; i++) { wsel[i] = free_workset_index(ctx->devs[i]); if (wsel[i] < 0) return set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned); }
+  std::vector<int> wsel;
+  if (int rc = free_sets(ctx, nd, wsel)) return rc;
   const int src_dev = ctx->devs[0].device;
   const uint64_t per = (n + nd - 1) / nd;
   auto lo_of = [&](size_t j) { return std::min<uint64_t>(n, per * j); };
@@ -1802,33 +1835,11 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
     if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
-  std::vector<te_sched::job_ref> jobs(nd);
-  for (size_t i = 1; i < nd; i++) jobs[i] = worker_of(ctx, i).post([&share, i] { return share(i); });
-  int rc = share(0);
-  for (size_t i = 1; i < nd; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
+  const int rc = te_sched::on_devices(*ctx, nd, share);
   // a device whose staging area other devices read must not reuse it before they are done: every set's next MSM waits for
-  // its own ev_done only, so the call ends with all of them complete (below) -- the copies are over by then
+  // its own ev_done only, so the call ends with all of them complete (settle_window_shards) -- the copies are over by then
   for (size_t i = 0; i < nd; i++) { ctx->stat_peer_copies += copies[i]; ctx->stat_peer_bytes += bytes[i]; }
-  std::vector<uint8_t> merged((size_t)p0.W * sz.row, 0);
-  int64_t entries = 0; bool carry = false;
-  for (size_t i = 0; i < nd; i++) {
-    gpu_t& d = ctx->devs[i];
-    workset_t& ws = d.ws[wsel[i]];
-    if (rc) { (void)hipSetDevice(d.device); (void)hipStreamSynchronize(ws.stream); continue; }      // leave nothing of a failed call in flight
-    HIP_TRY(ctx, hipSetDevice(d.device));
-    HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
-    carry = carry || *ws.h_err != 0;
-    entries += entries_of(ws);
-    for (int w = d.w_first; w < p0.W; w += d.w_step)
-      memcpy(&merged[(size_t)w * sz.row], ws.h_partials + (size_t)w * sz.row, sz.row);
-  }
-  if (rc) return rc;
-  ctx->stat_entries = entries;
-  if (carry) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
-  (void)collect_stage_ms(ctx, ctx->devs[0], ctx->devs[0].ws[wsel[0]]);
-  if (p0.curve == TE_MSM_CURVE_BLS12_377_G1) te377_host::horner_to_affine(merged.data(), p0.c, (int)p0.logB, p0.W, out);
-  else te_host::horner_to_affine(merged.data(), p0.c, (int)p0.logB, p0.W, out);
-  return 0;
+  return settle_window_shards(ctx, wsel, p0, rc, true, out);
 }
 
 // ---- input-point validation (option "check_points", te_msm_check_points*; kernels in check.hip.hpp) ----------------------------
@@ -1839,15 +1850,38 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
 // so the first piece that reports holds the lowest index of the whole buffer.
 constexpr uint64_t kCheckPiece = 1ull << 18;
 
+// The check lane of a device (its stream, report word and pinned host word: check_points_on, recover_on, mul_on), held while this
+// lives: chk_mu locked, the device made current, the three created on first use.  rc: 0, or the HIP error (noted) that left it unusable.
+struct check_lane {
+  gpu_t& d;
+  std::lock_guard<std::mutex> lk;
+  const int rc;
+  check_lane(te_ctx* ctx, gpu_t& dev) : d(dev), lk(*dev.chk_mu), rc(open(ctx, dev)) {}
+  hipStream_t stream() const { return d.chk_stream; }
+  // the report word on the host: 0, or TE_MSM_EPOINT and the lowest failing index among the m points it covers (check_decode)
+  int verdict(te_ctx* ctx, uint64_t m, int64_t* bad, int* reason) {
+    HIP_TRY(ctx, hipMemcpyAsync(d.chk_host, d.chk_word, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.chk_stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d.chk_stream));
+    if (!*d.chk_host) return 0;
+    te::check_decode(*d.chk_host, m, bad, reason);
+    return TE_MSM_EPOINT;
+  }
+ private:
+  static int open(te_ctx* ctx, gpu_t& d) {
+    HIP_TRY(ctx, hipSetDevice(d.device));
+    if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
+    if (!d.chk_word) HIP_TRY(ctx, hipMalloc(&d.chk_word, sizeof(unsigned long long)));
+    if (!d.chk_host) HIP_TRY(ctx, hipHostMalloc(&d.chk_host, sizeof(unsigned long long), hipHostMallocDefault));
+    return 0;
+  }
+};
+
 int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason) {
   *bad = -1; *reason = 0;
   if (n == 0) return 0;
   gpu_t& d = ctx->devs[di];
-  std::lock_guard<std::mutex> lk(*d.chk_mu);
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
-  if (!d.chk_word) HIP_TRY(ctx, hipMalloc(&d.chk_word, sizeof(unsigned long long)));
-  if (!d.chk_host) HIP_TRY(ctx, hipHostMalloc(&d.chk_host, sizeof(unsigned long long), hipHostMallocDefault));
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
   const size_t pb = sizes_of(curve).point_in;
   const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
   if (src_is_host && d.chk_cap < piece * pb) {
@@ -1855,7 +1889,7 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
     HIP_TRY(ctx, hipMalloc(&d.chk_pts, piece * pb));
     d.chk_cap = piece * pb;
   }
-  hipStream_t st = d.chk_stream;
+  hipStream_t st = lane.stream();
   for (uint64_t off = 0; off < n; off += piece) {
     const uint32_t m = (uint32_t)std::min(piece, n - off);
     const uint8_t* at = static_cast<const uint8_t*>(src) + off * pb;
@@ -1871,23 +1905,29 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
       if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<0>, grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(d.chk_host, d.chk_word, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (*d.chk_host) {
-      int64_t i = -1;
-      te::check_decode(*d.chk_host, m, &i, reason);
-      *bad = (int64_t)off + i;
-      return TE_MSM_EPOINT;
-    }
+    int64_t i = -1;
+    const int rc = lane.verdict(ctx, m, &i, reason);
+    if (rc == TE_MSM_EPOINT) *bad = (int64_t)off + i;
+    if (rc) return rc;
   }
   return 0;
 }
-// the verdict as the outcome of a call: the failure is remembered for get_option and described in the error text
-int note_bad_point(te_ctx* ctx, int64_t index, int reason) {
+// A failed check (kBadPoint) or recovery (kBadX, x-only points) as the outcome of a call: the failure is remembered for get_option
+// ("bad_point_index" / "bad_point_reason"), described in the error text and written to the caller's outputs where given.
+enum bad_kind { kBadPoint, kBadX };
+int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* first_bad = nullptr, int* reason_out = nullptr) {
   ctx->bad_point_index = index; ctx->bad_point_reason = reason;
+  if (first_bad) *first_bad = index;
+  if (reason_out) *reason_out = reason;
   char buf[256];
-  snprintf(buf, sizeof buf, "input point %lld failed the check of option \"check_points\": %s", (long long)index,
-           reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical coordinate" : reason == TE_MSM_POINT_OFF_CURVE ? "not on the curve (or map undefined)" : "not in the prime-order subgroup");
+  if (kind == kBadPoint)
+    snprintf(buf, sizeof buf, "input point %lld failed the check of option \"check_points\": %s", (long long)index,
+             reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical coordinate" : reason == TE_MSM_POINT_OFF_CURVE ? "not on the curve (or map undefined)" : "not in the prime-order subgroup");
+  else
+    snprintf(buf, sizeof buf, "x-coordinate %lld has no point (reason %d): %s", (long long)index, reason,
+             reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical (x >= modulus, or reserved flag bits set)"
+             : reason == TE_MSM_POINT_OFF_CURVE ? "no point on the curve has this x (or the point at infinity / map undefined)"
+                                                : "no point of the prime-order subgroup has this x");
   return set_err(ctx, TE_MSM_EPOINT, buf);
 }
 // option "check_points" in front of a call: 0 = go on, TE_MSM_EPOINT (noted) or a device error
@@ -1895,18 +1935,16 @@ int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64
   if (!ctx->opt_check_points) return 0;
   int64_t bad = -1; int reason = 0;
   const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points, &bad, &reason);
-  if (rc == TE_MSM_EPOINT) return note_bad_point(ctx, bad, reason);
+  if (rc == TE_MSM_EPOINT) return note_bad(ctx, kBadPoint, bad, reason);
   return rc;
 }
 
+int check_n(te_ctx* ctx, uint64_t n) { return n >= (1ull << 31) ? set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31") : 0; }
+
 int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, bool src_is_host, uint64_t n, uint8_t out[64]) {
   if (!ctx || !out) return TE_MSM_EINVAL;
-  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
-  if (n == 0) {                                                     // empty sum = identity: (0, 1), or infinity (all zero)
-    memset(out, 0, sizes_of(ctx->opt_curve).result);
-    if (ctx->opt_curve == TE_MSM_CURVE_TE_BLS12) out[32] = 1;
-    return 0;
-  }
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n == 0) { write_identity(ctx->opt_curve, out); return 0; }
   if (!src_points || !src_scalars) return set_err(ctx, TE_MSM_EINVAL, "null input buffer");
   // (device-resident inputs live on the first device: a multi-device call checks them there, before the scatter)
   if (int rc = check_call(ctx, 0, src_points, src_is_host, n)) return rc;
@@ -1922,13 +1960,8 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
     const int K = host_pieces(ctx, n);
     if (K > 1) return run_host_chunked(ctx, static_cast<const uint8_t*>(src_points), static_cast<const uint8_t*>(src_scalars), n, K, out);
   }
-  // the work set this call runs on: the selected one, unless a submitted MSM still owns it -- then any free one; with every
-  // set owned by a ticket the call is refused
-  int wsel = ctx->opt_workset;
-  if (te_sched::slot_ticket(d.ws[wsel].slot)) {
-    wsel = free_workset_index(d);
-    if (wsel < 0) return set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned);
-  }
+  const int wsel = lone_set(ctx, d, ctx->opt_workset);
+  if (wsel < 0) return wsel;
   plan_t p0; make_plan(ctx, d, n, p0);
   const curve_sizes sz = sizes_of(p0.curve);
   workset_t& ws = d.ws[wsel];
@@ -1953,8 +1986,7 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
   if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
   (void)collect_stage_ms(ctx, d, ws);
   // a window-sharded single-device context (te_msm_set_window_shard) folds its own rows only: the others read as zero
-  if (p0.curve == TE_MSM_CURVE_BLS12_377_G1) te377_host::horner_to_affine(ws.h_partials, p0.c, (int)p0.logB, p0.W, out);
-  else te_host::horner_to_affine(ws.h_partials, p0.c, (int)p0.logB, p0.W, out);
+  fold_rows(p0, ws.h_partials, out);
   return 0;
 }
 
@@ -2073,23 +2105,43 @@ namespace {
 //                           multi-device is the reference README's future work, README.md:551).  te_msm_run* stay the forms
 //                           for the lone call (point slices / window shards over all devices).
 
-// the lowest-numbered free work set of the device (each has its own stream: the MSMs overlap on the device).  Not ticket % sets:
-// with fewer MSMs in flight than sets only as many sets as needed are ever touched -- no buffer allocation in the middle
-// of a run, and a smaller footprint in the Infinity Cache.
+// the device the next ticket goes to (index into ctx->devs); prefer: the device that holds the inputs, or -1
+// (the bookkeeping itself is host_sched.hpp's: the same code runs under ThreadSanitizer in tests/csrc/sched_harness.cpp)
+int pick_device(te_ctx* ctx, int prefer) { return te_sched::pick_device_of(*ctx, TE_MSM_WORKSETS, prefer); }
+const char* const kAllInFlight = "every work set has an MSM in flight: collect one first";
+// The work set of a new ticket: on the device pick_device chooses (*di; made current), the lowest-numbered free work set (each has its
+// own stream: the MSMs overlap on the device).  Not ticket % sets: with fewer MSMs in flight than sets only as many sets as needed are
+// ever touched -- no buffer allocation in the middle of a run, and a smaller footprint in the Infinity Cache.
 // probe: the lazy hardware-queue measurement (16 ms, once per device) -- device-resident tickets only: a host-buffer ticket is bound
 // by its upload, not by how the work sets' streams share the hardware queues
-int take_free_workset(te_ctx* ctx, gpu_t& d, bool probe) {
-  if (d.in_flight >= TE_MSM_WORKSETS) return set_err(ctx, TE_MSM_ESTATE, "every work set has an MSM in flight: collect one first");
+int take_free_workset(te_ctx* ctx, int prefer, bool probe, int* di) {
+  *di = pick_device(ctx, prefer);
+  if (*di < 0) return set_err(ctx, TE_MSM_ESTATE, kAllInFlight);
+  gpu_t& d = ctx->devs[(size_t)*di];
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  if (d.in_flight >= TE_MSM_WORKSETS) return set_err(ctx, TE_MSM_ESTATE, kAllInFlight);
   if (probe && !d.queues_probed && ctx->opt_queue_probe && d.in_flight == 0) spread_streams_over_queues(d);      // once per device, with nothing of it in flight
   // the work sets' streams can still be re-dealt by a later te_msm_submit_device as long as the measurement is on and has not run
   d.streams_final = d.queues_probed || !ctx->opt_queue_probe;
   const int wi = free_workset_index(d);
-  if (wi < 0) return set_err(ctx, TE_MSM_ESTATE, "every work set has an MSM in flight: collect one first");
+  if (wi < 0) return set_err(ctx, TE_MSM_ESTATE, kAllInFlight);
   return wi;
 }
-// the device the next ticket goes to (index into ctx->devs); prefer: the device that holds the inputs, or -1
-// (the bookkeeping itself is host_sched.hpp's: the same code runs under ThreadSanitizer in tests/csrc/sched_harness.cpp)
-int pick_device(te_ctx* ctx, int prefer) { return te_sched::pick_device_of(*ctx, TE_MSM_WORKSETS, prefer); }
+// option "check_points" (level) on the points of a ticket, on device ci: 0 = go on; TE_MSM_EPOINT = the ticket's outcome, kept in the
+// set for te_msm_collect (nothing is enqueued for the ticket); else a device error
+int check_ticket(te_ctx* ctx, workset_t& ws, size_t ci, const void* src, bool src_is_host, uint64_t n, int curve, int level) {
+  if (!level) return 0;
+  ws.pt_rc = check_points_on(ctx, ci, src, src_is_host, n, curve, level, &ws.pt_index, &ws.pt_reason);
+  const int rc = ws.pt_rc;
+  if (rc != TE_MSM_EPOINT) ws.pt_rc = 0;
+  return rc;
+}
+// the status of a ticket's job on an upload lane; the error text of a failure is kept in the set for te_msm_collect (TE_MSM_EPOINT
+// is reported from the set's pt_index / pt_reason)
+int lane_status(te_ctx* ctx, workset_t& ws, int rc) {
+  if (rc && rc != TE_MSM_EPOINT) { std::lock_guard<std::mutex> lk(ctx->err_mu); ws.job_err = ctx->err; }
+  return rc;
+}
 void hand_out_ticket(te_ctx* ctx, int di, workset_t& ws, uint64_t* ticket, te_sched::job_ref job = nullptr) {
   te_sched::hand_out(*ctx, di, ws, ticket, std::move(job));          // te_msm_ticket_wait looks the ticket up from other threads
 }
@@ -2107,6 +2159,16 @@ int device_index_of_pointer(te_ctx* ctx, const void* p) {
   for (size_t i = 0; i < ctx->devs.size(); i++) if (ctx->devs[i].device == at.device) return (int)i;
   return -1;
 }
+// index into ctx->devs of the device whose memory holds every one of ptrs; else TE_MSM_EINVAL with the caller's message
+int owner_of(te_ctx* ctx, const char* msg, std::initializer_list<const void*> ptrs) {
+  int owner = -1;
+  for (const void* p : ptrs) {
+    const int o = device_index_of_pointer(ctx, p);
+    if (o < 0 || (owner >= 0 && o != owner)) return set_err(ctx, TE_MSM_EINVAL, msg);
+    owner = o;
+  }
+  return owner;
+}
 const char* const kNoTicket = "no such ticket in flight (already collected, or never handed out)";
 int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases);     // (resident bases, further down)
 }  // namespace
@@ -2117,20 +2179,17 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
   if (!d_points_xy_le || !d_scalars_le || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
   const bool multi = ctx->devs.size() > 1;
   // several devices: the inputs may live on any of them; the ticket goes to the least loaded one and pulls them over xGMI
-  const int owner = multi ? device_index_of_pointer(ctx, d_points_xy_le) : 0;
-  if (multi && (owner < 0 || device_index_of_pointer(ctx, d_scalars_le) != owner))
-    return set_err(ctx, TE_MSM_EINVAL, "te_msm_submit_device: points and scalars must be resident on one device of the context");
-  const int di = pick_device(ctx, owner);
-  if (di < 0) return set_err(ctx, TE_MSM_ESTATE, "every work set has an MSM in flight: collect one first");
-  gpu_t& d = ctx->devs[(size_t)di];
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  const int wi = take_free_workset(ctx, d, true);
+  const int owner = multi ? owner_of(ctx, "te_msm_submit_device: points and scalars must be resident on one device of the context", {d_points_xy_le, d_scalars_le}) : 0;
+  if (owner < 0) return owner;
+  int di = -1;
+  const int wi = take_free_workset(ctx, owner, true, &di);
   if (wi < 0) return wi;
+  gpu_t& d = ctx->devs[(size_t)di];
   workset_t& ws = d.ws[wi];
-  if (ctx->opt_check_points) {                        // checked where the inputs lie; a failure is the ticket's outcome (te_msm_collect)
-    ws.pt_rc = check_points_on(ctx, (size_t)owner, d_points_xy_le, false, n, ctx->opt_curve, ctx->opt_check_points, &ws.pt_index, &ws.pt_reason);
-    if (ws.pt_rc == TE_MSM_EPOINT) { hand_out_ticket(ctx, di, ws, ticket); return 0; }
-    if (const int rc = ws.pt_rc) { ws.pt_rc = 0; return rc; }
+  // checked where the inputs lie; a failure is the ticket's outcome (te_msm_collect)
+  if (const int rc = check_ticket(ctx, ws, (size_t)owner, d_points_xy_le, false, n, ctx->opt_curve, ctx->opt_check_points)) {
+    if (rc == TE_MSM_EPOINT) hand_out_ticket(ctx, di, ws, ticket);
+    return rc == TE_MSM_EPOINT ? 0 : rc;
   }
   const bool stage = multi && (d.device != ctx->devs[(size_t)owner].device || ctx->opt_stage_device_inputs);
   const int src_dev = ctx->devs[(size_t)owner].device;
@@ -2220,21 +2279,18 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (!points_xy_le || !scalars_le || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_submit computes whole MSMs: reset the window shard first");
-  const int di = pick_device(ctx, -1);
-  if (di < 0) return set_err(ctx, TE_MSM_ESTATE, "every work set has an MSM in flight: collect one first");
-  gpu_t& d = ctx->devs[(size_t)di];
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  const int wi = take_free_workset(ctx, d, false);
+  int di = -1;
+  const int wi = take_free_workset(ctx, -1, false, &di);
   if (wi < 0) return wi;
+  gpu_t& d = ctx->devs[(size_t)di];
   workset_t& ws = d.ws[wi];
   plan_t pf; make_plan(ctx, d, n, pf, 0, 1, 0, true);
   const int c = pf.c, K = host_pieces(ctx, n);
   const int level = ctx->opt_check_points, curve = ctx->opt_curve;
   if (!async) {
-    if (level) {                                      // a failure is the ticket's outcome (te_msm_collect)
-      ws.pt_rc = check_points_on(ctx, (size_t)di, points_xy_le, true, n, curve, level, &ws.pt_index, &ws.pt_reason);
-      if (ws.pt_rc == TE_MSM_EPOINT) { hand_out_ticket(ctx, di, ws, ticket); return 0; }
-      if (const int rc = ws.pt_rc) { ws.pt_rc = 0; return rc; }
+    if (const int rc = check_ticket(ctx, ws, (size_t)di, points_xy_le, true, n, curve, level)) {     // a failure is the ticket's outcome (te_msm_collect)
+      if (rc == TE_MSM_EPOINT) hand_out_ticket(ctx, di, ws, ticket);
+      return rc == TE_MSM_EPOINT ? 0 : rc;
     }
     if (int rc = enqueue_host_slice(ctx, d, ws, points_xy_le, scalars_le, n, c, K, true)) return rc;
     hand_out_ticket(ctx, di, ws, ticket);
@@ -2247,16 +2303,9 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
   workset_t* wsp = &ws; gpu_t* dp = &d;
   warm_upload_lanes(ctx);                            // (once per process and device: all of the context's devices together)
   te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, points_xy_le, scalars_le, n, c, K, di, level, curve]() -> int {
-    if (level) {                                      // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
-      wsp->pt_rc = check_points_on(ctx, (size_t)di, points_xy_le, true, n, curve, level, &wsp->pt_index, &wsp->pt_reason);
-      if (const int prc = wsp->pt_rc) {
-        if (prc != TE_MSM_EPOINT) { std::lock_guard<std::mutex> lk(ctx->err_mu); wsp->job_err = ctx->err; }
-        return prc;
-      }
-    }
-    const int rc = enqueue_host_slice(ctx, *dp, *wsp, points_xy_le, scalars_le, n, c, K, false);
-    if (rc) { std::lock_guard<std::mutex> lk(ctx->err_mu); wsp->job_err = ctx->err; }
-    return rc;
+    // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
+    if (const int rc = check_ticket(ctx, *wsp, (size_t)di, points_xy_le, true, n, curve, level)) return lane_status(ctx, *wsp, rc);
+    return lane_status(ctx, *wsp, enqueue_host_slice(ctx, *dp, *wsp, points_xy_le, scalars_le, n, c, K, false));
   });
   hand_out_ticket(ctx, di, ws, ticket, std::move(job));
   return 0;
@@ -2307,18 +2356,12 @@ int te_msm_collect(te_ctx* ctx, uint64_t ticket, uint8_t out_xy_le[64]) {
   workset_t* wsp = workset_of_ticket(ctx, ticket, &dp);
   if (!wsp) return set_err(ctx, TE_MSM_ESTATE, kNoTicket);
   workset_t& ws = *wsp; gpu_t& d = *dp;
-  if (!ws.slot.job && ws.pt_rc == TE_MSM_EPOINT) {    // its points failed the check in te_msm_submit[_device]: nothing was enqueued
-    const int64_t bad = ws.pt_index; const int reason = ws.pt_reason;
-    ws.pt_rc = 0;
-    retire_ticket(ctx, d, ws);
-    return note_bad_point(ctx, bad, reason);
-  }
-  if (const int jrc = await_job(ctx, d, ws)) {
-    if (jrc == TE_MSM_EPOINT) {                       // te_msm_submit_async: the lane's check failed, nothing was enqueued
+  if (const int jrc = !ws.slot.job && ws.pt_rc == TE_MSM_EPOINT ? TE_MSM_EPOINT : await_job(ctx, d, ws)) {
+    if (jrc == TE_MSM_EPOINT) {       // its points failed the check in te_msm_submit[_device] or on the lane of te_msm_submit_async: nothing was enqueued
       const int64_t bad = ws.pt_index; const int reason = ws.pt_reason;
       ws.pt_rc = 0;
       retire_ticket(ctx, d, ws);
-      return note_bad_point(ctx, bad, reason);
+      return note_bad(ctx, kBadPoint, bad, reason);
     }
     // the upload / enqueue failed on the device's host thread: the ticket is over, the set must not keep half an MSM
     (void)hipSetDevice(d.device);
@@ -2342,6 +2385,12 @@ namespace {
 bool valid_bases(const te_ctx* ctx, const te_bases* b) { return b && std::find(ctx->bases.begin(), ctx->bases.end(), b) != ctx->bases.end(); }
 const char* const kBadBases = "not a bound point set of this context (released, or bound to another context)";
 const char* const kBasesCurve = "the point set was bound under another curve than the one selected now (option \"curve\")";
+// a bound point set of this context, bound under the curve selected now
+int check_bases(te_ctx* ctx, const te_bases* b) {
+  if (!valid_bases(ctx, b)) return set_err(ctx, TE_MSM_EINVAL, kBadBases);
+  if (b->curve != ctx->opt_curve) return set_err(ctx, TE_MSM_EINVAL, kBasesCurve);
+  return 0;
+}
 
 void free_bases(te_ctx* ctx, te_bases* b) {
   for (size_t i = 0; i < b->recs.size() && i < ctx->devs.size(); i++)
@@ -2407,14 +2456,14 @@ int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src
 int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_bases** out) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   *out = nullptr;
-  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
+  if (int rc = check_n(ctx, n)) return rc;
   if (n > 0 && !src) return set_err(ctx, TE_MSM_EINVAL, "null point buffer");
   drain_workers(ctx);
   const size_t nd = ctx->devs.size();
   int src_dev = -1;
   if (!src_is_host && n > 0) {
-    const int owner = nd > 1 ? device_index_of_pointer(ctx, src) : 0;
-    if (owner < 0) return set_err(ctx, TE_MSM_EINVAL, "te_msm_bind_points_device: the points must be resident on a device of the context");
+    const int owner = nd > 1 ? owner_of(ctx, "te_msm_bind_points_device: the points must be resident on a device of the context", {src}) : 0;
+    if (owner < 0) return owner;
     src_dev = ctx->devs[(size_t)owner].device;
   }
   if (n > 0) {                                        // option "check_points": once, here (MSMs over the set never check again)
@@ -2432,13 +2481,7 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
     if ((uint64_t)b->fb_W * n >= (1ull << 31)) { delete b; return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base: windows x points must stay below 2^31"); }
   }
   b->recs.assign(nd, nullptr);
-  int rc = 0;
-  if (n > 0) {
-    std::vector<te_sched::job_ref> jobs(nd);
-    for (size_t i = 1; i < nd; i++) jobs[i] = worker_of(ctx, i).post([=] { return bind_on_device(ctx, b, i, src, src_is_host, src_dev); });
-    rc = bind_on_device(ctx, b, 0, src, src_is_host, src_dev);
-    for (size_t i = 1; i < nd; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
-  }
+  const int rc = n > 0 ? te_sched::on_devices(*ctx, nd, [=](size_t i) { return bind_on_device(ctx, b, i, src, src_is_host, src_dev); }) : 0;
   if (rc) { free_bases(ctx, b); delete b; return rc; }
   // a set bound from HOST memory announces tickets from host scalars: the lanes' first concurrent copies (15-30 ms once per process,
   // warm_upload_lanes) happen here, in the call that blocks anyway, not in the first te_msm_submit_scalars -- which the N-API addon
@@ -2486,6 +2529,15 @@ int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* base
   return 0;
 }
 
+// the n scalars at src (memory of device src_dev) into the set's staging area over the peer link, on the set's stream
+int pull_scalars(te_ctx* ctx, const gpu_t& d, workset_t& ws, const void* src, int src_dev, uint64_t n) {
+  const size_t bytes = n * sizes_of(ctx->opt_curve).scalar_in;
+  if (int rc = ensure_staging(ctx, ws, 0, bytes)) return rc;
+  if (ws.used && ws.ev_done) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));      // the staging area may still be read by the set's previous MSM
+  HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, src, src_dev, bytes, ws.stream));
+  return 0;
+}
+
 // te_msm_run_scalars_device on a context of D > 1 devices: WINDOW shards (device i computes windows i, i + D, ...).  Every
 // device needs all n scalars: the holder reads them in place, the others pull them over their peer link (32 bytes per point:
 // a third of what run_device_window_shards moves, so one copy each instead of its scatter + all-gather); every device gathers
@@ -2494,59 +2546,33 @@ int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_sc
   const size_t nd = ctx->devs.size();
   plan_t p0; make_plan(ctx, ctx->devs[0], n, p0);
   const curve_sizes sz = sizes_of(p0.curve);
-  const int owner = device_index_of_pointer(ctx, d_scalars);
-  if (owner < 0) return set_err(ctx, TE_MSM_EINVAL, "te_msm_run_scalars_device: the scalars must be resident on a device of the context");
+  const int owner = owner_of(ctx, "te_msm_run_scalars_device: the scalars must be resident on a device of the context", {d_scalars});
+  if (owner < 0) return owner;
   const int src_dev = ctx->devs[(size_t)owner].device;
-  std::vector<int> wsel(nd, 0);
-  for (size_t i = 0; i < nd; i++) { wsel[i] = free_workset_index(ctx->devs[i]); if (wsel[i] < 0) return set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned); }
+  std::vector<int> wsel;
+  if (int rc = free_sets(ctx, nd, wsel)) return rc;
   std::vector<int64_t> copies(nd, 0);
   auto share = [&](size_t i) -> int {
     gpu_t& d = ctx->devs[i]; workset_t& ws = d.ws[wsel[i]];
     HIP_TRY(ctx, hipSetDevice(d.device));
     const void* ds = d_scalars;
     if (d.device != src_dev || ctx->opt_stage_device_inputs) {
-      if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
-      if (ws.used && ws.ev_done) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));
-      HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, d_scalars, src_dev, n * sz.scalar_in, ws.stream));
+      if (int rc = pull_scalars(ctx, d, ws, d_scalars, src_dev, n)) return rc;
       copies[i] = 1; ds = ws.d_in_scalars;
     }
     if (int rc = enqueue_partial(ctx, d, ws, nullptr, ds, n, nullptr, ws.stream, nullptr, 0, false, 1, false, bases)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
-  std::vector<te_sched::job_ref> jobs(nd);
-  for (size_t i = 1; i < nd; i++) jobs[i] = worker_of(ctx, i).post([&share, i] { return share(i); });
-  int rc = share(0);
-  for (size_t i = 1; i < nd; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
+  const int rc = te_sched::on_devices(*ctx, nd, share);
   for (size_t i = 0; i < nd; i++) { ctx->stat_peer_copies += copies[i]; ctx->stat_peer_bytes += copies[i] * (int64_t)(n * sz.scalar_in); }
-  std::vector<uint8_t> merged((size_t)p0.W * sz.row, 0);
-  int64_t entries = 0; bool carry = false;
-  for (size_t i = 0; i < nd; i++) {
-    gpu_t& d = ctx->devs[i]; workset_t& ws = d.ws[wsel[i]];
-    if (rc) { (void)hipSetDevice(d.device); (void)hipStreamSynchronize(ws.stream); continue; }
-    HIP_TRY(ctx, hipSetDevice(d.device));
-    HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
-    carry = carry || *ws.h_err != 0;
-    entries += entries_of(ws);
-    for (int w = d.w_first; w < p0.W; w += d.w_step) memcpy(&merged[(size_t)w * sz.row], ws.h_partials + (size_t)w * sz.row, sz.row);
-  }
-  if (rc) return rc;
-  ctx->stat_entries = entries;
-  if (carry) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
-  if (p0.curve == TE_MSM_CURVE_BLS12_377_G1) te377_host::horner_to_affine(merged.data(), p0.c, (int)p0.logB, p0.W, out);
-  else te_host::horner_to_affine(merged.data(), p0.c, (int)p0.logB, p0.W, out);
-  return 0;
+  return settle_window_shards(ctx, wsel, p0, rc, false, out);
 }
 
 int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_is_host, uint8_t* out) {
   if (!ctx || !out) return TE_MSM_EINVAL;
-  if (!valid_bases(ctx, bases)) return set_err(ctx, TE_MSM_EINVAL, kBadBases);
-  if (bases->curve != ctx->opt_curve) return set_err(ctx, TE_MSM_EINVAL, kBasesCurve);
+  if (int rc = check_bases(ctx, bases)) return rc;
   const uint64_t n = bases->n;
-  if (n == 0) {
-    memset(out, 0, sizes_of(ctx->opt_curve).result);
-    if (ctx->opt_curve == TE_MSM_CURVE_TE_BLS12) out[32] = 1;
-    return 0;
-  }
+  if (n == 0) { write_identity(ctx->opt_curve, out); return 0; }
   if (!src) return set_err(ctx, TE_MSM_EINVAL, "null scalar buffer");
   size_t di = 0;
   if (ctx->devs.size() > 1) {
@@ -2556,14 +2582,15 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
     }
     // a fixed-base set has no windows or point slices to shard (one bucket set): the lone call runs on ONE device -- the holder of
     // device-resident scalars, else the first; MSMs in flight (tickets) are how several devices work on such a set
-    if (!src_is_host) { const int owner = device_index_of_pointer(ctx, src); if (owner < 0) return set_err(ctx, TE_MSM_EINVAL, "te_msm_run_scalars_device: the scalars must be resident on a device of the context"); di = (size_t)owner; }
+    if (!src_is_host) {
+      const int owner = owner_of(ctx, "te_msm_run_scalars_device: the scalars must be resident on a device of the context", {src});
+      if (owner < 0) return owner;
+      di = (size_t)owner;
+    }
   }
   gpu_t& d = ctx->devs[di];
-  int wsel = ctx->devs.size() > 1 ? 0 : ctx->opt_workset;
-  if (te_sched::slot_ticket(d.ws[wsel].slot)) {
-    wsel = free_workset_index(d);
-    if (wsel < 0) return set_err(ctx, TE_MSM_ESTATE, kAllSetsOwned);
-  }
+  const int wsel = lone_set(ctx, d, ctx->devs.size() > 1 ? 0 : ctx->opt_workset);
+  if (wsel < 0) return wsel;
   workset_t& ws = d.ws[wsel];
   HIP_TRY(ctx, hipSetDevice(d.device));
   plan_t p0; make_plan(ctx, d, n, p0);
@@ -2637,17 +2664,14 @@ int te_msm_run_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_scalar
 int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_le, uint64_t* ticket) {
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
-  if (!valid_bases(ctx, bases)) return set_err(ctx, TE_MSM_EINVAL, kBadBases);
-  if (bases->curve != ctx->opt_curve) return set_err(ctx, TE_MSM_EINVAL, kBasesCurve);
+  if (int rc = check_bases(ctx, bases)) return rc;
   const uint64_t n = bases->n;
   if (!scalars_le || n == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty point set has no tickets: te_msm_run_scalars returns the identity)");
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_submit_scalars computes whole MSMs: reset the window shard first");
-  const int di = pick_device(ctx, -1);
-  if (di < 0) return set_err(ctx, TE_MSM_ESTATE, "every work set has an MSM in flight: collect one first");
-  gpu_t& d = ctx->devs[(size_t)di];
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  const int wi = take_free_workset(ctx, d, false);
+  int di = -1;
+  const int wi = take_free_workset(ctx, -1, false, &di);
   if (wi < 0) return wi;
+  gpu_t& d = ctx->devs[(size_t)di];
   workset_t& ws = d.ws[wi];
   plan_t pf; make_plan(ctx, d, n, pf, 0, 1, 0, true);
   // pieces shorten ONE MSM's way through the device (its upload hides under its own first pieces); with other tickets in flight on
@@ -2658,10 +2682,8 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
   const uint8_t* recs = bases->recs[(size_t)di]; const int kind = bases->rec_kind;
   warm_upload_lanes(ctx);
   te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, bases, recs, kind, scalars_le, n, c, K]() -> int {
-    const int rc = bases->fb_c ? enqueue_fixed_base_host(ctx, *dp, *wsp, bases, scalars_le, n, false)
-                               : enqueue_scalar_slice(ctx, *dp, *wsp, recs, kind, scalars_le, n, c, K, false);
-    if (rc) { std::lock_guard<std::mutex> lk(ctx->err_mu); wsp->job_err = ctx->err; }
-    return rc;
+    return lane_status(ctx, *wsp, bases->fb_c ? enqueue_fixed_base_host(ctx, *dp, *wsp, bases, scalars_le, n, false)
+                                              : enqueue_scalar_slice(ctx, *dp, *wsp, recs, kind, scalars_le, n, c, K, false));
   });
   ws.bound = bases; bases->in_flight++;
   hand_out_ticket(ctx, di, ws, ticket, std::move(job));
@@ -2671,28 +2693,22 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
 int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_scalars_le, uint64_t* ticket) {
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
-  if (!valid_bases(ctx, bases)) return set_err(ctx, TE_MSM_EINVAL, kBadBases);
-  if (bases->curve != ctx->opt_curve) return set_err(ctx, TE_MSM_EINVAL, kBasesCurve);
+  if (int rc = check_bases(ctx, bases)) return rc;
   const uint64_t n = bases->n;
   if (!d_scalars_le || n == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty point set has no tickets: te_msm_run_scalars_device returns the identity)");
   const bool multi = ctx->devs.size() > 1;
-  const int owner = multi ? device_index_of_pointer(ctx, d_scalars_le) : 0;
-  if (multi && owner < 0) return set_err(ctx, TE_MSM_EINVAL, "te_msm_submit_scalars_device: the scalars must be resident on a device of the context");
-  const int di = pick_device(ctx, owner);
-  if (di < 0) return set_err(ctx, TE_MSM_ESTATE, "every work set has an MSM in flight: collect one first");
-  gpu_t& d = ctx->devs[(size_t)di];
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  const int wi = take_free_workset(ctx, d, true);
+  const int owner = multi ? owner_of(ctx, "te_msm_submit_scalars_device: the scalars must be resident on a device of the context", {d_scalars_le}) : 0;
+  if (owner < 0) return owner;
+  int di = -1;
+  const int wi = take_free_workset(ctx, owner, true, &di);
   if (wi < 0) return wi;
+  gpu_t& d = ctx->devs[(size_t)di];
   workset_t& ws = d.ws[wi];
   const int src_dev = ctx->devs[(size_t)owner].device;
   const void* ds = d_scalars_le;
   if (multi && (d.device != src_dev || ctx->opt_stage_device_inputs)) {
-    const curve_sizes sz = sizes_of(ctx->opt_curve);
-    if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
-    if (ws.used) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));
-    HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, d_scalars_le, src_dev, n * sz.scalar_in, ws.stream));
-    ctx->stat_peer_copies += 1; ctx->stat_peer_bytes += (int64_t)(n * sz.scalar_in);
+    if (int rc = pull_scalars(ctx, d, ws, d_scalars_le, src_dev, n)) return rc;
+    ctx->stat_peer_copies += 1; ctx->stat_peer_bytes += (int64_t)(n * sizes_of(ctx->opt_curve).scalar_in);
     ds = ws.d_in_scalars;
   }
   if (bases->fb_c && (multi || d.w_step == 1)) { if (int rc = enqueue_fixed_base(ctx, d, ws, bases, ds, n, 0, ws.stream)) return rc; }
@@ -2838,19 +2854,14 @@ int check_standalone(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n,
   if (first_bad) *first_bad = -1;
   if (reason) *reason = 0;
   if (level != 1 && level != 2) return set_err(ctx, TE_MSM_EINVAL, "te_msm_check_points: level must be 1 or 2");
-  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
+  if (int rc = check_n(ctx, n)) return rc;
   if (n > 0 && !src) return set_err(ctx, TE_MSM_EINVAL, "null point buffer");
-  size_t di = 0;
-  if (!src_is_host && n > 0 && ctx->devs.size() > 1) {
-    const int owner = device_index_of_pointer(ctx, src);
-    if (owner < 0) return set_err(ctx, TE_MSM_EINVAL, "te_msm_check_points_device: the points must be resident on a device of the context");
-    di = (size_t)owner;
-  }
-  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why);
+  const int di = !src_is_host && n > 0 && ctx->devs.size() > 1
+                     ? owner_of(ctx, "te_msm_check_points_device: the points must be resident on a device of the context", {src}) : 0;
+  if (di < 0) return di;
+  const int rc = check_points_on(ctx, (size_t)di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why);
   if (rc != TE_MSM_EPOINT) return rc;
-  if (first_bad) *first_bad = bad;
-  if (reason) *reason = why;
-  return note_bad_point(ctx, bad, why);
+  return note_bad(ctx, kBadPoint, bad, why, first_bad, reason);
 }
 }  // namespace
 
@@ -2892,15 +2903,12 @@ int recover_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64
   gpu_t& d = ctx->devs[di];
   const int curve = ctx->opt_curve;
   const size_t xb = x_bytes_of(curve), pb = sizes_of(curve).point_in;
-  std::lock_guard<std::mutex> lk(*d.chk_mu);
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
-  if (!d.chk_word) HIP_TRY(ctx, hipMalloc(&d.chk_word, sizeof(unsigned long long)));
-  if (!d.chk_host) HIP_TRY(ctx, hipHostMalloc(&d.chk_host, sizeof(unsigned long long), hipHostMallocDefault));
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
   const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
   dev_tmp stage;
   if (src_is_host) { if (int rc = tmp_alloc(ctx, d, stage, piece * xb)) return rc; }
-  hipStream_t st = d.chk_stream;
+  hipStream_t st = lane.stream();
   HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
   for (uint64_t off = 0; off < n; off += piece) {
     const uint32_t m = (uint32_t)std::min(piece, n - off);
@@ -2913,78 +2921,52 @@ int recover_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64
     else hipLaunchKernelGGL(te::k_points_from_x<0>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::kRootExpTe, te::kNafTeOrder);
     HIP_TRY(ctx, hipGetLastError());
   }
-  HIP_TRY(ctx, hipMemcpyAsync(d.chk_host, d.chk_word, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  if (*d.chk_host) {
-    te::check_decode(*d.chk_host, n, bad, reason);
-    return TE_MSM_EPOINT;
-  }
+  if (int rc = lane.verdict(ctx, n, bad, reason)) return rc;
   if (dst) {
     HIP_TRY(ctx, hipMemcpyAsync(dst, d_pts, n * pb, dst_is_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
   }
   return 0;
 }
-// a failed recovery as the outcome of a call: "bad_point_index" / "bad_point_reason" and the error text
-int note_bad_x(te_ctx* ctx, int64_t index, int reason) {
-  ctx->bad_point_index = index; ctx->bad_point_reason = reason;
-  char buf[256];
-  snprintf(buf, sizeof buf, "x-coordinate %lld has no point (reason %d): %s", (long long)index, reason,
-           reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical (x >= modulus, or reserved flag bits set)"
-           : reason == TE_MSM_POINT_OFF_CURVE ? "no point on the curve has this x (or the point at infinity / map undefined)"
-                                              : "no point of the prime-order subgroup has this x");
-  return set_err(ctx, TE_MSM_EPOINT, buf);
-}
 // host x -> points of the first device in t (allocated here): 0, TE_MSM_EPOINT (noted) or a device error
 int recover_host_to_first(te_ctx* ctx, const uint8_t* x_le, uint64_t n, dev_tmp& t) {
   if (int rc = tmp_alloc(ctx, ctx->devs[0], t, n * sizes_of(ctx->opt_curve).point_in)) return rc;
   int64_t bad = -1; int why = 0;
   const int rc = recover_on(ctx, 0, x_le, true, n, t.p, nullptr, false, &bad, &why);
-  if (rc == TE_MSM_EPOINT) return note_bad_x(ctx, bad, why);
+  if (rc == TE_MSM_EPOINT) return note_bad(ctx, kBadX, bad, why);
   return rc;
 }
 int from_x_args(te_ctx* ctx, const void* x, uint64_t n, const void* out) {
-  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
+  if (int rc = check_n(ctx, n)) return rc;
   if (n > 0 && (!x || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   return 0;
+}
+// te_msm_points_from_x (buffers on the host: recovery on the first device) and te_msm_points_from_x_device (on the device that holds them)
+int points_from_x_common(te_ctx* ctx, const void* x, bool on_host, uint64_t n, void* out, int64_t* first_bad, int* reason) {
+  if (!ctx) return TE_MSM_EINVAL;
+  if (first_bad) *first_bad = -1;
+  if (reason) *reason = 0;
+  if (int rc = from_x_args(ctx, x, n, out)) return rc;
+  if (n == 0) return 0;
+  const int di = on_host ? 0 : owner_of(ctx, "te_msm_points_from_x_device: x and the output must be resident on one device of the context", {x, out});
+  if (di < 0) return di;
+  dev_tmp pts;
+  if (int rc = tmp_alloc(ctx, ctx->devs[(size_t)di], pts, n * sizes_of(ctx->opt_curve).point_in)) return rc;
+  int64_t bad = -1; int why = 0;
+  const int rc = recover_on(ctx, (size_t)di, x, on_host, n, pts.p, out, on_host, &bad, &why);
+  if (rc != TE_MSM_EPOINT) return rc;
+  return note_bad(ctx, kBadX, bad, why, first_bad, reason);
 }
 }  // namespace
 
 int te_msm_points_from_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_points_xy_le, int64_t* first_bad, int* reason) {
   device_guard restore_callers_device;
-  if (!ctx) return TE_MSM_EINVAL;
-  if (first_bad) *first_bad = -1;
-  if (reason) *reason = 0;
-  if (int rc = from_x_args(ctx, x_le, n, out_points_xy_le)) return rc;
-  if (n == 0) return 0;
-  dev_tmp pts;
-  if (int rc = tmp_alloc(ctx, ctx->devs[0], pts, n * sizes_of(ctx->opt_curve).point_in)) return rc;
-  int64_t bad = -1; int why = 0;
-  const int rc = recover_on(ctx, 0, x_le, true, n, pts.p, out_points_xy_le, true, &bad, &why);
-  if (rc != TE_MSM_EPOINT) return rc;
-  if (first_bad) *first_bad = bad;
-  if (reason) *reason = why;
-  return note_bad_x(ctx, bad, why);
+  return points_from_x_common(ctx, x_le, true, n, out_points_xy_le, first_bad, reason);
 }
 
 int te_msm_points_from_x_device(te_ctx* ctx, const void* d_x_le, uint64_t n, void* d_out_points_xy_le, int64_t* first_bad, int* reason) {
   device_guard restore_callers_device;
-  if (!ctx) return TE_MSM_EINVAL;
-  if (first_bad) *first_bad = -1;
-  if (reason) *reason = 0;
-  if (int rc = from_x_args(ctx, d_x_le, n, d_out_points_xy_le)) return rc;
-  if (n == 0) return 0;
-  const int owner = device_index_of_pointer(ctx, d_x_le);
-  if (owner < 0 || device_index_of_pointer(ctx, d_out_points_xy_le) != owner)
-    return set_err(ctx, TE_MSM_EINVAL, "te_msm_points_from_x_device: x and the output must be resident on one device of the context");
-  dev_tmp pts;
-  if (int rc = tmp_alloc(ctx, ctx->devs[(size_t)owner], pts, n * sizes_of(ctx->opt_curve).point_in)) return rc;
-  int64_t bad = -1; int why = 0;
-  const int rc = recover_on(ctx, (size_t)owner, d_x_le, false, n, pts.p, d_out_points_xy_le, false, &bad, &why);
-  if (rc != TE_MSM_EPOINT) return rc;
-  if (first_bad) *first_bad = bad;
-  if (reason) *reason = why;
-  return note_bad_x(ctx, bad, why);
+  return points_from_x_common(ctx, d_x_le, false, n, d_out_points_xy_le, first_bad, reason);
 }
 
 int te_msm_bind_points_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, te_bases** out) {
@@ -3009,15 +2991,16 @@ int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
   const size_t sbytes = n * sizes_of(ctx->opt_curve).scalar_in;
   if (int rc = tmp_alloc(ctx, d, sc, sbytes)) return rc;
   {
-    std::lock_guard<std::mutex> lk(*d.chk_mu);                  // (recover_on made the stream)
-    HIP_TRY(ctx, hipMemcpyAsync(sc.p, scalars_le, sbytes, hipMemcpyHostToDevice, d.chk_stream));
-    HIP_TRY(ctx, hipStreamSynchronize(d.chk_stream));
+    check_lane lane(ctx, d);
+    if (lane.rc) return lane.rc;
+    HIP_TRY(ctx, hipMemcpyAsync(sc.p, scalars_le, sbytes, hipMemcpyHostToDevice, lane.stream()));
+    HIP_TRY(ctx, hipStreamSynchronize(lane.stream()));
   }
   return run_common(ctx, pts.p, sc.p, false, n, out_xy_le);      // as te_msm_run_device (window shards, check_points, TE_MSM_ESCALAR)
 }
 
 // ---- batch scalar multiplication (te_msm_mul[_device], te_msm_mul_x; kernels in scalar_mul.hip.hpp) ------------------------------
-// Host buffers: contiguous slices over the context's devices, one host thread per device (worker_of), as te_msm_run's point slices.
+// Host buffers: contiguous slices over the context's devices, one host thread per device (on_devices), as te_msm_run's point slices.
 // Every slice is staged whole on its device -- points (or x), scalars and results -- checked (recovery, option "check_points"),
 // multiplied, and copied out only when no slice reported a bad point: on a failure `out` is untouched.  The chain writes projective
 // results of a piece of kMulPiece points into a buffer of the call's own; the affine pass turns them into the wire format.  Every
@@ -3038,13 +3021,12 @@ int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t
   const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1;
   const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in;
   const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
-  std::lock_guard<std::mutex> lk(*d.chk_mu);
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
   const uint64_t piece = std::min(n, kMulPiece);
   dev_tmp proj;
   if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
-  hipStream_t st = d.chk_stream;
+  hipStream_t st = lane.stream();
   for (uint64_t off = 0; off < n; off += piece) {
     const uint32_t m = (uint32_t)std::min(piece, n - off);
     const uint4* p4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_pts) + off * pb);
@@ -3067,7 +3049,7 @@ int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t
   return 0;
 }
 int mul_args(te_ctx* ctx, const void* pts, const void* sc, uint64_t n, const void* out) {
-  if (n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31");
+  if (int rc = check_n(ctx, n)) return rc;
   if (n > 0 && (!pts || !sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   return 0;
 }
@@ -3114,20 +3096,12 @@ int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalar
     HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].res.p, m * pb, hipMemcpyDeviceToHost));
     return 0;
   };
-  auto on_all = [&](const std::function<int(size_t)>& f) -> int {
-    std::vector<te_sched::job_ref> jobs(D);
-    for (size_t i = 1; i < D; i++) jobs[i] = worker_of(ctx, i).post([&f, i] { return f(i); });
-    int rc = f(0);
-    for (size_t i = 1; i < D; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
-    return rc;
-  };
-  if (int rc = on_all(stage)) return rc;
+  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
   for (size_t i = 0; i < D; i++) {                                // slices in order: the first that reports holds the lowest index
     if (sl[i].bad < 0) continue;
-    const int64_t index = (int64_t)(per * i) + sl[i].bad;
-    return sl[i].from_x ? note_bad_x(ctx, index, sl[i].why) : note_bad_point(ctx, index, sl[i].why);
+    return note_bad(ctx, sl[i].from_x ? kBadX : kBadPoint, (int64_t)(per * i) + sl[i].bad, sl[i].why);
   }
-  return on_all(copy_out);
+  return te_sched::on_devices(*ctx, D, copy_out);
 }
 }  // namespace
 
@@ -3148,9 +3122,9 @@ int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_sca
   if (!ctx) return TE_MSM_EINVAL;
   if (int rc = mul_args(ctx, d_points_xy_le, d_scalars_le, n, d_out_points_xy_le)) return rc;
   if (n == 0) return 0;
-  const int owner = device_index_of_pointer(ctx, d_points_xy_le);
-  if (owner < 0 || device_index_of_pointer(ctx, d_scalars_le) != owner || device_index_of_pointer(ctx, d_out_points_xy_le) != owner)
-    return set_err(ctx, TE_MSM_EINVAL, "te_msm_mul_device: the points, the scalars and the output must be resident on one device of the context");
+  const int owner = owner_of(ctx, "te_msm_mul_device: the points, the scalars and the output must be resident on one device of the context",
+                             {d_points_xy_le, d_scalars_le, d_out_points_xy_le});
+  if (owner < 0) return owner;
   gpu_t& d = ctx->devs[(size_t)owner];
   te::naf_t kn = {};
   if (shared_scalar) {                                            // the NAF is built here: the scalar's first 32 bytes come back
@@ -3259,8 +3233,7 @@ int run_batch_on_device(te_ctx* ctx, size_t di, const te_bases* bases, const voi
 int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const void* src, bool src_is_host, uint8_t* out) {
   if (!ctx) return TE_MSM_EINVAL;
   drain_workers(ctx);
-  if (!valid_bases(ctx, bases)) return set_err(ctx, TE_MSM_EINVAL, kBadBases);
-  if (bases->curve != ctx->opt_curve) return set_err(ctx, TE_MSM_EINVAL, kBasesCurve);
+  if (int rc = check_bases(ctx, bases)) return rc;
   // (the window shards of a multi-device context are the engine's own, for its lone calls: a batch runs whole MSMs on every device)
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_EINVAL, "batched MSMs compute whole MSMs: reset the window shard first");
   if (count < 0) return set_err(ctx, TE_MSM_EINVAL, "count must be >= 0");
@@ -3274,12 +3247,10 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
   }
   if (total && !src) return set_err(ctx, TE_MSM_EINVAL, "null scalar buffer");
   const curve_sizes sz = sizes_of(ctx->opt_curve);
-  size_t holder = 0;
-  if (!src_is_host && total) {
-    const int owner = device_index_of_pointer(ctx, src);
-    if (owner < 0 && ctx->devs.size() > 1) return set_err(ctx, TE_MSM_EINVAL, "te_msm_run_scalars_batch_device: the scalars must be resident on a device of the context");
-    holder = owner < 0 ? 0 : (size_t)owner;
-  }
+  const int owner = !src_is_host && total && ctx->devs.size() > 1
+                        ? owner_of(ctx, "te_msm_run_scalars_batch_device: the scalars must be resident on a device of the context", {src}) : 0;
+  if (owner < 0) return owner;
+  const size_t holder = (size_t)owner;
   const size_t nd = src_is_host ? ctx->devs.size() : 1;
   te_batch::limits lim;
   lim.small_max = (uint64_t)ctx->opt_batch_small_max;
@@ -3330,15 +3301,7 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
     carry[i] = c;
     return r;
   };
-  int rc = 0;
-  if (nd == 1) rc = on(0);
-  else {
-    std::vector<te_sched::job_ref> jobs(nd);
-    for (size_t i = 1; i < nd; i++) jobs[i] = worker_of(ctx, i).post([&on, i] { return on(i); });
-    rc = on(0);
-    for (size_t i = 1; i < nd; i++) { const int r = worker_of(ctx, i).wait(jobs[i]); if (!rc) rc = r; }
-  }
-  if (rc) return rc;
+  if (int rc = te_sched::on_devices(*ctx, nd, on)) return rc;
   int64_t ent = 0; bool any_carry = false;
   for (size_t i = 0; i < nd; i++) { ent += entries[i]; any_carry = any_carry || carry[i]; }
   ctx->stat_entries = ent;
@@ -3363,7 +3326,7 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
     fold_part(0);
     for (std::thread& t : th) t.join();
   }
-  for (uint32_t m : P.empty) if (ctx->opt_curve == TE_MSM_CURVE_TE_BLS12) res[(size_t)m * sz.result + 32] = 1;     // the identity: (0, 1) / zeros
+  for (uint32_t m : P.empty) write_identity(ctx->opt_curve, &res[(size_t)m * sz.result]);
   memcpy(out, res.data(), res.size());
   return 0;
 }
