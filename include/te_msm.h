@@ -106,12 +106,16 @@ int te_msm_run_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_sca
  * prover calling MSMs back to back does not have to).
  * Inputs must stay valid AND UNCHANGED until the ticket is collected.  Tickets may be collected in any order (until round 4: in
  * submission order only).
- * Calls in flight that name the SAME point buffer (pointer, n) share one record slab (round 6, option "share_records" = 1): every call
- * still converts its points -- nothing is remembered across calls, the buffer may hold other points for the next call once this one is
- * collected --, but all of them convert into, and gather from, the same 128 bytes per point instead of one slab per work set: four MSMs in
- * flight keep their gathers inside the 256 MB Infinity Cache (+4-5 % MSM/s at n = 2^20: profiles/r06_share_records_ab.txt).  This is why
- * "unchanged" matters: overwriting a point buffer that a ticket in flight still names, and submitting it again, would rewrite the records
- * under that ticket.
+ * Calls in flight that name the SAME point buffer (pointer, n) share one record slab (round 6, option "share_records"): they convert into,
+ * and gather from, the same 128 bytes per point instead of one slab per work set -- four MSMs in flight keep their gathers inside the
+ * 256 MB Infinity Cache (+4-5 % MSM/s at n = 2^20: profiles/r06_share_records_ab.txt).  And they convert the points ONCE per occupancy
+ * run of that slab: a call that joins while another whole-MSM call (a ticket not collected yet, a te_msm_run_device still
+ * running) names the same buffer, and finds the conversion of that run complete, skips it (k_part_scatter instead of
+ * k_part_scatter_prep: 64 MB read, 128 MB written and three field products per point less).  When the last of them is collected the run
+ * ends and the slab forgets it: the buffer may hold other points for the next call.  This is why "unchanged" matters: overwriting a
+ * point buffer that a ticket in flight still names, and submitting it again, would gather the old records -- or rewrite them under that
+ * ticket.  Checked points (option "check_points"), x-only points and the building blocks te_msm_partial_device[_batch] convert on
+ * every call.
  * Contexts of several devices: the inputs may be resident on ANY device of the context (both buffers on the same one); the
  * ticket goes to the device with the fewest MSMs in flight -- ties to the device that holds the inputs -- and a device that
  * does not hold them pulls them over its peer link first (hipMemcpyPeerAsync on the work set's stream; option
@@ -351,8 +355,11 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *                   of a device-scalar MSM gather from different copies -- the gather footprint of a per-window table with the arithmetic
  *                   unchanged (profiles/r06_fixed_base_windows.txt, step 1).  Same results.
  *   "share_records" 1 (default) = whole-MSM calls from device-resident inputs (te_msm_submit_device, te_msm_run_device) that name the same
- *                   point buffer while in flight share one record slab, see te_msm_submit_device; 0 = one slab per work set (A/B; env
- *                   TE_MSM_SHARE_RECORDS).  Read-only "record_slabs": slabs allocated.
+ *                   point buffer while in flight share one record slab and convert it once per occupancy run, see te_msm_submit_device;
+ *                   2 = shared slabs, every call converts (the round-6 form); 0 = one slab per work set, every call converts (A/B; env
+ *                   TE_MSM_SHARE_RECORDS).  Read-only "record_slabs": slabs allocated; read-only "record_conversions": point -> record
+ *                   conversions the context's MSM launch sequences have enqueued (one per launch that converts; bound point sets
+ *                   not included).
  *   "lane_host_waits" 1 (default) = the lane thread of an asynchronous ticket (te_msm_submit_async, te_msm_submit_scalars) waits for each of
  *                   its uploads on the host before it enqueues the kernels that read it; 0 = a stream wait in front of those kernels, which
  *                   holds up other tickets' kernels in a shared hardware queue (A/B; env TE_MSM_LANE_HOST_WAITS; profiles/r06_lane_host_waits.txt).

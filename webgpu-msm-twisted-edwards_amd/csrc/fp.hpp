@@ -172,16 +172,16 @@ template <int M> TE_HD void mont_mul_x(const fp (&a)[M], const fp (&b)[M], fp (&
 //   h = a >> 222 (32 bits);  q = (h * K2D_Q) >> 49 with K2D_Q = floor(6042 * 2^49 / (floor(p / 2^222) + 1))  never exceeds
 //   6042 a / p and falls short of it by less than 1 + 2^-15, so 0 <= 6042 a - q p < 1.0001 p.  One signed pass over the limbs:
 //   acc += 6042 a_i - q p_i (|acc| < 2^43), the subtraction as  q (2^32 - p_i) - q 2^32  in unsigned 64-bit arithmetic.
-constexpr uint32_t K2D_SMALL = 6042u;            // 2 d, d = 3021 (reference/params/AleoConstants.ts:2-4)
-constexpr uint32_t K2D_Q = 0xa1d088f6u;          // checked against bigints in tests/test_host_logic.py::test_small_constant_product
-TE_HD fp fp_mul_k2d(const fp& a) {
+// (fp_mul_small: the pass for any constant C of at most 13 bits with its estimate constant CQ = floor(C * 2^SH / (floor(p / 2^222) + 1))
+// below 2^32; the bound above holds for each of them.)
+template <uint32_t C, uint32_t CQ, int SH> TE_HD fp fp_mul_small(const fp& a) {
   const uint32_t h = (a.v[8] << 10) | (a.v[7] >> 19);
-  const uint32_t q = (uint32_t)(((uint64_t)h * K2D_Q) >> 49);
+  const uint32_t q = (uint32_t)(((uint64_t)h * CQ) >> SH);
   fp r;
   uint64_t acc = 0;                              // a signed value in two's complement
 #pragma unroll
   for (int i = 0; i < NL; i++) {
-    acc += (uint64_t)a.v[i] * K2D_SMALL;
+    acc += (uint64_t)a.v[i] * C;
     acc += (uint64_t)q * (0u - p_limb(i));       // q (2^32 - p_i) ...
     acc -= (uint64_t)q << 32;                    // ... - q 2^32 = - q p_i
     if (i < NL - 1) { r.v[i] = (uint32_t)acc & LM; acc = (uint64_t)((int64_t)acc >> LB); }
@@ -189,6 +189,14 @@ TE_HD fp fp_mul_k2d(const fp& a) {
   }
   return r;
 }
+constexpr uint32_t K2D_SMALL = 6042u;            // 2 d, d = 3021 (reference/params/AleoConstants.ts:2-4)
+constexpr uint32_t K2D_Q = 0xa1d088f6u;          // checked against bigints in tests/test_host_logic.py::test_small_constant_product
+TE_HD fp fp_mul_k2d(const fp& a) { return fp_mul_small<K2D_SMALL, K2D_Q, 49>(a); }
+// a * d (d = 3021) the same way: the record conversion's -d x y (pnt_from_affine_raw in curve.hpp) -- d * 2^50 = 2d * 2^49, so the
+// estimate constant is K2D_Q again.  Checked against bigints in tests/test_record_conversion_host.py.
+constexpr uint32_t KD_SMALL = 3021u;
+constexpr uint32_t KD_Q = K2D_Q;
+TE_HD fp fp_mul_d(const fp& a) { return fp_mul_small<KD_SMALL, KD_Q, 50>(a); }
 
 // limb-wise a + b (N + N -> S).  No carries.
 TE_HD fp fp_add(const fp& a, const fp& b) {

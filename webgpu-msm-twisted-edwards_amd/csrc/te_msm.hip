@@ -134,6 +134,7 @@ struct workset_t {
   uint32_t* d_fb_fill = nullptr;      // ... [rows] entries reserved per row, in the zeroed block
   const void* fb_scalars = nullptr; uint64_t fb_n = 0;   // ... the scalars (device memory) of the MSM in flight: a row overflow falls back to the ordinary windows
   int slab = -1;                      // shared record slab the MSM in flight on this set uses (-1: its own d_recs, or a bound point set)
+  bool slab_run = false;              // ... and that MSM is a whole-MSM call of the slab's occupancy run (rec_slab_t::run_users)
   const uint8_t* recs_last = nullptr; // where the records of the set's last MSM are (te_msm_debug_read "records"): d_recs or a shared slab
   te_bases* bound = nullptr;          // the bound point set the set's ticket in flight gathers from (te_msm_submit_scalars*): released only after the collect
   // a ticket whose points failed the check (option "check_points"): nothing was enqueued for it, its te_msm_collect reports TE_MSM_EPOINT
@@ -162,8 +163,12 @@ struct gpu_t {
   // users: work sets whose latest MSM names the slab.  pending / ev[]: users that let go of it while their MSM could still be running (the
   // building blocks te_msm_partial_device[_batch], whose completion the engine does not see): an event recorded behind that MSM; whoever
   // takes the slab for ANOTHER point buffer waits for those events first (joining the same buffer needs no wait: the same bytes).
+  // run_users: the whole-MSM calls among the users (uncollected tickets, running synchronous calls) -- the slab's OCCUPANCY RUN lasts
+  // while there is one.  converted / conv_ev: a call of the current run has enqueued the conversion, and an event stands right behind
+  // that launch; a later call of the run whose query finds the event complete converts nothing (see acquire_shared_recs).
   struct rec_slab_t { const void* src = nullptr; uint64_t n = 0; int curve = 0; uint8_t* d = nullptr; size_t cap = 0; int users = 0;
-                      uint32_t pending = 0; hipEvent_t ev[TE_MSM_WORKSETS] = {}; };
+                      uint32_t pending = 0; hipEvent_t ev[TE_MSM_WORKSETS] = {};
+                      int run_users = 0; bool converted = false; hipEvent_t conv_ev = nullptr; };
   std::vector<rec_slab_t> slabs;
   // asynchronous scalars-only tickets (bound bases) cross the link ONE AT A TIME per device: lanes that upload side by side share the
   // link, every ticket reaches the device late and the tickets move in a convoy (two in flight: 1.05-1.23 ms per MSM with 2-4 lanes,
@@ -229,7 +234,9 @@ struct te_ctx {
   int opt_scalar_chunks = 0;     // te_msm_run_scalars / te_msm_submit_scalars: pieces the scalars of a bound set are uploaded and processed in (0 = from n)
   int opt_bind_fixed_base = 0;   // te_msm_bind_points (Twisted-Edwards curve): window bits c of a per-window table 2^(c w) P_i (16..21; 0 = none): MSMs over
                                  // the set then run fixed-base windows -- one bucket set for all windows (W x the record memory)
-  int opt_share_records = 1;     // shared record slabs for calls in flight that name the same device-resident point buffer (A/B: option "share_records", env TE_MSM_SHARE_RECORDS)
+  int opt_share_records = 1;     // shared record slabs for calls in flight that name the same device-resident point buffer, converted once per occupancy run;
+                                 // 2 = shared slabs, every call converts (the round-6 form; A/B: option "share_records", env TE_MSM_SHARE_RECORDS)
+  int64_t stat_record_conversions = 0;   // point -> record conversions the MSM launch sequences enqueued (get_option "record_conversions")
   int opt_lane_host_waits = 1;   // asynchronous tickets (a lane thread enqueues them): the thread WAITS for each upload before it enqueues the kernels that read
                                  // it, instead of putting a stream wait in front of them (see lane_wait; A/B: option "lane_host_waits", env TE_MSM_LANE_HOST_WAITS)
   int opt_exp_table_replicas = 1; // EXPERIMENT (profiles/r06_fixed_base_windows.txt): te_msm_bind_points keeps this many copies of the records and
@@ -438,6 +445,8 @@ struct msm_launch {
   bool host_rows = false;         // own rows go straight to the work set's pinned host block, written by k_reduce_tail (no copy at all)
   uint8_t* recs_rw = nullptr;     // a shared record slab: the conversion writes it and k_accumulate gathers from it (instead of ws.d_recs)
   uint8_t* recs_out() const { return recs_rw ? recs_rw : ws.d_recs; }
+  bool have_recs = false;         // recs_rw holds this call's records already (converted earlier in the slab's occupancy run): no conversion
+  void count_conversion() const { __atomic_fetch_add(&ctx->stat_record_conversions, (int64_t)1, __ATOMIC_RELAXED); }
   const uint32_t* fb_remap = nullptr;   // fixed-base windows: the digit rows were filled by k_fb_digits (no k_digits launch); the level-1 scatter maps positions through it
   int table_replicas = 1;         // experiment "exp_table_replicas": window k gathers from copy k / ceil(windows / copies) of the bound records
   const uint8_t* bound = nullptr; // records of a bound point set (te_msm_bind_points), already offset to this launch's first point: no conversion,
@@ -461,6 +470,7 @@ struct msm_launch {
   // device-resident inputs, no per-stage timing: the record conversion rides in the launch of the sort's first level
   bool can_fuse_prep() const { return ctx->opt_fuse_prep && prof < 2 && p.nw > 0; }
   int front() {
+    if (have_recs) return front_scalars();
     if (can_fuse_prep()) return front_scalars(true);
     if (int rc = front_scalars()) return rc;
     return front_points();
@@ -492,8 +502,10 @@ struct msm_launch {
   int front_points() {
     const uint32_t n32 = this->n32();
     mark(ST_PREP);
+    if (have_recs) return 0;
     te::batch_ptrs tab; te::batch_slabs row_slab;
     const int rows = prep_rows(tab, row_slab);
+    count_conversion();
     if (p.curve == TE_MSM_CURVE_BLS12_377_G1)
       hipLaunchKernelGGL(te::k_prep_points377, dim3((n32 + 255) / 256, rows), dim3(256), 0, stream, tab, row_slab, reinterpret_cast<te::rec_slot<14>*>(recs_out()), n32);
     else
@@ -566,6 +578,7 @@ struct msm_launch {
       if (with_prep) {
         te::batch_ptrs tab; te::batch_slabs row_slab;
         const uint32_t rows = (uint32_t)prep_rows(tab, row_slab), sblocks = p.CH * (uint32_t)p.nw;
+        count_conversion();
         if (bls()) {                                      // 512 points per conversion block, one per thread
           const uint32_t per_row = (n32 + 511u) / 512u;
           hipLaunchKernelGGL(te::k_part_scatter_prep377, dim3(sblocks + rows * per_row), dim3(512), 0, stream, sa, sblocks, tab, row_slab,
@@ -917,11 +930,20 @@ int finish_sequence(te_ctx* ctx, workset_t& ws, hipStream_t stream);
 // 4 x 128 MB of records (n = 2^20) -- twice the 256 MB Infinity Cache -- although a caller with MSMs in flight nearly always names ONE
 // point buffer (the harness: full_benchmarks.ts:63-68,100-105; a prover: its SRS).  A gather footprint beyond the cache costs clock under
 // the power ceiling (profiles/r06_fixed_base_windows.txt, step 1: 512 MB instead of 128 MB: -7 % MSMs in flight).  So whole-MSM calls
-// from device-resident inputs that name the same point buffer (pointer, n, curve) while they are in flight share one slab: EVERY call
-// still converts its points -- nothing is remembered across calls: the buffer's contents may change between calls, and a call's own
-// accumulation is ordered behind its own conversion on its stream -- but all of them write the same bytes to the same place and gather
-// from there (inputs of a call in flight must not change: include/te_msm.h).  The reference converts per call as well
-// (convert_point_coords...wgsl:37-77).  A slab serves another point buffer only when no call in flight uses it any more.
+// from device-resident inputs that name the same point buffer (pointer, n, curve) while they are in flight share one slab, and gather
+// from there (inputs of a call in flight must not change: include/te_msm.h).  A slab serves another point buffer only when no call in
+// flight uses it any more.
+// CONVERT ONCE PER OCCUPANCY RUN.  Until round 6 every call still converted its points into the slab (the same bytes again: 64 MB read,
+// 128 MB written and four products per point, k_part_scatter_prep 76 us against 46 for the plain k_part_scatter).  But a whole-MSM
+// call that joins a slab while another whole-MSM call of the same buffer is in flight (rec_slab_t::run_users > 0) finds that buffer
+// unchanged since the run's first conversion: every call since then named it while in flight, so none of them let it change.  Such a
+// call converts nothing when the event behind the run's conversion has completed (hipEventQuery: no packet, no wait); while that
+// conversion may still be running -- the calls submitted right behind the first one of a run -- it converts itself, as before (no
+// cross-stream wait: its own accumulation stays ordered behind its own conversion).  When the run ends (run_users 0), the slab is
+// re-purposed or freed, the state is gone: the next call converts again, the buffer may hold other points by then.  Only whole-MSM calls
+// whose completion the engine sees take part (share_mode SHARE_RUN): the building blocks te_msm_partial_device[_batch], x-only points,
+// checked points ("check_points") and "share_records" = 2 convert on every call (SHARE_CONVERT), host buffers into their own slab.
+// The reference converts per call (convert_point_coords...wgsl:37-77).
 // (the slab's earlier users may still be running -- see rec_slab_t::pending: `stream`, on which the new user's conversion is about to be
 // enqueued, waits for them; nullptr: the host waits -- trim, destroy)
 int settle_slab(te_ctx* ctx, gpu_t::rec_slab_t& sl, hipStream_t stream, bool host) {
@@ -931,12 +953,23 @@ int settle_slab(te_ctx* ctx, gpu_t::rec_slab_t& sl, hipStream_t stream, bool hos
   sl.pending = 0;
   return 0;
 }
-int acquire_shared_recs(te_ctx* ctx, gpu_t& d, const void* src, uint64_t n, int curve, hipStream_t stream, uint8_t** out) {
+// run: the caller is a whole-MSM call of the slab's occupancy run (SHARE_RUN); *have: its records are in the slab already (no conversion)
+int acquire_shared_recs(te_ctx* ctx, gpu_t& d, const void* src, uint64_t n, int curve, hipStream_t stream, bool run, uint8_t** out, bool* have) {
   const size_t need = (size_t)n * sizes_of(curve).rec;
   int pick = -1;
+  *have = false;
   // the same buffer, in use or just let go of (its records are the same bytes: no wait, and `pending` stays for whoever re-purposes the slab)
   for (size_t i = 0; i < d.slabs.size(); i++) if ((d.slabs[i].users > 0 || d.slabs[i].pending) && d.slabs[i].d && d.slabs[i].src == src && d.slabs[i].n == n && d.slabs[i].curve == curve) {
-    d.slabs[i].users++; *out = d.slabs[i].d; return (int)i;
+    gpu_t::rec_slab_t& sl = d.slabs[i];
+    if (run) {
+      if (sl.run_users > 0 && sl.converted) {
+        const hipError_t q = hipEventQuery(sl.conv_ev);
+        if (q == hipSuccess) *have = true;
+        else (void)hipGetLastError();                 // hipErrorNotReady is an answer, not an error: this call converts as well
+      }
+      sl.run_users++;
+    }
+    sl.users++; *out = sl.d; return (int)i;
   }
   // a free slab: one nobody is waiting on first, the smallest that is large enough
   if (pick < 0) for (size_t i = 0; i < d.slabs.size(); i++) if (d.slabs[i].users == 0 && !d.slabs[i].pending && d.slabs[i].d && d.slabs[i].cap >= need && (pick < 0 || d.slabs[i].cap < d.slabs[(size_t)pick].cap)) pick = (int)i;
@@ -944,6 +977,7 @@ int acquire_shared_recs(te_ctx* ctx, gpu_t& d, const void* src, uint64_t n, int 
   if (pick < 0) for (size_t i = 0; i < d.slabs.size(); i++) if (d.slabs[i].users == 0) { pick = (int)i; break; }
   if (pick < 0) { d.slabs.emplace_back(); pick = (int)d.slabs.size() - 1; }
   gpu_t::rec_slab_t& sl = d.slabs[(size_t)pick];
+  sl.converted = false;                                                  // (users = 0: no occupancy run holds it)
   if (!sl.d || sl.cap < need) {
     if (int rc = settle_slab(ctx, sl, nullptr, true)) return rc;
     if (sl.d) HIP_TRY(ctx, hipFree(sl.d));
@@ -952,9 +986,16 @@ int acquire_shared_recs(te_ctx* ctx, gpu_t& d, const void* src, uint64_t n, int 
     sl.cap = need;
   }
   if (int rc = settle_slab(ctx, sl, stream, false)) return rc;          // another buffer's records are about to be overwritten
-  sl.src = src; sl.n = n; sl.curve = curve; sl.users++;
+  sl.src = src; sl.n = n; sl.curve = curve; sl.users++; sl.run_users = run ? 1 : 0;
   *out = sl.d;
   return pick;
+}
+// behind the conversion launch of a run's call: later calls of the run may skip theirs once this event has completed
+int note_conversion(te_ctx* ctx, gpu_t::rec_slab_t& sl, hipStream_t stream) {
+  if (!sl.conv_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&sl.conv_ev, hipEventDisableTiming));
+  HIP_TRY(ctx, hipEventRecord(sl.conv_ev, stream));
+  sl.converted = true;
+  return 0;
 }
 // completed: the set's MSM is known to be over (a collected ticket, a synchronous call).  Otherwise (the building blocks: the set is simply
 // used again) an event behind that MSM -- on the stream it ran on, BEFORE anything new is enqueued there -- guards the slab.
@@ -962,6 +1003,7 @@ void release_shared_recs(gpu_t& d, workset_t& ws, bool completed = true) {
   if (ws.slab >= 0 && (size_t)ws.slab < d.slabs.size() && d.slabs[(size_t)ws.slab].users > 0) {
     gpu_t::rec_slab_t& sl = d.slabs[(size_t)ws.slab];
     sl.users--;
+    if (ws.slab_run && sl.run_users > 0 && --sl.run_users == 0) sl.converted = false;   // the occupancy run is over: the next call converts
     if (!completed && ws.last_stream) {
       const int wi = (int)(&ws - d.ws);
       if (!sl.ev[wi]) (void)hipEventCreateWithFlags(&sl.ev[wi], hipEventDisableTiming);
@@ -969,20 +1011,26 @@ void release_shared_recs(gpu_t& d, workset_t& ws, bool completed = true) {
       else (void)hipStreamSynchronize(ws.last_stream);                  // (no event: the host waits instead)
     }
   }
-  ws.slab = -1;
+  ws.slab = -1; ws.slab_run = false;
 }
 
+// Where a call's records live (enqueue_partial): the work set's own d_recs; a shared slab the call converts into (the building blocks,
+// whose completion the engine does not see, and whole-MSM calls whose input form keeps the per-call conversion); or a shared slab as a
+// whole-MSM call of its occupancy run, which converts only when no earlier call of the run has (see SHARED RECORD SLABS above).
+enum share_mode { SHARE_NONE = 0, SHARE_CONVERT = 1, SHARE_RUN = 2 };
+
 // bases: the launch sequence gathers from a bound point set (d_points is not read: no conversion); batch must be 1
-// share_recs: a whole-MSM call whose completion the engine sees (a ticket, a synchronous call): its records may live in a shared slab
+// share: the record slab of the call (share_mode); a shared slab only for device-resident points, without graphs or bound bases
 int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, const void* d_scalars, uint64_t n,
                     void* d_partials_out, hipStream_t stream, const std::function<int(hipStream_t)>* upload_points = nullptr, int force_c = 0,
-                    bool side_stream = false, int batch = 1, bool whole = false, const te_bases* bases = nullptr, bool share_recs = false) {
+                    bool side_stream = false, int batch = 1, bool whole = false, const te_bases* bases = nullptr, share_mode share = SHARE_NONE) {
   plan_t p; make_plan(ctx, d, n, p, force_c, batch, 0, whole);
   if (bases) p.rec_kind = bases->rec_kind;
   // (a batch shares when all its MSMs name ONE point buffer: the batch then holds one conversion anyway -- slab 0 of msm_launch::slabs())
   const void* share_src = d_points;
   if (batch > 1 && d_points) { share_src = static_cast<const void* const*>(d_points)[0]; for (int m = 1; m < batch; m++) if (static_cast<const void* const*>(d_points)[m] != share_src) share_src = nullptr; }
-  share_recs = share_recs && ctx->opt_share_records && !bases && !upload_points && !ctx->opt_graph && share_src != nullptr;
+  const bool share_recs = share != SHARE_NONE && ctx->opt_share_records && !bases && !upload_points && !ctx->opt_graph && share_src != nullptr;
+  const bool run = share_recs && share == SHARE_RUN && ctx->opt_share_records == 1 && !ctx->opt_check_points && batch == 1 && !side_stream;
   if (batch > 1 && (uint64_t)p.nw * p.nst >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch too large for this n: windows x points must stay below 2^31");
   HIP_TRY(ctx, hipSetDevice(d.device));
   if ((uint64_t)p.nw * p.B + (uint64_t)p.nw * (n / p.seg_len) + 1024u >= (1ull << 32))
@@ -990,7 +1038,14 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
   if (int rc = ensure_buffers(ctx, d, ws, n, p, bases == nullptr && !share_recs)) return rc;
   release_shared_recs(d, ws, false);                        // (a slab the set's previous MSM still named: guarded by an event unless that MSM was seen to end)
   uint8_t* shared = nullptr;
-  if (share_recs) { const int si = acquire_shared_recs(ctx, d, share_src, n, p.curve, stream, &shared); if (si < 0) return si; ws.slab = si; }
+  bool have_recs = false;
+  if (share_recs) {
+    const int si = acquire_shared_recs(ctx, d, share_src, n, p.curve, stream, run, &shared, &have_recs);
+    if (si < 0) return si;
+    ws.slab = si; ws.slab_run = run;
+  }
+  // a launch sequence that fails half-way lets go of its slab (and of the slab's occupancy run) at once
+  struct slab_guard { gpu_t& d; workset_t& ws; bool armed; ~slab_guard() { if (armed) release_shared_recs(d, ws, false); } } guard{d, ws, share_recs};
   if (ws.used && ws.last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ws.ev_done, 0));   // the set's buffers are still the previous MSM's
   ws.plan = p; ws.n = n; ws.used = true; ws.last_stream = stream; __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
   ws.prof_level = ctx->opt_profile;
@@ -1002,6 +1057,7 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
   L.host_rows = msm_launch::rows_to_host(ctx, d, p, own_rows);
   ws.rows_on_host = L.host_rows;
   L.recs_rw = shared;
+  L.have_recs = have_recs;
   ws.recs_last = bases ? nullptr : (shared ? shared : ws.d_recs);
   if (bases) {
     // resident bases: the scalar-only stages, then the accumulation straight from the bound records (never captured: option "graph"
@@ -1040,6 +1096,10 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
       if (upload_points) { if (int rc = (*upload_points)(stream)) return rc; }
       if (int rc = L.front_points()) return rc;
     }
+    if (run && !have_recs) {                                 // the conversion is enqueued: later calls of the slab's run may skip theirs
+      HIP_TRY(ctx, hipGetLastError());
+      if (int rc = note_conversion(ctx, d.slabs[(size_t)ws.slab], stream)) return rc;
+    }
     if (int rc = L.accumulate()) return rc;
     L.mark(ST_TREE);
     if (int rc = L.back()) return rc;
@@ -1062,6 +1122,7 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
   // block: the caller's fetch_rows() ends it
   if (!own_rows) { if (int rc = finish_sequence(ctx, ws, stream)) return rc; }
   HIP_TRY(ctx, hipGetLastError());
+  guard.armed = false;
   return 0;
 }
 
@@ -1137,7 +1198,11 @@ void free_workset_buffers(workset_t& ws) {      // the big device buffers of a w
 
 void free_dev(gpu_t& d) {
   (void)hipSetDevice(d.device);
-  for (auto& sl : d.slabs) { if (sl.d) { (void)hipFree(sl.d); sl.d = nullptr; } for (hipEvent_t& e : sl.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
+  for (auto& sl : d.slabs) {
+    if (sl.d) { (void)hipFree(sl.d); sl.d = nullptr; }
+    for (hipEvent_t& e : sl.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (sl.conv_ev) { (void)hipEventDestroy(sl.conv_ev); sl.conv_ev = nullptr; }
+  }
   d.slabs.clear();
   for (hipEvent_t& e : d.acc_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   d.acc_prev = nullptr; d.acc_prev_stream = nullptr;
@@ -1941,7 +2006,8 @@ int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64
 
 int check_n(te_ctx* ctx, uint64_t n) { return n >= (1ull << 31) ? set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31") : 0; }
 
-int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, bool src_is_host, uint64_t n, uint8_t out[64]) {
+// share: how a single-device call from device-resident points keeps its records (share_mode; x-only points: SHARE_CONVERT)
+int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, bool src_is_host, uint64_t n, uint8_t out[64], share_mode share = SHARE_RUN) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   if (int rc = check_n(ctx, n)) return rc;
   if (n == 0) { write_identity(ctx->opt_curve, out); return 0; }
@@ -1978,7 +2044,7 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
     // on the side stream, beside the scalar-only kernels on ws.stream; the conversion to records follows it there
     return upload(ctx, ws, ws.d_in_points, static_cast<const uint8_t*>(src_points), n * sz.point_in, side);
   };
-  if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream, src_is_host ? &upload_points : nullptr, 0, false, 1, false, nullptr, !src_is_host)) return rc;
+  if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream, src_is_host ? &upload_points : nullptr, 0, false, 1, false, nullptr, src_is_host ? SHARE_NONE : share)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));          // (pinned sources included: the call ends after its uploads)
   release_shared_recs(d, ws);                               // the call is over: its record slab (if shared) may serve another point buffer
@@ -2013,7 +2079,7 @@ int te_msm_init(const int* device_ids, int n_dev, te_ctx** out) {
   if (const char* e = getenv("TE_MSM_HOST_STAGING")) ctx->opt_host_staging = e[0] != '0'; // option "host_staging"
   if (const char* e = getenv("TE_MSM_UPLOAD_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 16) ctx->opt_upload_threads = v; }   // option "upload_threads"
   if (const char* e = getenv("TE_MSM_FOLD_PAIRS")) ctx->opt_fold_pairs = e[0] != '0';    // option "fold_pairs"
-  if (const char* e = getenv("TE_MSM_SHARE_RECORDS")) ctx->opt_share_records = e[0] != '0';       // option "share_records"
+  if (const char* e = getenv("TE_MSM_SHARE_RECORDS")) ctx->opt_share_records = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;   // option "share_records"
   if (const char* e = getenv("TE_MSM_LANE_HOST_WAITS")) ctx->opt_lane_host_waits = e[0] != '0';   // option "lane_host_waits"
   if (const char* e = getenv("TE_MSM_HOST_SPLIT")) {                                     // relative piece weights "w0,w1,..." (experiments)
     const char* q = e;
@@ -2209,7 +2275,7 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
       dp = ws.d_in_points; ds = ws.d_in_scalars;
     }
     // a single-device context keeps its window shard (te_msm_set_window_shard); on several devices a ticket is a whole MSM
-    if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream, nullptr, 0, false, 1, multi, nullptr, !stage)) return rc;
+    if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream, nullptr, 0, false, 1, multi, nullptr, stage ? SHARE_NONE : SHARE_RUN)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
   // (Handing this to a host thread, as te_msm_submit_async does with uploads, was measured: no gain at n = 2^16 .. 2^18, 3-7 %
@@ -2753,7 +2819,7 @@ int te_msm_trim(te_ctx* ctx, int keep_worksets) {
     for (auto& sl : d.slabs) if (sl.users == 0 && sl.d) {                    // idle shared record slabs
       if (int rc = settle_slab(ctx, sl, nullptr, true)) return rc;
       for (workset_t& ws : d.ws) if (ws.recs_last == sl.d) ws.recs_last = nullptr;
-      HIP_TRY(ctx, hipFree(sl.d)); sl.d = nullptr; sl.cap = 0; sl.src = nullptr;
+      HIP_TRY(ctx, hipFree(sl.d)); sl.d = nullptr; sl.cap = 0; sl.src = nullptr; sl.converted = false;
     }
   }
   return freed;
@@ -2786,7 +2852,7 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
   if (!strcmp(key, "upload_threads")) { if (value < 1 || value > 16) return set_err(ctx, TE_MSM_EINVAL, "upload_threads must be in [1, 16]"); ctx->opt_upload_threads = (int)value; return 0; }
   if (!strcmp(key, "bind_affine")) { ctx->opt_bind_affine = value ? 1 : 0; return 0; }
   if (!strcmp(key, "lane_host_waits")) { ctx->opt_lane_host_waits = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "share_records")) { ctx->opt_share_records = value ? 1 : 0; return 0; }
+  if (!strcmp(key, "share_records")) { ctx->opt_share_records = value == 2 ? 2 : value ? 1 : 0; return 0; }
   if (!strcmp(key, "bind_fixed_base")) { if (value != 0 && (value < 16 || value > 21)) return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base must be 0 or in [16, 21]"); ctx->opt_bind_fixed_base = (int)value; return 0; }
   if (!strcmp(key, "exp_table_replicas")) { if (value < 1 || value > TE_BATCH_MAX) return set_err(ctx, TE_MSM_EINVAL, "exp_table_replicas must be in [1, 8]"); ctx->opt_exp_table_replicas = (int)value; return 0; }
   if (!strcmp(key, "scalar_chunks")) { if (value < 0 || value > 64) return set_err(ctx, TE_MSM_EINVAL, "scalar_chunks out of range"); ctx->opt_scalar_chunks = (int)value; return 0; }
@@ -2826,6 +2892,7 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "bind_affine")) { *value = ctx->opt_bind_affine; return 0; }
   if (!strcmp(key, "lane_host_waits")) { *value = ctx->opt_lane_host_waits; return 0; }
   if (!strcmp(key, "share_records")) { *value = ctx->opt_share_records; return 0; }
+  if (!strcmp(key, "record_conversions")) { *value = __atomic_load_n(&ctx->stat_record_conversions, __ATOMIC_RELAXED); return 0; }
   if (!strcmp(key, "record_slabs")) { int64_t t = 0; for (const gpu_t& d : ctx->devs) for (const auto& sl : d.slabs) if (sl.d) t++; *value = t; return 0; }
   if (!strcmp(key, "scalar_chunks")) { *value = ctx->opt_scalar_chunks; return 0; }
   if (!strcmp(key, "batch_small_max")) { *value = ctx->opt_batch_small_max; return 0; }
@@ -2996,7 +3063,7 @@ int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
     HIP_TRY(ctx, hipMemcpyAsync(sc.p, scalars_le, sbytes, hipMemcpyHostToDevice, lane.stream()));
     HIP_TRY(ctx, hipStreamSynchronize(lane.stream()));
   }
-  return run_common(ctx, pts.p, sc.p, false, n, out_xy_le);      // as te_msm_run_device (window shards, check_points, TE_MSM_ESCALAR)
+  return run_common(ctx, pts.p, sc.p, false, n, out_xy_le, SHARE_CONVERT);   // as te_msm_run_device (window shards, check_points, TE_MSM_ESCALAR)
 }
 
 // ---- batch scalar multiplication (te_msm_mul[_device], te_msm_mul_x; kernels in scalar_mul.hip.hpp) ------------------------------
@@ -3373,7 +3440,7 @@ int te_msm_partial_device(te_ctx* ctx, const void* d_points_xy_le, const void* d
   if (te_sched::slot_ticket(ws.slot)) return set_err(ctx, TE_MSM_ESTATE, "the selected work set holds a submitted MSM that has not been collected");
   HIP_TRY(ctx, hipSetDevice(d.device));
   return enqueue_partial(ctx, d, ws, d_points_xy_le, d_scalars_le, n, d_partials, stream == TE_MSM_OWN_STREAM ? ws.stream : (hipStream_t)stream,
-                         nullptr, 0, false, 1, false, nullptr, true);
+                         nullptr, 0, false, 1, false, nullptr, SHARE_CONVERT);
 }
 
 int te_msm_partial_device_batch(te_ctx* ctx, const void* const* d_points_xy_le, const void* const* d_scalars_le, uint64_t n, int count,
@@ -3390,9 +3457,9 @@ int te_msm_partial_device_batch(te_ctx* ctx, const void* const* d_points_xy_le, 
   if (te_sched::slot_ticket(ws.slot)) return set_err(ctx, TE_MSM_ESTATE, "the selected work set holds a submitted MSM that has not been collected");
   HIP_TRY(ctx, hipSetDevice(d.device));
   hipStream_t st = stream == TE_MSM_OWN_STREAM ? ws.stream : (hipStream_t)stream;
-  if (count == 1) return enqueue_partial(ctx, d, ws, d_points_xy_le[0], d_scalars_le[0], n, d_partials, st, nullptr, 0, false, 1, false, nullptr, true);
+  if (count == 1) return enqueue_partial(ctx, d, ws, d_points_xy_le[0], d_scalars_le[0], n, d_partials, st, nullptr, 0, false, 1, false, nullptr, SHARE_CONVERT);
   // the pointer arrays are only read while the launches are enqueued
-  return enqueue_partial(ctx, d, ws, d_points_xy_le, d_scalars_le, n, d_partials, st, nullptr, 0, false, count, false, nullptr, true);
+  return enqueue_partial(ctx, d, ws, d_points_xy_le, d_scalars_le, n, d_partials, st, nullptr, 0, false, count, false, nullptr, SHARE_CONVERT);
 }
 
 int te_msm_workset_stream(te_ctx* ctx, int workset, void** stream, int* hw_queue_class) {
