@@ -314,10 +314,6 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *                   what the last MSM ran with)
  *   "profile"       1 = HIP events around the dominant kernel (accumulate) only, 2 = around every stage
  *                   (te_msm_stage_ms); 0 = none (default)
- *   "graph"         1 = replay the launches before and after the accumulate kernel (five and five) as two HIP graphs, captured on
- *                   first use and re-captured when pointers, n or options change; 0 = launch every kernel (default: on
- *                   ROCm 7.2 / MI355X the replay measured ~5 % slower than plain launches).
- *                   Ignored at profile level 2.
  *   "host_chunks"   te_msm_run / te_msm_submit: pieces the point buffer (of one device's slice) is uploaded and processed
  *                   in, so that PCIe transfer and device work overlap; 0 = from n (3 from 3 * 2^18 points, 2 from 2^17,
  *                   else 1), 1 = whole.  Twisted-Edwards: all scalars go first, in one copy (the link is the bottleneck);
@@ -325,7 +321,12 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *   "host_shard_min" multi-device te_msm_run: smallest slice worth a device of its own (default 4096 points)
  *   "upload_threads" host threads per device that take te_msm_submit_async / te_msm_submit_scalars tickets (1..16, default 4; env
  *                   TE_MSM_UPLOAD_THREADS).  Scalars-only tickets (bound bases) cross the link one at a time per device whatever the
- *                   number of threads (side by side they only delay each other: profiles/r06_bound_host_tickets_gap.txt)
+ *                   number of threads (side by side they only delay each other: profiles/r06_bound_host_tickets_gap.txt).
+ *                   A lane thread waits for each of its uploads on the host before it enqueues the kernels that read it (a stream wait in
+ *                   front of them would hold up other tickets' kernels in a shared hardware queue).  The calling thread of te_msm_run* /
+ *                   te_msm_submit waits the same way when its buffers are pageable (the copy call blocks for the copy anyway); pinned
+ *                   buffers keep the stream waits.  No packet of the upload path enters a hardware queue shared with other tickets'
+ *                   kernels (profiles/r06_caller_host_waits.txt).
  *   "host_staging"  0 (default) = host buffers are copied straight from the caller's memory: the fastest form while the caller
  *                   REUSES its buffers (the runtime keeps pages it has copied from registered: 2.35 ms per 2^20-point call), but
  *                   the first call on a buffer costs 4.7-5.0 ms and a caller that allocates fresh buffers for every call pays
@@ -351,25 +352,12 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *                   counts them).  A lone call on several devices runs on ONE of them (one bucket set: nothing to shard); tickets use all.
  *                   "window_bits", "signed_digits", "segment_len" = 0 do not apply to such MSMs; a window-sharded single-device context
  *                   keeps the ordinary windows.  Read at bind time.
- *   "exp_table_replicas" 1..8 (default 1; EXPERIMENT, read at bind time): keeps that many copies of the bound records and lets the windows
- *                   of a device-scalar MSM gather from different copies -- the gather footprint of a per-window table with the arithmetic
- *                   unchanged (profiles/r06_fixed_base_windows.txt, step 1).  Same results.
  *   "share_records" 1 (default) = whole-MSM calls from device-resident inputs (te_msm_submit_device, te_msm_run_device) that name the same
  *                   point buffer while in flight share one record slab and convert it once per occupancy run, see te_msm_submit_device;
  *                   2 = shared slabs, every call converts (the round-6 form); 0 = one slab per work set, every call converts (A/B; env
  *                   TE_MSM_SHARE_RECORDS).  Read-only "record_slabs": slabs allocated; read-only "record_conversions": point -> record
  *                   conversions the context's MSM launch sequences have enqueued (one per launch that converts; bound point sets
  *                   not included).
- *   "lane_host_waits" 1 (default) = the lane thread of an asynchronous ticket (te_msm_submit_async, te_msm_submit_scalars) waits for each of
- *                   its uploads on the host before it enqueues the kernels that read it; 0 = a stream wait in front of those kernels, which
- *                   holds up other tickets' kernels in a shared hardware queue (A/B; env TE_MSM_LANE_HOST_WAITS; profiles/r06_lane_host_waits.txt).
- *                   The calling thread of te_msm_run* / te_msm_submit waits the same way when its buffers are pageable (the copy call
- *                   blocks for the copy anyway); pinned buffers keep the stream waits.  No packet of the upload path enters a hardware
- *                   queue shared with other tickets' kernels (profiles/r06_bound_host_tickets_gap.txt, r06_caller_host_waits.txt).
- *                   The earlier forms stay behind environment switches for A/B runs, read once per process and covered by
- *                   tests/test_gpu_tickets.py::test_upload_path_switches_agree: TE_MSM_COPY_MARKER=1, TE_MSM_LANE_EVENT_WAITS=1,
- *                   TE_MSM_SCALAR_UPLOADS_SERIAL=0, TE_MSM_CALLER_HOST_WAITS=0, TE_MSM_COPY_PRIORITY=1|-1; TE_MSM_SERIAL_ACCUMULATE=1
- *                   chains the accumulations of the MSMs in flight (slower: profiles/r06_serial_accumulate_experiment.txt).
  *   "scalar_chunks" te_msm_run_scalars / te_msm_submit_scalars: pieces the scalars of a bound point set are uploaded and processed
  *                   in; 0 = from n (default), 1 = whole.  The result does not depend on it.
  *   "batch_small_max" te_msm_run_scalars_batch*: MSMs of at most this many points share launch sequences, longer ones run alone
@@ -400,9 +388,7 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *                   4 bytes per entry instead of 6; 0 = the general form (u16 key + u32 index; what larger n always uses).
  *                   Same result (A/B measurements, tests; env TE_MSM_PACKED)
  *   "fold_pairs"    1 (default) = a fold level of the bucket reduction with 32 768 .. 65 535 outputs (n <= 2^18) runs two lanes per
- *                   output -- half the dependent additions; 0 = one thread per output (A/B measurements; env TE_MSM_FOLD_PAIRS)
- *   "fuse_prep"     1 (default) = device-resident Twisted-Edwards inputs: the points -> records conversion shares the launch
- *                   of the sort's first level; 0 = a launch of its own (A/B measurements; env TE_MSM_FUSE_PREP) */
+ *                   output -- half the dependent additions; 0 = one thread per output (A/B measurements; env TE_MSM_FOLD_PAIRS) */
 int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value);
 int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value);
 

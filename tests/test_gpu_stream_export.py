@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # what the child runs: the recipe, a context close with a pinned tensor still alive, a second context that takes the parked
 # streams over, and pinned tensors that are only released at interpreter exit
 CHILD = r'''
-import importlib, os, sys
+import importlib, sys
 sys.path.insert(0, %(root)r)
 pkg = importlib.import_module("webgpu-msm-twisted-edwards_amd")
 import torch
@@ -53,23 +53,16 @@ for round_ in range(2):
             torch.cuda.ExternalStream(st).synchronize()
             got = pkg.finalize_host(host.numpy().tobytes(), cb, W)
             assert got == want, "rows copied on the exported stream"
-        if os.environ.get("TE_CHILD_RELEASE_EARLY") == "1":      # (tools/diag_exported_streams.py: the control -- nothing outlives the context)
-            del host
-            tmp = torch.zeros(1 << 20, dtype=torch.uint8).pin_memory()
-            del tmp
-            torch.cuda.synchronize()
-            continue
         keep.append(host)                                        # outlives the context: released after te_msm_destroy
     if round_ == 0:
         del host
         keep.clear()                                             # released between two contexts: event record on a parked stream
         tmp = torch.zeros(1 << 20, dtype=torch.uint8).pin_memory()   # makes the allocator process its pending events
         del tmp
-if os.environ.get("TE_MSM_PARK_STREAMS", "1") != "0":
-    # the second context took the first one's parked streams over (the same eight handles, in some order): the pool does not grow
-    assert len(all8[0]) == pkg.WORKSETS and all8[0] == all8[1], all8
-    s = torch.cuda.ExternalStream(handles[-1])
-    s.synchronize()                                              # still a valid stream after the context is gone
+# the second context took the first one's parked streams over (the same eight handles, in some order): the pool does not grow
+assert len(all8[0]) == pkg.WORKSETS and all8[0] == all8[1], all8
+s = torch.cuda.ExternalStream(handles[-1])
+s.synchronize()                                                  # still a valid stream after the context is gone
 print("child ok", len(keep), flush=True)
 # `keep` holds a pinned tensor used on an exported stream: it is released at interpreter exit
 '''

@@ -360,20 +360,32 @@ print("ok")
 
 
 def test_upload_path_switches_agree(pkg, wasm_golden):
-    """Round 6 took three marker packets out of the upload path of host-buffer MSMs (csrc/te_msm.hip: copy_stream_behind_previous,
-    lane_wait, gpu_t::scalar_link, caller_may_wait_on_host; profiles/r06_bound_host_tickets_gap.txt) and kept the old forms behind
-    environment switches for A/B runs: every combination gives the reference's own output -- tickets over bound bases, host-buffer
-    tickets (lane threads and the calling thread), lone calls, work sets reused across rounds, one and two "devices".
-    Child processes: the switches are read once per process."""
+    """The upload path of host-buffer MSMs without marker packets (csrc/te_msm.hip: copy_stream_behind_previous, lane_wait,
+    gpu_t::scalar_link, caller_may_wait_on_host; profiles/r06_bound_host_tickets_gap.txt), straight from the caller's memory and
+    through the pinned staging rings (TE_MSM_HOST_STAGING=1): both give the reference's own output -- tickets over bound bases,
+    host-buffer tickets (lane threads and the calling thread), lone calls, work sets reused across rounds, one and two "devices".
+    Child processes: the environment is read when a context is created."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     g = next(x for x in wasm_golden if x["name"] == "random_n65536")
     arg = json.dumps({k: g[k] for k in ("seed", "n", "mode", "x", "y")})
-    for env in ({}, {"TE_MSM_COPY_MARKER": "1", "TE_MSM_LANE_EVENT_WAITS": "1", "TE_MSM_SCALAR_UPLOADS_SERIAL": "0", "TE_MSM_CALLER_HOST_WAITS": "0"},
-                {"TE_MSM_LANE_EVENT_WAITS": "1"}, {"TE_MSM_SCALAR_UPLOADS_SERIAL": "0"}, {"TE_MSM_CALLER_HOST_WAITS": "0", "TE_MSM_LANE_HOST_WAITS": "0"},
-                {"TE_MSM_COPY_PRIORITY": "1"}, {"TE_MSM_HOST_STAGING": "1"}):
+    for env in ({}, {"TE_MSM_HOST_STAGING": "1"}):
         r = subprocess.run([sys.executable, "-c", UPLOAD_SWITCH_CHILD % {"root": root}, arg], env=dict(os.environ, **env),
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert r.returncode == 0 and r.stdout.decode().strip().endswith("ok"), (env, r.stderr.decode()[-2000:])
+
+
+RETIRED_OPTIONS = ("graph", "fuse_prep", "lane_host_waits", "exp_table_replicas")
+
+
+def test_retired_option_keys_are_refused(pkg):
+    """the keys of A/B forms that were measured and dropped are unknown options: set and get answer TE_MSM_EINVAL (-1)"""
+    with pkg.MsmContext((0,)) as c:
+        for key in RETIRED_OPTIONS:
+            for call in (lambda: c.set_option(key, 0), lambda: c.set_option(key, 1), lambda: c.get_option(key)):
+                with pytest.raises(pkg.MsmError) as e:
+                    call()
+                assert e.value.code == -1 and "unknown option" in str(e.value), (key, str(e.value))
+        assert c.get_option("prezero") == 1 and c.get_option("fold_pairs") == 1      # the context still answers

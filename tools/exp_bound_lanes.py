@@ -1,5 +1,5 @@
 """Bound bases, host scalars, 8 tickets in flight at n = 2^20 and 2^18: upload lanes 1..6 (option "upload_threads") with the lane thread waiting for
-its upload (lane_host_waits = 1), three rounds alternating.  python tools/exp_bound_lanes.py"""
+its upload on the host, three rounds alternating.  python tools/exp_bound_lanes.py"""
 import importlib, sys, time
 sys.path.insert(0, '.')
 pkg = importlib.import_module("webgpu-msm-twisted-edwards_amd")

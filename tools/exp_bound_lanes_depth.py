@@ -1,5 +1,5 @@
 """Bound bases, host scalars at n = 2^20 (and host-buffer tickets): upload lanes 1 / 2 / 3 / 4 x tickets in flight 2 / 4 / 6 / 8, two rounds, after the
-marker of the copy stream went away (tools/exp_bound_copy_queue.py).  python tools/exp_bound_lanes_depth.py"""
+marker of the copy stream went away (profiles/r06_bound_host_tickets_gap.txt).  python tools/exp_bound_lanes_depth.py"""
 import importlib, sys, time
 sys.path.insert(0, '.')
 pkg = importlib.import_module("webgpu-msm-twisted-edwards_amd")

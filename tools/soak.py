@@ -29,8 +29,8 @@ while time.time() < t_end:
     opts = {}
     for k, v in (("window_bits", rnd.choice([0, 0, 4, 7, 10, 13, 15, 16])), ("signed_digits", rnd.choice([1, 1, 0])),
                  ("segment_len", rnd.choice([0, 0, 64, 1, 7, 500])), ("sort_buckets", rnd.choice([1, 1, 0])), ("host_chunks", rnd.choice([0, 1, 3, 5])),
-                 ("graph", rnd.choice([0, 0, 1])), ("profile", rnd.choice([0, 0, 1, 2])), ("prezero", rnd.choice([1, 1, 0])),
-                 ("fuse_prep", rnd.choice([1, 1, 0])), ("packed_sort", rnd.choice([1, 1, 0])), ("fold_pairs", rnd.choice([1, 1, 0])),
+                 ("profile", rnd.choice([0, 0, 1, 2])), ("prezero", rnd.choice([1, 1, 0])),
+                 ("packed_sort", rnd.choice([1, 1, 0])), ("fold_pairs", rnd.choice([1, 1, 0])),
                  ("host_staging", rnd.choice([0, 0, 1]))):
         ctx.set_option(k, v)
         opts[k] = v
@@ -69,7 +69,6 @@ while time.time() < t_end:
     if bound_mode:
         # round 6: resident bases -- bind once (ordinary records; BLS12-377: affine or projective; Twisted-Edwards: now and then a
         # fixed-base table), then lone calls and tickets from host and device scalars in random order, a release and a second bind in between
-        ctx.set_option("graph", 0)
         ctx.set_option("scalar_chunks", rnd.choice([0, 0, 1, 2, 4]))
         ctx.set_option("bind_affine", rnd.choice([1, 1, 0]))
         ctx.set_option("bind_fixed_base", rnd.choice([0, 0, 0, 16, 17, 18, 19, 20, 21]) if ctx.curve == pkg.CURVE_TE_BLS12 else 0)
@@ -121,7 +120,6 @@ while time.time() < t_end:
     elif mode == "multi_tickets":
         # round 5: whole-MSM tickets on a context of several "devices" -- blocking, asynchronous and device-resident submits mixed,
         # collected in random order, now and then beside a lone call (point slices / window shards over all devices) and a trim
-        ctx.set_option("graph", 0)
         ctx.set_option("stage_device_inputs", rnd.choice([0, 1]))
         keep, tickets = [], []
         for p, s, n in batch:

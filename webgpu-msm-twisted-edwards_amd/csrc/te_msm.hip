@@ -80,8 +80,6 @@ struct plan_t {
   int fb_rb = 0, fb_c = 0, fb_W = 0;
 };
 
-struct graph_key { const void *pts, *sc, *out; uint64_t n, generation; int c, w_first, w_step, seg_len, sort; };
-
 // Everything one MSM in flight needs on the device.  A GPU owns TE_MSM_WORKSETS work sets with their own streams so that
 // several MSMs overlap ON THE DEVICE: the launch gaps and the latency-bound reduction tail of one are filled by the wide kernels of the
 // other (te_msm_submit_device alternates them; "workset" option for te_msm_partial_device callers).
@@ -121,8 +119,6 @@ struct workset_t {
   std::string job_err;                // why that job failed (written by the device's host thread before the job is marked done)
   int prof_level = 0;                 // profile level the events of the last enqueue were recorded at
   hipStream_t last_stream = nullptr;  // stream of the previous MSM on this set: a different one must wait for it (scratch reuse)
-  uint64_t generation = 0;            // bumped whenever ensure() reallocates a buffer of this set
-  hipGraphExec_t g_front = nullptr, g_back = nullptr; graph_key g_key = {};
   // host-buffer MSMs (te_msm_run, te_msm_submit): device copies of the caller's buffers, sized in bytes for the curve of the
   // call, and the "piece i has arrived" events of an upload in pieces
   void *d_in_points = nullptr, *d_in_scalars = nullptr; size_t cap_in_points = 0, cap_in_scalars = 0;
@@ -173,13 +169,8 @@ struct gpu_t {
   // asynchronous scalars-only tickets (bound bases) cross the link ONE AT A TIME per device: lanes that upload side by side share the
   // link, every ticket reaches the device late and the tickets move in a convoy (two in flight: 1.05-1.23 ms per MSM with 2-4 lanes,
   // 0.90-0.92 with one; tools/exp_bound_lanes_depth.py).  Host-buffer tickets (points + scalars) do not take it: their pageable copies
-  // fill each other's pin / unpin gaps (1.79 vs 1.89 ms with one lane).  TE_MSM_SCALAR_UPLOADS_SERIAL=0: off (experiments).
+  // fill each other's pin / unpin gaps (1.79 vs 1.89 ms with one lane).
   std::unique_ptr<std::mutex> scalar_link{new std::mutex};
-  // EXPERIMENT TE_MSM_SERIAL_ACCUMULATE=1 (tools/exp_serial_accumulate.py): the k_accumulate launches of a device form a chain -- each waits
-  // for the one enqueued before it on another stream --, so that ONE accumulation runs at full width beside the small kernels of the other
-  // MSMs in flight instead of two at half speed
-  std::unique_ptr<std::mutex> acc_mu{new std::mutex};
-  hipEvent_t acc_ev[16] = {}; uint32_t acc_next = 0; hipEvent_t acc_prev = nullptr; hipStream_t acc_prev_stream = nullptr;
   // input-point validation (option "check_points", te_msm_check_points*): a stream, a piece buffer for host points and the report word
   // of its own, shared by every thread that checks on this device (upload lanes of asynchronous tickets included) under chk_mu
   std::unique_ptr<std::mutex> chk_mu{new std::mutex};
@@ -208,7 +199,6 @@ struct te_ctx {
   int64_t stat_peer_bytes = 0;      // bytes those copies moved (get_option "peer_bytes")
   int64_t stat_fb_fallbacks = 0;    // fixed-base MSMs whose rows overflowed (skewed scalars) and were run again with the ordinary windows
   int64_t stat_entries = 0;         // non-zero window digits (= accumulated entries) of the MSM whose result was fetched last (get_option "entries_accumulated")
-  std::vector<double> host_split;   // TE_MSM_HOST_SPLIT (relative piece weights of a host-buffer upload; experiments), read once
   int opt_host_shard_min = 4096;    // multi-device te_msm_run: points per device below which fewer devices are used
   int opt_queue_probe = 1;          // 1 = the first te_msm_submit* measures the hardware queues (lazily); 0 = never; te_msm_probe_queues does it now
   int opt_window_bits = 0;
@@ -218,9 +208,7 @@ struct te_ctx {
   int opt_profile = 0;
   int opt_seg_len = 0;         // work segment: at most this many entries of one bucket per thread; 0 = from n (make_plan)
   int opt_host_chunks = 0;     // te_msm_run: pieces a large host buffer is uploaded and processed in (0 = choose from n)
-  int opt_graph = 0;           // replay the launch sequence around k_accumulate as HIP graphs
   int opt_workset = 0;         // work set used by te_msm_run* / te_msm_partial_device
-  int opt_fuse_prep = 1;       // device-resident inputs: convert the points in the launch of the sort's first level (k_part_scatter_prep)
   int opt_fold_pairs = 1;      // first fold level of small MSMs with two lanes per output (k_sum_groups<N, true>)
   int opt_packed = 1;          // level-1 sort entries as one 32-bit word where n <= 2^23 (make_plan)
   int opt_prezero = 1;         // clear a work set's zeroed block behind an MSM's read-back instead of in front of the next MSM's first kernel
@@ -237,10 +225,6 @@ struct te_ctx {
   int opt_share_records = 1;     // shared record slabs for calls in flight that name the same device-resident point buffer, converted once per occupancy run;
                                  // 2 = shared slabs, every call converts (the round-6 form; A/B: option "share_records", env TE_MSM_SHARE_RECORDS)
   int64_t stat_record_conversions = 0;   // point -> record conversions the MSM launch sequences enqueued (get_option "record_conversions")
-  int opt_lane_host_waits = 1;   // asynchronous tickets (a lane thread enqueues them): the thread WAITS for each upload before it enqueues the kernels that read
-                                 // it, instead of putting a stream wait in front of them (see lane_wait; A/B: option "lane_host_waits", env TE_MSM_LANE_HOST_WAITS)
-  int opt_exp_table_replicas = 1; // EXPERIMENT (profiles/r06_fixed_base_windows.txt): te_msm_bind_points keeps this many copies of the records and
-                                 // the windows of a device-scalar MSM gather from different copies -- the gather footprint of a per-window table
   int64_t opt_batch_small_max = 1ll << 15;   // te_msm_run_scalars_batch: MSMs up to this length share launch sequences (option "batch_small_max")
   int64_t stat_batch_sequences = 0;          // launch sequences the last batch call ran (get_option "batch_sequences")
 };
@@ -253,7 +237,6 @@ struct te_bases {
   int curve = TE_MSM_CURVE_TE_BLS12, rec_kind = 0;
   size_t rec_bytes = 0;
   std::vector<uint8_t*> recs;    // recs[i]: n records in the memory of ctx->devs[i]
-  int replicas = 1;              // experiment "exp_table_replicas": copies of the records behind each other in recs[i]
   int fb_c = 0, fb_W = 0;        // fixed-base windows: recs[i] holds fb_W tables of n records, table w = records of 2^(fb_c w) P_i (table 0 = the ordinary records)
   int in_flight = 0;             // tickets not collected that gather from it (the set cannot be released under them)
 };
@@ -371,7 +354,6 @@ void make_plan(const te_ctx* ctx, const gpu_t& d, uint64_t n, plan_t& p, int for
 template <typename T> int ensure(te_ctx* ctx, workset_t& ws, T*& ptr, size_t& cap_bytes, size_t need_elems) {
   const size_t need = need_elems * sizeof(T);
   if (ptr && need <= cap_bytes) return 0;
-  ws.generation++;                     // captured graphs hold the old pointer
   if (ptr) HIP_TRY(ctx, hipFree(ptr));
   ptr = nullptr; cap_bytes = 0;
   HIP_TRY(ctx, hipMalloc((void**)&ptr, need ? need : 16));
@@ -432,13 +414,12 @@ template <int C> void launch_digits_ragged(const void* sc, const te::ragged_tab&
 }
 static_assert(TE_RAGGED_MAX == TE_BATCH_SEQ_MAX && TE_BATCH_SEQ_MAX == TE_MSM_BATCH_SEQ_MAX, "ragged tables");
 
-// One MSM's device work in three parts, so that the parts before and after the dominant kernel can be replayed as HIP
-// graphs (one launch each instead of ~30: the host-side enqueue cost, ~0.35 ms, is what bounds small MSMs and the
-// per-rank step of a window-sharded one) while k_accumulate stays an ordinary launch bracketed by timing events.
+// One MSM's device work in three parts: the stages before the dominant kernel, k_accumulate (bracketed by timing events),
+// and the stages after it.
 struct msm_launch {
-  te_ctx* ctx; gpu_t& d; workset_t& ws; plan_t p;
+  te_ctx* ctx; workset_t& ws; plan_t p;
   const void* d_points; const void* d_scalars; uint64_t n; void* d_partials_out;   // batch > 1: d_points / d_scalars are arrays of p.batch device pointers (on the host)
-  int prof;                       // event marks inside front()/back() only at profile level 2 (never inside a capture)
+  int prof;                       // event marks inside front()/back() only at profile level 2
   hipStream_t stream;
   bool own_rows = false;          // rows go to ws.d_partials: the caller fetches flag + rows with one copy
   bool onto = false;              // a later piece of a host-buffer MSM: keep the final-carry flag, add onto the buckets
@@ -448,16 +429,15 @@ struct msm_launch {
   bool have_recs = false;         // recs_rw holds this call's records already (converted earlier in the slab's occupancy run): no conversion
   void count_conversion() const { __atomic_fetch_add(&ctx->stat_record_conversions, (int64_t)1, __ATOMIC_RELAXED); }
   const uint32_t* fb_remap = nullptr;   // fixed-base windows: the digit rows were filled by k_fb_digits (no k_digits launch); the level-1 scatter maps positions through it
-  int table_replicas = 1;         // experiment "exp_table_replicas": window k gathers from copy k / ceil(windows / copies) of the bound records
   const uint8_t* bound = nullptr; // records of a bound point set (te_msm_bind_points), already offset to this launch's first point: no conversion,
                                   // k_accumulate gathers from here instead of ws.d_recs (p.rec_kind tells which record form)
   const te::ragged_tab* ragged = nullptr;   // a ragged sequence (te_msm_run_scalars_batch): d_scalars is ONE packed buffer, MSM m's scalars at
                                   // ragged->off[m] with ragged->len[m] of them (k_digits_ragged); every window gathers from `bound` itself
   // Own rows of a context that computes ALL windows can be written to host memory by the tail kernel (every row slot is
   // rewritten by every MSM).  Not with window shards (rows of foreign windows must read as zero: they come from the cleared
-  // device block), not with captured graphs (fixed pointers), not with "prezero" = 0 (stage verifiers read the device rows).
+  // device block), not with "prezero" = 0 (stage verifiers read the device rows).
   static bool rows_to_host(const te_ctx* ctx, const gpu_t& d, const plan_t& p, bool own_rows) {
-    return own_rows && p.nw > 0 && p.batch == 1 && p.w_first == 0 && p.w_step == 1 && ctx->opt_prezero && !ctx->opt_graph;
+    return own_rows && p.nw > 0 && p.batch == 1 && p.w_first == 0 && p.w_step == 1 && ctx->opt_prezero;
   }
   uint32_t n32() const { return (uint32_t)n; }
   uint32_t total() const { return (uint32_t)p.nw * p.B; }
@@ -468,10 +448,10 @@ struct msm_launch {
   void mark(int i) const { if (prof >= 2 || (prof == 1 && (i == ST_ACCUM || i == ST_ACCUM + 1))) (void)hipEventRecord(ws.ev[i], stream); }
 
   // device-resident inputs, no per-stage timing: the record conversion rides in the launch of the sort's first level
-  bool can_fuse_prep() const { return ctx->opt_fuse_prep && prof < 2 && p.nw > 0; }
+  bool can_fuse_conversion() const { return prof < 2 && p.nw > 0; }
   int front() {
     if (have_recs) return front_scalars();
-    if (can_fuse_prep()) return front_scalars(true);
+    if (can_fuse_conversion()) return front_scalars(true);
     if (int rc = front_scalars()) return rc;
     return front_points();
   }
@@ -487,7 +467,6 @@ struct msm_launch {
 
   // record slab of MSM m: MSMs of one call that name the same point buffer share one conversion (same pointer in one call =
   // same data; nothing is remembered across calls).  slab = index of the first MSM with that pointer.
-  te::batch_slabs replica_slabs() const { te::batch_slabs r; for (int j = 0; j < TE_BATCH_MAX; j++) r.s[j] = (uint32_t)j; return r; }
   te::batch_slabs slabs() const {
     te::batch_slabs r; memset(&r, 0, sizeof r);
     for (int m = 0; m < p.batch; m++) {
@@ -636,25 +615,12 @@ struct msm_launch {
       const uint32_t n32 = this->n32(), smax = this->smax();
       const uint32_t* order = ctx->opt_sort ? ws.d_order : nullptr;
       using slot_t = typename te::rec_kind<N, RK>::slot;
-      static const bool serial = [] { const char* e = getenv("TE_MSM_SERIAL_ACCUMULATE"); return e && e[0] == '1'; }();
-      std::unique_lock<std::mutex> chain(*d.acc_mu, std::defer_lock);
-      if (serial && !ctx->opt_graph) {
-        chain.lock();
-        if (d.acc_prev && d.acc_prev_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, d.acc_prev, 0));
-      }
       hipLaunchKernelGGL((te::k_accumulate<N, RK>), dim3((smax + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const slot_t*>(bound ? bound : recs_out()), ws.d_sorted,
                          ws.d_bucket_start, ws.d_bucket_count, ws.d_seg_base, ws.d_seg_bucket, ws.d_seg_lenv, order, ws.d_num_seg,
                          reinterpret_cast<te::ete_t<N>*>(ws.d_buckets), reinterpret_cast<te::ete_t<N>*>(ws.d_seg_out), n32, p.logB, p.seg_len, smax, onto ? 1u : 0u,
                          // (a ragged sequence: every window's k / nw is 0 -- record slab 0, the bound set itself, for any number of MSMs)
-                         ragged ? (uint32_t)p.nw : table_replicas > 1 ? (uint32_t)((p.nw1 + table_replicas - 1) / table_replicas) : (uint32_t)p.nw1,
-                         ragged ? te::batch_slabs{} : table_replicas > 1 ? replica_slabs() : slabs(),
+                         ragged ? (uint32_t)p.nw : (uint32_t)p.nw1, ragged ? te::batch_slabs{} : slabs(),
                          prof ? reinterpret_cast<unsigned long long*>(ws.d_zero + Z_CLOCK) : nullptr);
-      if (chain.owns_lock()) {
-        hipEvent_t& ev = d.acc_ev[d.acc_next++ % 16u];
-        if (!ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventRecord(ev, stream));
-        d.acc_prev = ev; d.acc_prev_stream = stream;
-      }
     }
     return 0;
   }
@@ -753,21 +719,6 @@ struct msm_launch {
   }
 };
 
-// Captures fn (a sequence of launches on ws.stream) into an executable graph.
-template <typename F> int capture_graph(te_ctx* ctx, workset_t& ws, hipGraphExec_t& exec, F&& fn) {
-  if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
-  hipGraph_t graph = nullptr;
-  HIP_TRY(ctx, hipStreamBeginCapture(ws.stream, hipStreamCaptureModeThreadLocal));
-  const int rc = fn();
-  const hipError_t e = hipStreamEndCapture(ws.stream, &graph);
-  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  HIP_TRY(ctx, e);
-  const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  HIP_TRY(ctx, ei);
-  return 0;
-}
-
 // d_partials_out == nullptr: the rows go to the work set's own buffer (ws.d_partials, inside the block that is zeroed per
 // MSM) and the caller fetches flag + rows with fetch_rows().
 // upload_points (optional): enqueues the host-to-device copy of the points on the given (side) stream -- te_msm_run; the
@@ -781,15 +732,6 @@ template <typename F> int capture_graph(te_ctx* ctx, workset_t& ws, hipGraphExec
 // device-resident inputs owns one stream per work set
 int need_copy_stream(te_ctx* ctx, workset_t& ws) {
   if (ws.copy_stream) return 0;
-  // TE_MSM_COPY_PRIORITY=1 (experiment, tools/exp_bound_copy_queue.py): the runtime keeps streams of another priority on hardware
-  // queues of their own, so an upload would never stand behind a kernel of a work set that shares its queue
-  static const int prio = [] { const char* e = getenv("TE_MSM_COPY_PRIORITY"); return e ? atoi(e) : 0; }();
-  if (prio) {
-    int least = 0, greatest = 0;
-    HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIP_TRY(ctx, hipStreamCreateWithPriority(&ws.copy_stream, hipStreamNonBlocking, prio > 0 ? greatest : least));
-    return 0;
-  }
   HIP_TRY(ctx, hipStreamCreateWithFlags(&ws.copy_stream, hipStreamNonBlocking));
   return 0;
 }
@@ -859,10 +801,9 @@ void deal_over_classes(const int* cls, int n, int ncls, int* order) {
 // process aborts (round 5: tools/exp_batch_small.py "dumped core" after its last result line; profiles/r06_batch_small_abort.txt).
 // So the streams of a device whose handles were exported are PARKED by te_msm_destroy -- synchronised, kept alive, and taken
 // over by the next context on that device -- and stay valid hipStream_t values until the process exits.  A context that never
-// exported a handle destroys its streams as before.  (env TE_MSM_PARK_STREAMS=0: the old behaviour, for the diagnosis only.)
+// exported a handle destroys its streams as before.
 struct parked_streams_t { std::mutex mu; std::vector<std::pair<int, hipStream_t>> v; };
 parked_streams_t& parked_streams() { static parked_streams_t* p = new parked_streams_t(); return *p; }     // (leaked on purpose: no destructor at exit)
-bool park_exported_streams() { static const bool on = [] { const char* e = getenv("TE_MSM_PARK_STREAMS"); return !(e && e[0] == '0'); }(); return on; }
 hipStream_t take_parked_stream(int device) {
   parked_streams_t& ps = parked_streams();
   std::lock_guard<std::mutex> lk(ps.mu);
@@ -1020,7 +961,7 @@ void release_shared_recs(gpu_t& d, workset_t& ws, bool completed = true) {
 enum share_mode { SHARE_NONE = 0, SHARE_CONVERT = 1, SHARE_RUN = 2 };
 
 // bases: the launch sequence gathers from a bound point set (d_points is not read: no conversion); batch must be 1
-// share: the record slab of the call (share_mode); a shared slab only for device-resident points, without graphs or bound bases
+// share: the record slab of the call (share_mode); a shared slab only for device-resident points, without bound bases
 int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, const void* d_scalars, uint64_t n,
                     void* d_partials_out, hipStream_t stream, const std::function<int(hipStream_t)>* upload_points = nullptr, int force_c = 0,
                     bool side_stream = false, int batch = 1, bool whole = false, const te_bases* bases = nullptr, share_mode share = SHARE_NONE) {
@@ -1029,7 +970,7 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
   // (a batch shares when all its MSMs name ONE point buffer: the batch then holds one conversion anyway -- slab 0 of msm_launch::slabs())
   const void* share_src = d_points;
   if (batch > 1 && d_points) { share_src = static_cast<const void* const*>(d_points)[0]; for (int m = 1; m < batch; m++) if (static_cast<const void* const*>(d_points)[m] != share_src) share_src = nullptr; }
-  const bool share_recs = share != SHARE_NONE && ctx->opt_share_records && !bases && !upload_points && !ctx->opt_graph && share_src != nullptr;
+  const bool share_recs = share != SHARE_NONE && ctx->opt_share_records && !bases && !upload_points && share_src != nullptr;
   const bool run = share_recs && share == SHARE_RUN && ctx->opt_share_records == 1 && !ctx->opt_check_points && batch == 1 && !side_stream;
   if (batch > 1 && (uint64_t)p.nw * p.nst >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch too large for this n: windows x points must stay below 2^31");
   HIP_TRY(ctx, hipSetDevice(d.device));
@@ -1053,43 +994,22 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
   if (own_rows) d_partials_out = ws.d_partials;
   // profile 1: two events around the dominant kernel only (what bench.py times live); 2: every stage boundary
   // (an event between two kernels costs ~4 us of idle stream time, 11 of them ~2 % of a 2^20 MSM)
-  msm_launch L{ctx, d, ws, p, d_points, d_scalars, n, d_partials_out, ctx->opt_profile, stream, own_rows};
+  msm_launch L{ctx, ws, p, d_points, d_scalars, n, d_partials_out, ctx->opt_profile, stream, own_rows};
   L.host_rows = msm_launch::rows_to_host(ctx, d, p, own_rows);
   ws.rows_on_host = L.host_rows;
   L.recs_rw = shared;
   L.have_recs = have_recs;
   ws.recs_last = bases ? nullptr : (shared ? shared : ws.d_recs);
   if (bases) {
-    // resident bases: the scalar-only stages, then the accumulation straight from the bound records (never captured: option "graph"
-    // holds the pointers of device-resident point buffers)
+    // resident bases: the scalar-only stages, then the accumulation straight from the bound records
     L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];
-    L.table_replicas = bases->replicas;
     if (int rc = L.front_scalars()) return rc;
     L.mark(ST_PREP);
     if (int rc = L.accumulate()) return rc;
     L.mark(ST_TREE);
     if (int rc = L.back()) return rc;
-  } else if (ctx->opt_graph && ctx->opt_profile < 2 && !upload_points && batch == 1) {
-    // the graphs hold pointers and geometry: re-captured when any of them changes (including a buffer reallocation);
-    // the captured front always clears the zeroed block itself
-    ws.zero_clean_words = 0;
-    graph_key key; memset(&key, 0, sizeof key);          // padding bytes take part in the memcmp below
-    key.pts = d_points; key.sc = d_scalars; key.out = d_partials_out; key.n = n; key.generation = ws.generation;
-    key.c = p.c; key.w_first = p.w_first; key.w_step = p.w_step; key.seg_len = (int)p.seg_len;
-    key.sort = ctx->opt_sort | (ctx->opt_signed << 1) | (ctx->opt_curve << 2) | (ctx->opt_packed << 4) | (ctx->opt_fold_pairs << 5);
-    if (!ws.g_front || !ws.g_back || memcmp(&key, &ws.g_key, sizeof key) != 0) {
-      if (ws.g_front || ws.g_back) HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));   // a previous replay may still be running
-      msm_launch C = L; C.stream = ws.stream; C.prof = 0;
-      if (int rc = capture_graph(ctx, ws, ws.g_front, [&] { return C.front(); })) return rc;
-      if (int rc = capture_graph(ctx, ws, ws.g_back, [&] { return C.back(); })) return rc;
-      ws.g_key = key;
-    }
-    HIP_TRY(ctx, hipGraphLaunch(ws.g_front, stream));
-    if (int rc = L.accumulate()) return rc;
-    L.mark(ST_TREE);
-    HIP_TRY(ctx, hipGraphLaunch(ws.g_back, stream));
   } else if (ctx->opt_profile >= 2 || !(side_stream || upload_points)) {
-    if (!upload_points && L.can_fuse_prep()) {
+    if (!upload_points && L.can_fuse_conversion()) {
       if (int rc = L.front()) return rc;
     } else {
       if (int rc = L.front_scalars()) return rc;
@@ -1137,11 +1057,11 @@ int fetch_rows(te_ctx* ctx, workset_t& ws, hipStream_t stream) {
 
 // End of an MSM's launch sequence on `stream`: flag and rows are on their way to the host (ev_result); behind them the
 // zeroed block is cleared for the set's NEXT MSM -- 4 us of fill and a launch gap that would otherwise sit in front of that
-// MSM's first kernel, on its critical path -- and ev_done marks the set free.  Not with captured graphs (the fill is part of
-// the captured front) and not with "prezero" = 0 (stage verifiers read counters and rows from the block afterwards).
+// MSM's first kernel, on its critical path -- and ev_done marks the set free.  Not with "prezero" = 0 (stage verifiers read
+// counters and rows from the block afterwards).
 int finish_sequence(te_ctx* ctx, workset_t& ws, hipStream_t stream) {
   HIP_TRY(ctx, hipEventRecord(ws.ev_result, stream));
-  if (ctx->opt_prezero && !ctx->opt_graph) {
+  if (ctx->opt_prezero) {
     HIP_TRY(ctx, hipMemsetAsync(ws.d_zero, 0, ws.zero_words * sizeof(uint32_t), stream));
     ws.zero_clean_words = ws.zero_words;
   }
@@ -1191,9 +1111,7 @@ void free_workset_buffers(workset_t& ws) {      // the big device buffers of a w
   memset(ws.cap, 0, sizeof ws.cap); ws.cap_in_points = ws.cap_in_scalars = 0;
   ws.zero_words = ws.zero_clean_words = 0;
   ws.d_err = ws.d_num_seg = ws.d_size_hist = ws.d_size_cursor = ws.d_counts1 = ws.d_bucket_count = ws.d_part_ticket = nullptr; ws.d_partials = nullptr;
-  if (ws.g_front) { (void)hipGraphExecDestroy(ws.g_front); ws.g_front = nullptr; }
-  if (ws.g_back) { (void)hipGraphExecDestroy(ws.g_back); ws.g_back = nullptr; }
-  ws.generation++; ws.used = false;
+  ws.used = false;
 }
 
 void free_dev(gpu_t& d) {
@@ -1204,8 +1122,6 @@ void free_dev(gpu_t& d) {
     if (sl.conv_ev) { (void)hipEventDestroy(sl.conv_ev); sl.conv_ev = nullptr; }
   }
   d.slabs.clear();
-  for (hipEvent_t& e : d.acc_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-  d.acc_prev = nullptr; d.acc_prev_stream = nullptr;
   if (d.chk_stream) (void)hipStreamDestroy(d.chk_stream);
   if (d.chk_pts) (void)hipFree(d.chk_pts);
   if (d.chk_word) (void)hipFree(d.chk_word);
@@ -1225,7 +1141,7 @@ void free_dev(gpu_t& d) {
     for (hipEvent_t e : ws.piece_events) (void)hipEventDestroy(e);
     if (ws.copy_stream) (void)hipStreamDestroy(ws.copy_stream);
     // a stream whose handle left the library stays alive (see "EXPORTED STREAMS ARE NEVER DESTROYED"); te_msm_destroy has synchronised it
-    if (ws.stream) { if (d.streams_exported && park_exported_streams()) park_stream(d.device, ws.stream); else (void)hipStreamDestroy(ws.stream); }
+    if (ws.stream) { if (d.streams_exported) park_stream(d.device, ws.stream); else (void)hipStreamDestroy(ws.stream); }
     ws.stream = nullptr; ws.copy_stream = nullptr;
   }
 }
@@ -1268,15 +1184,11 @@ bool host_memory_is_pinned(const void* p) {
 // ring of the work set and travel from there; the call returns when the last chunk has left the caller's buffer.
 constexpr size_t TE_RING_SLOT = 2u << 20;      // bytes per slot: 48 DMA calls per 96 MB, ~0.2 ms of enqueue cost
 constexpr int TE_RING_SLOTS = 16;              // 32 MB pinned per work set that stages
-constexpr int TE_STAGERS_MAX = 32;
-// crew size: each thread copies ~5 GB/s into the ring while the DMA engine reads behind it (env TE_MSM_STAGERS, measurements:
+// crew size: each thread copies ~5 GB/s into the ring while the DMA engine reads behind it (measurements:
 // profiles/r05_host_staging_copy_ab.txt)
-int stager_count() {
-  static const int n = [] { const char* e = getenv("TE_MSM_STAGERS"); int v = e ? atoi(e) : 8; return v < 1 ? 1 : v > TE_STAGERS_MAX ? TE_STAGERS_MAX : v; }();
-  return n;
-}
+constexpr int TE_STAGERS = 8;
 // chunk copy of the crew: the destination (a ring slot) is read next by the DMA engine, never by a core -- streaming stores keep it
-// out of the caches and skip the read-for-ownership of every destination line (env TE_MSM_STAGING_COPY=memcpy: plain memcpy, A/B)
+// out of the caches and skip the read-for-ownership of every destination line
 #if defined(__x86_64__)
 __attribute__((target("avx2"))) void copy_streaming_avx2(uint8_t* to, const uint8_t* from, size_t len) {
   size_t i = 0;
@@ -1294,7 +1206,7 @@ __attribute__((target("avx2"))) void copy_streaming_avx2(uint8_t* to, const uint
 #endif
 void staging_chunk_copy(uint8_t* to, const uint8_t* from, size_t len) {
 #if defined(__x86_64__)
-  static const bool streaming = [] { const char* e = getenv("TE_MSM_STAGING_COPY"); return !(e && e[0] == 'm') && __builtin_cpu_supports("avx2"); }();
+  static const bool streaming = __builtin_cpu_supports("avx2");
   if (streaming) { copy_streaming_avx2(to, from, len); return; }
 #endif
   memcpy(to, from, len);
@@ -1313,7 +1225,7 @@ int ensure_ring(te_ctx* ctx, workset_t& ws) {
 // context's error lock: the devices' host threads may get here together
 int ensure_stagers(te_ctx* ctx) {
   std::lock_guard<std::mutex> lk(ctx->err_mu);
-  while ((int)ctx->stagers.size() < stager_count()) ctx->stagers.emplace_back(new te_sched::worker_t());
+  while ((int)ctx->stagers.size() < TE_STAGERS) ctx->stagers.emplace_back(new te_sched::worker_t());
   return 0;
 }
 // dst (device) <- src (host), `bytes`, on `stream`, through the set's ring; returns when src has been read completely
@@ -1335,10 +1247,10 @@ int staged_copy(te_ctx* ctx, workset_t& ws, void* dst, const uint8_t* src, size_
     const size_t len = std::min(TE_RING_SLOT, bytes - off);
     const size_t turn = ws.ring_next++;
     const int slot = (int)(turn % TE_RING_SLOTS);
-    if ((int)fifo.size() >= std::min(stager_count(), TE_RING_SLOTS - 4)) { if (int rc = flush_one()) return rc; }   // one chunk per crew thread filling, the rest of the ring draining
+    if ((int)fifo.size() >= std::min(TE_STAGERS, TE_RING_SLOTS - 4)) { if (int rc = flush_one()) return rc; }   // one chunk per crew thread filling, the rest of the ring draining
     if (turn >= (size_t)TE_RING_SLOTS) HIP_TRY(ctx, hipEventSynchronize(ws.ring_ev[(size_t)slot]));   // the slot's previous chunk has left it
     uint8_t* to = ws.h_ring + (size_t)slot * TE_RING_SLOT; const uint8_t* from = src + off;
-    te_sched::worker_t* who = ctx->stagers[turn % (size_t)stager_count()].get();
+    te_sched::worker_t* who = ctx->stagers[turn % (size_t)TE_STAGERS].get();
     fifo.push_back({who->post([to, from, len] { staging_chunk_copy(to, from, len); return 0; }), who, slot, off, len});
   }
   while (!fifo.empty()) { if (int rc = flush_one()) return rc; }
@@ -1356,16 +1268,13 @@ int upload(te_ctx* ctx, workset_t& ws, void* dst, const uint8_t* src, size_t byt
 // stream shares with other work sets, and stands there behind THEIR kernels (a k_accumulate of 1.2-1.4 ms with eight tickets in flight):
 // a third of the 32 MB scalar uploads of bound-bases tickets took 1.6-1.9 ms instead of 0.61 (TE_MSM_TRACE_HOST stamps,
 // profiles/r06_bound_host_tickets_gap.txt).  A set whose previous MSM has delivered its result -- every ticket that was collected --
-// needs no marker: everything that read the staging area precedes ev_result.  TE_MSM_COPY_MARKER=1: always (the old behaviour).
+// needs no marker: everything that read the staging area precedes ev_result.
 int copy_stream_behind_previous(te_ctx* ctx, workset_t& ws) {
   if (int rc = need_copy_stream(ctx, ws)) return rc;
-  static const bool always = [] { const char* e = getenv("TE_MSM_COPY_MARKER"); return e && e[0] == '1'; }();
-  if (!always) {
-    if (!ws.used) return 0;
-    const hipError_t q = hipEventQuery(ws.ev_result);
-    if (q == hipSuccess) return 0;
-    (void)hipGetLastError();                                                      // hipErrorNotReady is an answer, not an error
-  }
+  if (!ws.used) return 0;
+  const hipError_t q = hipEventQuery(ws.ev_result);
+  if (q == hipSuccess) return 0;
+  (void)hipGetLastError();                                                        // hipErrorNotReady is an answer, not an error
   HIP_TRY(ctx, hipEventRecord(ws.ev_start, ws.stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ws.copy_stream, ws.ev_start, 0));
   return 0;
@@ -1381,29 +1290,25 @@ const char* const kFinalCarry = "final carry is 1: a scalar does not fit the sig
 //     lanes sharing the link), and the runtime multiplexes the eight work-set streams onto four hardware queues, whose packets run in
 //     order: the kernels of ANOTHER ticket that shares the queue stood behind that wait -- tickets from host scalars over bound bases
 //     ran at 1.02-1.09 ms per MSM where the same tickets from device scalars take 0.89-0.92, with neither the link nor the device busy
-//     (profiles/r06_lane_host_waits.txt).  The lane thread has nothing else to do.
+//     (the round-6 lane measurement).  The lane thread has nothing else to do.
 //     It waits for the copy STREAM, not for an event recorded behind the upload: an event record is one more packet in a hardware
 //     queue the side stream shares with other work sets' streams, and stood behind their kernels for 0.5-0.7 ms in every fourth
 //     ticket (stamps: "upload awaited"); the stream's last command -- the copy -- is known to the runtime without a packet.
-//     TE_MSM_LANE_EVENT_WAITS=1: the event form (experiments).
 // lane: the host form is wanted (a lane thread, or a calling thread whose copies have blocked anyway)
 int lane_wait(te_ctx* ctx, workset_t& ws, hipEvent_t ev, bool lane) {
-  static const bool by_event = [] { const char* e = getenv("TE_MSM_LANE_EVENT_WAITS"); return e && e[0] == '1'; }();
-  if (lane && ctx->opt_lane_host_waits && !by_event) { HIP_TRY(ctx, hipStreamSynchronize(ws.copy_stream)); return 0; }
+  if (lane) { HIP_TRY(ctx, hipStreamSynchronize(ws.copy_stream)); return 0; }
   HIP_TRY(ctx, hipEventRecord(ev, ws.copy_stream));
-  if (lane && ctx->opt_lane_host_waits) HIP_TRY(ctx, hipEventSynchronize(ev));
-  else HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ev, 0));
+  HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ev, 0));
   return 0;
 }
 
 // te_msm_run* / te_msm_submit (the calling thread uploads): from PAGEABLE memory hipMemcpyAsync returns when the copy is over, so
 // waiting for the copy stream on the host costs nothing and keeps the event record and the stream wait out of the hardware queues
 // as well: te_msm_run 2.30 vs 2.35 ms, te_msm_run_scalars 1.355 vs 1.38, te_msm_submit x8 in flight 1.90 vs 1.93-2.01 at 2^20;
-// 0.78 vs 0.81, 0.573 vs 0.595, 0.555 vs 0.56-0.63 at 2^18 (tools/exp_caller_host_waits.py, profiles/r06_caller_host_waits.txt).
-// Pinned sources keep the stream waits (their copies are asynchronous).  TE_MSM_CALLER_HOST_WAITS=0: stream waits for all.
-bool caller_may_wait_on_host(const te_ctx* ctx, const void* a, const void* b) {
-  static const bool on = [] { const char* e = getenv("TE_MSM_CALLER_HOST_WAITS"); return !(e && e[0] == '0'); }();
-  return on && ctx->opt_lane_host_waits && !(a && host_memory_is_pinned(a)) && !(b && host_memory_is_pinned(b));
+// 0.78 vs 0.81, 0.573 vs 0.595, 0.555 vs 0.56-0.63 at 2^18 (profiles/r06_caller_host_waits.txt).
+// Pinned sources keep the stream waits (their copies are asynchronous).
+bool caller_may_wait_on_host(const void* a, const void* b) {
+  return !(a && host_memory_is_pinned(a)) && !(b && host_memory_is_pinned(b));
 }
 
 // pieces a host buffer of n points is uploaded and processed in on ONE device (option "host_chunks", else from n).
@@ -1429,7 +1334,7 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
   plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true);
   const curve_sizes sz = sizes_of(pf.curve);
   if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sz.scalar_in)) return rc;
-  const bool host_waits = !wait_for_pinned || caller_may_wait_on_host(ctx, src_points, src_scalars);
+  const bool host_waits = !wait_for_pinned || caller_may_wait_on_host(src_points, src_scalars);
   uint8_t* dpts = static_cast<uint8_t*>(ws.d_in_points);
   uint8_t* dscs = static_cast<uint8_t*>(ws.d_in_scalars);
   // Pieces of n / K points: piece i crosses PCIe on the side stream while piece i-1 is converted and ACCUMULATED ONTO THE SAME
@@ -1439,18 +1344,9 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
   // previous piece's kernels.
   // Measured (n = 2^20, tools/host_path.py, TE_MSM_TRACE_HOST=1, profiles/r03_host_buffer_path.txt): three equal pieces 2.48 ms,
   // two 2.56, four 2.59 (the device falls behind the uploads: every piece pays a sort and ~10 launches on a fraction of the
-  // points), falling piece sizes 2.51-2.56; the link alone needs 1.85 ms.
-  // piece boundaries: equal pieces, or TE_MSM_HOST_SPLIT="w0,w1,..." (relative weights, experiments; read once in te_msm_init)
-  std::vector<uint64_t> bounds((size_t)K + 1, n);
-  {
-    std::vector<double> wgt((size_t)K, 1.0);
-    for (size_t i = 0; i < ctx->host_split.size() && i < (size_t)K; i++) wgt[i] = ctx->host_split[i];
-    double tot = 0, run = 0; for (double v : wgt) tot += v;
-    for (int i = 0; i < K; i++) { bounds[(size_t)i] = (uint64_t)((double)n * (run / tot)); run += wgt[(size_t)i]; }
-    bounds[0] = 0; bounds[(size_t)K] = n;
-    for (int i = 1; i <= K; i++) if (bounds[(size_t)i] < bounds[(size_t)i - 1]) bounds[(size_t)i] = bounds[(size_t)i - 1];
-  }
-  auto piece_lo = [&](int i) -> uint64_t { return i >= K ? n : bounds[(size_t)i]; };     // first point of piece i
+  // points), falling piece sizes 2.51-2.56 (profiles/r06_host_split_experiment.txt: equal thirds confirmed); the link alone needs 1.85 ms.
+  // Equal pieces, in floating point (the integer n i / K of enqueue_scalar_slice differs by one point for some n)
+  auto piece_lo = [&](int i) -> uint64_t { return i >= K ? n : (uint64_t)((double)n * ((double)i / K)); };     // first point of piece i
   uint64_t m_max = 0;
   for (int i = 0; i < K; i++) m_max = std::max(m_max, piece_lo(i + 1) - piece_lo(i));
   uint32_t seg_all = 0;
@@ -1493,7 +1389,7 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
     if (m == 0) continue;
     make_plan(ctx, d, m, p, pf.c, 1, seg_all, true);
     if (int rc = ensure_buffers(ctx, d, ws, m, p)) return rc;              // no reallocation: only the pointers into the zeroed block move
-    msm_launch L{ctx, d, ws, p, dpts + lo * sz.point_in, dscs + lo * sz.scalar_in, m, ws.d_partials, 0, ws.stream, true, !first};
+    msm_launch L{ctx, ws, p, dpts + lo * sz.point_in, dscs + lo * sz.scalar_in, m, ws.d_partials, 0, ws.stream, true, !first};
     L.host_rows = msm_launch::rows_to_host(ctx, d, p, true);
     ws.rows_on_host = L.host_rows;
     first = false;
@@ -1575,19 +1471,18 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
     const uint64_t lo = piece_lo(i), m = piece_lo(i + 1) - lo;
     if (m == 0) continue;
     {
-      static const bool serial = [] { const char* e = getenv("TE_MSM_SCALAR_UPLOADS_SERIAL"); return !(e && e[0] == '0'); }();
       std::unique_lock<std::mutex> link(*d.scalar_link, std::defer_lock);
-      if (!wait_for_pinned && serial && ctx->opt_lane_host_waits) link.lock();       // (a lane thread: see gpu_t::scalar_link)
+      if (!wait_for_pinned) link.lock();                                        // (a lane thread: see gpu_t::scalar_link)
       stamp("upload begins", i);
       if (int rc = upload(ctx, ws, dscs + lo * sz.scalar_in, src_scalars + lo * sz.scalar_in, m * sz.scalar_in, ws.copy_stream)) return rc;
       stamp("upload call returned", i);
-      if (int rc = lane_wait(ctx, ws, evs[(size_t)i], !wait_for_pinned || caller_may_wait_on_host(ctx, src_scalars, nullptr))) return rc;
+      if (int rc = lane_wait(ctx, ws, evs[(size_t)i], !wait_for_pinned || caller_may_wait_on_host(src_scalars, nullptr))) return rc;
       stamp("upload awaited", i);
     }
     make_plan(ctx, d, m, p, pf.c, 1, seg_all, true);
     p.rec_kind = rec_kind;
     if (int rc = ensure_buffers(ctx, d, ws, m, p, false)) return rc;           // no reallocation: only the pointers into the zeroed block move
-    msm_launch L{ctx, d, ws, p, nullptr, dscs + lo * sz.scalar_in, m, ws.d_partials, 0, ws.stream, true, !first};
+    msm_launch L{ctx, ws, p, nullptr, dscs + lo * sz.scalar_in, m, ws.d_partials, 0, ws.stream, true, !first};
     L.host_rows = msm_launch::rows_to_host(ctx, d, p, true);
     L.bound = recs + lo * rec_bytes;
     ws.rows_on_host = L.host_rows;
@@ -1657,7 +1552,7 @@ int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bas
   ws.plan = p; ws.n = cap; ws.used = true; ws.last_stream = stream; __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
   ws.prof_level = ctx->opt_profile;
   ws.fb_scalars = d_scalars; ws.fb_n = n;
-  msm_launch L{ctx, d, ws, p, nullptr, d_scalars, cap, ws.d_partials, ctx->opt_profile, stream, true};
+  msm_launch L{ctx, ws, p, nullptr, d_scalars, cap, ws.d_partials, ctx->opt_profile, stream, true};
   L.host_rows = msm_launch::rows_to_host(ctx, d, p, true);
   ws.rows_on_host = L.host_rows;
   L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];
@@ -2073,18 +1968,12 @@ int te_msm_init(const int* device_ids, int n_dev, te_ctx** out) {
     return TE_MSM_EDEVICE;
   }
   te_ctx* ctx = new te_ctx();
-  if (const char* e = getenv("TE_MSM_FUSE_PREP")) ctx->opt_fuse_prep = e[0] != '0';      // A/B measurements; option "fuse_prep"
   if (const char* e = getenv("TE_MSM_QUEUE_PROBE")) ctx->opt_queue_probe = e[0] != '0';  // option "queue_probe"
   if (const char* e = getenv("TE_MSM_PACKED")) ctx->opt_packed = e[0] != '0';            // option "packed_sort"
   if (const char* e = getenv("TE_MSM_HOST_STAGING")) ctx->opt_host_staging = e[0] != '0'; // option "host_staging"
   if (const char* e = getenv("TE_MSM_UPLOAD_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 16) ctx->opt_upload_threads = v; }   // option "upload_threads"
   if (const char* e = getenv("TE_MSM_FOLD_PAIRS")) ctx->opt_fold_pairs = e[0] != '0';    // option "fold_pairs"
   if (const char* e = getenv("TE_MSM_SHARE_RECORDS")) ctx->opt_share_records = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;   // option "share_records"
-  if (const char* e = getenv("TE_MSM_LANE_HOST_WAITS")) ctx->opt_lane_host_waits = e[0] != '0';   // option "lane_host_waits"
-  if (const char* e = getenv("TE_MSM_HOST_SPLIT")) {                                     // relative piece weights "w0,w1,..." (experiments)
-    const char* q = e;
-    while (*q) { char* end = nullptr; const double v = strtod(q, &end); if (end == q) break; ctx->host_split.push_back(v > 0 ? v : 1.0); q = *end == ',' ? end + 1 : end; }
-  }
   ctx->devs.resize(n_dev);
   for (int i = 0; i < n_dev; i++) {
     gpu_t& d = ctx->devs[i];
@@ -2291,7 +2180,7 @@ namespace {
 // profiles/r05_point_shard_rehearsal.txt, r05_point_shard_sdma_experiment.txt: ~5 such pauses for eight threads, one for four,
 // once per process).  With upload lanes that would fall into the first few asynchronous tickets of a process; instead the lanes
 // of every device of the context copy 2 MB each in lockstep, twice, before the first asynchronous ticket is taken (15-30 ms the
-// first time in a process, ~1 ms for a later context).  env TE_MSM_WARM_UPLOADS=0 turns it off.
+// first time in a process, ~1 ms for a later context).
 void warm_upload_lanes(te_ctx* ctx) {
   static std::mutex mu; static uint64_t warmed = 0;           // per process and HIP device (ids < 64)
   const int L = ctx->opt_upload_threads;
@@ -2305,7 +2194,6 @@ void warm_upload_lanes(te_ctx* ctx) {
       todo.push_back(di);
     }
   }
-  if (const char* e = getenv("TE_MSM_WARM_UPLOADS")) if (e[0] == '0') return;
   if (L < 2 || todo.empty()) return;
   struct gate_t { std::mutex m; std::condition_variable cv; int waiting = 0, round = 0, parties = 0; } gate;
   gate.parties = L * (int)todo.size();
@@ -2473,7 +2361,7 @@ int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src
   const uint64_t n = b->n;
   uint8_t* recs = nullptr; void* raw = nullptr; void* proj = nullptr; hipStream_t st = nullptr;
   struct cleanup_t { void*& raw; void*& proj; hipStream_t& st; ~cleanup_t() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } if (raw) (void)hipFree(raw); if (proj) (void)hipFree(proj); } } cleanup{raw, proj, st};
-  HIP_TRY(ctx, hipMalloc((void**)&recs, (size_t)n * b->rec_bytes * (size_t)b->replicas * (size_t)(b->fb_c ? b->fb_W : 1)));
+  HIP_TRY(ctx, hipMalloc((void**)&recs, (size_t)n * b->rec_bytes * (size_t)(b->fb_c ? b->fb_W : 1)));
   b->recs[i] = recs;                                                       // (freed by the caller on failure: free_bases)
   HIP_TRY(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   const void* pts = src;
@@ -2501,8 +2389,6 @@ int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src
   } else {
     hipLaunchKernelGGL(te::k_prep_points, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, reinterpret_cast<te::pnt_slot*>(recs), n32);
   }
-  for (int r = 1; r < b->replicas; r++)
-    HIP_TRY(ctx, hipMemcpyAsync(recs + (size_t)r * n * b->rec_bytes, recs, (size_t)n * b->rec_bytes, hipMemcpyDeviceToDevice, st));
   if (b->fb_c) {
     // fixed-base windows: table w = the records of 2^(c w) P_i; the extended points travel from window to window by c doublings
     HIP_TRY(ctx, hipMalloc(&proj, (size_t)n * sizeof(te::ete)));       // (the second temporary: unused on this curve otherwise)
@@ -2541,9 +2427,8 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
   b->ctx = ctx; b->n = n; b->curve = ctx->opt_curve;
   b->rec_kind = (b->curve == TE_MSM_CURVE_BLS12_377_G1 && ctx->opt_bind_affine) ? 1 : 0;
   b->rec_bytes = rec_bytes_of(b->curve, b->rec_kind);
-  b->replicas = ctx->opt_exp_table_replicas;
   if (ctx->opt_bind_fixed_base && b->curve == TE_MSM_CURVE_TE_BLS12 && n > 0) {
-    b->fb_c = ctx->opt_bind_fixed_base; b->fb_W = fb_windows_for(b->fb_c); b->replicas = 1;
+    b->fb_c = ctx->opt_bind_fixed_base; b->fb_W = fb_windows_for(b->fb_c);
     if ((uint64_t)b->fb_W * n >= (1ull << 31)) { delete b; return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base: windows x points must stay below 2^31"); }
   }
   b->recs.assign(nd, nullptr);
@@ -2565,7 +2450,7 @@ int enqueue_fixed_base_host(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases
   const curve_sizes sz = sizes_of(bases->curve);
   if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
   if (ws.used && ws.ev_done) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));      // the staging area may still be read by the set's previous MSM
-  if (!wait_for_pinned && ctx->opt_lane_host_waits) {
+  if (!wait_for_pinned) {
     // an asynchronous ticket: the lane thread waits for the upload itself (lane_wait), no wait enters the work set's stream
     if (ws.used && ws.ev_done) HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
     if (int rc = need_copy_stream(ctx, ws)) return rc;
@@ -2836,10 +2721,8 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
     ctx->opt_curve = (int)value; return 0;
   }
   if (!strcmp(key, "profile")) { ctx->opt_profile = value < 0 ? 0 : (value > 2 ? 2 : (int)value); ctx->have_stage_ms = false; return 0; }
-  if (!strcmp(key, "graph")) { ctx->opt_graph = value ? 1 : 0; return 0; }
   if (!strcmp(key, "prezero")) { ctx->opt_prezero = value ? 1 : 0; return 0; }
   if (!strcmp(key, "check_points")) { if (value < 0 || value > 2) return set_err(ctx, TE_MSM_EINVAL, "check_points must be 0, 1 or 2"); ctx->opt_check_points = (int)value; return 0; }
-  if (!strcmp(key, "fuse_prep")) { ctx->opt_fuse_prep = value ? 1 : 0; return 0; }
   if (!strcmp(key, "host_chunks")) { if (value < 0 || value > 64) return set_err(ctx, TE_MSM_EINVAL, "host_chunks out of range"); ctx->opt_host_chunks = (int)value; return 0; }
   if (!strcmp(key, "workset")) { if (value < 0 || value >= TE_MSM_WORKSETS) return set_err(ctx, TE_MSM_EINVAL, "workset out of range"); ctx->opt_workset = (int)value; return 0; }
   if (!strcmp(key, "segment_len")) { if (value < 0 || value > 1000000) return set_err(ctx, TE_MSM_EINVAL, "segment_len must be 0 (from n) or in [1, 1e6]"); ctx->opt_seg_len = (int)value; return 0; }
@@ -2851,10 +2734,8 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
   if (!strcmp(key, "host_staging")) { ctx->opt_host_staging = value ? 1 : 0; return 0; }
   if (!strcmp(key, "upload_threads")) { if (value < 1 || value > 16) return set_err(ctx, TE_MSM_EINVAL, "upload_threads must be in [1, 16]"); ctx->opt_upload_threads = (int)value; return 0; }
   if (!strcmp(key, "bind_affine")) { ctx->opt_bind_affine = value ? 1 : 0; return 0; }
-  if (!strcmp(key, "lane_host_waits")) { ctx->opt_lane_host_waits = value ? 1 : 0; return 0; }
   if (!strcmp(key, "share_records")) { ctx->opt_share_records = value == 2 ? 2 : value ? 1 : 0; return 0; }
   if (!strcmp(key, "bind_fixed_base")) { if (value != 0 && (value < 16 || value > 21)) return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base must be 0 or in [16, 21]"); ctx->opt_bind_fixed_base = (int)value; return 0; }
-  if (!strcmp(key, "exp_table_replicas")) { if (value < 1 || value > TE_BATCH_MAX) return set_err(ctx, TE_MSM_EINVAL, "exp_table_replicas must be in [1, 8]"); ctx->opt_exp_table_replicas = (int)value; return 0; }
   if (!strcmp(key, "scalar_chunks")) { if (value < 0 || value > 64) return set_err(ctx, TE_MSM_EINVAL, "scalar_chunks out of range"); ctx->opt_scalar_chunks = (int)value; return 0; }
   if (!strcmp(key, "batch_small_max")) { if (value < 0 || value > (1ll << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch_small_max must be in [0, 2^31]"); ctx->opt_batch_small_max = value; return 0; }
   return set_err(ctx, TE_MSM_EINVAL, "unknown option");
@@ -2877,12 +2758,10 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "segment_len")) { *value = ctx->opt_seg_len; return 0; }
   if (!strcmp(key, "segment_len_used")) { drain_workers(ctx); const gpu_t& d0 = ctx->devs[0]; *value = d0.ws[d0.last_ws].used ? (int64_t)d0.ws[d0.last_ws].plan.seg_len : 0; return 0; }
   if (!strcmp(key, "workset")) { *value = ctx->opt_workset; return 0; }
-  if (!strcmp(key, "graph")) { *value = ctx->opt_graph; return 0; }
   if (!strcmp(key, "prezero")) { *value = ctx->opt_prezero; return 0; }
   if (!strcmp(key, "check_points")) { *value = ctx->opt_check_points; return 0; }
   if (!strcmp(key, "bad_point_index")) { *value = ctx->bad_point_index; return 0; }
   if (!strcmp(key, "bad_point_reason")) { *value = ctx->bad_point_reason; return 0; }
-  if (!strcmp(key, "fuse_prep")) { *value = ctx->opt_fuse_prep; return 0; }
   if (!strcmp(key, "host_chunks")) { *value = ctx->opt_host_chunks; return 0; }
   if (!strcmp(key, "host_shard_min")) { *value = ctx->opt_host_shard_min; return 0; }
   if (!strcmp(key, "queue_probe")) { *value = ctx->opt_queue_probe; return 0; }
@@ -2890,7 +2769,6 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "fold_pairs")) { *value = ctx->opt_fold_pairs; return 0; }
   if (!strcmp(key, "streams_final")) { *value = ctx->devs[0].streams_final ? 1 : 0; return 0; }
   if (!strcmp(key, "bind_affine")) { *value = ctx->opt_bind_affine; return 0; }
-  if (!strcmp(key, "lane_host_waits")) { *value = ctx->opt_lane_host_waits; return 0; }
   if (!strcmp(key, "share_records")) { *value = ctx->opt_share_records; return 0; }
   if (!strcmp(key, "record_conversions")) { *value = __atomic_load_n(&ctx->stat_record_conversions, __ATOMIC_RELAXED); return 0; }
   if (!strcmp(key, "record_slabs")) { int64_t t = 0; for (const gpu_t& d : ctx->devs) for (const auto& sl : d.slabs) if (sl.d) t++; *value = t; return 0; }
@@ -2900,7 +2778,7 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "bind_fixed_base")) { *value = ctx->opt_bind_fixed_base; return 0; }
   if (!strcmp(key, "fixed_base_fallbacks")) { *value = ctx->stat_fb_fallbacks; return 0; }
   if (!strcmp(key, "bases_bound")) { *value = (int64_t)ctx->bases.size(); return 0; }
-  if (!strcmp(key, "bases_bytes")) { int64_t t = 0; for (const te_bases* b : ctx->bases) for (const uint8_t* r : b->recs) if (r) t += (int64_t)(b->n * b->rec_bytes) * b->replicas * (b->fb_c ? b->fb_W : 1); *value = t; return 0; }
+  if (!strcmp(key, "bases_bytes")) { int64_t t = 0; for (const te_bases* b : ctx->bases) for (const uint8_t* r : b->recs) if (r) t += (int64_t)(b->n * b->rec_bytes) * (b->fb_c ? b->fb_W : 1); *value = t; return 0; }
   if (!strcmp(key, "in_flight")) { int64_t t = 0; for (const gpu_t& d : ctx->devs) t += d.in_flight; *value = t; return 0; }
   if (!strcmp(key, "device_bytes")) {      drain_workers(ctx);      // device memory this context holds in work-set buffers (te_msm_trim gives it back)
     int64_t tot = 0;
@@ -3241,7 +3119,7 @@ int enqueue_ragged(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, 
   if (ws.used && ws.last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ws.ev_done, 0));
   ws.plan = p; ws.n = n_max; ws.used = true; ws.last_stream = stream; __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
   ws.prof_level = 0; ws.rows_on_host = false; ws.recs_last = nullptr;
-  msm_launch L{ctx, d, ws, p, nullptr, d_scalars, n_max, ws.d_batch_rows, 0, stream, false};
+  msm_launch L{ctx, ws, p, nullptr, d_scalars, n_max, ws.d_batch_rows, 0, stream, false};
   L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];      // (a fixed-base set: table 0, the ordinary records)
   L.ragged = &tab;
   if (int rc = L.front_scalars()) return rc;
@@ -3619,7 +3497,7 @@ int64_t te_msm_bases_read(te_ctx* ctx, const te_bases* bases, int device_index, 
   device_guard restore_callers_device;
   if (!ctx || !dst) return TE_MSM_EINVAL;
   if (!valid_bases(ctx, bases)) return set_err(ctx, TE_MSM_EINVAL, kBadBases);
-  const uint64_t total = bases->n * (uint64_t)bases->replicas * (uint64_t)(bases->fb_c ? bases->fb_W : 1);      // (a fixed-base set: table w at records [w n, (w + 1) n))
+  const uint64_t total = bases->n * (uint64_t)(bases->fb_c ? bases->fb_W : 1);      // (a fixed-base set: table w at records [w n, (w + 1) n))
   if (device_index < 0 || (size_t)device_index >= ctx->devs.size() || first > total || count > total - first) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
   if (record_bytes) *record_bytes = (int)bases->rec_bytes;
   uint64_t bytes = count * bases->rec_bytes;
