@@ -224,6 +224,49 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
 int te_msm_run_scalars_batch(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const uint8_t* scalars_le, uint8_t* out);
 int te_msm_run_scalars_batch_device(te_ctx* ctx, te_bases* bases, int count, const uint64_t* lens, const void* d_scalars_le, uint8_t* out);
 
+/* ---- MSMs over an indexed subset of a bound point set -----------------------------------------------------------------------------
+ * Real scalar vectors over an SRS are mostly zeros (a witness, a selector), touch a few thousand of a million points (a sparse basis) or a
+ * strided range of them -- neither the set nor a prefix.  te_msm_run_scalars* makes such a caller zero-pad to te_msm_bases_count(bases)
+ * scalars: 32 bytes per BOUND point over PCIe, a digit pass and a sort over n entries, a plan made for n.  These calls take the pairs:
+ *   result = sum_{j < m} k_j P_{idx[j]}.  idx: m little-endian u32, each below te_msm_bases_count(bases), in any order, repeats allowed
+ *   (the sum is defined either way); scalars_le: m scalar records in the MSM's own format (32 bytes Twisted-Edwards, 48-byte records for
+ *   BLS12-377).  m may exceed the set's size and is bounded as n of te_msm_run (m < 2^31).  The result is encoded as te_msm_run_scalars_batch
+ *   encodes it (64 / 96 bytes); m == 0 gives the identity.
+ *   How it runs (csrc/indexed_plan.hpp): entry j's scalar is record j of the CALL, so the digit pass, the sort and the
+ *   schedule run over m entries, and window bits, digit form and segment length follow the options with m standing for n.  The sort's first
+ *   level writes idx[j] where it writes the position j for every other call (a kernel of its own: the other paths keep their code), and the
+ *   accumulation gathers from the set's records as it always does.  The packed level-1 entries ("packed_sort") give the index 23 bits, and
+ *   here the field holds a POINT index: they are used when the SET's count is at most 2^23, whatever m is; larger sets take the general
+ *   form.  A set bound with "bind_fixed_base" is served from its table 0 (the ordinary records) with the ordinary windows.
+ *   Host form: one device uploads and processes the pairs in pieces (option "scalar_chunks"; each piece carries its slice of both arrays);
+ *   several devices take contiguous slices of the m pairs over their own links (as te_msm_run_scalars cuts its scalars; "host_shard_min"
+ *   applies to m) -- every device holds all records.  Device form: both buffers lie on ONE device of the context (else TE_MSM_EINVAL) and
+ *   the whole MSM runs on that device.
+ *   Tickets: te_msm_submit_scalars_indexed[_device] behave as te_msm_submit_scalars[_device] -- the host form is ASYNCHRONOUS (idx as well as
+ *   scalars_le must stay valid and unchanged until te_msm_ticket_wait or te_msm_collect has returned for the ticket), the ticket goes to
+ *   the device with the fewest in flight (a device that does not hold device-resident pairs pulls them over its peer link), "in_flight"
+ *   counts it, tickets are collected in any order, and a set with tickets in flight cannot be released.  m == 0 has no ticket
+ *   (TE_MSM_EINVAL, as an empty set has none).
+ *   Errors, all with the output untouched and the context usable.  TE_MSM_EINVAL: a null pointer while m > 0; a bases handle that was
+ *   released or belongs to the other curve; a context with a window shard set (te_msm_set_window_shard, step > 1).  TE_MSM_ESCALAR: a
+ *   scalar trips the final-carry check.  TE_MSM_EINVAL: an index >= te_msm_bases_count(bases); the LOWEST offending position j is reported
+ *   in the read-only option "bad_index_position" (-1 before any).  The indices are checked ON THE DEVICE, where they are first read, every
+ *   one of them whatever its scalar; a bad index is replaced by a valid one before any address is formed from it (no kernel ever gathers
+ *   outside the record slab), the MSM runs to its end and the call -- for a ticket: its te_msm_collect, as with TE_MSM_ESCALAR; other
+ *   tickets are not affected -- reports the error instead of a result.
+ *   Synchronous calls leave the calling thread's current device as it was.
+ * COST (MI355X, a set of 2^20 points, against te_msm_run_scalars* over the zero-padded vector; tools/indexed_sparse.py,
+ *   profiles/indexed_subset_sparse.txt).  The identity index list (m = n) prices the translation and the 4 more
+ *   bytes per entry: +2 % per MSM with four tickets in flight, host or device buffers (0.98 against 0.97 ms, 0.91 against 0.89 ms),
+ *   +9 % for the lone host call (1.51 against 1.38 ms: one more upload call per piece on its critical path); BLS12-377: 0 to +1 % in
+ *   flight, +8 % lone.  A dense vector belongs to te_msm_run_scalars*.  At density 1/2 the indexed call gains 1.0-1.2x (the zero digits of a
+ *   padded vector are never sorted or accumulated either; what is saved is link bytes), at 1/8 2.1x lone, 3.4x with host tickets in
+ *   flight, 1.3x device-resident, at 1/64 3.4x, 7.0x and 1.9x (BLS12-377: 2.4x, 4.9x, 1.4x). */
+int te_msm_run_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* idx, const uint8_t* scalars_le, uint64_t m, uint8_t* out_xy_le);
+int te_msm_run_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const void* d_idx, const void* d_scalars_le, uint64_t m, uint8_t* out_xy_le);
+int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* idx, const uint8_t* scalars_le, uint64_t m, uint64_t* ticket);
+int te_msm_submit_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const void* d_idx, const void* d_scalars_le, uint64_t m, uint64_t* ticket);
+
 /* ---- input-point validation ------------------------------------------------------------------------------------------------
  * The engine trusts its points unless asked: the wire format above says what a caller must pass, and a point that breaks it gives a
  * wrong result, not an error.  Level 1, FORM: both coordinates canonical (below p / q), the curve equation holds
@@ -381,6 +424,8 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *                   the option set (TE_MSM_EINVAL): use te_msm_check_points_device in front of them.  The context stays usable.
  *   read-only:      "bad_point_index" (the lowest failing index -- into the caller's whole buffer -- of the last call that returned
  *                   TE_MSM_EPOINT, -1 before any), "bad_point_reason" (its TE_MSM_POINT_* code, 0 before any)
+ *   read-only:      "bad_index_position" (te_msm_run_scalars_indexed*: the lowest position j -- into the caller's whole list -- whose index was
+ *                   not below te_msm_bases_count(bases), of the last call or collect that failed on one; -1 before any)
  *   "prezero"       1 (default) = a work set's block of counters is cleared BEHIND an MSM's read-back, for its next MSM
  *                   (the next MSM starts with its first kernel instead of a fill); 0 = cleared in front of every MSM --
  *                   te_msm_debug_read of "bucket_count" / "num_segments" / "partials" needs 0 (it refuses otherwise)

@@ -25,7 +25,8 @@ X_BYTES, X_BYTES_BLS12_377 = 32, 48      # TE_MSM_X_BYTES*: one x-only point (po
 
 
 class MsmError(RuntimeError):
-    """code: the TE_MSM_E* value.  index / reason: the lowest failing point and TE_MSM_POINT_* when code is EPOINT, else None."""
+    """code: the TE_MSM_E* value.  index / reason: the lowest failing point and TE_MSM_POINT_* when code is EPOINT; index alone: the
+    lowest position of an index outside the bound set (run_scalars_indexed*, code -1); else None."""
 
     def __init__(self, code: int, msg: str, index: int | None = None, reason: int | None = None):
         super().__init__(f"te_msm error {code}: {msg}")
@@ -127,6 +128,14 @@ def _lib() -> ctypes.CDLL:
         L.te_msm_submit_scalars.restype = ci
         L.te_msm_submit_scalars_device.argtypes = [vp, vp, vp, ctypes.POINTER(u64)]
         L.te_msm_submit_scalars_device.restype = ci
+        L.te_msm_run_scalars_indexed.argtypes = [vp, vp, vp, cp, u64, cp]
+        L.te_msm_run_scalars_indexed.restype = ci
+        L.te_msm_run_scalars_indexed_device.argtypes = [vp, vp, vp, vp, u64, cp]
+        L.te_msm_run_scalars_indexed_device.restype = ci
+        L.te_msm_submit_scalars_indexed.argtypes = [vp, vp, vp, cp, u64, ctypes.POINTER(u64)]
+        L.te_msm_submit_scalars_indexed.restype = ci
+        L.te_msm_submit_scalars_indexed_device.argtypes = [vp, vp, vp, vp, u64, ctypes.POINTER(u64)]
+        L.te_msm_submit_scalars_indexed_device.restype = ci
         L.te_msm_bases_read.argtypes = [vp, vp, ci, u64, u64, vp, u64, ctypes.POINTER(ci)]
         L.te_msm_bases_read.restype = ctypes.c_int64
         L.te_msm_probe_queues.argtypes = [vp]
@@ -230,6 +239,8 @@ class MsmContext:
             msg = self._L.te_msm_last_error(self._h).decode()
             if rc == EPOINT:
                 raise MsmError(rc, msg, self.get_option("bad_point_index"), self.get_option("bad_point_reason"))
+            if rc == -1 and msg.startswith("index at position "):       # an indexed MSM (a call, or the collect of its ticket)
+                raise MsmError(rc, msg, self.get_option("bad_index_position"))
             raise MsmError(rc, msg)
         return rc
 
@@ -490,6 +501,58 @@ class MsmContext:
         fn = self._L.te_msm_run_scalars_batch_device if device else self._L.te_msm_run_scalars_batch
         self._check(fn(self._h, bases._h, count, lv, scalars, out))
         return [out.raw[rb * m:rb * (m + 1)] for m in range(count)]
+
+    # ---- MSMs over an indexed subset of a bound point set: sum_j k_j P_{idx[j]} (include/te_msm.h)
+    def _pairs_of(self, bases: "Bases", indices, scalars):
+        """(the index list as a contiguous <u4 numpy array, the scalars as bytes, m)"""
+        import numpy as np
+        if bases._h is None or bases._ctx is not self:
+            raise MsmError(-1, "not a bound point set of this context")
+        if isinstance(indices, (bytes, bytearray, memoryview)):
+            raw = bytes(indices)
+            if len(raw) % 4:
+                raise MsmError(-1, "indices given as bytes must hold whole little-endian u32 values")
+            idx = np.frombuffer(raw, dtype="<u4")
+        else:
+            a = np.asarray(indices)
+            if a.dtype != np.dtype("<u4"):          # (a <u4 array is passed as it is: no copy, no pass over it -- the device checks the range)
+                if a.size and (a.dtype.kind not in "ui" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+                    raise MsmError(-1, "indices must be integers that fit 32 unsigned bits")
+                a = a.astype("<u4")
+            idx = np.ascontiguousarray(a.reshape(-1))
+        sb = self._sizes[1]
+        scalars = bytes(scalars) if isinstance(scalars, (bytes, bytearray)) else bytes(memoryview(scalars).cast("B"))
+        if len(scalars) != sb * idx.size:
+            raise MsmError(-1, f"scalars must be {sb}*{idx.size} bytes for {idx.size} indices")
+        return idx, scalars, int(idx.size)
+
+    def run_scalars_indexed(self, bases: "Bases", indices, scalars) -> bytes:
+        """te_msm_run_scalars_indexed: sum_j scalars[j] * P[indices[j]] over a bound point set.  indices: anything numpy turns into <u4
+        (a list, an array), or bytes of little-endian u32; any order, repeats allowed, each below bases.n -- else MsmError(-1) with
+        .index = the lowest offending position.  Only the pairs cross PCIe, and the sort runs over len(indices) entries."""
+        idx, scalars, m = self._pairs_of(bases, indices, scalars)
+        out = ctypes.create_string_buffer(96)
+        self._check(self._L.te_msm_run_scalars_indexed(self._h, bases._h, idx.ctypes.data if m else None, scalars if m else None, m, out))
+        return out.raw[:self._sizes[2]]
+
+    def run_scalars_indexed_device(self, bases: "Bases", d_indices: int, d_scalars: int, m: int) -> bytes:
+        """te_msm_run_scalars_indexed_device: m u32 indices and m scalar records resident on ONE device of the context"""
+        out = ctypes.create_string_buffer(96)
+        self._check(self._L.te_msm_run_scalars_indexed_device(self._h, bases._h, d_indices, d_scalars, m, out))
+        return out.raw[:self._sizes[2]]
+
+    def submit_scalars_indexed(self, bases: "Bases", indices, scalars) -> int:
+        """te_msm_submit_scalars_indexed: asynchronous ticket (this object holds both buffers until the ticket is collected)"""
+        idx, scalars, m = self._pairs_of(bases, indices, scalars)
+        t = ctypes.c_uint64()
+        self._check(self._L.te_msm_submit_scalars_indexed(self._h, bases._h, idx.ctypes.data if m else None, scalars if m else None, m, ctypes.byref(t)))
+        self._held[t.value] = (idx, scalars)
+        return t.value
+
+    def submit_scalars_indexed_device(self, bases: "Bases", d_indices: int, d_scalars: int, m: int) -> int:
+        t = ctypes.c_uint64()
+        self._check(self._L.te_msm_submit_scalars_indexed_device(self._h, bases._h, d_indices, d_scalars, m, ctypes.byref(t)))
+        return t.value
 
     def submit_scalars(self, bases: "Bases", scalars: bytes) -> int:
         """te_msm_submit_scalars: asynchronous ticket over a bound point set (this object holds the scalars until the ticket

@@ -382,8 +382,16 @@ struct scatter_args {
 // index, key and partition in ONE LDS store and ONE load per entry (round 3 staged a u32 index and two u16 words: three
 // stores, and five loads in the copy-out with the two offset tables; LDS instructions per thread and tile 72 -> 32).
 #define TE_SCATTER_LDS_WORDS (TE_TILE + 4u * 512u + 17u)
-// chunk `ch` of local window `k` (block of 512 threads; lds: TE_SCATTER_LDS_WORDS words)
-__device__ __forceinline__ void part_scatter_block(uint32_t ch, uint32_t k, uint32_t* __restrict__ lds, const scatter_args& a) {
+// INDEXED SUBSETS (te_msm_run_scalars_indexed): the entry at position j of every row is bound record idx[j], not record j.  idx is ONE
+// array of g.n words shared by all windows (already offset to the piece); count = records of the bound set.  An index >= count never
+// reaches an address: the copy-out replaces it by 0, and the blocks of the launch's first window report it -- bit 1 of err[0] and
+// err[1] = max over ~(pos_base + j), i.e. the LOWEST bad position of the whole call (the words are zeroed per MSM and kept from piece
+// to piece) -- for EVERY j, whatever its scalar: an entry whose digits are all 0 is sorted nowhere.
+struct index_args { const uint32_t* idx; uint32_t count, pos_base; uint32_t* err; };
+// chunk `ch` of local window `k` (block of 512 threads; lds: TE_SCATTER_LDS_WORDS words).  IDX: the indexed form (k_part_scatter_indexed,
+// x is read); a compile-time twin, so that the kernels of the headline path keep their code.
+template <bool IDX>
+__device__ __forceinline__ void part_scatter_block(uint32_t ch, uint32_t k, uint32_t* __restrict__ lds, const scatter_args& a, const index_args& x) {
   uint32_t* const st = lds;
   uint32_t* const tile_cnt = lds + TE_TILE; uint32_t* const tile_off = tile_cnt + 512; uint32_t* const run_base = tile_cnt + 1024;
   uint32_t* const gdelta = tile_cnt + 1536;            // run_base - tile_off of the current tile: global position of LDS slot s = s + gdelta[partition]
@@ -425,7 +433,15 @@ __device__ __forceinline__ void part_scatter_block(uint32_t ch, uint32_t k, uint
       if (t == 0) part_count[a.nw * g.P + k] = ovt;
     }
   }
-  const uint32_t lo = ch * g.chunk_len, hi = min(a.remap ? min(a.row_fill[k], g.nst) : g.nst, lo + g.chunk_len);
+  const uint32_t lo = ch * g.chunk_len, hi = min((!IDX && a.remap) ? min(a.row_fill[k], g.nst) : g.nst, lo + g.chunk_len);
+  if constexpr (IDX) {
+    if (k == 0) {                                         // uniform: the chunk's indices are checked once per launch, coalesced
+      bool bad = false;
+      for (uint32_t j = lo + t; j < min(hi, g.n); j += 512u)
+        if (x.idx[j] >= x.count) { bad = true; atomicMax(x.err + 1, ~(x.pos_base + j)); }
+      if (bad) atomicOr(x.err, 2u);
+    }
+  }
   const uint4* d4 = reinterpret_cast<const uint4*>(digits + (size_t)k * g.nst);
   const uint32_t last8 = (g.nst >> 3) - 1u;
   uint16_t* ok = part_keys + (size_t)k * g.nst;
@@ -461,6 +477,15 @@ __device__ __forceinline__ void part_scatter_block(uint32_t ch, uint32_t k, uint
         st[tile_off[part[e]] + rank[e]] = (t * 8u + (uint32_t)e) | (part[e] << 12) | ((key[e] & 0xffu) << 20) | ((key[e] >> 15) << 28);
     }
     __syncthreads();
+    if constexpr (IDX) {                                  // the index comes from the call's table (a 16 KB window per tile), clamped into the set
+      const uint32_t* __restrict__ ix = x.idx + base;
+      for (uint32_t s = t; s < tile_total; s += 512u) {
+        const uint32_t w = st[s];
+        const uint32_t gpos = s + gdelta[(w >> 12) & 0xffu], r = ix[w & 0xfffu], pi = r < x.count ? r : 0u;
+        if (g.packed) oi[gpos] = pi | (((w >> 20) & 0xffu) << 23) | ((w >> 28) << 31);       // (count <= 2^23: the plan's rule)
+        else { ok[gpos] = (uint16_t)(((w >> 20) & 0xffu) | ((w >> 28) << 15)); oi[gpos] = pi; }
+      }
+    } else
     if (g.packed) {                                       // uniform: key and index leave as one word (4 bytes per entry instead of 6)
       for (uint32_t s = t; s < tile_total; s += 512u) {
         const uint32_t w = st[s];
@@ -489,7 +514,12 @@ __device__ __forceinline__ void part_scatter_block(uint32_t ch, uint32_t k, uint
 // grid (CH, nw), block 512
 __global__ void __launch_bounds__(512) k_part_scatter(scatter_args a) {
   __shared__ uint32_t lds[TE_SCATTER_LDS_WORDS];
-  part_scatter_block(blockIdx.x, blockIdx.y, lds, a);
+  part_scatter_block<false>(blockIdx.x, blockIdx.y, lds, a, index_args{});
+}
+// the indexed form (see index_args): the same grid, a kernel of its own
+__global__ void __launch_bounds__(512) k_part_scatter_indexed(scatter_args a, index_args x) {
+  __shared__ uint32_t lds[TE_SCATTER_LDS_WORDS];
+  part_scatter_block<true>(blockIdx.x, blockIdx.y, lds, a, x);
 }
 
 // Level 1 of the sort and the record conversion in ONE launch (device-resident inputs): neither needs the other, the
@@ -506,7 +536,7 @@ __global__ void __launch_bounds__(512, TE_SCATTER_PREP_WAVES) k_part_scatter_pre
   const uint64_t tot = (uint64_t)scatter_blocks + prep_blocks, b = blockIdx.x;
   const uint32_t s_before = (uint32_t)(b * scatter_blocks / tot), s_after = (uint32_t)((b + 1u) * scatter_blocks / tot);
   if (s_after > s_before) {                               // this block is scatter block number s_before
-    part_scatter_block(s_before % a.g.CH, s_before / a.g.CH, reinterpret_cast<uint32_t*>(lds4), a);
+    part_scatter_block<false>(s_before % a.g.CH, s_before / a.g.CH, reinterpret_cast<uint32_t*>(lds4), a, index_args{});
   } else {
     const uint32_t pb = (uint32_t)b - s_before, row = pb / prep_blocks_per_row, blk = pb - row * prep_blocks_per_row;
     prep_points_block(blk, lds4, in.p[row], recs + (size_t)row_slab.s[row] * n, n);
@@ -1521,7 +1551,7 @@ __global__ void __launch_bounds__(512, 4) k_part_scatter_prep377(scatter_args a,
   const uint64_t tot = (uint64_t)scatter_blocks + prep_blocks, b = blockIdx.x;
   const uint32_t s_before = (uint32_t)(b * scatter_blocks / tot), s_after = (uint32_t)((b + 1u) * scatter_blocks / tot);
   if (s_after > s_before) {                               // this block is scatter block number s_before
-    part_scatter_block(s_before % a.g.CH, s_before / a.g.CH, lds, a);
+    part_scatter_block<false>(s_before % a.g.CH, s_before / a.g.CH, lds, a, index_args{});
   } else {
     const uint32_t pb = (uint32_t)b - s_before, row = pb / prep_blocks_per_row, blk = pb - row * prep_blocks_per_row;
     const uint32_t i = blk * 512u + threadIdx.x;

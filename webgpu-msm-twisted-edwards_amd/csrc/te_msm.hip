@@ -38,6 +38,7 @@
 #include "host_tail377.hpp"
 #include "host_sched.hpp"
 #include "batch_plan.hpp"
+#include "indexed_plan.hpp"
 
 namespace {
 
@@ -95,7 +96,8 @@ struct workset_t {
   uint32_t *d_seg_base = nullptr, *d_seg_bucket = nullptr, *d_seg_lenv = nullptr, *d_order = nullptr;
   uint32_t *d_split_list = nullptr, *d_chunk_list = nullptr;
   uint8_t *d_seg_out = nullptr, *d_buckets = nullptr, *d_red[4] = {};   // accumulators of the plan's curve (te::ete_t<N>); d_red: ping/pong of the two fold chains
-  // ONE zeroed block per MSM (a single memset), words: [0] final-carry flag, [2..3] non-zero window digits as ONE 64-bit count (= entries
+  // ONE zeroed block per MSM (a single memset), words: [0] bit 0 final-carry flag, bit 1 an index of an indexed MSM lies outside the bound
+  // set; [1] fixed-base windows: a row overflowed / indexed MSMs: ~(lowest bad position of the call), see te::index_args; [2..3] non-zero window digits as ONE 64-bit count (= entries
   // accumulated; W * n passes 2^32 inside the allowed range n < 2^31: round-5 advisor; [0..3] survive the pieces of a host-buffer MSM),
   // [4] number of segments, [5..7] split / giant
   // bucket counters, [Z_ROWS..) the partial rows of the MSM (so that flag and rows come back in ONE device-to-host copy),
@@ -136,6 +138,7 @@ struct workset_t {
   // a ticket whose points failed the check (option "check_points"): nothing was enqueued for it, its te_msm_collect reports TE_MSM_EPOINT
   int pt_rc = 0; int64_t pt_index = -1; int pt_reason = 0;
   uint8_t* d_batch_rows = nullptr;    // te_msm_run_scalars_batch: the rows of a ragged sequence (all its MSMs; cap[28])
+  uint32_t* d_in_idx = nullptr;       // te_msm_run_scalars_indexed*: device copy of a call's index list (host form, peer copies of tickets; cap[29])
 };
 constexpr int TE_MAX_WINDOWS = 64;    // window_bits >= 4
 // words [Z_CLOCK, Z_ROWS): k_accumulate's profiling words, 4 x TE_CLK_SLOTS 64-bit values (first wave in / last wave out on the
@@ -214,6 +217,7 @@ struct te_ctx {
   int opt_prezero = 1;         // clear a work set's zeroed block behind an MSM's read-back instead of in front of the next MSM's first kernel
   int opt_check_points = 0;    // validate input points before an MSM / a bind: 0 off, 1 form, 2 form + subgroup (include/te_msm.h)
   int64_t bad_point_index = -1; int bad_point_reason = 0;   // the last TE_MSM_EPOINT (get_option "bad_point_index" / "bad_point_reason")
+  int64_t bad_index_position = -1;  // te_msm_run_scalars_indexed*: lowest position of an index outside the bound set, of the last call that failed on one
   float stage_ms[ST_COUNT + 2] = {};
   bool have_stage_ms = false;
   int64_t stat_peer_copies = 0;  // hipMemcpyPeerAsync calls issued so far (multi-device contexts fed from device 0's memory; get_option "peer_copies")
@@ -433,6 +437,10 @@ struct msm_launch {
                                   // k_accumulate gathers from here instead of ws.d_recs (p.rec_kind tells which record form)
   const te::ragged_tab* ragged = nullptr;   // a ragged sequence (te_msm_run_scalars_batch): d_scalars is ONE packed buffer, MSM m's scalars at
                                   // ragged->off[m] with ragged->len[m] of them (k_digits_ragged); every window gathers from `bound` itself
+  // an indexed subset (te_msm_run_scalars_indexed*): entry j gathers record idx[j] of `bound` (which then stays at the set's FIRST record:
+  // no per-piece offset); idx: device memory, this launch's n entries.  idx_count: records of the set; idx_pos: position of entry 0 in the
+  // caller's whole list (what a bad index is reported at).  p.packed follows the SET's count (indexed_plan.hpp)
+  const uint32_t* idx = nullptr; uint32_t idx_count = 0, idx_pos = 0;
   // Own rows of a context that computes ALL windows can be written to host memory by the tail kernel (every row slot is
   // rewritten by every MSM).  Not with window shards (rows of foreign windows must read as zero: they come from the cleared
   // device block), not with "prezero" = 0 (stage verifiers read the device rows).
@@ -567,6 +575,8 @@ struct msm_launch {
           hipLaunchKernelGGL(te::k_part_scatter_prep, dim3(sblocks + rows * per_row), dim3(512), 0, stream, sa, sblocks, tab, row_slab,
                              reinterpret_cast<te::pnt_slot*>(recs_out()), n32, per_row, rows * per_row);
         }
+      } else if (idx) {
+        hipLaunchKernelGGL(te::k_part_scatter_indexed, dim3(p.CH, p.nw), dim3(512), 0, stream, sa, te::index_args{idx, idx_count, idx_pos, ws.d_err});
       } else {
         hipLaunchKernelGGL(te::k_part_scatter, dim3(p.CH, p.nw), dim3(512), 0, stream, sa);
       }
@@ -964,9 +974,14 @@ enum share_mode { SHARE_NONE = 0, SHARE_CONVERT = 1, SHARE_RUN = 2 };
 // share: the record slab of the call (share_mode); a shared slab only for device-resident points, without bound bases
 int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, const void* d_scalars, uint64_t n,
                     void* d_partials_out, hipStream_t stream, const std::function<int(hipStream_t)>* upload_points = nullptr, int force_c = 0,
-                    bool side_stream = false, int batch = 1, bool whole = false, const te_bases* bases = nullptr, share_mode share = SHARE_NONE) {
-  plan_t p; make_plan(ctx, d, n, p, force_c, batch, 0, whole);
+                    bool side_stream = false, int batch = 1, bool whole = false, const te_bases* bases = nullptr, share_mode share = SHARE_NONE,
+                    const uint32_t* d_idx = nullptr) {
+  // d_idx (with bases): an indexed subset -- the n entries gather records d_idx[0 .. n) of the set (device memory of d)
+  // (the plan is made for the n entries; only the entry form follows the set's count: indexed_plan.hpp)
+  const te_indexed::call_plan ip = te_indexed::plan_for(n, d_idx ? bases->n : n, ctx->opt_packed);
+  plan_t p; make_plan(ctx, d, ip.plan_n, p, force_c, batch, 0, whole);
   if (bases) p.rec_kind = bases->rec_kind;
+  if (d_idx) p.packed = ip.packed;
   // (a batch shares when all its MSMs name ONE point buffer: the batch then holds one conversion anyway -- slab 0 of msm_launch::slabs())
   const void* share_src = d_points;
   if (batch > 1 && d_points) { share_src = static_cast<const void* const*>(d_points)[0]; for (int m = 1; m < batch; m++) if (static_cast<const void* const*>(d_points)[m] != share_src) share_src = nullptr; }
@@ -1003,6 +1018,7 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
   if (bases) {
     // resident bases: the scalar-only stages, then the accumulation straight from the bound records
     L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];
+    if (d_idx) { L.idx = d_idx; L.idx_count = (uint32_t)bases->n; }
     if (int rc = L.front_scalars()) return rc;
     L.mark(ST_PREP);
     if (int rc = L.accumulate()) return rc;
@@ -1105,7 +1121,7 @@ void free_workset_buffers(workset_t& ws) {      // the big device buffers of a w
                    (void**)&ws.d_part_idx, (void**)&ws.d_seg_part_base, (void**)&ws.d_bucket_start, (void**)&ws.d_bucket_cursor, (void**)&ws.d_sorted,
                    (void**)&ws.d_seg_base, (void**)&ws.d_seg_bucket, (void**)&ws.d_seg_lenv, (void**)&ws.d_order, (void**)&ws.d_split_list,
                    (void**)&ws.d_chunk_list, (void**)&ws.d_seg_out, (void**)&ws.d_buckets, (void**)&ws.d_red[0], (void**)&ws.d_red[1],
-                   (void**)&ws.d_red[2], (void**)&ws.d_red[3], &ws.d_in_points, &ws.d_in_scalars, (void**)&ws.d_fb_remap, (void**)&ws.d_batch_rows};
+                   (void**)&ws.d_red[2], (void**)&ws.d_red[3], &ws.d_in_points, &ws.d_in_scalars, (void**)&ws.d_fb_remap, (void**)&ws.d_batch_rows, (void**)&ws.d_in_idx};
   for (void** q : ptrs) if (*q) { (void)hipFree(*q); *q = nullptr; }
   if (ws.h_ring) { (void)hipHostFree(ws.h_ring); ws.h_ring = nullptr; }       // the pinned ring of option "host_staging" (its events stay)
   memset(ws.cap, 0, sizeof ws.cap); ws.cap_in_points = ws.cap_in_scalars = 0;
@@ -1434,24 +1450,29 @@ int scalar_pieces(const te_ctx* ctx, uint64_t n) {
 // ONTO THE SAME BUCKETS on the main stream (its records are at recs + lo * record bytes) --, one bucket reduction at the end,
 // flag + rows on their way to the set's pinned block when the call returns.  Does not wait: the caller synchronises ws.ev_result.
 // All windows, window bits forced to c.  wait_for_pinned: as enqueue_host_slice.
+// src_idx (te_msm_run_scalars_indexed*): the slice is n (index, scalar) pairs over a set of idx_count records -- `recs` is the set's FIRST
+// record, every piece carries its slice of both arrays and gathers records idx[j] (msm_launch::idx); idx_pos: position of the slice's
+// first pair in the caller's list.  The entry form follows the set's count, everything else n (indexed_plan.hpp).
 int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* recs, int rec_kind, const uint8_t* src_scalars, uint64_t n, int c, int K,
-                         bool wait_for_pinned = true) {
+                         bool wait_for_pinned = true, const uint32_t* src_idx = nullptr, uint64_t idx_count = 0, uint64_t idx_pos = 0) {
   HIP_TRY(ctx, hipSetDevice(d.device));
   plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true);
   pf.rec_kind = rec_kind;
   const curve_sizes sz = sizes_of(pf.curve);
   const size_t rec_bytes = rec_bytes_of(pf.curve, rec_kind);
   if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
+  if (src_idx) { if (int rc = ensure(ctx, ws, ws.d_in_idx, ws.cap[29], (size_t)n)) return rc; }
   uint8_t* dscs = static_cast<uint8_t*>(ws.d_in_scalars);
   if (K < 1) K = 1;
   if ((uint64_t)K > n) K = (int)n;
-  auto piece_lo = [&](int i) -> uint64_t { return i >= K ? n : (uint64_t)(((unsigned __int128)n * (unsigned)i) / (unsigned)K); };
+  auto piece_lo = [&](int i) -> uint64_t { return te_indexed::piece_lo(n, K, i); };
   uint64_t m_max = 0;
   for (int i = 0; i < K; i++) m_max = std::max(m_max, piece_lo(i + 1) - piece_lo(i));
   uint32_t seg_all = 0;
   {
     plan_t pm; make_plan(ctx, d, m_max, pm, pf.c, 1, 0, true);
     pm.rec_kind = rec_kind;
+    if (src_idx) pm.packed = te_indexed::plan_for(m_max, idx_count, ctx->opt_packed).packed;
     seg_all = pm.seg_len;
     if (int rc = ensure_buffers(ctx, d, ws, m_max, pm, false)) return rc;      // every buffer at its final size before the first piece
   }
@@ -1474,17 +1495,20 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
       std::unique_lock<std::mutex> link(*d.scalar_link, std::defer_lock);
       if (!wait_for_pinned) link.lock();                                        // (a lane thread: see gpu_t::scalar_link)
       stamp("upload begins", i);
+      if (src_idx) { if (int rc = upload(ctx, ws, ws.d_in_idx + lo, reinterpret_cast<const uint8_t*>(src_idx + lo), m * sizeof(uint32_t), ws.copy_stream)) return rc; }
       if (int rc = upload(ctx, ws, dscs + lo * sz.scalar_in, src_scalars + lo * sz.scalar_in, m * sz.scalar_in, ws.copy_stream)) return rc;
       stamp("upload call returned", i);
-      if (int rc = lane_wait(ctx, ws, evs[(size_t)i], !wait_for_pinned || caller_may_wait_on_host(src_scalars, nullptr))) return rc;
+      if (int rc = lane_wait(ctx, ws, evs[(size_t)i], !wait_for_pinned || caller_may_wait_on_host(src_scalars, src_idx))) return rc;
       stamp("upload awaited", i);
     }
     make_plan(ctx, d, m, p, pf.c, 1, seg_all, true);
     p.rec_kind = rec_kind;
+    if (src_idx) p.packed = te_indexed::plan_for(m, idx_count, ctx->opt_packed).packed;
     if (int rc = ensure_buffers(ctx, d, ws, m, p, false)) return rc;           // no reallocation: only the pointers into the zeroed block move
     msm_launch L{ctx, ws, p, nullptr, dscs + lo * sz.scalar_in, m, ws.d_partials, 0, ws.stream, true, !first};
     L.host_rows = msm_launch::rows_to_host(ctx, d, p, true);
-    L.bound = recs + lo * rec_bytes;
+    L.bound = src_idx ? recs : recs + lo * rec_bytes;
+    if (src_idx) { L.idx = ws.d_in_idx + lo; L.idx_count = (uint32_t)idx_count; L.idx_pos = (uint32_t)(idx_pos + lo); }
     ws.rows_on_host = L.host_rows;
     first = false;
     if (int rc = L.front_scalars()) return rc;
@@ -1497,7 +1521,7 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
   __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipGetLastError());
-  if (wait_for_pinned && !ctx->opt_host_staging && host_memory_is_pinned(src_scalars)) HIP_TRY(ctx, hipEventSynchronize(evs[(size_t)K - 1]));
+  if (wait_for_pinned && !ctx->opt_host_staging && (host_memory_is_pinned(src_scalars) || (src_idx && host_memory_is_pinned(src_idx)))) HIP_TRY(ctx, hipEventSynchronize(evs[(size_t)K - 1]));
   return 0;
 }
 
@@ -1626,6 +1650,16 @@ int lone_set(te_ctx* ctx, const gpu_t& d, int selected) {
 int64_t entries_of(const workset_t& ws) { uint64_t v; memcpy(&v, ws.h_err + Z_ENTRIES, sizeof v); return (int64_t)v; }
 void note_entries(te_ctx* ctx, const workset_t& ws) { ctx->stat_entries = entries_of(ws); }
 
+// Indexed MSMs (te_msm_run_scalars_indexed*): an index outside the bound set, seen by the device (te::index_args) -- the flag words of the
+// work set are on the host.  -1: none; else the lowest bad position the set's launch sequences saw.
+int64_t bad_index_of(const workset_t& ws) { return (ws.h_err[0] & 2u) ? (int64_t)(uint32_t)~ws.h_err[1] : -1; }
+int note_bad_index(te_ctx* ctx, int64_t position) {
+  ctx->bad_index_position = position;
+  char buf[160];
+  snprintf(buf, sizeof buf, "index at position %lld is not below te_msm_bases_count of the bound point set", (long long)position);
+  return set_err(ctx, TE_MSM_EINVAL, buf);
+}
+
 // te_msm_run for a large MSM on one device: enqueue_host_slice on a free work set, wait, host tail
 int run_host_chunked(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_scalars, uint64_t n, int K, uint8_t out[64]) {
   gpu_t& d = ctx->devs[0];
@@ -1651,22 +1685,28 @@ int run_host_chunked(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
 // (te_msm_submit / te_msm_submit_async below): no replicated bucket reduction, no row merge.
 // bases: the MSM runs over a bound point set -- every device holds all records, so device i takes slice i of the SCALARS over its
 // link and gathers from its own copy of the records at the slice's offset (src_points is not read).
-int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_scalars, uint64_t n, uint8_t* out, const te_bases* bases = nullptr) {
+// src_idx (with bases): an indexed subset of n (index, scalar) pairs -- device i takes slice i of BOTH arrays (indexed_plan.hpp: slices
+// of near-equal size) and gathers from all of its records.
+int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_scalars, uint64_t n, uint8_t* out, const te_bases* bases = nullptr,
+                     const uint32_t* src_idx = nullptr) {
   const size_t nd = ctx->devs.size();
   uint64_t per_min = ctx->opt_host_shard_min > 0 ? (uint64_t)ctx->opt_host_shard_min : 1;
-  size_t D = (size_t)std::min<uint64_t>(nd, std::max<uint64_t>(1, n / per_min));
+  size_t D = src_idx ? te_indexed::devices_for(n, nd, per_min) : (size_t)std::min<uint64_t>(nd, std::max<uint64_t>(1, n / per_min));
   const uint64_t per = (n + D - 1) / D;
+  auto slice_lo = [&](size_t i) -> uint64_t { return src_idx ? te_indexed::slice_lo(n, D, i) : std::min<uint64_t>(n, per * i); };
   plan_t p0; make_plan(ctx, ctx->devs[0], per, p0, 0, 1, 0, true);     // geometry of every slice's rows (window bits from the slice size)
   const curve_sizes sz = sizes_of(p0.curve);
-  const int K = bases ? scalar_pieces(ctx, per) : host_pieces(ctx, per);
+  const int K = src_idx ? te_indexed::pieces(per, ctx->opt_scalar_chunks) : bases ? scalar_pieces(ctx, per) : host_pieces(ctx, per);
   std::vector<int> wsel;
   if (int rc = free_sets(ctx, D, wsel)) return rc;
   auto slice = [&](size_t i) -> int {
-    const uint64_t lo = std::min<uint64_t>(n, per * i), hi = std::min<uint64_t>(n, lo + per);
+    const uint64_t lo = slice_lo(i), hi = src_idx ? slice_lo(i + 1) : std::min<uint64_t>(n, lo + per);
     gpu_t& d = ctx->devs[i];
     if (hi == lo) return 0;
     workset_t& ws = d.ws[wsel[i]];
-    if (bases) {
+    if (src_idx) {
+      if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[i], bases->rec_kind, src_scalars + lo * sz.scalar_in, hi - lo, p0.c, K, true, src_idx + lo, bases->n, lo)) return rc;
+    } else if (bases) {
       if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[i] + lo * bases->rec_bytes, bases->rec_kind, src_scalars + lo * sz.scalar_in, hi - lo, p0.c, K)) return rc;
     } else {
       if (int rc = enqueue_host_slice(ctx, d, ws, src_points + lo * sz.point_in, src_scalars + lo * sz.scalar_in, hi - lo, p0.c, K)) return rc;
@@ -1677,8 +1717,13 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
   if (int rc = te_sched::on_devices(*ctx, D, slice)) return rc;
   std::vector<const uint8_t*> sets;
   int64_t entries = 0;
+  if (src_idx) {                                            // an index outside the set, on any device: the lowest position of the call
+    int64_t bad = -1;
+    for (size_t i = 0; i < D; i++) { const int64_t b = bad_index_of(ctx->devs[i].ws[wsel[i]]); if (b >= 0 && (bad < 0 || b < bad)) bad = b; }
+    if (bad >= 0) return note_bad_index(ctx, bad);
+  }
   for (size_t i = 0; i < D; i++) {
-    if (per * i >= n) break;
+    if (slice_lo(i) >= n) break;
     workset_t& ws = ctx->devs[i].ws[wsel[i]];
     if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
     entries += entries_of(ws);
@@ -2329,6 +2374,7 @@ int te_msm_collect(te_ctx* ctx, uint64_t ticket, uint8_t out_xy_le[64]) {
   (void)collect_stage_ms(ctx, d, ws);
   note_entries(ctx, ws);
   retire_ticket(ctx, d, ws);                         // the MSM is over, with a result or with a scalar-range error
+  if (const int64_t bad = bad_index_of(ws); bad >= 0) return note_bad_index(ctx, bad);      // (indexed tickets only: nothing else sets the bit)
   if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
   fold_rows(ws.plan, ws.h_partials, out_xy_le);
   return 0;
@@ -2670,6 +2716,126 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
   return 0;
 }
 
+// ---- MSMs over an indexed subset of a bound point set (include/te_msm.h) ------------------------------------------------------
+namespace {
+// the arguments all four calls share; 0 = go on
+int indexed_args(te_ctx* ctx, const te_bases* bases, const void* idx, const void* scalars, uint64_t m) {
+  if (int rc = check_bases(ctx, bases)) return rc;
+  if (int rc = check_n(ctx, m)) return rc;
+  if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_EINVAL, "indexed MSMs are whole MSMs: reset the window shard first");
+  if (m > 0 && (!idx || !scalars)) return set_err(ctx, TE_MSM_EINVAL, "null index or scalar buffer");
+  if (m > 0 && bases->n == 0) { ctx->bad_index_position = 0; return set_err(ctx, TE_MSM_EINVAL, "the bound point set is empty: no index is below its count"); }
+  return 0;
+}
+const char* const kIndexedResident = "indexed MSM: indices and scalars must be resident on one device of the context";
+
+// the m pairs at d_idx / d_scalars (memory of device src_dev) into the set's staging area over the peer link, on the set's stream
+int pull_pairs(te_ctx* ctx, const gpu_t& d, workset_t& ws, const void* d_idx, const void* d_scalars, int src_dev, uint64_t m) {
+  if (int rc = ensure(ctx, ws, ws.d_in_idx, ws.cap[29], (size_t)m)) return rc;
+  if (int rc = pull_scalars(ctx, d, ws, d_scalars, src_dev, m)) return rc;
+  HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_idx, d.device, d_idx, src_dev, m * sizeof(uint32_t), ws.stream));
+  ctx->stat_peer_copies += 2; ctx->stat_peer_bytes += (int64_t)(m * (sizes_of(ctx->opt_curve).scalar_in + sizeof(uint32_t)));
+  return 0;
+}
+
+// The end of a lone indexed call on one work set: result awaited, bad index / final carry reported, rows folded.
+int settle_indexed(te_ctx* ctx, gpu_t& d, workset_t& ws, uint8_t* out) {
+  HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
+  note_entries(ctx, ws);
+  if (const int64_t bad = bad_index_of(ws); bad >= 0) return note_bad_index(ctx, bad);
+  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  (void)collect_stage_ms(ctx, d, ws);
+  fold_rows(ws.plan, ws.h_partials, out);
+  return 0;
+}
+
+int run_indexed_common(te_ctx* ctx, te_bases* bases, const void* idx, const void* src, bool src_is_host, uint64_t m, uint8_t* out) {
+  if (!ctx || !out) return TE_MSM_EINVAL;
+  if (int rc = indexed_args(ctx, bases, idx, src, m)) return rc;
+  if (m == 0) { write_identity(ctx->opt_curve, out); return 0; }
+  const bool multi = ctx->devs.size() > 1;
+  if (src_is_host && multi) return run_host_sharded(ctx, nullptr, static_cast<const uint8_t*>(src), m, out, bases, static_cast<const uint32_t*>(idx));
+  // device form: the whole MSM on the device that holds the pairs
+  const int owner = src_is_host ? 0 : owner_of(ctx, kIndexedResident, {idx, src});
+  if (owner < 0) return owner;
+  gpu_t& d = ctx->devs[(size_t)owner];
+  const int wsel = lone_set(ctx, d, multi ? 0 : ctx->opt_workset);
+  if (wsel < 0) return wsel;
+  workset_t& ws = d.ws[wsel];
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  if (src_is_host) {
+    plan_t p0; make_plan(ctx, d, m, p0, 0, 1, 0, true);
+    if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[(size_t)owner], bases->rec_kind, static_cast<const uint8_t*>(src), m, p0.c,
+                                      te_indexed::pieces(m, ctx->opt_scalar_chunks), true, static_cast<const uint32_t*>(idx), bases->n, 0)) return rc;
+  } else {
+    if (int rc = enqueue_partial(ctx, d, ws, nullptr, src, m, nullptr, ws.stream, nullptr, 0, false, 1, true, bases, SHARE_NONE, static_cast<const uint32_t*>(idx))) return rc;
+    if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
+  }
+  return settle_indexed(ctx, d, ws, out);
+}
+}  // namespace
+
+int te_msm_run_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* idx, const uint8_t* scalars_le, uint64_t m, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  return run_indexed_common(ctx, bases, idx, scalars_le, true, m, out_xy_le);
+}
+
+int te_msm_run_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const void* d_idx, const void* d_scalars_le, uint64_t m, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  return run_indexed_common(ctx, bases, d_idx, d_scalars_le, false, m, out_xy_le);
+}
+
+int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* idx, const uint8_t* scalars_le, uint64_t m, uint64_t* ticket) {
+  device_guard restore_callers_device;
+  if (!ctx || !ticket) return TE_MSM_EINVAL;
+  if (int rc = indexed_args(ctx, bases, idx, scalars_le, m)) return rc;
+  if (m == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty index list has no tickets: te_msm_run_scalars_indexed returns the identity)");
+  int di = -1;
+  const int wi = take_free_workset(ctx, -1, false, &di);
+  if (wi < 0) return wi;
+  gpu_t& d = ctx->devs[(size_t)di];
+  workset_t& ws = d.ws[wi];
+  plan_t pf; make_plan(ctx, d, m, pf, 0, 1, 0, true);
+  // (pieces: the rule of te_msm_submit_scalars -- with other tickets in flight the upload hides under their device work)
+  const int c = pf.c, K = (ctx->opt_scalar_chunks || d.in_flight == 0) ? te_indexed::pieces(m, ctx->opt_scalar_chunks) : 1;
+  ws.job_err.clear();
+  workset_t* wsp = &ws; gpu_t* dp = &d;
+  const uint8_t* recs = bases->recs[(size_t)di]; const int kind = bases->rec_kind; const uint64_t count = bases->n;
+  warm_upload_lanes(ctx);
+  te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, recs, kind, idx, scalars_le, m, c, K, count]() -> int {
+    return lane_status(ctx, *wsp, enqueue_scalar_slice(ctx, *dp, *wsp, recs, kind, scalars_le, m, c, K, false, idx, count, 0));
+  });
+  ws.bound = bases; bases->in_flight++;
+  hand_out_ticket(ctx, di, ws, ticket, std::move(job));
+  return 0;
+}
+
+int te_msm_submit_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const void* d_idx, const void* d_scalars_le, uint64_t m, uint64_t* ticket) {
+  device_guard restore_callers_device;
+  if (!ctx || !ticket) return TE_MSM_EINVAL;
+  if (int rc = indexed_args(ctx, bases, d_idx, d_scalars_le, m)) return rc;
+  if (m == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty index list has no tickets: te_msm_run_scalars_indexed_device returns the identity)");
+  const bool multi = ctx->devs.size() > 1;
+  const int owner = owner_of(ctx, kIndexedResident, {d_idx, d_scalars_le});
+  if (owner < 0) return owner;
+  int di = -1;
+  const int wi = take_free_workset(ctx, owner, true, &di);
+  if (wi < 0) return wi;
+  gpu_t& d = ctx->devs[(size_t)di];
+  workset_t& ws = d.ws[wi];
+  const int src_dev = ctx->devs[(size_t)owner].device;
+  const void* ds = d_scalars_le; const uint32_t* dx = static_cast<const uint32_t*>(d_idx);
+  if (multi && (d.device != src_dev || ctx->opt_stage_device_inputs)) {
+    if (int rc = pull_pairs(ctx, d, ws, d_idx, d_scalars_le, src_dev, m)) return rc;
+    ds = ws.d_in_scalars; dx = ws.d_in_idx;
+  }
+  if (int rc = enqueue_partial(ctx, d, ws, nullptr, ds, m, nullptr, ws.stream, nullptr, 0, false, 1, true, bases, SHARE_NONE, dx)) return rc;
+  if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
+  ws.bound = bases; bases->in_flight++;
+  hand_out_ticket(ctx, di, ws, ticket);
+  return 0;
+}
+
 int te_msm_probe_queues(te_ctx* ctx) {
   device_guard restore_callers_device;
   if (!ctx) return TE_MSM_EINVAL;
@@ -2762,6 +2928,7 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "check_points")) { *value = ctx->opt_check_points; return 0; }
   if (!strcmp(key, "bad_point_index")) { *value = ctx->bad_point_index; return 0; }
   if (!strcmp(key, "bad_point_reason")) { *value = ctx->bad_point_reason; return 0; }
+  if (!strcmp(key, "bad_index_position")) { *value = ctx->bad_index_position; return 0; }
   if (!strcmp(key, "host_chunks")) { *value = ctx->opt_host_chunks; return 0; }
   if (!strcmp(key, "host_shard_min")) { *value = ctx->opt_host_shard_min; return 0; }
   if (!strcmp(key, "queue_probe")) { *value = ctx->opt_queue_probe; return 0; }

@@ -320,6 +320,46 @@ napi_value MsmBatch(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+// msmIndexed(indices: Uint32Array, scalars: Buffer): Buffer -- one MSM over an indexed subset of the set bound by setBases
+// (include/te_msm.h, te_msm_run_scalars_indexed): sum_j scalars[j] * P[indices[j]], indices in any order, repeats allowed, each below the
+// set's size.  Returns 64 bytes x || y (the identity as (0, 1)); compute_msm.js wraps it into a promise of {x, y}.  Run like msmBatch
+// (under the context's lock once no promise is pending); without setBases, with an index outside the set (the Error names the lowest
+// offending position, also as .index) or with a scalar out of range it throws.
+napi_value MsmIndexed(napi_env env, napi_callback_info info) {
+  const char* const sig = "msmIndexed(indices: Uint32Array, scalars: Buffer)";
+  size_t argc = 2; napi_value argv[2];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool is_ta = false, is_buf = false;
+  if (argc >= 2) { napi_is_typedarray(env, argv[0], &is_ta); napi_is_buffer(env, argv[1], &is_buf); }
+  if (!is_ta || !is_buf) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  napi_typedarray_type tt; size_t m = 0; void* ip = nullptr; napi_value ab; size_t off = 0;
+  napi_get_typedarray_info(env, argv[0], &tt, &m, &ip, &ab, &off);
+  if (tt != napi_uint32_array) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  void* s = nullptr; size_t sl = 0;
+  napi_get_buffer_info(env, argv[1], &s, &sl);
+  if (sl != m * TE_MSM_SCALAR_BYTES) { napi_throw_range_error(env, nullptr, "msmIndexed: scalars must be 32 bytes per index"); return nullptr; }
+  uint8_t out[TE_MSM_POINT_BYTES];
+  int64_t bad = -1;
+  std::string err;
+  const int rc = g_proto.with_bases([&](te_ctx* c, te_bases* b) {
+    const int r = te_msm_run_scalars_indexed(c, b, static_cast<const uint32_t*>(ip), static_cast<const uint8_t*>(s), m, out);
+    if (r == TE_MSM_EINVAL && !strncmp(te_msm_last_error(c), "index at position ", 18)) (void)te_msm_get_option(c, "bad_index_position", &bad);
+    return r;
+  }, TE_MSM_ESTATE, err);
+  if (rc) {
+    const std::string msg_s = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_value msg, errv;
+    napi_create_string_utf8(env, msg_s.c_str(), msg_s.size(), &msg);
+    napi_create_error(env, nullptr, msg, &errv);
+    if (bad >= 0) { napi_value iv; napi_create_int64(env, bad, &iv); napi_set_named_property(env, errv, "index", iv); }
+    napi_throw(env, errv);
+    return nullptr;
+  }
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, sizeof out, out, &dst, &buf);
+  return buf;
+}
+
 napi_value ScalarMul(napi_env env, napi_callback_info info) { return MulCommon(env, info, false); }
 napi_value ScalarMulX(napi_env env, napi_callback_info info) { return MulCommon(env, info, true); }
 
@@ -364,7 +404,7 @@ napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
       {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints},
-      {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}};
+      {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

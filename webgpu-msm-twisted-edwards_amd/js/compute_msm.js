@@ -77,4 +77,13 @@ const msmBatch = (scalarBuffers) => {
   return res;
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX, scalarMul, scalarMulX, msmBatch };
+// And msmIndexed(indices, scalars): one MSM over an indexed subset of the set bound by setBases -- sum_j scalars[j] * P[indices[j]], a
+// sparse witness or a strided range of the SRS without zero padding.  indices: a Uint32Array (any order, repeats allowed, each below the
+// set's size); scalars: a Buffer of 32 bytes per index.  Resolves to {x, y} in compute_msm's form; rejects without setBases, on a scalar
+// out of range, and on an index outside the set (the Error names the lowest offending position, also as .index).
+const msmIndexed = async (indices, scalars) => {
+  const out = native.msmIndexed(indices, scalars);
+  return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
+};
+
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed };

@@ -28,3 +28,7 @@ export declare const scalarMulX: (xs: Buffer, scalars: Buffer) => Buffer;
 // Not in the reference: batched MSMs over prefixes of the set bound by setBases; MSM m runs over the first scalarBuffers[m].length / 32
 // points.  Results in input order, in compute_msm's form; throws without setBases or for a buffer longer than the set.
 export declare const msmBatch: (scalarBuffers: Buffer[]) => { x: bigint; y: bigint }[];
+// Not in the reference: one MSM over an indexed subset of the set bound by setBases, sum_j scalars[j] * P[indices[j]] (indices in any
+// order, repeats allowed, each below the set's size; 32 scalar bytes per index).  Rejects without setBases, for a scalar out of range and
+// for an index outside the set (the Error's .index is the lowest offending position).
+export declare const msmIndexed: (indices: Uint32Array, scalars: Buffer) => Promise<{ x: bigint; y: bigint }>;
