@@ -978,3 +978,49 @@ def test_giant_buckets(ctx, model, ora):
     ctx.set_option("packed_sort", 0)
     assert ctx.run(pts, same) == ora.msm(pts, same, threads=16) and ctx.run(pts, sc) == exp
     ctx.set_option("packed_sort", 1)
+
+
+def test_one_work_set_through_every_enqueue_form(pkg, ora):
+    """One work set of one context driven through every way a launch sequence begins on it -- device-resident inputs, host buffers in
+    two pieces, host scalars over a bound set, an indexed subset, a ragged batch, fixed-base windows -- with sizes that make its
+    buffers grow and then be reused smaller, a trim in the middle (everything is given back and allocated again), and the second
+    curve at the end (other record and accumulator sizes in the same buffers)."""
+    import torch
+    from oracle import oracle377
+    small, big, nb, m, nf = 300, 70000, 5000, 9000, 2000
+    pts, sc = ora.gen_points(91, big), ora.gen_scalars(92, big)
+    want = lambda p, s, k: ora.msm(p[:64 * k], s[:32 * k], threads=8)
+    dp, ds = _dev(pts[:64 * small]), _dev(sc[:32 * small])
+    torch.cuda.synchronize()
+    exp_small = want(pts, sc, small)
+    with pkg.MsmContext((0,)) as c:
+        assert c.get_option("device_bytes") == 0
+        assert c.run_device(dp.data_ptr(), ds.data_ptr(), small) == exp_small
+        c.set_option("host_chunks", 2)                          # (one piece is the rule below 2^17 points)
+        assert c.run(pts, sc) == want(pts, sc, big)
+        c.set_option("host_chunks", 0)
+        grown = c.get_option("device_bytes")
+        b = c.bind_points(pts[:64 * nb])
+        assert c.run_scalars(b, sc[:32 * nb]) == want(pts, sc, nb)
+        idx = np.random.default_rng(93).integers(0, nb, size=m, dtype=np.uint32)
+        assert len(np.unique(idx)) < m                          # with repeats
+        gathered = np.frombuffer(pts, dtype=np.uint8).reshape(-1, 64)[idx].tobytes()
+        assert c.run_scalars_indexed(b, idx, sc[:32 * m]) == ora.msm(gathered, sc[:32 * m], threads=8)
+        sc2 = ora.gen_scalars(94, 37)
+        assert c.run_scalars_batch(b, [sc[:32 * nb], sc2]) == [want(pts, sc, nb), want(pts, sc2, 37)]
+        c.release_points(b)
+        c.set_option("bind_fixed_base", 16)
+        fb = c.bind_points(pts[:64 * nf])
+        c.set_option("bind_fixed_base", 0)
+        assert c.run_scalars(fb, sc[:32 * nf]) == want(pts, sc, nf)
+        assert c.get_option("fixed_base_fallbacks") == 0
+        c.release_points(fb)
+        assert c.get_option("device_bytes") >= grown            # nothing shrank on the way
+        assert c.trim(0) >= 1 and c.get_option("device_bytes") == 0
+        assert c.run_device(dp.data_ptr(), ds.data_ptr(), small) == exp_small
+        assert 0 < c.get_option("device_bytes") < grown
+        c.set_option("curve", pkg.CURVE_BLS12_377_G1)
+        p377, s377 = oracle377.gen_points(95, small), oracle377.gen_scalars(96, small)
+        dp377, ds377 = _dev(p377), _dev(s377)
+        torch.cuda.synchronize()
+        assert c.run_device(dp377.data_ptr(), ds377.data_ptr(), small) == oracle377.msm(p377, s377, threads=8)

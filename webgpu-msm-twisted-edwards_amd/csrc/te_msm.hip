@@ -23,6 +23,7 @@
 #include <mutex>
 #include <condition_variable>
 #include <memory>
+#include <type_traits>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -81,6 +82,13 @@ struct plan_t {
   int fb_rb = 0, fb_c = 0, fb_W = 0;
 };
 
+// A grow-only device allocation and its one owner: the pointer and its capacity in bytes.  make_room() (below) grows it, release() gives it back.
+template <typename T> struct dev_buf {
+  T* p = nullptr; size_t cap = 0;
+  operator T*() const { return p; }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
 // Everything one MSM in flight needs on the device.  A GPU owns TE_MSM_WORKSETS work sets with their own streams so that
 // several MSMs overlap ON THE DEVICE: the launch gaps and the latency-bound reduction tail of one are filled by the wide kernels of the
 // other (te_msm_submit_device alternates them; "workset" option for te_msm_partial_device callers).
@@ -88,14 +96,13 @@ struct workset_t {
   hipStream_t stream = nullptr, copy_stream = nullptr;   // copy_stream: host-buffer uploads beside the compute stream (created on first use)
   int hw_queue_class = -1;            // which of the measured hardware-queue classes `stream` is on (-1: not probed)
   hipEvent_t ev_copy = nullptr, ev_start = nullptr;
-  size_t cap[40] = {};                                  // per-buffer capacity in bytes (ensure())
-  uint8_t* d_recs = nullptr;          // record slots of the plan's curve (te::rec_slot<N>)
-  uint16_t *d_digits = nullptr, *d_part_keys = nullptr;
-  uint32_t *d_counts1 = nullptr, *d_part_start = nullptr, *d_part_count = nullptr, *d_part_idx = nullptr, *d_seg_part_base = nullptr;
-  uint32_t *d_bucket_count = nullptr, *d_bucket_start = nullptr, *d_bucket_cursor = nullptr, *d_sorted = nullptr;
-  uint32_t *d_seg_base = nullptr, *d_seg_bucket = nullptr, *d_seg_lenv = nullptr, *d_order = nullptr;
-  uint32_t *d_split_list = nullptr, *d_chunk_list = nullptr;
-  uint8_t *d_seg_out = nullptr, *d_buckets = nullptr, *d_red[4] = {};   // accumulators of the plan's curve (te::ete_t<N>); d_red: ping/pong of the two fold chains
+  dev_buf<uint8_t> d_recs;            // record slots of the plan's curve (te::rec_slot<N>)
+  dev_buf<uint16_t> d_digits, d_part_keys;
+  dev_buf<uint32_t> d_part_start, d_part_count, d_part_idx, d_seg_part_base;
+  dev_buf<uint32_t> d_bucket_start, d_bucket_cursor, d_sorted;
+  dev_buf<uint32_t> d_seg_base, d_seg_bucket, d_seg_lenv, d_order;
+  dev_buf<uint32_t> d_split_list, d_chunk_list;
+  dev_buf<uint8_t> d_seg_out, d_buckets, d_red[4];   // accumulators of the plan's curve (te::ete_t<N>); d_red: ping/pong of the two fold chains
   // ONE zeroed block per MSM (a single memset), words: [0] bit 0 final-carry flag, bit 1 an index of an indexed MSM lies outside the bound
   // set; [1] fixed-base windows: a row overflowed / indexed MSMs: ~(lowest bad position of the call), see te::index_args; [2..3] non-zero window digits as ONE 64-bit count (= entries
   // accumulated; W * n passes 2^32 inside the allowed range n < 2^31: round-5 advisor; [0..3] survive the pieces of a host-buffer MSM),
@@ -103,10 +110,10 @@ struct workset_t {
   // bucket counters, [Z_ROWS..) the partial rows of the MSM (so that flag and rows come back in ONE device-to-host copy),
   // [Z_HIST..) segment-length histogram (TE_HIST_COPIES copies), [Z_CURSOR..) reservation cursors of the schedule, [Z_END..) the level-1 histogram
   // counts1[window][chunk][partition], then bucket_count[window][bucket].  d_err .. d_bucket_count point into d_zero.
-  uint32_t *d_zero = nullptr; size_t zero_words = 0;
+  dev_buf<uint32_t> d_zero; size_t zero_words = 0;
   size_t zero_clean_words = 0;        // words of d_zero known to be zero on the set's stream: the block is cleared AFTER an MSM's read-back
                                       // (finish_sequence), so that the next MSM on the set starts with its first kernel, not a fill
-  uint32_t *d_err = nullptr, *d_num_seg = nullptr, *d_size_hist = nullptr, *d_size_cursor = nullptr;
+  uint32_t *d_err = nullptr, *d_num_seg = nullptr, *d_size_hist = nullptr, *d_size_cursor = nullptr, *d_counts1 = nullptr, *d_bucket_count = nullptr;
   uint32_t* d_part_ticket = nullptr;  // [window][partition]: pieces of a multi-piece partition counted so far (k_l2_local), behind bucket_count in the zeroed block
   uint8_t* d_partials = nullptr;      // = d_zero + Z_ROWS: TE_MAX_WINDOWS rows
   uint32_t* h_err = nullptr;          // pinned: mirror of d_zero[0 .. Z_ROWS + rows)
@@ -123,12 +130,12 @@ struct workset_t {
   hipStream_t last_stream = nullptr;  // stream of the previous MSM on this set: a different one must wait for it (scratch reuse)
   // host-buffer MSMs (te_msm_run, te_msm_submit): device copies of the caller's buffers, sized in bytes for the curve of the
   // call, and the "piece i has arrived" events of an upload in pieces
-  void *d_in_points = nullptr, *d_in_scalars = nullptr; size_t cap_in_points = 0, cap_in_scalars = 0;
+  dev_buf<uint8_t> d_in_points, d_in_scalars;
   std::vector<hipEvent_t> piece_events;
   // option "host_staging": the set's own pinned ring for host-buffer uploads (allocated on first use; te_msm_trim / destroy free it)
   uint8_t* h_ring = nullptr; std::vector<hipEvent_t> ring_ev; size_t ring_next = 0;
   uint64_t idle_calls = 0;            // te_msm_trim: context-level calls since the set was last used
-  uint32_t* d_fb_remap = nullptr;     // fixed-base windows: [rows][cap] table index | sign << 31 of every entry (beside d_digits' codes)
+  dev_buf<uint32_t> d_fb_remap;       // fixed-base windows: [rows][cap] table index | sign << 31 of every entry (beside d_digits' codes)
   uint32_t* d_fb_fill = nullptr;      // ... [rows] entries reserved per row, in the zeroed block
   const void* fb_scalars = nullptr; uint64_t fb_n = 0;   // ... the scalars (device memory) of the MSM in flight: a row overflow falls back to the ordinary windows
   int slab = -1;                      // shared record slab the MSM in flight on this set uses (-1: its own d_recs, or a bound point set)
@@ -137,8 +144,15 @@ struct workset_t {
   te_bases* bound = nullptr;          // the bound point set the set's ticket in flight gathers from (te_msm_submit_scalars*): released only after the collect
   // a ticket whose points failed the check (option "check_points"): nothing was enqueued for it, its te_msm_collect reports TE_MSM_EPOINT
   int pt_rc = 0; int64_t pt_index = -1; int pt_reason = 0;
-  uint8_t* d_batch_rows = nullptr;    // te_msm_run_scalars_batch: the rows of a ragged sequence (all its MSMs; cap[28])
-  uint32_t* d_in_idx = nullptr;       // te_msm_run_scalars_indexed*: device copy of a call's index list (host form, peer copies of tickets; cap[29])
+  dev_buf<uint8_t> d_batch_rows;      // te_msm_run_scalars_batch: the rows of a ragged sequence (all its MSMs)
+  dev_buf<uint32_t> d_in_idx;         // te_msm_run_scalars_indexed*: device copy of a call's index list (host form, peer copies of tickets)
+  // EVERY dev_buf of the set, once: what te_msm_trim / destroy free is what "device_bytes" counts
+  template <typename WS, typename F> static void each_buffer(WS& ws, F&& f) {
+    f(ws.d_recs); f(ws.d_digits); f(ws.d_part_keys); f(ws.d_part_start); f(ws.d_part_count); f(ws.d_part_idx); f(ws.d_seg_part_base);
+    f(ws.d_bucket_start); f(ws.d_bucket_cursor); f(ws.d_sorted); f(ws.d_seg_base); f(ws.d_seg_bucket); f(ws.d_seg_lenv); f(ws.d_order);
+    f(ws.d_split_list); f(ws.d_chunk_list); f(ws.d_seg_out); f(ws.d_buckets); for (auto& b : ws.d_red) f(b);
+    f(ws.d_zero); f(ws.d_in_points); f(ws.d_in_scalars); f(ws.d_fb_remap); f(ws.d_batch_rows); f(ws.d_in_idx);
+  }
 };
 constexpr int TE_MAX_WINDOWS = 64;    // window_bits >= 4
 // words [Z_CLOCK, Z_ROWS): k_accumulate's profiling words, 4 x TE_CLK_SLOTS 64-bit values (first wave in / last wave out on the
@@ -177,7 +191,7 @@ struct gpu_t {
   // input-point validation (option "check_points", te_msm_check_points*): a stream, a piece buffer for host points and the report word
   // of its own, shared by every thread that checks on this device (upload lanes of asynchronous tickets included) under chk_mu
   std::unique_ptr<std::mutex> chk_mu{new std::mutex};
-  hipStream_t chk_stream = nullptr; uint8_t* chk_pts = nullptr; size_t chk_cap = 0;
+  hipStream_t chk_stream = nullptr; dev_buf<uint8_t> chk_pts;
   unsigned long long *chk_word = nullptr, *chk_host = nullptr;
   bool streams_exported = false;         // te_msm_workset_stream handed a handle out: te_msm_destroy parks the streams instead of destroying them
   bool streams_final = false;            // ... and the work sets' streams will not be re-dealt any more
@@ -355,58 +369,74 @@ void make_plan(const te_ctx* ctx, const gpu_t& d, uint64_t n, plan_t& p, int for
   p.packed = (ctx->opt_packed && n <= (1ull << 23)) ? 1u : 0u;
 }
 
-template <typename T> int ensure(te_ctx* ctx, workset_t& ws, T*& ptr, size_t& cap_bytes, size_t need_elems) {
+// room for need_elems elements: never shrinks, the contents do NOT survive a growth, a need of 0 still allocates (16 bytes)
+template <typename T> int make_room(te_ctx* ctx, dev_buf<T>& b, size_t need_elems) {
   const size_t need = need_elems * sizeof(T);
-  if (ptr && need <= cap_bytes) return 0;
-  if (ptr) HIP_TRY(ctx, hipFree(ptr));
-  ptr = nullptr; cap_bytes = 0;
-  HIP_TRY(ctx, hipMalloc((void**)&ptr, need ? need : 16));
-  cap_bytes = need;
+  if (b.p && need <= b.cap) return 0;
+  if (b.p) HIP_TRY(ctx, hipFree(b.p));
+  b.p = nullptr; b.cap = 0;
+  HIP_TRY(ctx, hipMalloc((void**)&b.p, need ? need : 16));
+  b.cap = need;
   return 0;
+}
+
+// The element counts that both an allocation (ensure_buffers) and a kernel argument (msm_launch) depend on, stated once.
+struct seq_sizes {
+  size_t wb, smax;                     // buckets of the sequence; segment ids: segments <= buckets + entries / seg_len
+  // entries of d_chunk_list (pairs): a giant bucket contributes one chunk per TE_GIANT_RUN parts: at most one per bucket plus one per
+  // TE_GIANT_RUN segments (slack: what the allocation adds to smax)
+  size_t chunk_cap(size_t slack = 0) const { return wb + (smax + slack) / TE_GIANT_RUN + 2; }
+};
+inline seq_sizes sizes_for(const plan_t& p, uint64_t n) {
+  const size_t wb = (size_t)p.nw * p.B;
+  return {wb, wb + (size_t)p.nw * (size_t)(n / (uint64_t)p.seg_len)};
 }
 
 // need_recs = false: the launch sequence gathers from a bound point set, the work set needs no record slab of its own
 int ensure_buffers(te_ctx* ctx, gpu_t& d, workset_t& ws, uint64_t n, const plan_t& p, bool need_recs = true) {
   HIP_TRY(ctx, hipSetDevice(d.device));
   // + 64: k_accumulate fetches its sorted indices TE_IDX_STRIP at a time and may read that far past the end of a list
-  const size_t nd = (size_t)p.nw * p.nst + 64, wb = (size_t)p.nw * p.B, ab = sizes_of(p.curve).acc;
+  const seq_sizes sz = sizes_for(p, n);
+  const size_t nd = (size_t)p.nw * p.nst + 64, wb = sz.wb, ab = sizes_of(p.curve).acc;
   int rc = 0;
-  if (need_recs && (rc = ensure(ctx, ws, ws.d_recs, ws.cap[0], (size_t)n * sizes_of(p.curve).rec * (size_t)p.batch))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_digits, ws.cap[1], nd))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_sorted, ws.cap[2], nd))) return rc;
+  if (need_recs && (rc = make_room(ctx, ws.d_recs, (size_t)n * sizes_of(p.curve).rec * (size_t)p.batch))) return rc;
+  if ((rc = make_room(ctx, ws.d_digits, nd))) return rc;
+  if ((rc = make_room(ctx, ws.d_sorted, nd))) return rc;
   {
     const size_t c1 = (size_t)p.nw * p.CH * p.P;
     ws.zero_words = Z_END + c1 + wb + (size_t)p.nw * p.P + 64;            // (+ 64: the row fill counters of fixed-base windows)
-    { const uint32_t* before = ws.d_zero; if ((rc = ensure(ctx, ws, ws.d_zero, ws.cap[3], ws.zero_words))) return rc; if (ws.d_zero != before) ws.zero_clean_words = 0; }
+    { const uint32_t* before = ws.d_zero; if ((rc = make_room(ctx, ws.d_zero, ws.zero_words))) return rc; if (ws.d_zero != before) ws.zero_clean_words = 0; }
     ws.d_err = ws.d_zero; ws.d_num_seg = ws.d_zero + Z_KEEP; ws.d_size_hist = ws.d_zero + Z_HIST; ws.d_size_cursor = ws.d_zero + Z_CURSOR;
     ws.d_partials = reinterpret_cast<uint8_t*>(ws.d_zero + Z_ROWS);
     ws.d_counts1 = ws.d_zero + Z_END; ws.d_bucket_count = ws.d_counts1 + c1; ws.d_part_ticket = ws.d_bucket_count + wb;
     ws.d_fb_fill = ws.d_part_ticket + (size_t)p.nw * p.P;
   }
-  if (p.fb_rb && (rc = ensure(ctx, ws, ws.d_fb_remap, ws.cap[27], nd))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_bucket_start, ws.cap[5], wb))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_bucket_cursor, ws.cap[16], wb))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_seg_part_base, ws.cap[17], (size_t)p.nw * p.P))) return rc;
-  const size_t smax = wb + (size_t)p.nw * (n / (uint64_t)p.seg_len) + 16;      // segments <= buckets + entries / seg_len
-  if ((rc = ensure(ctx, ws, ws.d_order, ws.cap[7], smax))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_seg_bucket, ws.cap[20], smax))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_seg_lenv, ws.cap[21], smax))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_seg_out, ws.cap[22], smax * ab))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_seg_base, ws.cap[23], wb + 1))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_split_list, ws.cap[24], wb + 1))) return rc;
-  // a giant bucket contributes one chunk per TE_GIANT_RUN parts: at most one per bucket plus one per TE_GIANT_RUN segments
-  if ((rc = ensure(ctx, ws, ws.d_chunk_list, ws.cap[26], 2 * (wb + smax / TE_GIANT_RUN + 2)))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_part_start, ws.cap[6], (size_t)p.nw * p.P))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_buckets, ws.cap[8], wb * ab))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_part_count, ws.cap[9], (size_t)p.nw * p.P + (size_t)p.nw))) return rc;      // + the overflow pieces of each window
-  if ((rc = ensure(ctx, ws, ws.d_part_keys, ws.cap[14], p.packed ? 8 : nd))) return rc;       // packed level-1 entries carry their key
-  if ((rc = ensure(ctx, ws, ws.d_part_idx, ws.cap[15], nd))) return rc;
+  if (p.fb_rb && (rc = make_room(ctx, ws.d_fb_remap, nd))) return rc;
+  if ((rc = make_room(ctx, ws.d_bucket_start, wb))) return rc;
+  if ((rc = make_room(ctx, ws.d_bucket_cursor, wb))) return rc;
+  if ((rc = make_room(ctx, ws.d_seg_part_base, (size_t)p.nw * p.P))) return rc;
+  const size_t smax = sz.smax + 16;
+  if ((rc = make_room(ctx, ws.d_order, smax))) return rc;
+  if ((rc = make_room(ctx, ws.d_seg_bucket, smax))) return rc;
+  if ((rc = make_room(ctx, ws.d_seg_lenv, smax))) return rc;
+  if ((rc = make_room(ctx, ws.d_seg_out, smax * ab))) return rc;
+  if ((rc = make_room(ctx, ws.d_seg_base, wb + 1))) return rc;
+  if ((rc = make_room(ctx, ws.d_split_list, wb + 1))) return rc;
+  if ((rc = make_room(ctx, ws.d_chunk_list, 2 * sz.chunk_cap(16)))) return rc;
+  if ((rc = make_room(ctx, ws.d_part_start, (size_t)p.nw * p.P))) return rc;
+  if ((rc = make_room(ctx, ws.d_buckets, wb * ab))) return rc;
+  if ((rc = make_room(ctx, ws.d_part_count, (size_t)p.nw * p.P + (size_t)p.nw))) return rc;      // + the overflow pieces of each window
+  if ((rc = make_room(ctx, ws.d_part_keys, p.packed ? 8 : nd))) return rc;       // packed level-1 entries carry their key
+  if ((rc = make_room(ctx, ws.d_part_idx, nd))) return rc;
   // fold levels (by 8, 4 or 2): the first output is at most B/2 per window, the second at most B/4
-  if ((rc = ensure(ctx, ws, ws.d_red[0], ws.cap[10], (wb / 2 + 1) * ab))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_red[1], ws.cap[11], (wb / 4 + 1) * ab))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_red[2], ws.cap[12], (wb / 2 + 1) * ab))) return rc;
-  if ((rc = ensure(ctx, ws, ws.d_red[3], ws.cap[13], (wb / 4 + 1) * ab))) return rc;
+  for (int k = 0; k < 4; k++) if ((rc = make_room(ctx, ws.d_red[k], (wb / (k % 2 ? 4 : 2) + 1) * ab))) return rc;
   return 0;
+}
+
+// f(integral_constant<int, C>) for the window bits C = c of the range [LO, HI]; any other c is served by HI
+template <int LO, int HI, typename F> void with_window_bits(int c, F&& f) {
+  if constexpr (LO < HI) { if (c != LO) return with_window_bits<LO + 1, HI>(c, f); }
+  f(std::integral_constant<int, LO>{});
 }
 
 template <int C> void launch_digits(const te::batch_ptrs& sc, int batch, uint16_t* dg, const te::digits_params& prm, uint32_t* err, uint32_t* counts1, hipStream_t s) {
@@ -422,9 +452,12 @@ static_assert(TE_RAGGED_MAX == TE_BATCH_SEQ_MAX && TE_BATCH_SEQ_MAX == TE_MSM_BA
 // and the stages after it.
 struct msm_launch {
   te_ctx* ctx; workset_t& ws; plan_t p;
-  const void* d_points; const void* d_scalars; uint64_t n; void* d_partials_out;   // batch > 1: d_points / d_scalars are arrays of p.batch device pointers (on the host)
-  int prof;                       // event marks inside front()/back() only at profile level 2
-  hipStream_t stream;
+  const void* d_points = nullptr; const void* d_scalars = nullptr; uint64_t n = 0;   // batch > 1: d_points / d_scalars are arrays of p.batch device pointers (on the host)
+  void* d_partials_out = nullptr;
+  int prof = 0;                   // event marks inside front()/back() only at profile level 2
+  hipStream_t stream = nullptr;
+  // the work set, the plan and what the launch runs over; everything else is set by name
+  msm_launch(te_ctx* ctx_, workset_t& ws_, const plan_t& p_, uint64_t n_, hipStream_t stream_) : ctx(ctx_), ws(ws_), p(p_), n(n_), stream(stream_) {}
   bool own_rows = false;          // rows go to ws.d_partials: the caller fetches flag + rows with one copy
   bool onto = false;              // a later piece of a host-buffer MSM: keep the final-carry flag, add onto the buckets
   bool host_rows = false;         // own rows go straight to the work set's pinned host block, written by k_reduce_tail (no copy at all)
@@ -444,13 +477,10 @@ struct msm_launch {
   // Own rows of a context that computes ALL windows can be written to host memory by the tail kernel (every row slot is
   // rewritten by every MSM).  Not with window shards (rows of foreign windows must read as zero: they come from the cleared
   // device block), not with "prezero" = 0 (stage verifiers read the device rows).
-  static bool rows_to_host(const te_ctx* ctx, const gpu_t& d, const plan_t& p, bool own_rows) {
-    return own_rows && p.nw > 0 && p.batch == 1 && p.w_first == 0 && p.w_step == 1 && ctx->opt_prezero;
-  }
+  bool rows_to_host() const { return own_rows && p.nw > 0 && p.batch == 1 && p.w_first == 0 && p.w_step == 1 && ctx->opt_prezero; }
   uint32_t n32() const { return (uint32_t)n; }
-  uint32_t total() const { return (uint32_t)p.nw * p.B; }
-  uint32_t smax() const { return total() + (uint32_t)((uint64_t)p.nw * (n / p.seg_len)); }
-  uint32_t chunk_cap() const { return total() + smax() / TE_GIANT_RUN + 2u; }     // entries of d_chunk_list (pairs), see ensure_buffers
+  uint32_t smax() const { return (uint32_t)sizes_for(p, n).smax; }
+  uint32_t chunk_cap() const { return (uint32_t)sizes_for(p, n).chunk_cap(); }
   const void* points_of(int m) const { return p.batch > 1 ? static_cast<const void* const*>(d_points)[m] : d_points; }
   const void* scalars_of(int m) const { return p.batch > 1 ? static_cast<const void* const*>(d_scalars)[m] : d_scalars; }
   void mark(int i) const { if (prof >= 2 || (prof == 1 && (i == ST_ACCUM || i == ST_ACCUM + 1))) (void)hipEventRecord(ws.ev[i], stream); }
@@ -524,37 +554,8 @@ struct msm_launch {
       if (!ragged) for (int m = 0; m < p.batch; m++) sc.p[m] = (const uint4*)scalars_of(m);
       uint16_t* dg = ws.d_digits;
       uint32_t* c1 = ws.d_counts1;
-      if (ragged) {
-        switch (p.c) {
-          case 4: launch_digits_ragged<4>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 5: launch_digits_ragged<5>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 6: launch_digits_ragged<6>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 7: launch_digits_ragged<7>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 8: launch_digits_ragged<8>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 9: launch_digits_ragged<9>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 10: launch_digits_ragged<10>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 11: launch_digits_ragged<11>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 12: launch_digits_ragged<12>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 13: launch_digits_ragged<13>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 14: launch_digits_ragged<14>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          case 15: launch_digits_ragged<15>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-          default: launch_digits_ragged<16>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        }
-      } else switch (p.c) {
-        case 4: launch_digits<4>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 5: launch_digits<5>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 6: launch_digits<6>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 7: launch_digits<7>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 8: launch_digits<8>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 9: launch_digits<9>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 10: launch_digits<10>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 11: launch_digits<11>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 12: launch_digits<12>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 13: launch_digits<13>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 14: launch_digits<14>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        case 15: launch_digits<15>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-        default: launch_digits<16>(sc, p.batch, dg, prm, ws.d_err, c1, stream); break;
-      }
+      if (ragged) with_window_bits<4, 16>(p.c, [&](auto C) { launch_digits_ragged<decltype(C)::value>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); });
+      else with_window_bits<4, 16>(p.c, [&](auto C) { launch_digits<decltype(C)::value>(sc, p.batch, dg, prm, ws.d_err, c1, stream); });
     }
     const uint32_t cap_w = p.B + (uint32_t)(n / p.seg_len);        // segment ids of one window (see k_part_scatter)
     mark(ST_SCATTER);
@@ -627,7 +628,7 @@ struct msm_launch {
       using slot_t = typename te::rec_kind<N, RK>::slot;
       hipLaunchKernelGGL((te::k_accumulate<N, RK>), dim3((smax + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const slot_t*>(bound ? bound : recs_out()), ws.d_sorted,
                          ws.d_bucket_start, ws.d_bucket_count, ws.d_seg_base, ws.d_seg_bucket, ws.d_seg_lenv, order, ws.d_num_seg,
-                         reinterpret_cast<te::ete_t<N>*>(ws.d_buckets), reinterpret_cast<te::ete_t<N>*>(ws.d_seg_out), n32, p.logB, p.seg_len, smax, onto ? 1u : 0u,
+                         reinterpret_cast<te::ete_t<N>*>(ws.d_buckets.p), reinterpret_cast<te::ete_t<N>*>(ws.d_seg_out.p), n32, p.logB, p.seg_len, smax, onto ? 1u : 0u,
                          // (a ragged sequence: every window's k / nw is 0 -- record slab 0, the bound set itself, for any number of MSMs)
                          ragged ? (uint32_t)p.nw : (uint32_t)p.nw1, ragged ? te::batch_slabs{} : slabs(),
                          prof ? reinterpret_cast<unsigned long long*>(ws.d_zero + Z_CLOCK) : nullptr);
@@ -642,7 +643,7 @@ struct msm_launch {
     if (p.nw <= 0) return 0;
     using E = te::ete_t<N>;
     hipLaunchKernelGGL(te::k_seg_combine_all<N>, dim3(256 + 1024), dim3(256), 0, stream, ws.d_split_list, ws.d_num_seg + 1, ws.d_chunk_list,
-                       ws.d_bucket_count, ws.d_seg_base, reinterpret_cast<E*>(ws.d_seg_out), reinterpret_cast<E*>(ws.d_buckets), p.seg_len, chunk_cap(), 256u,
+                       ws.d_bucket_count, ws.d_seg_base, reinterpret_cast<E*>(ws.d_seg_out.p), reinterpret_cast<E*>(ws.d_buckets.p), p.seg_len, chunk_cap(), 256u,
                        ws.d_bucket_start, ws.d_bucket_cursor);
     return 0;
   }
@@ -660,9 +661,9 @@ struct msm_launch {
       const uint32_t w0 = p.dw[0], w1 = p.dw[1], w2 = p.dw[2], w3 = p.dw[3];
       const uint32_t L = 1u << (w0 + w1), H = 1u << (w2 + w3);
       struct chain_t { const E* cur; uint32_t n, r; E* buf[2]; int pp; };
-      E* const bk = reinterpret_cast<E*>(ws.d_buckets);
-      chain_t ch[2] = {{bk, p.B, L, {reinterpret_cast<E*>(ws.d_red[0]), reinterpret_cast<E*>(ws.d_red[1])}, 0},
-                       {bk, p.B, H, {reinterpret_cast<E*>(ws.d_red[2]), reinterpret_cast<E*>(ws.d_red[3])}, 0}};
+      E* const bk = reinterpret_cast<E*>(ws.d_buckets.p);
+      chain_t ch[2] = {{bk, p.B, L, {reinterpret_cast<E*>(ws.d_red[0].p), reinterpret_cast<E*>(ws.d_red[1].p)}, 0},
+                       {bk, p.B, H, {reinterpret_cast<E*>(ws.d_red[2].p), reinterpret_cast<E*>(ws.d_red[3].p)}, 0}};
       for (;;) {
         te::sum_jobs_t<N> js; memset(&js, 0, sizeof js);
         uint32_t most = 0; int nj = 0;
@@ -734,7 +735,7 @@ struct msm_launch {
 // upload_points (optional): enqueues the host-to-device copy of the points on the given (side) stream -- te_msm_run; the
 // upload then overlaps digits, sort and schedule.
 // With an upload, the points -> records conversion follows it on the work set's side stream, beside the scalar-only
-// stages, and joins before the accumulation.  Running it there for device-resident inputs as well (side_stream) was
+// stages, and joins before the accumulation.  Running it there for device-resident inputs as well was
 // measured and is not used: for one MSM the conversion and the sort stages are both bandwidth-bound and merely slow each
 // other down (latency 1.36 -> 1.38 ms), and with several MSMs in flight every extra stream competes for the runtime's few
 // hardware queues (four by default; GPU_MAX_HW_QUEUES=8 did not help) and serialises the others: 941 -> 862 MSM/s.
@@ -970,61 +971,85 @@ void release_shared_recs(gpu_t& d, workset_t& ws, bool completed = true) {
 // whole-MSM call of its occupancy run, which converts only when no earlier call of the run has (see SHARED RECORD SLABS above).
 enum share_mode { SHARE_NONE = 0, SHARE_CONVERT = 1, SHARE_RUN = 2 };
 
-// bases: the launch sequence gathers from a bound point set (d_points is not read: no conversion); batch must be 1
-// share: the record slab of the call (share_mode); a shared slab only for device-resident points, without bound bases
-int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, const void* d_scalars, uint64_t n,
-                    void* d_partials_out, hipStream_t stream, const std::function<int(hipStream_t)>* upload_points = nullptr, int force_c = 0,
-                    bool side_stream = false, int batch = 1, bool whole = false, const te_bases* bases = nullptr, share_mode share = SHARE_NONE,
-                    const uint32_t* d_idx = nullptr) {
-  // d_idx (with bases): an indexed subset -- the n entries gather records d_idx[0 .. n) of the set (device memory of d)
+// HOW EVERY LAUNCH SEQUENCE BEGINS ON A WORK SET (the four enqueue functions and enqueue_ragged).  The set lets go of the shared slab its previous MSM still
+// named (guarded by an event unless that MSM was seen to end); L.stream waits for the set's previous MSM when that ran on another stream
+// (the set's buffers are still the previous MSM's); the launch learns where its own rows go.  recs_last: where te_msm_debug_read finds the
+// records of the sequence.  share (enqueue_partial alone): the sequence takes a shared record slab for that point buffer, which then is
+// its recs_last -- taken between the two steps, so that the slab's own wait on L.stream stands in front of the set's.
+struct slab_request { const void* src; bool run; };       // run: a whole-MSM call of the slab's occupancy run (SHARE_RUN)
+int begin_sequence(gpu_t& d, msm_launch& L, const uint8_t* recs_last, const slab_request* share = nullptr) {
+  te_ctx* const ctx = L.ctx; workset_t& ws = L.ws;
+  release_shared_recs(d, ws, false);
+  ws.recs_last = recs_last;
+  if (share) {
+    const int si = acquire_shared_recs(ctx, d, share->src, L.n, L.p.curve, L.stream, share->run, &L.recs_rw, &L.have_recs);
+    if (si < 0) return si;
+    ws.slab = si; ws.slab_run = share->run; ws.recs_last = L.recs_rw;
+  }
+  if (ws.used && ws.last_stream != L.stream) HIP_TRY(ctx, hipStreamWaitEvent(L.stream, ws.ev_done, 0));
+  L.host_rows = L.rows_to_host();
+  ws.rows_on_host = L.host_rows;
+  return 0;
+}
+// ... and what it leaves on the set for the next sequence and for the read-back of its result.  The whole forms note it before their first
+// launch; the piece forms after their last piece: copy_stream_behind_previous, behind begin_sequence, asks whether the set was used BEFORE
+// this sequence, and plan and n are the last piece's.  (the device's host thread may be the writer of last_ws: asynchronous submits)
+void note_sequence(gpu_t& d, workset_t& ws, const plan_t& p, uint64_t n, hipStream_t stream, int prof_level) {
+  ws.plan = p; ws.n = n; ws.used = true; ws.last_stream = stream; ws.prof_level = prof_level;
+  __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
+}
+
+// One launch sequence from device-resident inputs (enqueue_partial).  Only the scalars, n and the stream are always needed.
+struct partial_req {
+  const void* d_points = nullptr; const void* d_scalars = nullptr; uint64_t n = 0;   // batch > 1: arrays of `batch` device pointers (on the host)
+  void* d_partials_out = nullptr;     // nullptr: the rows go to the work set's own buffer, the caller fetches flag + rows with fetch_rows()
+  hipStream_t stream = nullptr;
+  const std::function<int(hipStream_t)>* upload_points = nullptr;   // enqueues the host-to-device copy of the points on the given (side) stream
+  int batch = 1;
+  bool whole = false;                 // every window instead of the device's window shard (make_plan)
+  const te_bases* bases = nullptr;    // the launch sequence gathers from a bound point set (d_points is not read: no conversion); batch must be 1
+  share_mode share = SHARE_NONE;      // the record slab of the call; a shared slab only for device-resident points, without bound bases
+  const uint32_t* d_idx = nullptr;    // (with bases) an indexed subset: the n entries gather records d_idx[0 .. n) of the set (device memory of d)
+};
+int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const partial_req& r) {
+  const void* const d_points = r.d_points; const uint64_t n = r.n; hipStream_t const stream = r.stream;
+  const int batch = r.batch; const te_bases* const bases = r.bases; const auto* const upload_points = r.upload_points;
   // (the plan is made for the n entries; only the entry form follows the set's count: indexed_plan.hpp)
-  const te_indexed::call_plan ip = te_indexed::plan_for(n, d_idx ? bases->n : n, ctx->opt_packed);
-  plan_t p; make_plan(ctx, d, ip.plan_n, p, force_c, batch, 0, whole);
+  const te_indexed::call_plan ip = te_indexed::plan_for(n, r.d_idx ? bases->n : n, ctx->opt_packed);
+  plan_t p; make_plan(ctx, d, ip.plan_n, p, 0, batch, 0, r.whole);
   if (bases) p.rec_kind = bases->rec_kind;
-  if (d_idx) p.packed = ip.packed;
+  if (r.d_idx) p.packed = ip.packed;
   // (a batch shares when all its MSMs name ONE point buffer: the batch then holds one conversion anyway -- slab 0 of msm_launch::slabs())
   const void* share_src = d_points;
   if (batch > 1 && d_points) { share_src = static_cast<const void* const*>(d_points)[0]; for (int m = 1; m < batch; m++) if (static_cast<const void* const*>(d_points)[m] != share_src) share_src = nullptr; }
-  const bool share_recs = share != SHARE_NONE && ctx->opt_share_records && !bases && !upload_points && share_src != nullptr;
-  const bool run = share_recs && share == SHARE_RUN && ctx->opt_share_records == 1 && !ctx->opt_check_points && batch == 1 && !side_stream;
+  const bool share_recs = r.share != SHARE_NONE && ctx->opt_share_records && !bases && !upload_points && share_src != nullptr;
+  const bool run = share_recs && r.share == SHARE_RUN && ctx->opt_share_records == 1 && !ctx->opt_check_points && batch == 1;
   if (batch > 1 && (uint64_t)p.nw * p.nst >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch too large for this n: windows x points must stay below 2^31");
   HIP_TRY(ctx, hipSetDevice(d.device));
   if ((uint64_t)p.nw * p.B + (uint64_t)p.nw * (n / p.seg_len) + 1024u >= (1ull << 32))
     return set_err(ctx, TE_MSM_EINVAL, "segment_len is too small for this n: more than 2^32 segments");
   if (int rc = ensure_buffers(ctx, d, ws, n, p, bases == nullptr && !share_recs)) return rc;
-  release_shared_recs(d, ws, false);                        // (a slab the set's previous MSM still named: guarded by an event unless that MSM was seen to end)
-  uint8_t* shared = nullptr;
-  bool have_recs = false;
-  if (share_recs) {
-    const int si = acquire_shared_recs(ctx, d, share_src, n, p.curve, stream, run, &shared, &have_recs);
-    if (si < 0) return si;
-    ws.slab = si; ws.slab_run = run;
-  }
-  // a launch sequence that fails half-way lets go of its slab (and of the slab's occupancy run) at once
-  struct slab_guard { gpu_t& d; workset_t& ws; bool armed; ~slab_guard() { if (armed) release_shared_recs(d, ws, false); } } guard{d, ws, share_recs};
-  if (ws.used && ws.last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ws.ev_done, 0));   // the set's buffers are still the previous MSM's
-  ws.plan = p; ws.n = n; ws.used = true; ws.last_stream = stream; __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
-  ws.prof_level = ctx->opt_profile;
-  const bool own_rows = d_partials_out == nullptr;
-  if (own_rows) d_partials_out = ws.d_partials;
   // profile 1: two events around the dominant kernel only (what bench.py times live); 2: every stage boundary
   // (an event between two kernels costs ~4 us of idle stream time, 11 of them ~2 % of a 2^20 MSM)
-  msm_launch L{ctx, ws, p, d_points, d_scalars, n, d_partials_out, ctx->opt_profile, stream, own_rows};
-  L.host_rows = msm_launch::rows_to_host(ctx, d, p, own_rows);
-  ws.rows_on_host = L.host_rows;
-  L.recs_rw = shared;
-  L.have_recs = have_recs;
-  ws.recs_last = bases ? nullptr : (shared ? shared : ws.d_recs);
+  msm_launch L(ctx, ws, p, n, stream);
+  L.d_points = d_points; L.d_scalars = r.d_scalars; L.prof = ctx->opt_profile;
+  L.own_rows = r.d_partials_out == nullptr;
+  L.d_partials_out = L.own_rows ? ws.d_partials : r.d_partials_out;
+  // a launch sequence that fails half-way lets go of its slab (and of the slab's occupancy run) at once
+  struct slab_guard { gpu_t& d; workset_t& ws; bool armed; ~slab_guard() { if (armed) release_shared_recs(d, ws, false); } } guard{d, ws, share_recs};
+  const slab_request slab{share_src, run};
+  if (int rc = begin_sequence(d, L, bases ? nullptr : ws.d_recs.p, share_recs ? &slab : nullptr)) return rc;
+  note_sequence(d, ws, p, n, stream, ctx->opt_profile);
   if (bases) {
     // resident bases: the scalar-only stages, then the accumulation straight from the bound records
     L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];
-    if (d_idx) { L.idx = d_idx; L.idx_count = (uint32_t)bases->n; }
+    if (r.d_idx) { L.idx = r.d_idx; L.idx_count = (uint32_t)bases->n; }
     if (int rc = L.front_scalars()) return rc;
     L.mark(ST_PREP);
     if (int rc = L.accumulate()) return rc;
     L.mark(ST_TREE);
     if (int rc = L.back()) return rc;
-  } else if (ctx->opt_profile >= 2 || !(side_stream || upload_points)) {
+  } else if (ctx->opt_profile >= 2 || !upload_points) {
     if (!upload_points && L.can_fuse_conversion()) {
       if (int rc = L.front()) return rc;
     } else {
@@ -1032,7 +1057,7 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
       if (upload_points) { if (int rc = (*upload_points)(stream)) return rc; }
       if (int rc = L.front_points()) return rc;
     }
-    if (run && !have_recs) {                                 // the conversion is enqueued: later calls of the slab's run may skip theirs
+    if (run && !L.have_recs) {                                 // the conversion is enqueued: later calls of the slab's run may skip theirs
       HIP_TRY(ctx, hipGetLastError());
       if (int rc = note_conversion(ctx, d.slabs[(size_t)ws.slab], stream)) return rc;
     }
@@ -1040,11 +1065,11 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
     L.mark(ST_TREE);
     if (int rc = L.back()) return rc;
   } else {
-    // side stream: [upload of the points] -> records; it starts behind everything already enqueued on `stream`
+    // side stream: upload of the points -> records; it starts behind everything already enqueued on `stream`
     HIP_TRY(ctx, hipEventRecord(ws.ev_start, stream));
     if (int rc = need_copy_stream(ctx, ws)) return rc;
     HIP_TRY(ctx, hipStreamWaitEvent(ws.copy_stream, ws.ev_start, 0));
-    if (upload_points) { if (int rc = (*upload_points)(ws.copy_stream)) return rc; }
+    if (int rc = (*upload_points)(ws.copy_stream)) return rc;
     msm_launch S = L; S.stream = ws.copy_stream;
     if (int rc = S.front_points()) return rc;
     HIP_TRY(ctx, hipEventRecord(ws.ev_copy, ws.copy_stream));
@@ -1056,7 +1081,7 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const void* d_points, 
   }
   // rows in the caller's buffer: the sequence ends here (the flag's read-back is part of reduce()); rows in the set's own
   // block: the caller's fetch_rows() ends it
-  if (!own_rows) { if (int rc = finish_sequence(ctx, ws, stream)) return rc; }
+  if (!L.own_rows) { if (int rc = finish_sequence(ctx, ws, stream)) return rc; }
   HIP_TRY(ctx, hipGetLastError());
   guard.armed = false;
   return 0;
@@ -1117,14 +1142,8 @@ int collect_stage_ms(te_ctx* ctx, const gpu_t& d, workset_t& ws) {
 }
 
 void free_workset_buffers(workset_t& ws) {      // the big device buffers of a work set (te_msm_trim, free_dev); streams, events and the pinned block stay
-  void** ptrs[] = {(void**)&ws.d_recs, (void**)&ws.d_digits, (void**)&ws.d_part_keys, (void**)&ws.d_zero, (void**)&ws.d_part_start, (void**)&ws.d_part_count,
-                   (void**)&ws.d_part_idx, (void**)&ws.d_seg_part_base, (void**)&ws.d_bucket_start, (void**)&ws.d_bucket_cursor, (void**)&ws.d_sorted,
-                   (void**)&ws.d_seg_base, (void**)&ws.d_seg_bucket, (void**)&ws.d_seg_lenv, (void**)&ws.d_order, (void**)&ws.d_split_list,
-                   (void**)&ws.d_chunk_list, (void**)&ws.d_seg_out, (void**)&ws.d_buckets, (void**)&ws.d_red[0], (void**)&ws.d_red[1],
-                   (void**)&ws.d_red[2], (void**)&ws.d_red[3], &ws.d_in_points, &ws.d_in_scalars, (void**)&ws.d_fb_remap, (void**)&ws.d_batch_rows, (void**)&ws.d_in_idx};
-  for (void** q : ptrs) if (*q) { (void)hipFree(*q); *q = nullptr; }
+  workset_t::each_buffer(ws, [](auto& b) { b.release(); });
   if (ws.h_ring) { (void)hipHostFree(ws.h_ring); ws.h_ring = nullptr; }       // the pinned ring of option "host_staging" (its events stay)
-  memset(ws.cap, 0, sizeof ws.cap); ws.cap_in_points = ws.cap_in_scalars = 0;
   ws.zero_words = ws.zero_clean_words = 0;
   ws.d_err = ws.d_num_seg = ws.d_size_hist = ws.d_size_cursor = ws.d_counts1 = ws.d_bucket_count = ws.d_part_ticket = nullptr; ws.d_partials = nullptr;
   ws.used = false;
@@ -1139,10 +1158,10 @@ void free_dev(gpu_t& d) {
   }
   d.slabs.clear();
   if (d.chk_stream) (void)hipStreamDestroy(d.chk_stream);
-  if (d.chk_pts) (void)hipFree(d.chk_pts);
+  d.chk_pts.release();
   if (d.chk_word) (void)hipFree(d.chk_word);
   if (d.chk_host) (void)hipHostFree(d.chk_host);
-  d.chk_stream = nullptr; d.chk_pts = nullptr; d.chk_cap = 0; d.chk_word = d.chk_host = nullptr;
+  d.chk_stream = nullptr; d.chk_word = d.chk_host = nullptr;
   if (d.h_batch_rows) (void)hipHostFree(d.h_batch_rows);
   d.h_batch_rows = nullptr; d.h_batch_cap = 0;
   for (workset_t& ws : d.ws) {
@@ -1165,19 +1184,8 @@ void free_dev(gpu_t& d) {
 // device copies of a host-buffer call's inputs, in bytes of the call's curve (64 + 32 per point for the Twisted-Edwards
 // wire format, 96 + 48 for BLS12-377)
 int ensure_staging(te_ctx* ctx, workset_t& ws, size_t bytes_points, size_t bytes_scalars) {
-  if (bytes_points > ws.cap_in_points) {
-    if (ws.d_in_points) HIP_TRY(ctx, hipFree(ws.d_in_points));
-    ws.d_in_points = nullptr; ws.cap_in_points = 0;
-    HIP_TRY(ctx, hipMalloc(&ws.d_in_points, bytes_points));
-    ws.cap_in_points = bytes_points;
-  }
-  if (bytes_scalars > ws.cap_in_scalars) {
-    if (ws.d_in_scalars) HIP_TRY(ctx, hipFree(ws.d_in_scalars));
-    ws.d_in_scalars = nullptr; ws.cap_in_scalars = 0;
-    HIP_TRY(ctx, hipMalloc(&ws.d_in_scalars, bytes_scalars));
-    ws.cap_in_scalars = bytes_scalars;
-  }
-  return 0;
+  if (int rc = make_room(ctx, ws.d_in_points, bytes_points)) return rc;
+  return make_room(ctx, ws.d_in_scalars, bytes_scalars);
 }
 
 // Is this host address pinned (hipHostMalloc) or registered (hipHostRegister) memory?  A copy from such memory does not
@@ -1371,8 +1379,10 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
     seg_all = pm.seg_len;
     if (int rc = ensure_buffers(ctx, d, ws, m_max, pm)) return rc;        // every buffer at its final size before the first piece
   }
-  release_shared_recs(d, ws, false); ws.recs_last = ws.d_recs;      // a host-buffer MSM converts into the set's own slab
-  if (ws.used && ws.last_stream != ws.stream) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));
+  // what every piece's launch shares; the piece sets its plan, its inputs and `onto`
+  msm_launch L0(ctx, ws, pf, n, ws.stream);
+  L0.d_partials_out = ws.d_partials; L0.own_rows = true;
+  if (int rc = begin_sequence(d, L0, ws.d_recs)) return rc;          // a host-buffer MSM converts into the set's own slab
   if (int rc = copy_stream_behind_previous(ctx, ws)) return rc;
   const bool tr = getenv("TE_MSM_TRACE_HOST") != nullptr;
   const auto t00 = std::chrono::steady_clock::now();
@@ -1405,9 +1415,8 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
     if (m == 0) continue;
     make_plan(ctx, d, m, p, pf.c, 1, seg_all, true);
     if (int rc = ensure_buffers(ctx, d, ws, m, p)) return rc;              // no reallocation: only the pointers into the zeroed block move
-    msm_launch L{ctx, ws, p, dpts + lo * sz.point_in, dscs + lo * sz.scalar_in, m, ws.d_partials, 0, ws.stream, true, !first};
-    L.host_rows = msm_launch::rows_to_host(ctx, d, p, true);
-    ws.rows_on_host = L.host_rows;
+    msm_launch L = L0;
+    L.p = p; L.d_points = dpts + lo * sz.point_in; L.d_scalars = dscs + lo * sz.scalar_in; L.n = m; L.onto = !first;
     first = false;
     if (!scalars_first) {
       if (int rc = upload(ctx, ws, dscs + lo * sz.scalar_in, src_scalars + lo * sz.scalar_in, m * sz.scalar_in, ws.copy_stream)) return rc;
@@ -1425,8 +1434,7 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
     if (i == last_piece) { if (int rc = L.reduce()) return rc; }
     stamp("piece enqueued", i);
   }
-  ws.plan = p; ws.n = piece_lo(last_piece + 1) - piece_lo(last_piece); ws.used = true; ws.last_stream = ws.stream; ws.prof_level = 0;
-  __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);      // (the device's host thread may be the writer: asynchronous submits)
+  note_sequence(d, ws, p, piece_lo(last_piece + 1) - piece_lo(last_piece), ws.stream, 0);
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipGetLastError());
   if (wait_for_pinned && !ctx->opt_host_staging && (host_memory_is_pinned(src_points) || host_memory_is_pinned(src_scalars))) {
@@ -1461,7 +1469,7 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
   const curve_sizes sz = sizes_of(pf.curve);
   const size_t rec_bytes = rec_bytes_of(pf.curve, rec_kind);
   if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
-  if (src_idx) { if (int rc = ensure(ctx, ws, ws.d_in_idx, ws.cap[29], (size_t)n)) return rc; }
+  if (src_idx) { if (int rc = make_room(ctx, ws.d_in_idx, (size_t)n)) return rc; }
   uint8_t* dscs = static_cast<uint8_t*>(ws.d_in_scalars);
   if (K < 1) K = 1;
   if ((uint64_t)K > n) K = (int)n;
@@ -1476,8 +1484,10 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
     seg_all = pm.seg_len;
     if (int rc = ensure_buffers(ctx, d, ws, m_max, pm, false)) return rc;      // every buffer at its final size before the first piece
   }
-  release_shared_recs(d, ws, false); ws.recs_last = nullptr;
-  if (ws.used && ws.last_stream != ws.stream) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));
+  // what every piece's launch shares; the piece sets its plan, its inputs and `onto`
+  msm_launch L0(ctx, ws, pf, n, ws.stream);
+  L0.d_partials_out = ws.d_partials; L0.own_rows = true;
+  if (int rc = begin_sequence(d, L0, nullptr)) return rc;
   if (int rc = copy_stream_behind_previous(ctx, ws)) return rc;                 // the staging area may still be read by the set's previous MSM
   std::vector<hipEvent_t>& evs = ws.piece_events;
   while ((int)evs.size() < K + 1) { hipEvent_t e; HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming)); evs.push_back(e); }
@@ -1505,11 +1515,10 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
     p.rec_kind = rec_kind;
     if (src_idx) p.packed = te_indexed::plan_for(m, idx_count, ctx->opt_packed).packed;
     if (int rc = ensure_buffers(ctx, d, ws, m, p, false)) return rc;           // no reallocation: only the pointers into the zeroed block move
-    msm_launch L{ctx, ws, p, nullptr, dscs + lo * sz.scalar_in, m, ws.d_partials, 0, ws.stream, true, !first};
-    L.host_rows = msm_launch::rows_to_host(ctx, d, p, true);
+    msm_launch L = L0;
+    L.p = p; L.d_scalars = dscs + lo * sz.scalar_in; L.n = m; L.onto = !first;
     L.bound = src_idx ? recs : recs + lo * rec_bytes;
     if (src_idx) { L.idx = ws.d_in_idx + lo; L.idx_count = (uint32_t)idx_count; L.idx_pos = (uint32_t)(idx_pos + lo); }
-    ws.rows_on_host = L.host_rows;
     first = false;
     if (int rc = L.front_scalars()) return rc;
     if (int rc = L.accumulate()) return rc;
@@ -1517,8 +1526,7 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
     if (i == K - 1) { if (int rc = L.reduce()) return rc; }
     stamp("piece enqueued", i);
   }
-  ws.plan = p; ws.n = piece_lo(K) - piece_lo(K - 1); ws.used = true; ws.last_stream = ws.stream; ws.prof_level = 0;
-  __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
+  note_sequence(d, ws, p, piece_lo(K) - piece_lo(K - 1), ws.stream, 0);
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipGetLastError());
   if (wait_for_pinned && !ctx->opt_host_staging && (host_memory_is_pinned(src_scalars) || (src_idx && host_memory_is_pinned(src_idx)))) HIP_TRY(ctx, hipEventSynchronize(evs[(size_t)K - 1]));
@@ -1571,14 +1579,11 @@ int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bas
   if ((uint64_t)p.nw * cap >= (1ull << 31) || (uint64_t)bases->fb_W * bases->n >= (1ull << 31))
     return set_err(ctx, TE_MSM_EINVAL, "fixed-base windows: windows x points must stay below 2^31");
   if (int rc = ensure_buffers(ctx, d, ws, cap, p, false)) return rc;
-  release_shared_recs(d, ws, false); ws.recs_last = nullptr;
-  if (ws.used && ws.last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ws.ev_done, 0));
-  ws.plan = p; ws.n = cap; ws.used = true; ws.last_stream = stream; __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
-  ws.prof_level = ctx->opt_profile;
+  msm_launch L(ctx, ws, p, cap, stream);
+  L.d_scalars = d_scalars; L.d_partials_out = ws.d_partials; L.own_rows = true; L.prof = ctx->opt_profile;
+  if (int rc = begin_sequence(d, L, nullptr)) return rc;
+  note_sequence(d, ws, p, cap, stream, ctx->opt_profile);
   ws.fb_scalars = d_scalars; ws.fb_n = n;
-  msm_launch L{ctx, ws, p, nullptr, d_scalars, cap, ws.d_partials, ctx->opt_profile, stream, true};
-  L.host_rows = msm_launch::rows_to_host(ctx, d, p, true);
-  ws.rows_on_host = L.host_rows;
   L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];
   L.fb_remap = ws.d_fb_remap;
   // the zeroed block (flags, counters, level-1 histogram, row fill) -- then the digits.  The digit rows are NOT cleared: the sort's
@@ -1594,14 +1599,7 @@ int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bas
     a.chunk_len = p.chunk_len; a.CH = p.CH; a.P = p.P; a.logS = p.logS;
     a.digits = ws.d_digits; a.remap = ws.d_fb_remap; a.row_fill = ws.d_fb_fill; a.counts1 = ws.d_counts1; a.err = ws.d_err;
     const size_t lds = (size_t)(2u * a.rows + a.rows * 2u * a.P) * sizeof(uint32_t);
-    switch (p.fb_c) {
-      case 16: launch_fb_digits<16>(d_scalars, a, a.n, lds, stream); break;
-      case 17: launch_fb_digits<17>(d_scalars, a, a.n, lds, stream); break;
-      case 18: launch_fb_digits<18>(d_scalars, a, a.n, lds, stream); break;
-      case 19: launch_fb_digits<19>(d_scalars, a, a.n, lds, stream); break;
-      case 20: launch_fb_digits<20>(d_scalars, a, a.n, lds, stream); break;
-      default: launch_fb_digits<21>(d_scalars, a, a.n, lds, stream); break;
-    }
+    with_window_bits<16, 21>(p.fb_c, [&](auto C) { launch_fb_digits<decltype(C)::value>(d_scalars, a, a.n, lds, stream); });
   }
   // the engine's own stages from here on (front_scalars skips k_digits for a fixed-base plan)
   if (int rc = L.front_scalars()) return rc;
@@ -1837,7 +1835,8 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
       }
       dp = ws.d_in_points; ds = ws.d_in_scalars;
     }
-    if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream)) return rc;
+    partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream;
+    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
   const int rc = te_sched::on_devices(*ctx, nd, share);
@@ -1889,11 +1888,7 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
   if (lane.rc) return lane.rc;
   const size_t pb = sizes_of(curve).point_in;
   const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
-  if (src_is_host && d.chk_cap < piece * pb) {
-    if (d.chk_pts) { HIP_TRY(ctx, hipFree(d.chk_pts)); d.chk_pts = nullptr; d.chk_cap = 0; }
-    HIP_TRY(ctx, hipMalloc(&d.chk_pts, piece * pb));
-    d.chk_cap = piece * pb;
-  }
+  if (src_is_host) { if (int rc = make_room(ctx, d.chk_pts, piece * pb)) return rc; }
   hipStream_t st = lane.stream();
   for (uint64_t off = 0; off < n; off += piece) {
     const uint32_t m = (uint32_t)std::min(piece, n - off);
@@ -1984,7 +1979,9 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
     // on the side stream, beside the scalar-only kernels on ws.stream; the conversion to records follows it there
     return upload(ctx, ws, ws.d_in_points, static_cast<const uint8_t*>(src_points), n * sz.point_in, side);
   };
-  if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream, src_is_host ? &upload_points : nullptr, 0, false, 1, false, nullptr, src_is_host ? SHARE_NONE : share)) return rc;
+  partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream;
+  if (src_is_host) r.upload_points = &upload_points; else r.share = share;
+  if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));          // (pinned sources included: the call ends after its uploads)
   release_shared_recs(d, ws);                               // the call is over: its record slab (if shared) may serve another point buffer
@@ -2209,7 +2206,8 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
       dp = ws.d_in_points; ds = ws.d_in_scalars;
     }
     // a single-device context keeps its window shard (te_msm_set_window_shard); on several devices a ticket is a whole MSM
-    if (int rc = enqueue_partial(ctx, d, ws, dp, ds, n, nullptr, ws.stream, nullptr, 0, false, 1, multi, nullptr, stage ? SHARE_NONE : SHARE_RUN)) return rc;
+    partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.whole = multi; r.share = stage ? SHARE_NONE : SHARE_RUN;
+    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
   // (Handing this to a host thread, as te_msm_submit_async does with uploads, was measured: no gain at n = 2^16 .. 2^18, 3-7 %
@@ -2520,7 +2518,8 @@ int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* base
   if (!ws.plan.fb_rb || *ws.h_err || !ws.h_err[1]) return 0;
   ctx->stat_fb_fallbacks++;
   HIP_TRY(ctx, hipSetDevice(d.device));
-  if (int rc = enqueue_partial(ctx, d, ws, nullptr, ws.fb_scalars, ws.fb_n, nullptr, ws.stream, nullptr, 0, false, 1, true, bases)) return rc;
+  partial_req r; r.d_scalars = ws.fb_scalars; r.n = ws.fb_n; r.stream = ws.stream; r.whole = true; r.bases = bases;
+  if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
   return 0;
@@ -2557,7 +2556,8 @@ int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_sc
       if (int rc = pull_scalars(ctx, d, ws, d_scalars, src_dev, n)) return rc;
       copies[i] = 1; ds = ws.d_in_scalars;
     }
-    if (int rc = enqueue_partial(ctx, d, ws, nullptr, ds, n, nullptr, ws.stream, nullptr, 0, false, 1, false, bases)) return rc;
+    partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.bases = bases;
+    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
   const int rc = te_sched::on_devices(*ctx, nd, share);
@@ -2607,7 +2607,8 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
       if (int rc = upload(ctx, ws, ws.d_in_scalars, static_cast<const uint8_t*>(src), n * sz.scalar_in, ws.stream)) return rc;
       ds = ws.d_in_scalars;
     }
-    if (int rc = enqueue_partial(ctx, d, ws, nullptr, ds, n, nullptr, ws.stream, nullptr, 0, false, 1, false, bases)) return rc;
+    partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.bases = bases;
+    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   }
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
@@ -2709,7 +2710,10 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
     ds = ws.d_in_scalars;
   }
   if (bases->fb_c && (multi || d.w_step == 1)) { if (int rc = enqueue_fixed_base(ctx, d, ws, bases, ds, n, 0, ws.stream)) return rc; }
-  else if (int rc = enqueue_partial(ctx, d, ws, nullptr, ds, n, nullptr, ws.stream, nullptr, 0, false, 1, multi, bases)) return rc;
+  else {
+    partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.whole = multi; r.bases = bases;
+    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
+  }
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   ws.bound = bases; bases->in_flight++;
   hand_out_ticket(ctx, di, ws, ticket);
@@ -2731,7 +2735,7 @@ const char* const kIndexedResident = "indexed MSM: indices and scalars must be r
 
 // the m pairs at d_idx / d_scalars (memory of device src_dev) into the set's staging area over the peer link, on the set's stream
 int pull_pairs(te_ctx* ctx, const gpu_t& d, workset_t& ws, const void* d_idx, const void* d_scalars, int src_dev, uint64_t m) {
-  if (int rc = ensure(ctx, ws, ws.d_in_idx, ws.cap[29], (size_t)m)) return rc;
+  if (int rc = make_room(ctx, ws.d_in_idx, (size_t)m)) return rc;
   if (int rc = pull_scalars(ctx, d, ws, d_scalars, src_dev, m)) return rc;
   HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_idx, d.device, d_idx, src_dev, m * sizeof(uint32_t), ws.stream));
   ctx->stat_peer_copies += 2; ctx->stat_peer_bytes += (int64_t)(m * (sizes_of(ctx->opt_curve).scalar_in + sizeof(uint32_t)));
@@ -2768,7 +2772,8 @@ int run_indexed_common(te_ctx* ctx, te_bases* bases, const void* idx, const void
     if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[(size_t)owner], bases->rec_kind, static_cast<const uint8_t*>(src), m, p0.c,
                                       te_indexed::pieces(m, ctx->opt_scalar_chunks), true, static_cast<const uint32_t*>(idx), bases->n, 0)) return rc;
   } else {
-    if (int rc = enqueue_partial(ctx, d, ws, nullptr, src, m, nullptr, ws.stream, nullptr, 0, false, 1, true, bases, SHARE_NONE, static_cast<const uint32_t*>(idx))) return rc;
+    partial_req r; r.d_scalars = src; r.n = m; r.stream = ws.stream; r.whole = true; r.bases = bases; r.d_idx = static_cast<const uint32_t*>(idx);
+    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   }
   return settle_indexed(ctx, d, ws, out);
@@ -2829,7 +2834,8 @@ int te_msm_submit_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const voi
     if (int rc = pull_pairs(ctx, d, ws, d_idx, d_scalars_le, src_dev, m)) return rc;
     ds = ws.d_in_scalars; dx = ws.d_in_idx;
   }
-  if (int rc = enqueue_partial(ctx, d, ws, nullptr, ds, m, nullptr, ws.stream, nullptr, 0, false, 1, true, bases, SHARE_NONE, dx)) return rc;
+  partial_req r; r.d_scalars = ds; r.n = m; r.stream = ws.stream; r.whole = true; r.bases = bases; r.d_idx = dx;
+  if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   ws.bound = bases; bases->in_flight++;
   hand_out_ticket(ctx, di, ws, ticket);
@@ -2950,7 +2956,7 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "device_bytes")) {      drain_workers(ctx);      // device memory this context holds in work-set buffers (te_msm_trim gives it back)
     int64_t tot = 0;
     for (const gpu_t& d : ctx->devs) {
-      for (const workset_t& ws : d.ws) { for (size_t cb : ws.cap) tot += (int64_t)cb; tot += (int64_t)(ws.cap_in_points + ws.cap_in_scalars); }
+      for (const workset_t& ws : d.ws) workset_t::each_buffer(ws, [&](const auto& b) { tot += (int64_t)b.cap; });
       for (const auto& sl : d.slabs) if (sl.d) tot += (int64_t)sl.cap;
     }
     *value = tot; return 0;
@@ -3280,13 +3286,12 @@ int enqueue_ragged(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, 
     return set_err(ctx, TE_MSM_EINVAL, "segment_len is too small for this batch: more than 2^32 segments");
   if (int rc = ensure_buffers(ctx, d, ws, n_max, p, false)) return rc;
   const size_t row_bytes = (size_t)p.batch * p.W * sizes_of(p.curve).row;
-  if (int rc = ensure(ctx, ws, ws.d_batch_rows, ws.cap[28], row_bytes)) return rc;
-  release_shared_recs(d, ws, false);
+  if (int rc = make_room(ctx, ws.d_batch_rows, row_bytes)) return rc;
   hipStream_t stream = ws.stream;
-  if (ws.used && ws.last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ws.ev_done, 0));
-  ws.plan = p; ws.n = n_max; ws.used = true; ws.last_stream = stream; __atomic_store_n(&d.last_ws, (int)(&ws - d.ws), __ATOMIC_RELAXED);
-  ws.prof_level = 0; ws.rows_on_host = false; ws.recs_last = nullptr;
-  msm_launch L{ctx, ws, p, nullptr, d_scalars, n_max, ws.d_batch_rows, 0, stream, false};
+  msm_launch L(ctx, ws, p, n_max, stream);
+  L.d_scalars = d_scalars; L.d_partials_out = ws.d_batch_rows;        // (not the set's own rows: none of them go to the pinned block)
+  if (int rc = begin_sequence(d, L, nullptr)) return rc;
+  note_sequence(d, ws, p, n_max, stream, 0);
   L.bound = bases->recs[(size_t)(&d - ctx->devs.data())];      // (a fixed-base set: table 0, the ordinary records)
   L.ragged = &tab;
   if (int rc = L.front_scalars()) return rc;
@@ -3484,8 +3489,9 @@ int te_msm_partial_device(te_ctx* ctx, const void* d_points_xy_le, const void* d
   workset_t& ws = d.ws[ctx->opt_workset];
   if (te_sched::slot_ticket(ws.slot)) return set_err(ctx, TE_MSM_ESTATE, "the selected work set holds a submitted MSM that has not been collected");
   HIP_TRY(ctx, hipSetDevice(d.device));
-  return enqueue_partial(ctx, d, ws, d_points_xy_le, d_scalars_le, n, d_partials, stream == TE_MSM_OWN_STREAM ? ws.stream : (hipStream_t)stream,
-                         nullptr, 0, false, 1, false, nullptr, SHARE_CONVERT);
+  partial_req r; r.d_points = d_points_xy_le; r.d_scalars = d_scalars_le; r.n = n; r.d_partials_out = d_partials; r.share = SHARE_CONVERT;
+  r.stream = stream == TE_MSM_OWN_STREAM ? ws.stream : (hipStream_t)stream;
+  return enqueue_partial(ctx, d, ws, r);
 }
 
 int te_msm_partial_device_batch(te_ctx* ctx, const void* const* d_points_xy_le, const void* const* d_scalars_le, uint64_t n, int count,
@@ -3501,10 +3507,11 @@ int te_msm_partial_device_batch(te_ctx* ctx, const void* const* d_points_xy_le, 
   workset_t& ws = d.ws[ctx->opt_workset];
   if (te_sched::slot_ticket(ws.slot)) return set_err(ctx, TE_MSM_ESTATE, "the selected work set holds a submitted MSM that has not been collected");
   HIP_TRY(ctx, hipSetDevice(d.device));
-  hipStream_t st = stream == TE_MSM_OWN_STREAM ? ws.stream : (hipStream_t)stream;
-  if (count == 1) return enqueue_partial(ctx, d, ws, d_points_xy_le[0], d_scalars_le[0], n, d_partials, st, nullptr, 0, false, 1, false, nullptr, SHARE_CONVERT);
+  partial_req r; r.n = n; r.d_partials_out = d_partials; r.share = SHARE_CONVERT; r.batch = count;
+  r.stream = stream == TE_MSM_OWN_STREAM ? ws.stream : (hipStream_t)stream;
   // the pointer arrays are only read while the launches are enqueued
-  return enqueue_partial(ctx, d, ws, d_points_xy_le, d_scalars_le, n, d_partials, st, nullptr, 0, false, count, false, nullptr, SHARE_CONVERT);
+  if (count == 1) { r.d_points = d_points_xy_le[0]; r.d_scalars = d_scalars_le[0]; } else { r.d_points = d_points_xy_le; r.d_scalars = d_scalars_le; }
+  return enqueue_partial(ctx, d, ws, r);
 }
 
 int te_msm_workset_stream(te_ctx* ctx, int workset, void** stream, int* hw_queue_class) {
