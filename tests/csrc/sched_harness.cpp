@@ -6,8 +6,9 @@
 // merge (csrc/host_tail.hpp: te_host::merge_window_rows, as the multi-device te_msm_run uses it).  What is faked is the GPU:
 // a "device" is a thread that computes an MSM's partial rows with the device arithmetic compiled for the host
 // (fpc_partial_rows, tests/csrc/fpcheck.cpp) and then signals an event, the way a stream signals ev_result.
-// The fake engine below mirrors csrc/te_msm.hip's submit_host / te_msm_ticket_wait / te_msm_collect line by line around
-// those shared pieces.  Built with -fsanitize=thread by tests/sanitize/Makefile; any report fails the run.
+// The fake engine below makes the calls into te_sched:: that csrc/te_msm.hip makes, in its order: fk_submit is submit_host with
+// take_free_workset, post_to_lane (clear job_err, pick the lane, post, keep a failure's text: lane_status) and hand_out_ticket written
+// out; fk_ticket_wait and fk_collect are te_msm_ticket_wait and te_msm_collect (find, await_job, the result's event, retire, status).  Built with -fsanitize=thread by tests/sanitize/Makefile; any report fails the run.
 // SURVEY.md section 5 "race detection / sanitizers" (the reference is single-threaded JavaScript).
 #include "fpcheck.cpp"
 #include "../../webgpu-msm-twisted-edwards_amd/csrc/host_tail.hpp"

@@ -147,6 +147,95 @@ def test_device_resident_tickets_on_a_multi_device_context(pkg, ora):
         assert part1 != want and c1.collect(c1.submit_device(dp.data_ptr(), ds.data_ptr(), n)) == want
 
 
+def test_every_ticket_form_counters_capacity_and_refusals(pkg, ora):
+    """The seven submit forms (te_msm_submit, _async, _device, _scalars, _scalars_device, _scalars_indexed, _scalars_indexed_device) on
+    n_dev = 2 of one GPU, over per-call inputs, a bound set, an indexed subset and a fixed-base set: every form once against the
+    oracle; what each form adds to the peer counters when the inputs are pulled ("stage_device_inputs"); the entries a ticket
+    notes; all 16 work sets taken -- every form is refused and nothing leaks --; a refused argument leaves nothing behind"""
+    import numpy as np
+    import torch
+    n, m, nf = 300, 500, 2000
+    pts, sc = ora.gen_points(1450, nf), ora.gen_scalars(1451, nf)
+    p, s = pts[:64 * n], sc[:32 * n]
+    idx = np.random.default_rng(1452).integers(0, n, size=m, dtype=np.uint32)
+    assert len(np.unique(idx)) < m                                                         # with repeats
+    sm = sc[:32 * m]
+    want = ora.msm(p, s, threads=8)
+    want_idx = ora.msm(np.frombuffer(p, dtype=np.uint8).reshape(-1, 64)[idx].tobytes(), sm, threads=8)
+    want_fb = ora.msm(pts, sc, threads=8)
+    dp, ds, dsm, dsf, dx = _dev(p), _dev(s), _dev(sm), _dev(sc), torch.from_numpy(idx.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    with pkg.MsmContext((0, 0)) as c:
+        b = c.bind_points(p)
+        c.set_option("bind_fixed_base", 16)
+        fb = c.bind_points(pts)
+        c.set_option("bind_fixed_base", 0)
+        forms = [(lambda: c.submit(p, s), want), (lambda: c.submit_async(p, s), want),
+                 (lambda: c.submit_device(dp.data_ptr(), ds.data_ptr(), n), want),
+                 (lambda: c.submit_scalars(b, s), want), (lambda: c.submit_scalars_device(b, ds.data_ptr()), want),
+                 (lambda: c.submit_scalars_indexed(b, idx, sm), want_idx),
+                 (lambda: c.submit_scalars_indexed_device(b, dx.data_ptr(), dsm.data_ptr(), m), want_idx)]
+        fixed = [(lambda: c.submit_scalars(fb, sc), want_fb), (lambda: c.submit_scalars_device(fb, dsf.data_ptr()), want_fb)]
+        peer = lambda: (c.get_option("peer_copies"), c.get_option("peer_bytes"))
+        # every form once, no copy between the two names of the one GPU
+        c.set_option("stage_device_inputs", 0)
+        ts = [(f(), w) for f, w in forms + fixed]
+        assert c.get_option("in_flight") == len(ts) == 9
+        for i, (t, w) in reversed(list(enumerate(ts))):
+            assert c.collect(t) == w, i
+        assert peer() == (0, 0) and c.get_option("in_flight") == 0
+        # the peer counters, form by form
+        c.set_option("stage_device_inputs", 1)
+        moved = [(0, 0), (0, 0), (2, 96 * n), (0, 0), (1, 32 * n), (0, 0), (2, 36 * m)]
+        for i, ((f, w), (copies, nbytes)) in enumerate(zip(forms, moved)):
+            before = peer()
+            t = f()
+            assert (peer()[0] - before[0], peer()[1] - before[1]) == (copies, nbytes), i
+            assert c.collect(t) == w, i
+            assert (peer()[0] - before[0], peer()[1] - before[1]) == (copies, nbytes), i
+        before = peer()
+        assert c.run_scalars_device(b, ds.data_ptr()) == want                              # the lone call: window shards, every device pulls
+        assert (peer()[0] - before[0], peer()[1] - before[1]) == (2, 64 * n)
+        # the entries a device ticket notes at its collect are those of the lone call over the same inputs
+        assert c.run_device(dp.data_ptr(), ds.data_ptr(), n) == want
+        entries = c.get_option("entries_accumulated")
+        assert entries > 0
+        assert c.collect(c.submit(pts, sc)) == want_fb and c.get_option("entries_accumulated") != entries
+        assert c.collect(c.submit_device(dp.data_ptr(), ds.data_ptr(), n)) == want and c.get_option("entries_accumulated") == entries
+        # capacity: every work set of both devices holds a ticket
+        ts = [c.submit_device(dp.data_ptr(), ds.data_ptr(), n) for _ in range(2 * pkg.WORKSETS)]
+        assert c.get_option("in_flight") == 16
+        for i, (f, _) in enumerate(forms):
+            with pytest.raises(pkg.MsmError) as e:
+                f()
+            assert e.value.code == -4 and "every work set has an MSM in flight" in str(e.value), (i, str(e.value))
+            assert c.get_option("in_flight") == 16
+        assert all(c.collect(t) == want for t in ts)
+        assert c.get_option("in_flight") == 0
+        for i, (f, w) in enumerate(forms):
+            assert c.collect(f()) == w, i
+        # refused arguments: nothing is taken, the next submit goes through
+        gone = c.bind_points(p)
+        stale = type(gone)(c, gone._h, n, gone.curve)
+        c.release_points(gone)
+        held = c.submit_device(dp.data_ptr(), ds.data_ptr(), n)
+        refused = [lambda: c.submit_scalars(stale, s), lambda: c.submit_scalars_device(stale, ds.data_ptr()),
+                   lambda: c.submit_scalars_indexed(stale, idx, sm), lambda: c.submit_scalars_indexed_device(stale, dx.data_ptr(), dsm.data_ptr(), m),
+                   lambda: c.submit_device(dp.data_ptr(), 0, n), lambda: c.submit_scalars_device(b, 0),
+                   lambda: c.submit_scalars_indexed_device(b, dx.data_ptr(), 0, m),
+                   lambda: c.submit_scalars_indexed(b, [], b""), lambda: c.submit_scalars_indexed_device(b, dx.data_ptr(), dsm.data_ptr(), 0)]
+        for i, f in enumerate(refused):
+            with pytest.raises(pkg.MsmError) as e:
+                f()
+            assert e.value.code == -1, (i, str(e.value))
+            assert c.get_option("in_flight") == 1, i
+            fn, w = forms[i % len(forms)]
+            assert c.collect(fn()) == w, i
+        assert c.collect(held) == want and c.get_option("in_flight") == 0
+        c.release_points(b)
+        c.release_points(fb)
+
+
 def test_pinned_host_buffers_are_released_at_return(pkg, ora):
     """te_msm_submit / te_msm_run promise that the caller's buffers are free when the call returns.  Copies from PINNED memory
     are truly asynchronous, so the call has to wait for its uploads: the buffers are overwritten right after it returns"""

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <condition_variable>
 #include <memory>
+#include <optional>
 #include <type_traits>
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -1187,6 +1188,37 @@ int ensure_staging(te_ctx* ctx, workset_t& ws, size_t bytes_points, size_t bytes
   if (int rc = make_room(ctx, ws.d_in_points, bytes_points)) return rc;
   return make_room(ctx, ws.d_in_scalars, bytes_scalars);
 }
+// The staging area may still be read by the set's previous MSM: the set's stream goes on behind it.  (ev_done exists from
+// te_msm_init to te_msm_destroy, so `used` alone says whether there is a previous MSM -- as in begin_sequence.)
+int wait_behind_previous(te_ctx* ctx, workset_t& ws) {
+  if (ws.used) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));
+  return 0;
+}
+
+// Device-resident inputs of a call, and the peer pull that brings them from the memory of device src_dev into the staging area of a
+// work set on another device of the context (tickets that land beside their inputs, the shares of run_bound_window_shards).
+struct device_inputs { const void* scalars = nullptr; const void* points = nullptr; const uint32_t* idx = nullptr; };     // points / idx: where the call has them
+struct peer_traffic { int64_t copies = 0, bytes = 0; };
+// must device d pull what lies on src_dev?  ("stage_device_inputs": also when d IS the holder -- the one-GPU rehearsal)
+bool must_pull(const te_ctx* ctx, const gpu_t& d, int src_dev) { return ctx->devs.size() > 1 && (d.device != src_dev || ctx->opt_stage_device_inputs); }
+// The n entries of `in` over the peer link, on the set's stream; `in` then names the staging area.  moved: what was copied -- the caller
+// adds it to the context's counters (plain integers: run_bound_window_shards pulls from one host thread per device and adds after the join).
+int pull_inputs(te_ctx* ctx, const gpu_t& d, workset_t& ws, int src_dev, uint64_t n, device_inputs& in, peer_traffic& moved) {
+  const curve_sizes sz = sizes_of(ctx->opt_curve);
+  if (in.idx) { if (int rc = make_room(ctx, ws.d_in_idx, (size_t)n)) return rc; }
+  if (int rc = ensure_staging(ctx, ws, in.points ? n * sz.point_in : 0, n * sz.scalar_in)) return rc;
+  if (int rc = wait_behind_previous(ctx, ws)) return rc;
+  HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, in.scalars, src_dev, n * sz.scalar_in, ws.stream));
+  if (in.points) HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_points, d.device, in.points, src_dev, n * sz.point_in, ws.stream));
+  if (in.idx) HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_idx, d.device, in.idx, src_dev, n * sizeof(uint32_t), ws.stream));
+  moved.copies += 1 + (in.points != nullptr) + (in.idx != nullptr);
+  moved.bytes += (int64_t)(n * (sz.scalar_in + (in.points ? sz.point_in : 0) + (in.idx ? sizeof(uint32_t) : 0)));
+  in.scalars = ws.d_in_scalars;
+  if (in.points) in.points = ws.d_in_points;
+  if (in.idx) in.idx = ws.d_in_idx;
+  return 0;
+}
+void note_peer_traffic(te_ctx* ctx, const peer_traffic& moved) { ctx->stat_peer_copies += moved.copies; ctx->stat_peer_bytes += moved.bytes; }
 
 // Is this host address pinned (hipHostMalloc) or registered (hipHostRegister) memory?  A copy from such memory does not
 // stage: hipMemcpyAsync returns before the data has left it.  Ordinary (pageable) memory is unknown to the runtime: the query
@@ -1657,6 +1689,15 @@ int note_bad_index(te_ctx* ctx, int64_t position) {
   snprintf(buf, sizeof buf, "index at position %lld is not below te_msm_bases_count of the bound point set", (long long)position);
   return set_err(ctx, TE_MSM_EINVAL, buf);
 }
+// The status of the MSM whose flag words are in the set's pinned block (ev_result has passed): its entries noted, an index outside
+// the bound set reported (bit 1 of word 0: only the indexed first-level scatter sets it -- the fixed-base overflow is word 1 alone),
+// else the final carry.  entries_of_failed = false (te_msm_finalize): a failed MSM leaves "entries_accumulated" as it was.
+int settle_status(te_ctx* ctx, const workset_t& ws, bool entries_of_failed = true) {
+  if (entries_of_failed || !*ws.h_err) note_entries(ctx, ws);
+  if (const int64_t bad = bad_index_of(ws); bad >= 0) return note_bad_index(ctx, bad);
+  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  return 0;
+}
 
 // te_msm_run for a large MSM on one device: enqueue_host_slice on a free work set, wait, host tail
 int run_host_chunked(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_scalars, uint64_t n, int K, uint8_t out[64]) {
@@ -1665,8 +1706,7 @@ int run_host_chunked(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
   plan_t pf; make_plan(ctx, d, n, pf, 0, 1, 0, true);
   if (int rc = enqueue_host_slice(ctx, d, ws, src_points, src_scalars, n, pf.c, K)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
-  note_entries(ctx, ws);
-  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  if (int rc = settle_status(ctx, ws)) return rc;
   fold_rows(pf, ws.h_partials, out);
   return 0;
 }
@@ -1805,7 +1845,7 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
     gpu_t& d = ctx->devs[i]; workset_t& ws = d.ws[wsel[i]];
     HIP_TRY(ctx, hipSetDevice(d.device));
     if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sz.scalar_in)) return rc;
-    if (ws.used && ws.ev_done) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));      // the staging area may still be read by the set's previous MSM
+    if (int rc = wait_behind_previous(ctx, ws)) return rc;
     const uint64_t lo = lo_of(i), m = lo_of(i + 1) - lo;
     if (m) {
       HIP_TRY(ctx, hipMemcpyPeerAsync(static_cast<uint8_t*>(ws.d_in_points) + lo * sz.point_in, d.device, sp + lo * sz.point_in, src_dev, m * sz.point_in, ws.stream));
@@ -1985,9 +2025,8 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));          // (pinned sources included: the call ends after its uploads)
   release_shared_recs(d, ws);                               // the call is over: its record slab (if shared) may serve another point buffer
-  note_entries(ctx, ws);
-  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
-  (void)collect_stage_ms(ctx, d, ws);
+  if (int rc = settle_status(ctx, ws)) return rc;
+  (void)collect_stage_ms(ctx, d, ws);                       // (of a call that succeeded: a failed lone call leaves the previous stage times)
   // a window-sharded single-device context (te_msm_set_window_shard) folds its own rows only: the others read as zero
   fold_rows(p0, ws.h_partials, out);
   return 0;
@@ -2106,15 +2145,17 @@ namespace {
 // (the bookkeeping itself is host_sched.hpp's: the same code runs under ThreadSanitizer in tests/csrc/sched_harness.cpp)
 int pick_device(te_ctx* ctx, int prefer) { return te_sched::pick_device_of(*ctx, TE_MSM_WORKSETS, prefer); }
 const char* const kAllInFlight = "every work set has an MSM in flight: collect one first";
-// The work set of a new ticket: on the device pick_device chooses (*di; made current), the lowest-numbered free work set (each has its
+// The work set a new ticket is opened on, as every submit form uses it: index of its device in ctx->devs, the device, the set.
+struct ticket_set { int di; gpu_t& d; workset_t& ws; };
+// The work set of a new ticket: on the device pick_device chooses (made current), the lowest-numbered free work set (each has its
 // own stream: the MSMs overlap on the device).  Not ticket % sets: with fewer MSMs in flight than sets only as many sets as needed are
 // ever touched -- no buffer allocation in the middle of a run, and a smaller footprint in the Infinity Cache.
 // probe: the lazy hardware-queue measurement (16 ms, once per device) -- device-resident tickets only: a host-buffer ticket is bound
 // by its upload, not by how the work sets' streams share the hardware queues
-int take_free_workset(te_ctx* ctx, int prefer, bool probe, int* di) {
-  *di = pick_device(ctx, prefer);
-  if (*di < 0) return set_err(ctx, TE_MSM_ESTATE, kAllInFlight);
-  gpu_t& d = ctx->devs[(size_t)*di];
+int take_free_workset(te_ctx* ctx, int prefer, bool probe, std::optional<ticket_set>& t) {
+  const int di = pick_device(ctx, prefer);
+  if (di < 0) return set_err(ctx, TE_MSM_ESTATE, kAllInFlight);
+  gpu_t& d = ctx->devs[(size_t)di];
   HIP_TRY(ctx, hipSetDevice(d.device));
   if (d.in_flight >= TE_MSM_WORKSETS) return set_err(ctx, TE_MSM_ESTATE, kAllInFlight);
   if (probe && !d.queues_probed && ctx->opt_queue_probe && d.in_flight == 0) spread_streams_over_queues(d);      // once per device, with nothing of it in flight
@@ -2122,7 +2163,8 @@ int take_free_workset(te_ctx* ctx, int prefer, bool probe, int* di) {
   d.streams_final = d.queues_probed || !ctx->opt_queue_probe;
   const int wi = free_workset_index(d);
   if (wi < 0) return set_err(ctx, TE_MSM_ESTATE, kAllInFlight);
-  return wi;
+  t.emplace(ticket_set{di, d, d.ws[wi]});
+  return 0;
 }
 // option "check_points" (level) on the points of a ticket, on device ci: 0 = go on; TE_MSM_EPOINT = the ticket's outcome, kept in the
 // set for te_msm_collect (nothing is enqueued for the ticket); else a device error
@@ -2139,8 +2181,19 @@ int lane_status(te_ctx* ctx, workset_t& ws, int rc) {
   if (rc && rc != TE_MSM_EPOINT) { std::lock_guard<std::mutex> lk(ctx->err_mu); ws.job_err = ctx->err; }
   return rc;
 }
-void hand_out_ticket(te_ctx* ctx, int di, workset_t& ws, uint64_t* ticket, te_sched::job_ref job = nullptr) {
-  te_sched::hand_out(*ctx, di, ws, ticket, std::move(job));          // te_msm_ticket_wait looks the ticket up from other threads
+// bound: the point set the ticket gathers from (te_msm_submit_scalars*) -- it cannot be released before the collect (retire_ticket)
+void hand_out_ticket(te_ctx* ctx, const ticket_set& t, uint64_t* ticket, te_bases* bound = nullptr, te_sched::job_ref job = nullptr) {
+  if (bound) { t.ws.bound = bound; bound->in_flight++; }
+  te_sched::hand_out(*ctx, t.di, t.ws, ticket, std::move(job));      // te_msm_ticket_wait looks the ticket up from other threads
+}
+// check_ticket on the thread that submits, and what its answer means for the call: false = the points passed, go on; true = the call
+// is over with *rc -- 0 with the ticket handed out (TE_MSM_EPOINT is the ticket's outcome: te_msm_collect reports it), or a device error
+bool ticket_ends_at_check(te_ctx* ctx, const ticket_set& t, size_t ci, const void* src, bool src_is_host, uint64_t n, uint64_t* ticket, int* rc) {
+  *rc = check_ticket(ctx, t.ws, ci, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points);
+  if (*rc != TE_MSM_EPOINT) return *rc != 0;
+  hand_out_ticket(ctx, t, ticket);
+  *rc = 0;
+  return true;
 }
 workset_t* workset_of_ticket(te_ctx* ctx, uint64_t ticket, gpu_t** dev = nullptr) {
   int di = -1;
@@ -2166,6 +2219,18 @@ int owner_of(te_ctx* ctx, const char* msg, std::initializer_list<const void*> pt
   }
   return owner;
 }
+// The device-resident inputs of a ticket (on device `owner` of the context), where its launch sequence reads them: in place, or -- the
+// ticket went to another device -- pulled into its set's staging area and counted.  pulled: which of the two.
+int pull_for_ticket(te_ctx* ctx, const ticket_set& t, int owner, uint64_t n, device_inputs& in, bool* pulled = nullptr) {
+  const int src_dev = ctx->devs[(size_t)owner].device;
+  const bool pull = must_pull(ctx, t.d, src_dev);
+  if (pulled) *pulled = pull;
+  if (!pull) return 0;
+  peer_traffic moved;
+  if (int rc = pull_inputs(ctx, t.d, t.ws, src_dev, n, in, moved)) return rc;
+  note_peer_traffic(ctx, moved);
+  return 0;
+}
 const char* const kNoTicket = "no such ticket in flight (already collected, or never handed out)";
 int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases);     // (resident bases, further down)
 }  // namespace
@@ -2178,42 +2243,23 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
   // several devices: the inputs may live on any of them; the ticket goes to the least loaded one and pulls them over xGMI
   const int owner = multi ? owner_of(ctx, "te_msm_submit_device: points and scalars must be resident on one device of the context", {d_points_xy_le, d_scalars_le}) : 0;
   if (owner < 0) return owner;
-  int di = -1;
-  const int wi = take_free_workset(ctx, owner, true, &di);
-  if (wi < 0) return wi;
-  gpu_t& d = ctx->devs[(size_t)di];
-  workset_t& ws = d.ws[wi];
-  // checked where the inputs lie; a failure is the ticket's outcome (te_msm_collect)
-  if (const int rc = check_ticket(ctx, ws, (size_t)owner, d_points_xy_le, false, n, ctx->opt_curve, ctx->opt_check_points)) {
-    if (rc == TE_MSM_EPOINT) hand_out_ticket(ctx, di, ws, ticket);
-    return rc == TE_MSM_EPOINT ? 0 : rc;
-  }
-  const bool stage = multi && (d.device != ctx->devs[(size_t)owner].device || ctx->opt_stage_device_inputs);
-  const int src_dev = ctx->devs[(size_t)owner].device;
-  if (stage) { const curve_sizes sz = sizes_of(ctx->opt_curve); ctx->stat_peer_copies += 2; ctx->stat_peer_bytes += (int64_t)(n * (sz.point_in + sz.scalar_in)); }
-  workset_t* wsp = &ws; gpu_t* dvp = &d;
-  // the peer copies (if any), the ~10 launches of the MSM and its read-back
-  auto work = [ctx, dvp, wsp, d_points_xy_le, d_scalars_le, n, stage, src_dev, multi]() -> int {
-    gpu_t& d = *dvp; workset_t& ws = *wsp;
-    HIP_TRY(ctx, hipSetDevice(d.device));
-    const void *dp = d_points_xy_le, *ds = d_scalars_le;
-    if (stage) {
-      const curve_sizes sz = sizes_of(ctx->opt_curve);
-      if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sz.scalar_in)) return rc;
-      if (ws.used) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));
-      HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, d_scalars_le, src_dev, n * sz.scalar_in, ws.stream));
-      HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_points, d.device, d_points_xy_le, src_dev, n * sz.point_in, ws.stream));
-      dp = ws.d_in_points; ds = ws.d_in_scalars;
-    }
-    // a single-device context keeps its window shard (te_msm_set_window_shard); on several devices a ticket is a whole MSM
-    partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.whole = multi; r.share = stage ? SHARE_NONE : SHARE_RUN;
-    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
-    return fetch_rows(ctx, ws, ws.stream);
-  };
-  // (Handing this to a host thread, as te_msm_submit_async does with uploads, was measured: no gain at n = 2^16 .. 2^18, 3-7 %
-  // slower at 2^19 / 2^20 -- the submitting thread is not what bounds small MSMs in flight; profiles/r05_enqueue_async_experiment.txt.)
-  if (int rc = work()) return rc;
-  hand_out_ticket(ctx, di, ws, ticket);
+  std::optional<ticket_set> taken;
+  if (int rc = take_free_workset(ctx, owner, true, taken)) return rc;
+  const ticket_set& t = *taken;
+  // checked where the inputs lie
+  if (int rc; ticket_ends_at_check(ctx, t, (size_t)owner, d_points_xy_le, false, n, ticket, &rc)) return rc;
+  // The peer copies (if any), the ~10 launches of the MSM and its read-back, on the calling thread.  (Handing them to a host thread, as
+  // te_msm_submit_async does with uploads, was measured: no gain at n = 2^16 .. 2^18, 3-7 % slower at 2^19 / 2^20 -- the submitting
+  // thread is not what bounds small MSMs in flight; profiles/r05_enqueue_async_experiment.txt.)
+  HIP_TRY(ctx, hipSetDevice(t.d.device));
+  device_inputs in; in.scalars = d_scalars_le; in.points = d_points_xy_le;
+  bool pull = false;
+  if (int rc = pull_for_ticket(ctx, t, owner, n, in, &pull)) return rc;
+  // a single-device context keeps its window shard (te_msm_set_window_shard); on several devices a ticket is a whole MSM
+  partial_req r; r.d_points = in.points; r.d_scalars = in.scalars; r.n = n; r.stream = t.ws.stream; r.whole = multi; r.share = pull ? SHARE_NONE : SHARE_RUN;
+  if (int rc = enqueue_partial(ctx, t.d, t.ws, r)) return rc;
+  if (int rc = fetch_rows(ctx, t.ws, t.ws.stream)) return rc;
+  hand_out_ticket(ctx, t, ticket);
   return 0;
 }
 
@@ -2272,43 +2318,44 @@ void warm_upload_lanes(te_ctx* ctx) {
   for (size_t i = 0; i < jobs.size(); i++) (void)who[i]->wait(jobs[i]);
 }
 
+// An asynchronous ticket: `enqueue` (the upload and the launches of one whole MSM; 0 or an error already noted) runs on an upload lane
+// of the ticket's device, and the call returns at once -- D of them keep D links busy.  The job's status, and the error text of a failure,
+// stay with the set for te_msm_collect (lane_status).  The job reads the context's options as they are NOW only by accident of timing
+// -- so te_msm_set_option waits for the host threads first (drain_workers); what the enqueue depends on is fixed by its captures.
+// (a template inside the C-ABI block: C++ linkage said by name)
+extern "C++" template <typename F> te_sched::job_ref post_to_lane(te_ctx* ctx, const ticket_set& t, F enqueue) {
+  t.ws.job_err.clear();
+  warm_upload_lanes(ctx);                            // (once per process and device: all of the context's devices together)
+  workset_t* wsp = &t.ws;
+  return te_sched::next_lane_of(*ctx, (size_t)t.di, ctx->opt_upload_threads).post([ctx, wsp, enqueue]() -> int { return lane_status(ctx, *wsp, enqueue()); });
+}
+
 int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars_le, uint64_t n, uint64_t* ticket, bool async) {
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (!points_xy_le || !scalars_le || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_submit computes whole MSMs: reset the window shard first");
-  int di = -1;
-  const int wi = take_free_workset(ctx, -1, false, &di);
-  if (wi < 0) return wi;
-  gpu_t& d = ctx->devs[(size_t)di];
-  workset_t& ws = d.ws[wi];
-  plan_t pf; make_plan(ctx, d, n, pf, 0, 1, 0, true);
-  const int c = pf.c, K = host_pieces(ctx, n);
-  const int level = ctx->opt_check_points, curve = ctx->opt_curve;
+  std::optional<ticket_set> taken;
+  if (int rc = take_free_workset(ctx, -1, false, taken)) return rc;
+  const ticket_set& t = *taken;
+  plan_t pf; make_plan(ctx, t.d, n, pf, 0, 1, 0, true);
+  const int c = pf.c, K = host_pieces(ctx, n);               // the plan's window bits and pieces are fixed here
   if (!async) {
-    if (const int rc = check_ticket(ctx, ws, (size_t)di, points_xy_le, true, n, curve, level)) {     // a failure is the ticket's outcome (te_msm_collect)
-      if (rc == TE_MSM_EPOINT) hand_out_ticket(ctx, di, ws, ticket);
-      return rc == TE_MSM_EPOINT ? 0 : rc;
-    }
-    if (int rc = enqueue_host_slice(ctx, d, ws, points_xy_le, scalars_le, n, c, K, true)) return rc;
-    hand_out_ticket(ctx, di, ws, ticket);
+    if (int rc; ticket_ends_at_check(ctx, t, (size_t)t.di, points_xy_le, true, n, ticket, &rc)) return rc;
+    if (int rc = enqueue_host_slice(ctx, t.d, t.ws, points_xy_le, scalars_le, n, c, K, true)) return rc;
+    hand_out_ticket(ctx, t, ticket);
     return 0;
   }
-  // the upload and the enqueue run on the device's host thread: this call returns at once, D of them keep D links busy.
-  // The job reads the context's options as they are NOW only by accident of timing -- so te_msm_set_option waits for the host
-  // threads first (drain_workers); the plan's window bits and pieces are fixed here.
-  ws.job_err.clear();
-  workset_t* wsp = &ws; gpu_t* dp = &d;
-  warm_upload_lanes(ctx);                            // (once per process and device: all of the context's devices together)
-  te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, points_xy_le, scalars_le, n, c, K, di, level, curve]() -> int {
+  const int level = ctx->opt_check_points, curve = ctx->opt_curve;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, points_xy_le, scalars_le, n, c, K, level, curve]() -> int {
     // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
-    if (const int rc = check_ticket(ctx, *wsp, (size_t)di, points_xy_le, true, n, curve, level)) return lane_status(ctx, *wsp, rc);
-    return lane_status(ctx, *wsp, enqueue_host_slice(ctx, *dp, *wsp, points_xy_le, scalars_le, n, c, K, false));
+    if (const int rc = check_ticket(ctx, t.ws, (size_t)t.di, points_xy_le, true, n, curve, level)) return rc;
+    return enqueue_host_slice(ctx, t.d, t.ws, points_xy_le, scalars_le, n, c, K, false);
   });
-  hand_out_ticket(ctx, di, ws, ticket, std::move(job));
+  hand_out_ticket(ctx, t, ticket, nullptr, std::move(job));
   return 0;
 }
 // the enqueue of an asynchronous ticket has run (any thread); its status
-int await_job(te_ctx*, gpu_t&, workset_t& ws) { return te_sched::await_job(ws); }
+int await_job(workset_t& ws) { return te_sched::await_job(ws); }
 void retire_ticket(te_ctx* ctx, gpu_t& d, workset_t& ws) {
   if (ws.bound) { ws.bound->in_flight--; ws.bound = nullptr; }       // the ticket gathered from a bound point set: it may be released now
   release_shared_recs(d, ws);                                        // the ticket's MSM is over: its record slab may serve another point buffer
@@ -2329,10 +2376,9 @@ int te_msm_submit_async(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t*
 int te_msm_ticket_wait(te_ctx* ctx, uint64_t ticket) {
   device_guard restore_callers_device;
   if (!ctx) return TE_MSM_EINVAL;
-  gpu_t* d = nullptr;
-  workset_t* ws = workset_of_ticket(ctx, ticket, &d);
+  workset_t* ws = workset_of_ticket(ctx, ticket);
   if (!ws) return set_err(ctx, TE_MSM_ESTATE, kNoTicket);
-  if (const int rc = await_job(ctx, *d, *ws)) return rc;      // te_msm_collect reports it (and frees the ticket)
+  if (const int rc = await_job(*ws)) return rc;      // te_msm_collect reports it (and frees the ticket)
   HIP_TRY(ctx, hipEventSynchronize(ws->ev_result));
   return 0;
 }
@@ -2353,7 +2399,7 @@ int te_msm_collect(te_ctx* ctx, uint64_t ticket, uint8_t out_xy_le[64]) {
   workset_t* wsp = workset_of_ticket(ctx, ticket, &dp);
   if (!wsp) return set_err(ctx, TE_MSM_ESTATE, kNoTicket);
   workset_t& ws = *wsp; gpu_t& d = *dp;
-  if (const int jrc = !ws.slot.job && ws.pt_rc == TE_MSM_EPOINT ? TE_MSM_EPOINT : await_job(ctx, d, ws)) {
+  if (const int jrc = !ws.slot.job && ws.pt_rc == TE_MSM_EPOINT ? TE_MSM_EPOINT : await_job(ws)) {
     if (jrc == TE_MSM_EPOINT) {       // its points failed the check in te_msm_submit[_device] or on the lane of te_msm_submit_async: nothing was enqueued
       const int64_t bad = ws.pt_index; const int reason = ws.pt_reason;
       ws.pt_rc = 0;
@@ -2369,11 +2415,10 @@ int te_msm_collect(te_ctx* ctx, uint64_t ticket, uint8_t out_xy_le[64]) {
   }
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));   // on failure the ticket stays collectable
   if (ws.bound) { if (int rc = fixed_base_settle(ctx, d, ws, ws.bound)) return rc; }      // (a fixed-base ticket whose rows overflowed: run again with the ordinary windows)
-  (void)collect_stage_ms(ctx, d, ws);
-  note_entries(ctx, ws);
-  retire_ticket(ctx, d, ws);                         // the MSM is over, with a result or with a scalar-range error
-  if (const int64_t bad = bad_index_of(ws); bad >= 0) return note_bad_index(ctx, bad);      // (indexed tickets only: nothing else sets the bit)
-  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  (void)collect_stage_ms(ctx, d, ws);                // (a ticket reports its stage times whatever its status)
+  const int rc = settle_status(ctx, ws);
+  retire_ticket(ctx, d, ws);                         // the MSM is over, with a result, a bad index or a scalar-range error
+  if (rc) return rc;
   fold_rows(ws.plan, ws.h_partials, out_xy_le);
   return 0;
 }
@@ -2493,10 +2538,10 @@ int enqueue_fixed_base_host(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases
   HIP_TRY(ctx, hipSetDevice(d.device));
   const curve_sizes sz = sizes_of(bases->curve);
   if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
-  if (ws.used && ws.ev_done) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));      // the staging area may still be read by the set's previous MSM
+  if (int rc = wait_behind_previous(ctx, ws)) return rc;
   if (!wait_for_pinned) {
     // an asynchronous ticket: the lane thread waits for the upload itself (lane_wait), no wait enters the work set's stream
-    if (ws.used && ws.ev_done) HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
+    if (ws.used) HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
     if (int rc = need_copy_stream(ctx, ws)) return rc;
     if (int rc = upload(ctx, ws, ws.d_in_scalars, src_scalars, n * sz.scalar_in, ws.copy_stream)) return rc;
     if (int rc = lane_wait(ctx, ws, ws.ev_copy, true)) return rc;
@@ -2525,15 +2570,6 @@ int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* base
   return 0;
 }
 
-// the n scalars at src (memory of device src_dev) into the set's staging area over the peer link, on the set's stream
-int pull_scalars(te_ctx* ctx, const gpu_t& d, workset_t& ws, const void* src, int src_dev, uint64_t n) {
-  const size_t bytes = n * sizes_of(ctx->opt_curve).scalar_in;
-  if (int rc = ensure_staging(ctx, ws, 0, bytes)) return rc;
-  if (ws.used && ws.ev_done) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));      // the staging area may still be read by the set's previous MSM
-  HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, src, src_dev, bytes, ws.stream));
-  return 0;
-}
-
 // te_msm_run_scalars_device on a context of D > 1 devices: WINDOW shards (device i computes windows i, i + D, ...).  Every
 // device needs all n scalars: the holder reads them in place, the others pull them over their peer link (32 bytes per point:
 // a third of what run_device_window_shards moves, so one copy each instead of its scatter + all-gather); every device gathers
@@ -2541,27 +2577,23 @@ int pull_scalars(te_ctx* ctx, const gpu_t& d, workset_t& ws, const void* src, in
 int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_scalars, uint64_t n, uint8_t* out) {
   const size_t nd = ctx->devs.size();
   plan_t p0; make_plan(ctx, ctx->devs[0], n, p0);
-  const curve_sizes sz = sizes_of(p0.curve);
   const int owner = owner_of(ctx, "te_msm_run_scalars_device: the scalars must be resident on a device of the context", {d_scalars});
   if (owner < 0) return owner;
   const int src_dev = ctx->devs[(size_t)owner].device;
   std::vector<int> wsel;
   if (int rc = free_sets(ctx, nd, wsel)) return rc;
-  std::vector<int64_t> copies(nd, 0);
+  std::vector<peer_traffic> moved(nd);
   auto share = [&](size_t i) -> int {
     gpu_t& d = ctx->devs[i]; workset_t& ws = d.ws[wsel[i]];
     HIP_TRY(ctx, hipSetDevice(d.device));
-    const void* ds = d_scalars;
-    if (d.device != src_dev || ctx->opt_stage_device_inputs) {
-      if (int rc = pull_scalars(ctx, d, ws, d_scalars, src_dev, n)) return rc;
-      copies[i] = 1; ds = ws.d_in_scalars;
-    }
-    partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.bases = bases;
+    device_inputs in; in.scalars = d_scalars;
+    if (must_pull(ctx, d, src_dev)) { if (int rc = pull_inputs(ctx, d, ws, src_dev, n, in, moved[i])) return rc; }
+    partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = ws.stream; r.bases = bases;
     if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
   const int rc = te_sched::on_devices(*ctx, nd, share);
-  for (size_t i = 0; i < nd; i++) { ctx->stat_peer_copies += copies[i]; ctx->stat_peer_bytes += copies[i] * (int64_t)(n * sz.scalar_in); }
+  for (const peer_traffic& m : moved) note_peer_traffic(ctx, m);
   return settle_window_shards(ctx, wsel, p0, rc, false, out);
 }
 
@@ -2603,7 +2635,7 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
     const void* ds = src;
     if (src_is_host) {
       if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
-      if (ws.used && ws.ev_done) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ws.ev_done, 0));
+      if (int rc = wait_behind_previous(ctx, ws)) return rc;
       if (int rc = upload(ctx, ws, ws.d_in_scalars, static_cast<const uint8_t*>(src), n * sz.scalar_in, ws.stream)) return rc;
       ds = ws.d_in_scalars;
     }
@@ -2613,8 +2645,7 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
   }
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
   if (int rc = fixed_base_settle(ctx, d, ws, bases)) return rc;
-  note_entries(ctx, ws);
-  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  if (int rc = settle_status(ctx, ws)) return rc;
   (void)collect_stage_ms(ctx, d, ws);
   fold_rows(ws.plan, ws.h_partials, out);
   return 0;
@@ -2666,25 +2697,19 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
   const uint64_t n = bases->n;
   if (!scalars_le || n == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty point set has no tickets: te_msm_run_scalars returns the identity)");
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_submit_scalars computes whole MSMs: reset the window shard first");
-  int di = -1;
-  const int wi = take_free_workset(ctx, -1, false, &di);
-  if (wi < 0) return wi;
-  gpu_t& d = ctx->devs[(size_t)di];
-  workset_t& ws = d.ws[wi];
-  plan_t pf; make_plan(ctx, d, n, pf, 0, 1, 0, true);
+  std::optional<ticket_set> taken;
+  if (int rc = take_free_workset(ctx, -1, false, taken)) return rc;
+  const ticket_set& t = *taken;
+  plan_t pf; make_plan(ctx, t.d, n, pf, 0, 1, 0, true);
   // pieces shorten ONE MSM's way through the device (its upload hides under its own first pieces); with other tickets in flight on
   // the device the upload hides under THEIR device work, and one piece keeps the sort and the accumulation at full width
-  const int c = pf.c, K = (ctx->opt_scalar_chunks || d.in_flight == 0) ? scalar_pieces(ctx, n) : 1;
-  ws.job_err.clear();
-  workset_t* wsp = &ws; gpu_t* dp = &d;
-  const uint8_t* recs = bases->recs[(size_t)di]; const int kind = bases->rec_kind;
-  warm_upload_lanes(ctx);
-  te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, bases, recs, kind, scalars_le, n, c, K]() -> int {
-    return lane_status(ctx, *wsp, bases->fb_c ? enqueue_fixed_base_host(ctx, *dp, *wsp, bases, scalars_le, n, false)
-                                              : enqueue_scalar_slice(ctx, *dp, *wsp, recs, kind, scalars_le, n, c, K, false));
+  const int c = pf.c, K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, n) : 1;
+  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, bases, recs, kind, scalars_le, n, c, K]() -> int {
+    return bases->fb_c ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, scalars_le, n, false)
+                       : enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, n, c, K, false);
   });
-  ws.bound = bases; bases->in_flight++;
-  hand_out_ticket(ctx, di, ws, ticket, std::move(job));
+  hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
 }
 
@@ -2697,26 +2722,18 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
   const bool multi = ctx->devs.size() > 1;
   const int owner = multi ? owner_of(ctx, "te_msm_submit_scalars_device: the scalars must be resident on a device of the context", {d_scalars_le}) : 0;
   if (owner < 0) return owner;
-  int di = -1;
-  const int wi = take_free_workset(ctx, owner, true, &di);
-  if (wi < 0) return wi;
-  gpu_t& d = ctx->devs[(size_t)di];
-  workset_t& ws = d.ws[wi];
-  const int src_dev = ctx->devs[(size_t)owner].device;
-  const void* ds = d_scalars_le;
-  if (multi && (d.device != src_dev || ctx->opt_stage_device_inputs)) {
-    if (int rc = pull_scalars(ctx, d, ws, d_scalars_le, src_dev, n)) return rc;
-    ctx->stat_peer_copies += 1; ctx->stat_peer_bytes += (int64_t)(n * sizes_of(ctx->opt_curve).scalar_in);
-    ds = ws.d_in_scalars;
-  }
-  if (bases->fb_c && (multi || d.w_step == 1)) { if (int rc = enqueue_fixed_base(ctx, d, ws, bases, ds, n, 0, ws.stream)) return rc; }
+  std::optional<ticket_set> taken;
+  if (int rc = take_free_workset(ctx, owner, true, taken)) return rc;
+  const ticket_set& t = *taken;
+  device_inputs in; in.scalars = d_scalars_le;
+  if (int rc = pull_for_ticket(ctx, t, owner, n, in)) return rc;
+  if (bases->fb_c && (multi || t.d.w_step == 1)) { if (int rc = enqueue_fixed_base(ctx, t.d, t.ws, bases, in.scalars, n, 0, t.ws.stream)) return rc; }
   else {
-    partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.whole = multi; r.bases = bases;
-    if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
+    partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = t.ws.stream; r.whole = multi; r.bases = bases;
+    if (int rc = enqueue_partial(ctx, t.d, t.ws, r)) return rc;
   }
-  if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
-  ws.bound = bases; bases->in_flight++;
-  hand_out_ticket(ctx, di, ws, ticket);
+  if (int rc = fetch_rows(ctx, t.ws, t.ws.stream)) return rc;
+  hand_out_ticket(ctx, t, ticket, bases);
   return 0;
 }
 
@@ -2733,21 +2750,10 @@ int indexed_args(te_ctx* ctx, const te_bases* bases, const void* idx, const void
 }
 const char* const kIndexedResident = "indexed MSM: indices and scalars must be resident on one device of the context";
 
-// the m pairs at d_idx / d_scalars (memory of device src_dev) into the set's staging area over the peer link, on the set's stream
-int pull_pairs(te_ctx* ctx, const gpu_t& d, workset_t& ws, const void* d_idx, const void* d_scalars, int src_dev, uint64_t m) {
-  if (int rc = make_room(ctx, ws.d_in_idx, (size_t)m)) return rc;
-  if (int rc = pull_scalars(ctx, d, ws, d_scalars, src_dev, m)) return rc;
-  HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_idx, d.device, d_idx, src_dev, m * sizeof(uint32_t), ws.stream));
-  ctx->stat_peer_copies += 2; ctx->stat_peer_bytes += (int64_t)(m * (sizes_of(ctx->opt_curve).scalar_in + sizeof(uint32_t)));
-  return 0;
-}
-
 // The end of a lone indexed call on one work set: result awaited, bad index / final carry reported, rows folded.
 int settle_indexed(te_ctx* ctx, gpu_t& d, workset_t& ws, uint8_t* out) {
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
-  note_entries(ctx, ws);
-  if (const int64_t bad = bad_index_of(ws); bad >= 0) return note_bad_index(ctx, bad);
-  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, kFinalCarry);
+  if (int rc = settle_status(ctx, ws)) return rc;
   (void)collect_stage_ms(ctx, d, ws);
   fold_rows(ws.plan, ws.h_partials, out);
   return 0;
@@ -2795,23 +2801,17 @@ int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* 
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (int rc = indexed_args(ctx, bases, idx, scalars_le, m)) return rc;
   if (m == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty index list has no tickets: te_msm_run_scalars_indexed returns the identity)");
-  int di = -1;
-  const int wi = take_free_workset(ctx, -1, false, &di);
-  if (wi < 0) return wi;
-  gpu_t& d = ctx->devs[(size_t)di];
-  workset_t& ws = d.ws[wi];
-  plan_t pf; make_plan(ctx, d, m, pf, 0, 1, 0, true);
+  std::optional<ticket_set> taken;
+  if (int rc = take_free_workset(ctx, -1, false, taken)) return rc;
+  const ticket_set& t = *taken;
+  plan_t pf; make_plan(ctx, t.d, m, pf, 0, 1, 0, true);
   // (pieces: the rule of te_msm_submit_scalars -- with other tickets in flight the upload hides under their device work)
-  const int c = pf.c, K = (ctx->opt_scalar_chunks || d.in_flight == 0) ? te_indexed::pieces(m, ctx->opt_scalar_chunks) : 1;
-  ws.job_err.clear();
-  workset_t* wsp = &ws; gpu_t* dp = &d;
-  const uint8_t* recs = bases->recs[(size_t)di]; const int kind = bases->rec_kind; const uint64_t count = bases->n;
-  warm_upload_lanes(ctx);
-  te_sched::job_ref job = te_sched::next_lane_of(*ctx, (size_t)di, ctx->opt_upload_threads).post([ctx, dp, wsp, recs, kind, idx, scalars_le, m, c, K, count]() -> int {
-    return lane_status(ctx, *wsp, enqueue_scalar_slice(ctx, *dp, *wsp, recs, kind, scalars_le, m, c, K, false, idx, count, 0));
+  const int c = pf.c, K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? te_indexed::pieces(m, ctx->opt_scalar_chunks) : 1;
+  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind; const uint64_t count = bases->n;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, recs, kind, idx, scalars_le, m, c, K, count]() -> int {
+    return enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, m, c, K, false, idx, count, 0);
   });
-  ws.bound = bases; bases->in_flight++;
-  hand_out_ticket(ctx, di, ws, ticket, std::move(job));
+  hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
 }
 
@@ -2820,25 +2820,17 @@ int te_msm_submit_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const voi
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (int rc = indexed_args(ctx, bases, d_idx, d_scalars_le, m)) return rc;
   if (m == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty index list has no tickets: te_msm_run_scalars_indexed_device returns the identity)");
-  const bool multi = ctx->devs.size() > 1;
   const int owner = owner_of(ctx, kIndexedResident, {d_idx, d_scalars_le});
   if (owner < 0) return owner;
-  int di = -1;
-  const int wi = take_free_workset(ctx, owner, true, &di);
-  if (wi < 0) return wi;
-  gpu_t& d = ctx->devs[(size_t)di];
-  workset_t& ws = d.ws[wi];
-  const int src_dev = ctx->devs[(size_t)owner].device;
-  const void* ds = d_scalars_le; const uint32_t* dx = static_cast<const uint32_t*>(d_idx);
-  if (multi && (d.device != src_dev || ctx->opt_stage_device_inputs)) {
-    if (int rc = pull_pairs(ctx, d, ws, d_idx, d_scalars_le, src_dev, m)) return rc;
-    ds = ws.d_in_scalars; dx = ws.d_in_idx;
-  }
-  partial_req r; r.d_scalars = ds; r.n = m; r.stream = ws.stream; r.whole = true; r.bases = bases; r.d_idx = dx;
-  if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
-  if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
-  ws.bound = bases; bases->in_flight++;
-  hand_out_ticket(ctx, di, ws, ticket);
+  std::optional<ticket_set> taken;
+  if (int rc = take_free_workset(ctx, owner, true, taken)) return rc;
+  const ticket_set& t = *taken;
+  device_inputs in; in.scalars = d_scalars_le; in.idx = static_cast<const uint32_t*>(d_idx);
+  if (int rc = pull_for_ticket(ctx, t, owner, m, in)) return rc;
+  partial_req r; r.d_scalars = in.scalars; r.n = m; r.stream = t.ws.stream; r.whole = true; r.bases = bases; r.d_idx = in.idx;
+  if (int rc = enqueue_partial(ctx, t.d, t.ws, r)) return rc;
+  if (int rc = fetch_rows(ctx, t.ws, t.ws.stream)) return rc;
+  hand_out_ticket(ctx, t, ticket, bases);
   return 0;
 }
 
@@ -3532,10 +3524,8 @@ int te_msm_partial_wait(te_ctx* ctx, int workset) {
   workset_t& ws = ctx->devs[0].ws[workset];
   if (!ws.used) return 0;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
-  (void)collect_stage_ms(ctx, ctx->devs[0], ws);     // stage times of that launch sequence, when it was profiled (te_msm_stage_ms)
-  note_entries(ctx, ws);
-  if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, "final carry is 1: a scalar does not fit the signed window decomposition");
-  return 0;
+  (void)collect_stage_ms(ctx, ctx->devs[0], ws);     // stage times of that launch sequence, when it was profiled (te_msm_stage_ms), whatever its status
+  return settle_status(ctx, ws);
 }
 
 int te_msm_finalize(te_ctx* ctx, const uint8_t* partials, int window_bits, int num_windows, uint8_t out_xy_le[64]) {
@@ -3546,9 +3536,8 @@ int te_msm_finalize(te_ctx* ctx, const uint8_t* partials, int window_bits, int n
   int bucket_bits = ctx->opt_signed ? window_bits - 1 : window_bits;
   if (ws.used) {
     HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
-    if (*ws.h_err) return set_err(ctx, TE_MSM_ESCALAR, "final carry is 1: a scalar does not fit the signed window decomposition");
+    if (int rc = settle_status(ctx, ws, false)) return rc;
     (void)collect_stage_ms(ctx, d, ws);
-    note_entries(ctx, ws);
     // the rows were produced under ws.plan: its digit form decides, not an option changed since
     if (window_bits != ws.plan.c || num_windows != ws.plan.W)
       return set_err(ctx, TE_MSM_ESTATE, "te_msm_finalize: window_bits / num_windows differ from the plan of the last te_msm_partial_device call (use te_msm_finalize_host_ex for rows produced elsewhere)");
