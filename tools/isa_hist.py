@@ -21,6 +21,10 @@ COST = {"v_mad_u64_u32": 4.49, "v_add_u32": 2.62, "v_sub_u32": 2.62, "v_subrev_u
         "v_bitop3_b32": 2.71, "v_not_b32": 2.46, "v_sad_u32": 4.31}
 
 
+# v_mad_u64_u32 of one addition in k_accumulate's per-point loop, by the kernel's mangled template arguments (products x mads per product)
+MADS_PER_ADDITION = (("k_accumulateILi9ELi0", 7 * 153), ("k_accumulateILi14ELi0", 8 * 364), ("k_accumulateILi14ELi1", 7 * 364))
+
+
 def kernel_body(lines, name):
     start = None
     for i, l in enumerate(lines):
@@ -51,7 +55,7 @@ def sources_sha():
     return h.hexdigest()[:16]
 
 
-def analyse(path, name, loop_only, quiet=False):
+def analyse(path, name, loop_only, quiet=False, mads_per_addition=None):
     lines = open(path).read().split("\n")
     body = kernel_body(lines, name)
     # instructions with their label context
@@ -88,16 +92,28 @@ def analyse(path, name, loop_only, quiet=False):
     valu = {k: v for k, v in ops.items() if k.startswith("v_")}
     cyc = sum(COST.get(k, 4.3) * v for k, v in valu.items())
     if quiet:
-        return {"valu_issue_cycles": round(cyc, 1), "valu_instructions": sum(valu.values()), "mads": ops.get("v_mad_u64_u32", 0),
-                "instructions": total, "s_nop": ops.get("s_nop", 0),
-                "note": "%d v_mad_u64_u32 (%.2f clk each) + %d other VALU instructions per 64 accumulated points (tools/isa_hist.py on the built listing)"
-                        % (ops.get("v_mad_u64_u32", 0), COST["v_mad_u64_u32"], sum(valu.values()) - ops.get("v_mad_u64_u32", 0))}
+        # the per-point loop adds two entries per pass (two named records, kernels.hip.hpp): figures are per 64 accumulated points,
+        # i.e. per addition of a wave, whatever the unroll
+        per = max(1, round(ops.get("v_mad_u64_u32", 0) / mads_per_addition)) if mads_per_addition else 1
+        nv, nm = sum(valu.values()) / per, ops.get("v_mad_u64_u32", 0) / per
+        fmt = lambda x: int(x) if float(x).is_integer() else round(x, 1)
+        return {"valu_issue_cycles": round(cyc / per, 1), "valu_instructions": fmt(nv), "mads": fmt(nm),
+                "instructions": fmt(total / per), "s_nop": fmt(ops.get("s_nop", 0) / per), "additions_per_pass": per,
+                "note": "%s v_mad_u64_u32 (%.2f clk each) + %s other VALU instructions per 64 accumulated points (tools/isa_hist.py on the built listing)"
+                        % (fmt(nm), COST["v_mad_u64_u32"], fmt(nv - nm))}
     print("kernel %s: %s, %d instructions (%d VALU, %d SALU, %d memory, %d other)" % (
         name, "hottest loop" if loop_only else "whole kernel", total, sum(valu.values()),
         sum(v for k, v in ops.items() if k.startswith("s_") and not k.startswith(("s_waitcnt", "s_nop", "s_cbranch", "s_branch"))),
         sum(v for k, v in ops.items() if k.startswith(("global_", "flat_", "buffer_", "ds_", "scratch_"))),
         sum(v for k, v in ops.items() if k.startswith(("s_waitcnt", "s_nop", "s_cbranch", "s_branch")))))
     print("estimated VALU issue: %.0f cycles per wave pass (mads %.0f)" % (cyc, COST["v_mad_u64_u32"] * ops.get("v_mad_u64_u32", 0)))
+    if loop_only and mads_per_addition is None:
+        mads_per_addition = next((m for key, m in MADS_PER_ADDITION if key in name or name in key), None)
+    if loop_only and mads_per_addition:
+        # the counts below are per PASS of the loop; a pass may add several entries (k_accumulate: two), --json reports per addition
+        per = max(1, round(ops.get("v_mad_u64_u32", 0) / mads_per_addition))
+        print("a pass holds %d addition(s): per addition (64 accumulated points) %.1f VALU instructions, %.1f mads, %.0f VALU issue cycles" % (
+            per, sum(valu.values()) / per, ops.get("v_mad_u64_u32", 0) / per, cyc / per))
     for k, v in sorted(ops.items(), key=lambda kv: -kv[1]):
         print("  %-24s %6d  %5.1f %%%s" % (k, v, 100.0 * v / total, ("   ~%.2f cyc" % COST[k]) if k in COST else ""))
 
@@ -108,10 +124,10 @@ def main():
         import json
         path, outp = sys.argv[1], sys.argv[sys.argv.index("--json") + 1]
         j = {"listing": path, "kernel_sources_sha": sources_sha(),
-             "k_accumulate<9>": analyse(path, "k_accumulateILi9ELi0", True, quiet=True),
-             "k_accumulate<14>": analyse(path, "k_accumulateILi14ELi0", True, quiet=True),
+             "k_accumulate<9>": analyse(path, MADS_PER_ADDITION[0][0], True, quiet=True, mads_per_addition=MADS_PER_ADDITION[0][1]),
+             "k_accumulate<14>": analyse(path, MADS_PER_ADDITION[1][0], True, quiet=True, mads_per_addition=MADS_PER_ADDITION[1][1]),
              # round 6: BLS12-377 over BOUND bases -- affine records, 7 products per gathered point (k_accumulate<14, 1>)
-             "k_accumulate<14,affine>": analyse(path, "k_accumulateILi14ELi1", True, quiet=True)}
+             "k_accumulate<14,affine>": analyse(path, MADS_PER_ADDITION[2][0], True, quiet=True, mads_per_addition=MADS_PER_ADDITION[2][1])}
         json.dump(j, open(outp, "w"), indent=1)
         print(json.dumps(j, indent=1))
         return

@@ -165,7 +165,8 @@ TE_HD ete_t<14> ete_madd(const ete_t<14>& a, const pnt_aff377& b) {
 // neutral element + b without the products whose result is known: with (X1 : Y1 : Z1 : T1) = (0 : 1 : 1 : 0) the mixed addition
 // has A' = hm, B' = hp, C' = 0, D' = z2, i.e. (X3, Y3, T3, Z3) = (E z2, H z2, E H, z2^2) with E = hp - hm, H = hp + hm: three
 // products for an affine record (z2 = 1: E and H only pass through a product by one to become class N below 2p), four for a
-// projective one, instead of 7 / 8.  Every segment of k_accumulate starts with this step (one in ~31 additions).
+// projective one, instead of 7 / 8.  k_accumulate starts a segment of ONE entry with this step, and every segment of projective
+// records (ete_from_pair below); k_fb_ext_from_recs converts whole point sets with it.
 TE_HD ete ete_from_pnt(const pnt& b) {
   const fp one = fp_R1();
   const fp E = fp_sub<2>(b.hp, b.hm), H = fp_add(b.hp, b.hm);
@@ -196,6 +197,46 @@ TE_HD ete_t<14> ete_from_pnt(const pnt_aff377& b) {          // z2 = 1: (E, H, E
   r.x = o[0]; r.y = o[1]; r.t = o[2]; r.z = one;
   return r;
 }
+
+// a + b of two RECORDS: the first two entries of a segment of k_accumulate, in 1 + 7 products instead of the 3 + 7 of
+// ete_madd(ete_from_pnt(a), b).  ete_from_pnt's X1 = E 1 and Y1 = H 1 (E = hp1 - hm1, H = hp1 + hm1) are products by one whose only
+// purpose is to bring E and H into class N for the next addition's Y1 - X1 and Y1 + X1 -- which are H - E = 2 hm1 and H + E = 2 hp1
+// of the record itself.  So with T1 = E H (the one real product of the conversion) and Z1 = 1 the mixed addition opens with
+//   A' = (2 hm1) hm2,   B' = (2 hp1) hp2,   C' = T1 dt2
+// and closes as ete_madd does with a.z = 1: F = 1 + C', G = 1 - C'.  Unified and complete like ete_madd (b = a, b = -a and the
+// neutral element as either operand are ordinary inputs); a's dt is not used.  The result is congruent mod p, coordinate by
+// coordinate, to ete_madd(ete_from_pnt(a), b).
+// Limb classes (N = 9): E = fp_sub<2>(hp1, hm1) is D (hm1 is a record field: class N, value < 1.1p < 2p), H is S, T1 = H x E is S x D
+// (the pairing of pnt_from_affine_raw); 2 hm1 and 2 hp1 are S and meet the class-N hm2, hp2; T1 (N) meets dt2 (N, or limbs < 2^30.6
+// when b is negated); 1 is class N, so F is S and G is D as in ete_madd, and ete_close sees what it sees there.  Output: class N.
+// Values: E < 3.1p, H < 2.2p, T1 < 1.02p; 2 hm1, 2 hp1 < 2.2p; A', B', C' < 1.02p; E3, G < 3.1p, H3, F < 2.1p; outputs < 1.02p.
+TE_HD ete ete_from_pair(const pnt& a, const pnt& b) {
+  const fp one = fp_R1();
+  const fp T1 = mont_mul(fp_add(a.hp, a.hm), fp_sub<2>(a.hp, a.hm));
+  const fp in1[3] = {fp_add(a.hm, a.hm), fp_add(a.hp, a.hp), T1}, in2[3] = {b.hm, b.hp, b.dt};
+  fp abc[3];
+  mont_mul_x<3>(in1, in2, abc);
+  const fp &A = abc[0], &B = abc[1], &Cn = abc[2];
+  return ete_close<9>(fp_sub<2>(B, A), fp_add(B, A), fp_add(one, Cn), fp_sub<2>(one, Cn));
+}
+// The same for the affine BLS12-377 record under the 14-limb rule (one operand of every product normalised): E is normalised before
+// it meets H (as in ete_from_pnt); the second record's fields are class N (a negated dt, limbs < 2^30.6, meets T1, class N) and meet
+// the sums 2 hm1, 2 hp1 (limbs < 2^30); ete_close normalises E3 and G.  Values as above with q for p.
+TE_HD ete_t<14> ete_from_pair(const pnt_aff377& a, const pnt_aff377& b) {
+  const fel<14> one = fe_one<14>();
+  const fel<14> T1 = fe_mul(fe_add(a.hp, a.hm), fe_norm(fe_sub<2>(a.hp, a.hm)));
+  const fel<14> in1[3] = {fe_add(a.hm, a.hm), fe_add(a.hp, a.hp), T1}, in2[3] = {b.hm, b.hp, b.dt};
+  fel<14> p[3];
+  fe_mul_x<3>(in1, in2, p);
+  const fel<14> &A = p[0], &B = p[1], &Cn = p[2];
+  return ete_close<14>(fe_sub<2>(B, A), fe_add(B, A), fe_add(one, Cn), fe_sub<2>(one, Cn));
+}
+// The projective BLS12-377 record keeps the rule it had, 4 + 8 products.  With z1 != 1 the shortcut does not exist: Y1 - X1 of the
+// converted point is 2 hm1 z1, a product in its own right, and forming the addition from the two records directly (A' = hm1 hm2,
+// B' = hp1 hp2, D' = z1 z2) leaves C' = d T1 T2 to be had from dt1 dt2 = d^2 T1 T2 -- a product by 1/d, and one by 1/2 to put D' on
+// the records' common scale: 6 + 4 against 12, for a record kind that only per-call BLS12-377 MSMs use (bound point sets gather the
+// affine record above), with two constants and a limb-bound analysis of their own.  Not taken.
+TE_HD ete_t<14> ete_from_pair(const pnt_t<14>& a, const pnt_t<14>& b) { return ete_madd(ete_from_pnt(a), b); }
 
 // Full addition a + b of two accumulators (add-2008-hwcd-3 shape, k = 2d), 9 products.
 // One operand of the opening product of two differences and F are normalised, so that no product sees two wide operands:

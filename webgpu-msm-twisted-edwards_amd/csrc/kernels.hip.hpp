@@ -955,9 +955,11 @@ static_assert(sizeof(rec_slot<9>) == sizeof(pnt_slot) && sizeof(rec_slot<14>) ==
 
 // ------------------------------------------------------------------------------------------------
 // K3: bucket accumulation, one thread per segment, scheduled through order[] (or natural order when
-// order == nullptr).  The next record is fetched while the current addition runs; the first entry of a segment is not
-// added to the neutral element but converted (ete_from_pnt, 3 products instead of 7).  A bucket that is a single
-// segment is written straight to buckets[]; parts of a split bucket go to seg_out[] for k_seg_combine*.
+// order == nullptr).  A segment's first two entries are added as records (ete_from_pair: 1 + 7 products, where converting the first
+// and adding the second took 3 + 7); a segment of one entry is converted (ete_from_pnt, 3 products); a segment that continues
+// a bucket (a later piece of a host-buffer call) adds all its entries to the bucket's value.  Behind the start the loop consumes
+// two entries per pass over two named records: each is fetched while the other is added, and none is copied between registers.
+// A bucket that is a single segment is written straight to buckets[]; parts of a split bucket go to seg_out[] for k_seg_combine*.
 // (A variant that fused level 2 of the sort into this kernel -- one block per 256 buckets, lists consumed
 // straight from LDS -- was measured at 2.8 ms against 1.4 ms: block-granular scheduling leaves < 1 wave per
 // SIMD resident on average (SQ_WAVE_CYCLES / GRBM_GUI_ACTIVE = 0.78), far too few to hide gather latency.)
@@ -1052,24 +1054,25 @@ struct __attribute__((aligned(4))) idx4 { uint32_t v[4]; };      // 16 bytes at 
 #define TE_CLK_SLOTS 64u       // copies of k_accumulate's four profiling words (64-bit each), see the kernel
 #define TE_IDX_STRIP 16u       // sorted indices a lane fetches at a time (k_accumulate); d_sorted is padded by as many words
 // registers: N = 9 fits four waves per SIMD in 128 VGPRs (six of them spilled) and ran that way in rounds 1-3; round 4 asks for
-// THREE (133 VGPRs, nothing spilled): the VALU is as busy with three waves per SIMD (0.93-0.94 of the issue estimate either way),
+// THREE: the VALU is as busy with three waves per SIMD (0.93-0.94 of the issue estimate either way),
 // and boxes whose clock sags under this kernel sustain a higher one with fewer waves in flight -- 2.11-2.19 GHz against 2.00-2.07,
 // the kernel alone 0.77-0.79 ms against 0.82-0.85, +2-4 % MSM/s there, nothing lost on boxes that hold 2.15 GHz anyway
-// (profiles/r04_accumulate_occupancy_experiment.txt).  N = 14 holds 56 + 2 x 56 words of points alone: two waves
+// (profiles/r04_accumulate_occupancy_experiment.txt).  N = 14 holds 56 + 2 x 56 words of points alone: two waves.
+// The count is stated as BOTH bounds of amdgpu_waves_per_eu, not as __launch_bounds__' minimum alone: with two named records the
+// N = 9 loop fits 126 VGPRs, the scheduler then aims at four waves -- it sinks every record load to its first use to stay below
+// 128 -- and the hardware would run four.  With the upper bound it allocates 138 (room up to 168), keeps a record's seven loads
+// together at the head of the addition that hides them, and the kernel launches three waves per SIMD as before
+// (profiles/bucket_start_isa.txt).
 template <int N, int RK = 0>
-__global__ void __launch_bounds__(256, N == 9 ? 3 : 2) k_accumulate(const typename rec_kind<N, RK>::slot* __restrict__ recs, const uint32_t* __restrict__ sorted,
+__global__ void __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves_per_eu(N == 9 ? 3 : 2, N == 9 ? 3 : 2))) k_accumulate(const typename rec_kind<N, RK>::slot* __restrict__ recs, const uint32_t* __restrict__ sorted,
                                                     const uint32_t* __restrict__ bucket_start, const uint32_t* __restrict__ bucket_count,
                                                     const uint32_t* __restrict__ seg_base, const uint32_t* __restrict__ seg_bucket,
                                                     const uint32_t* __restrict__ seg_lenv, const uint32_t* __restrict__ order,
                                                     const uint32_t* __restrict__ num_segments, ete_t<N>* __restrict__ buckets,
                                                     ete_t<N>* __restrict__ seg_out, uint32_t n, uint32_t logB, uint32_t seg_len, uint32_t ids, uint32_t onto,
                                                     uint32_t win_per_msm, batch_slabs slabs, unsigned long long* __restrict__ clk) {
-  __shared__ uint32_t idx_strip[256 * TE_IDX_STRIP];
+  __shared__ __attribute__((aligned(16))) uint32_t idx_strip[256 * TE_IDX_STRIP];     // a lane's strip is read 8 bytes at a time below
   using RT = rec_kind<N, RK>; using P = typename RT::pnt;
-#if defined(TE_ACC_TWO_WAVES)
-  // A/B builds only: naming a high register makes the kernel's VGPR allocation 176, i.e. two waves per SIMD without touching LDS
-  if constexpr (N == 9) asm volatile("" ::: "v175");
-#endif
   // profiling: ~clock of the first wave in and clock of the last wave out, by atomic max on zeroed words -- the kernel's
   // own duration on the device, which an event pair around the launch overstates when other streams' kernels hold the
   // CUs (te_msm_stage_ms "accumulate_on_device"); per-wave shader-clock and wall-clock ticks give the core clock it ran at.
@@ -1100,14 +1103,26 @@ __global__ void __launch_bounds__(256, N == 9 ? 3 : 2) k_accumulate(const typena
     const uint32_t last = cnt - 1u;
     uint32_t j0 = 0;
     uint32_t e = lst[0], e_n = lst[min(1u, last)];
+    const uint32_t e_2 = lst[min(2u, last)], e_3 = lst[min(3u, last)];
     P cur = RT::load(recs, e);
     if (!(onto && part == 0u)) {
-      // first entry: neutral element + P needs 3 (4) products, not 7 (8) -- except where the segment continues a bucket
+      // the segment starts a sum -- everywhere except where it continues a bucket: its first two entries are added as records
+      // (ete_from_pair: 1 + 7 products, not the 3 + 7 of a conversion and an addition), a single entry is converted (3 products)
       const P first = pnt_cneg(cur, (e >> 31) != 0u);
-      e = e_n; e_n = lst[min(2u, last)];
-      cur = RT::load(recs, e);
-      acc = ete_from_pnt(first);
-      j0 = 1;
+      if (cnt >= 2u) {
+        const P second = pnt_cneg(RT::load(recs, e_n), (e_n >> 31) != 0u);
+        e = e_2; e_n = e_3;
+        // entry 2 is in flight while the pair is added.  cnt = 2 has none and gathers entry 1 again (e_2 is clamped to `last`), as
+        // the tail below gathers the record at hand again where entry j+1 does not exist: seven loads that hit the cache and are not
+        // used, once per segment at most.  Under `if (cnt > 2)` / `if (two)` the loads join a path with seven outstanding and one
+        // with none, and the listing pays for it: 138 -> 166 VGPRs for N = 9, two spilled registers in k_accumulate<14, 0>
+        cur = RT::load(recs, e);
+        acc = ete_from_pair(first, second);
+        j0 = 2;
+      } else {
+        acc = ete_from_pnt(first);
+        j0 = 1;                                            // = cnt: the loop below does not run
+      }
     }
     // Indices come through a private LDS strip, TE_IDX_STRIP at a time: a lane's list is 4 B per addition, and between two
     // of its accesses the wave front has pulled megabytes of records through the L2 -- read one by one, every index access
@@ -1125,15 +1140,33 @@ __global__ void __launch_bounds__(256, N == 9 ? 3 : 2) k_accumulate(const typena
       }
     };
     if (((j0 + 2u) & (TE_IDX_STRIP - 1u)) != 0u) refill((j0 + 2u) & ~(TE_IDX_STRIP - 1u));
-    for (uint32_t j = j0; j < cnt; j++) {
-      const uint32_t e_cur = e;
-      P nxt = cur;
+    // Two additions per pass over two named records, each loaded while the other is added: a single `cur` / `nxt` pair had to be
+    // rotated (cur = nxt) behind every addition, 26 v_mov_b64 per 64 points.  A pass runs while entry j+2 exists, so both of its
+    // loads are unconditional: a load under a lane mask joins a path with seven loads outstanding and one with none, and the wait
+    // for the OTHER record behind that join can only be vmcnt(0) -- the latency of the load just issued, exposed in every pass.
+    // j is even wherever a pass runs (j0 is 0 or 2; j0 = 1 comes with cnt = 1), so only its first half can meet a strip boundary,
+    // and the indices of entries j+2 and j+3 sit side by side in the strip: one 8-byte LDS read per pass.
+    P rec_b;
+    uint32_t j = j0;
+    for (; j + 2u < cnt; j += 2u) {
       const uint32_t pn = j + 2u;
       if ((pn & (TE_IDX_STRIP - 1u)) == 0u) refill(pn);
-      const uint32_t e_nn = strip[pn & (TE_IDX_STRIP - 1u)];
-      if (j + 1 < cnt) { e = e_n; nxt = RT::load(recs, e); }
-      acc = ete_madd(acc, pnt_cneg(cur, (e_cur >> 31) != 0u));
-      cur = nxt; e_n = e_nn;
+      const uint2 e_nn = *reinterpret_cast<const uint2*>(strip + (pn & (TE_IDX_STRIP - 1u)));
+      rec_b = RT::load(recs, e_n);
+      acc = ete_madd(acc, pnt_cneg(cur, (e >> 31) != 0u));
+      // nothing of the second addition moves in front of this line: left free, the scheduler starts its sign selection ~300
+      // instructions before the first addition's last product, and the wait for rec_b with it (1 065 instead of 1 420 instructions
+      // behind the loads)
+      __builtin_amdgcn_sched_barrier(0);
+      cur = RT::load(recs, e_nn.x);
+      acc = ete_madd(acc, pnt_cneg(rec_b, (e_n >> 31) != 0u));
+      e = e_nn.x; e_n = e_nn.y;
+    }
+    if (j < cnt) {                                         // the last one or two entries; `cur` holds entry j
+      const bool two = j + 1u < cnt;
+      rec_b = RT::load(recs, two ? e_n : e);               // (no entry j+1: the record at hand again, not used -- see the pair start)
+      acc = ete_madd(acc, pnt_cneg(cur, (e >> 31) != 0u));
+      if (two) acc = ete_madd(acc, pnt_cneg(rec_b, (e_n >> 31) != 0u));
     }
   }
   const bool whole = bucket_count[g] <= seg_len;
