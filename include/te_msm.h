@@ -13,6 +13,10 @@
  *   scalars: n x 32 B little-endian integers (< p < 2^253; signed digits accept anything below 2^254 - 2^240 at every
  *            window size -- TE_MSM_ESCALAR above --, unsigned digits any 256-bit value)
  *   result : x[32 B LE] || y[32 B LE], canonical affine  ( == result.toAffine(), submission.ts:412 )
+ * A NATIVE PROVER'S FORM (arkworks, snarkVM: a field element is a = k * 2^256 mod m in four u64 limbs -- in memory a 32-byte little-endian
+ * integer -- six limbs and 2^384 for the BLS12-377 base field): options "scalars_montgomery" and "points_montgomery" below make the engine
+ * read exactly those bytes, the scalars on every MSM call and the points at te_msm_bind_points*.  Record sizes do not change; results are
+ * always canonical.
  *
  * All functions return 0 on success or a negative TE_MSM_E* code; te_msm_last_error() gives text.
  * A context is not thread-safe: serialise the calls on one context (the one exception is te_msm_ticket_wait).
@@ -346,6 +350,32 @@ int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_sca
 int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le);
 
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
+ *   "scalars_montgomery" 0 (default) = scalar records hold the integers themselves (the wire format above); 1 = every scalar record holds
+ *                   a = k * 2^256 mod m and the MSM uses k = a * 2^-256 mod m, where m is the scalar field of the curve in force:
+ *                     TE_MSM_CURVE_TE_BLS12      L = 2111115437357092606062206234695386632838870926408408195193685246394721360383
+ *                     TE_MSM_CURVE_BLS12_377_G1  r = 8444461749428370424248824938781546531375899335154063827935233455917409239041
+ *                   ANY 256-bit a is accepted and stands for its residue; the decoded k is canonical (< m), so under the option signed digits
+ *                   never return TE_MSM_ESCALAR on the Twisted-Edwards curve, and on BLS12-377 only for a non-zero byte 32..47 of a 48-byte
+ *                   record (the value is in bytes 0..31, as always).  The reduction runs where the scalars are first read, in the digit
+ *                   kernels (csrc/scalar_form.hpp: 8 rounds over 32-bit words, ~70 multiply-accumulates a scalar, in registers): no pass
+ *                   over the scalars of its own, nothing for the caller to convert.  Read when a call STARTS, by: te_msm_run[_device],
+ *                   te_msm_submit / _async / _device, te_msm_run_scalars[_device], te_msm_submit_scalars[_device],
+ *                   te_msm_run_scalars_batch[_device], te_msm_run_scalars_indexed[_device], te_msm_submit_scalars_indexed[_device],
+ *                   te_msm_partial_device[_batch]; MSMs over a "bind_fixed_base" set included, with their fallback to the ordinary
+ *                   windows.  A ticket keeps the form it was submitted with: changing the option affects later calls only.
+ *                   te_msm_mul* and te_msm_run_x take canonical scalars only: with the option set they return TE_MSM_EINVAL and leave the
+ *                   output untouched (a silent canonical reading would be a wrong answer).
+ *                   COST: not measured yet.  tools/montgomery_inputs.py times the option on against off and the CPU pass it takes off
+ *                   the caller; until its output is filed, take the option as a convenience of unknown cost.
+ *   "points_montgomery" 0 (default); 1 = te_msm_bind_points[_device] read coordinates as Montgomery residues: x * 2^256 mod p in 32 bytes
+ *                   (Twisted-Edwards), x * 2^384 mod q in 48 bytes (BLS12-377).  Read at BIND time, like "bind_affine": the conversion
+ *                   kernels take another constant in their first products, no more arithmetic; the records, and every MSM over the set
+ *                   (ordinary and fixed-base), are identical to those of the set bound from canonical coordinates.  With "check_points" = 0
+ *                   any 256- / 384-bit value stands for its residue, as above.  "check_points" at the bind, and te_msm_check_points[_device]
+ *                   while the option is set, decode the same way: "canonical" stays "the STORED value is below p / q", the curve equation
+ *                   and the subgroup are checked on the decoded coordinates.  The per-call point paths (te_msm_run*, te_msm_submit*,
+ *                   te_msm_partial_device*, te_msm_mul*) do NOT read this option -- their points, and their "check_points", stay canonical --
+ *                   and te_msm_bind_points_x keeps its own x-only format.
  *   "window_bits"   c in [4,16]; 0 = choose from n (default)
  *   "signed_digits" 1 = signed window digits, 2^(c-1) buckets per window (default; the reference's shipped behaviour,
  *                   miscellaneous/utils.ts:52-95); 0 = plain unsigned windows, 2^c buckets (utils.ts:34-50): same

@@ -352,21 +352,40 @@ class MsmContext:
         self._check(self._L.te_msm_ticket_wait(self._h, ticket))
 
     # ---- resident bases: points bound once, scalars per call (te_msm_bind_points ...)
-    def bind_points(self, points: bytes) -> "Bases":
+    def _bind(self, montgomery: bool, call) -> ctypes.c_void_p:
+        """One bind call.  montgomery=True: option "points_montgomery" (read at bind time) is 1 for that call and put back afterwards.
+        False asks for nothing: the option stays as set_option left it, so the keyword can switch the form on for one set but not off
+        on a context whose option is 1 -- set_option("points_montgomery", 0) does that."""
+        h = ctypes.c_void_p()
+        if not montgomery:
+            self._check(call(ctypes.byref(h)))
+            return h
+        before = self.get_option("points_montgomery")
+        self.set_option("points_montgomery", 1)
+        try:
+            self._check(call(ctypes.byref(h)))
+        finally:
+            self.set_option("points_montgomery", before)
+        return h
+
+    def bind_points(self, points: bytes, montgomery: bool = False) -> "Bases":
         """Uploads the points once, converts them to records on every device of the context and keeps only the records
         (te_msm_bind_points).  The harness hands the same point buffer to compute_msm for every run of a size
-        (submission/miscellaneous/full_benchmarks.ts:63-68,100-105)."""
+        (submission/miscellaneous/full_benchmarks.ts:63-68,100-105).
+        montgomery=True: the coordinates are a native prover's Montgomery residues (x * 2^256 mod p in 32 bytes; BLS12-377: x * 2^384
+        mod q in 48) -- option "points_montgomery" = 1 for this call; False leaves the option as set_option left it.  The records, and every
+        MSM over the set, are the same either way.  (The scalars' counterpart is the option "scalars_montgomery" alone: set_option.)"""
         pb = self._sizes[0]
         n = len(points) // pb
         if len(points) != pb * n:
             raise MsmError(-1, f"points must be {pb}*n bytes")
-        h = ctypes.c_void_p()
-        self._check(self._L.te_msm_bind_points(self._h, bytes(points), n, ctypes.byref(h)))
+        points = bytes(points)
+        h = self._bind(montgomery, lambda out: self._L.te_msm_bind_points(self._h, points, n, out))
         return Bases(self, h, n, self.curve)
 
-    def bind_points_device(self, d_points: int, n: int) -> "Bases":
-        h = ctypes.c_void_p()
-        self._check(self._L.te_msm_bind_points_device(self._h, d_points, n, ctypes.byref(h)))
+    def bind_points_device(self, d_points: int, n: int, montgomery: bool = False) -> "Bases":
+        """te_msm_bind_points_device; montgomery: as bind_points"""
+        h = self._bind(montgomery, lambda out: self._L.te_msm_bind_points_device(self._h, d_points, n, out))
         return Bases(self, h, n, self.curve)
 
     # ---- x-only points (include/te_msm.h "x-only points"): y recovered on the device; a bad x raises MsmError(EPOINT) with .index / .reason

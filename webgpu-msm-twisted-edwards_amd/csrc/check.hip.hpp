@@ -75,21 +75,24 @@ TE_HD bool fe_is_zero(const te377::fq& v) {
 }
 
 // ---- Twisted-Edwards BLS12: 16 words, x = w[0..7], y = w[8..15] --------------------------------------------------------------
-// coordinates in Montgomery form (any 256-bit input: x R^2 / R < 1.04 p)
-TE_HD void te_coords(const uint32_t (&w)[16], fp& X, fp& Y) {
+// coordinates in Montgomery form (any 256-bit input: x R^2 / R < 1.04 p).  MONT (option "points_montgomery"): the words hold x 2^256
+// mod p, decoded by the constant R^2 / 2^256 -- also a canonical residue: the same bound
+template <bool MONT = false> TE_HD void te_coords(const uint32_t (&w)[16], fp& X, fp& Y) {
   uint32_t xw[8], yw[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) { xw[i] = w[i]; yw[i] = w[8 + i]; }
-  const fp a[2] = {fp_from_words32(xw), fp_from_words32(yw)}, b[2] = {fp_R2(), fp_R2()};
+  const fp k = MONT ? fp_R2_A() : fp_R2();
+  const fp a[2] = {fp_from_words32(xw), fp_from_words32(yw)}, b[2] = {k, k};
   fp o[2];
   mont_mul_x<2>(a, b, o);
   X = o[0]; Y = o[1];
 }
-// 0, TE_MSM_POINT_NONCANONICAL (1) or TE_MSM_POINT_OFF_CURVE (2)
-TE_HD int check_form_te(const uint32_t (&w)[16]) {
+// 0, TE_MSM_POINT_NONCANONICAL (1) or TE_MSM_POINT_OFF_CURVE (2).  MONT: "canonical" stays "the stored value is below p"; the curve
+// equation is checked on the decoded coordinates
+template <bool MONT = false> TE_HD int check_form_te(const uint32_t (&w)[16]) {
   const bool canon = words_lt<8>(w, P_W32) && words_lt<8>(w + 8, P_W32);
   fp X, Y;
-  te_coords(w, X, Y);
+  te_coords<MONT>(w, X, Y);
   const fp a1[2] = {X, Y};
   fp sq[2];
   mont_mul_x<2>(a1, a1, sq);                                       // x^2, y^2
@@ -121,31 +124,33 @@ TE_HD ete mul_order_te(const fp& X, const fp& Y, const naf_t& k) {
   return acc;
 }
 // [L] P = O on the whole curve (ete_add is complete there: a square, d not)
-TE_HD bool in_subgroup_te(const uint32_t (&w)[16], const naf_t& k) {
+template <bool MONT = false> TE_HD bool in_subgroup_te(const uint32_t (&w)[16], const naf_t& k) {
   fp X, Y;
-  te_coords(w, X, Y);
+  te_coords<MONT>(w, X, Y);
   const ete acc = mul_order_te(X, Y, k);
   // the neutral element (0 : Z : Z : 0), Z != 0
   return fe_is_zero(acc.x) && fe_is_zero(fp_sub<2>(acc.y, acc.z)) && !fe_is_zero(acc.z);
 }
 
 // ---- BLS12-377 G1: 24 words, x = w[0..11], y = w[12..23] ----------------------------------------------------------------------
-TE_HD void c377_coords(const uint32_t (&w)[24], te377::fq& X, te377::fq& Y, te377::fq& sx) {
+// MONT (option "points_montgomery"): the words hold x 2^384 mod q; R^2 / 2^384 and s R^2 / 2^384 decode them
+template <bool MONT = false> TE_HD void c377_coords(const uint32_t (&w)[24], te377::fq& X, te377::fq& Y, te377::fq& sx) {
   using namespace te377;
   uint32_t xw[12], yw[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) { xw[i] = w[i]; yw[i] = w[12 + i]; }
   const fq xl = fq_from_words32(xw);
-  const fq a[3] = {xl, fq_from_words32(yw), xl}, b[3] = {fq_R2(), fq_R2(), fq_S_R2()};
+  const fq k = MONT ? fq_R2_A() : fq_R2();
+  const fq a[3] = {xl, fq_from_words32(yw), xl}, b[3] = {k, k, MONT ? fq_S_R2_A() : fq_S_R2()};
   fq o[3];
   fe_mul_x<3>(a, b, o);
   X = o[0]; Y = o[1]; sx = o[2];                                   // x, y, s x   (Montgomery form, as in pnt_from_sw377)
 }
-TE_HD int check_form_377(const uint32_t (&w)[24]) {
+template <bool MONT = false> TE_HD int check_form_377(const uint32_t (&w)[24]) {
   using namespace te377;
   const bool canon = words_lt<12>(w, Q_W32) && words_lt<12>(w + 12, Q_W32);
   fq X, Y, sx;
-  c377_coords(w, X, Y, sx);
+  c377_coords<MONT>(w, X, Y, sx);
   const fq a1[2] = {X, Y};
   fq sq[2];
   fe_mul_x<2>(a1, a1, sq);                                       // x^2, y^2
@@ -222,10 +227,10 @@ TE_HD sw377 sw377_dbl(const sw377& P) {
   return r;
 }
 // [r] P = O on y^2 = x^3 + 1 (never in the engine's twisted-Edwards form: see the top of this file)
-TE_HD bool in_subgroup_377(const uint32_t (&w)[24], const naf_t& k) {
+template <bool MONT = false> TE_HD bool in_subgroup_377(const uint32_t (&w)[24], const naf_t& k) {
   using namespace te377;
   fq X, Y, sx;
-  c377_coords(w, X, Y, sx);
+  c377_coords<MONT>(w, X, Y, sx);
   sw377 P; P.x = X; P.y = Y; P.z = fq_R1();
   sw377 N = P; N.y = te377::mont_mul(fq_neg<4>(Y), fq_R1());       // -P = (x, -y, 1)
   sw377 acc = P;
@@ -245,7 +250,7 @@ TE_HD void check_decode(uint64_t code, uint64_t n, int64_t* index, int* reason) 
 
 #if defined(__HIPCC__)
 // one lane per point; every lane of a launch runs the same instructions (no early exit: a wave's chain is uniform)
-template <int CURVE> __global__ __launch_bounds__(256) void k_check_form(const uint4* __restrict__ pts, uint32_t n, unsigned long long* word) {
+template <int CURVE, bool MONT = false> __global__ __launch_bounds__(256) void k_check_form(const uint4* __restrict__ pts, uint32_t n, unsigned long long* word) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   constexpr int Q4 = CURVE == 1 ? 6 : 4;                            // 16-byte words of one point (96 / 64 bytes)
@@ -253,11 +258,11 @@ template <int CURVE> __global__ __launch_bounds__(256) void k_check_form(const u
 #pragma unroll
   for (int k = 0; k < Q4; k++) { const uint4 v = pts[(size_t)i * Q4 + k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
   int reason;
-  if constexpr (CURVE == 1) reason = check_form_377(w);
-  else reason = check_form_te(w);
+  if constexpr (CURVE == 1) reason = check_form_377<MONT>(w);
+  else reason = check_form_te<MONT>(w);
   if (reason) atomicMax(word, (unsigned long long)check_code(n, i, reason));
 }
-template <int CURVE> __global__ __launch_bounds__(256) void k_check_subgroup(const uint4* __restrict__ pts, uint32_t n, unsigned long long* word, naf_t k) {
+template <int CURVE, bool MONT = false> __global__ __launch_bounds__(256) void k_check_subgroup(const uint4* __restrict__ pts, uint32_t n, unsigned long long* word, naf_t k) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   constexpr int Q4 = CURVE == 1 ? 6 : 4;
@@ -265,8 +270,8 @@ template <int CURVE> __global__ __launch_bounds__(256) void k_check_subgroup(con
 #pragma unroll
   for (int j = 0; j < Q4; j++) { const uint4 v = pts[(size_t)i * Q4 + j]; w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w; }
   bool in;
-  if constexpr (CURVE == 1) in = in_subgroup_377(w, k);
-  else in = in_subgroup_te(w, k);
+  if constexpr (CURVE == 1) in = in_subgroup_377<MONT>(w, k);
+  else in = in_subgroup_te<MONT>(w, k);
   if (!in) atomicMax(word, (unsigned long long)check_code(n, i, 3));
 }
 #endif

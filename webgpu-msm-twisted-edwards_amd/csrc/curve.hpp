@@ -82,8 +82,13 @@ TE_HD pnt_aff377 pnt_cneg(const pnt_aff377& a, bool neg) {
 // The constant folds the conversion to Montgomery form and the halving into the first two products (16p > 2^256 keeps y - x
 // non-negative for non-canonical inputs).  Limb classes: hp + hm is S, hm - hp + 2p is D (S x D is exact, fp.hpp).  Values: hm, hp
 // < 1.07p; the third product is below 2.14p * 3.07p / R + p < 1.02p, and dt < 1.0001p.
-TE_HD pnt pnt_from_affine_raw(const fp& x, const fp& y) {
-  const fp a[2] = {fp_sub<16>(y, x), fp_add(y, x)}, b[2] = {fp_R2_HALF(), fp_R2_HALF()};
+// MONT (option "points_montgomery", bind time only): x and y are the caller's Montgomery residues x R_a, R_a = 2^256, again ANY 256-bit
+// value; the constant becomes R^2 / R_a / 2 and the products give the same (y -+ x) R / 2.  Every bound above carries over unchanged: they
+// use of the inputs only "below 2^256, limbs of class N" and of the constant only "a canonical residue (< p) in class N" -- both still
+// hold, so hm, hp < 1.07p as before and everything behind the first two products sees the same classes and ranges.
+template <bool MONT = false> TE_HD pnt pnt_from_affine_raw(const fp& x, const fp& y) {
+  const fp k = MONT ? fp_R2_HALF_A() : fp_R2_HALF();
+  const fp a[2] = {fp_sub<16>(y, x), fp_add(y, x)}, b[2] = {k, k};
   fp o[2];
   mont_mul_x<2>(a, b, o);
   pnt r;
@@ -99,9 +104,13 @@ TE_HD pnt pnt_from_affine_raw(const fp& x, const fp& y) {
 //   (X : Y : Z : T) = (a w : b y : y w : a b)   (X Y / Z = a b).
 //   record, times 2:  hm = Y - X,  hp = Y + X,  dt = -2 d T,  z = 2 Z.
 // Undefined (all-zero record, the neutral element's weight is lost) for y = 0 or w = 0: points of order 2 and 4, never in G1.
-TE_HD pnt_t<14> pnt_from_sw377(const fel<14>& x, const fel<14>& y) {
+// MONT (option "points_montgomery", bind time only): x and y are x R_a, R_a = 2^384 (any 384-bit value); the three constants of the first
+// products carry 1 / R_a and o1 is s x, y, f x in the engine's Montgomery form exactly as before.  The inputs are still "below 2^384, class
+// N" and the constants still canonical residues (< q) in class N, so o1 has the bounds it had; the constants added to o1 and the last
+// product's act on the engine's own Montgomery values and stay.
+template <bool MONT = false> TE_HD pnt_t<14> pnt_from_sw377(const fel<14>& x, const fel<14>& y) {
   using namespace te377;
-  const fq a1[3] = {x, y, x}, b1[3] = {fq_S_R2(), fq_R2(), fq_F_R2()};
+  const fq a1[3] = {x, y, x}, b1[3] = {MONT ? fq_S_R2_A() : fq_S_R2(), MONT ? fq_R2_A() : fq_R2(), MONT ? fq_F_R2_A() : fq_F_R2()};
   fq o1[3];
   fe_mul_x<3>(a1, b1, o1);                                   // s x, y, f x   (Montgomery form, class N)
   const fq w = fe_norm(fe_add(o1[0], fq_SP1_MONT())), bb = fe_add(o1[0], fq_SM1_MONT()), aa = fe_norm(fe_add(o1[2], fq_F_MONT()));

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "curve.hpp"
+#include "scalar_form.hpp"
 
 namespace te {
 
@@ -45,6 +46,9 @@ struct pnt_slot { uint4 q[8]; };
 // that both the per-record writes and the per-piece reads are conflict-free.
 // The first 256 threads of the block convert points [256 blk, 256 blk + 256) of one buffer; lds: 256 * 8 uint4 (32 KB).
 // Threads beyond 256 (the fused launch below has 512-thread blocks) only take part in the barriers.
+// MONT (te_msm_bind_points with option "points_montgomery"): the coordinates are x * 2^256 mod p -- another constant in the first products
+// (curve.hpp); the per-call conversions, fused or not, are the <false> instantiation.
+template <bool MONT = false>
 __device__ __forceinline__ void prep_points_block(uint32_t blk, uint4* __restrict__ lds, const uint4* __restrict__ pts, pnt_slot* __restrict__ recs, uint32_t n) {
   const uint32_t t = threadIdx.x, base = blk * 256u;
   const bool active = t < 256u;                          // whole waves: no divergence
@@ -64,7 +68,7 @@ __device__ __forceinline__ void prep_points_block(uint32_t blk, uint4* __restric
   if (active) {
     const uint32_t xw[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
     const uint32_t yw[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-    const pnt r = pnt_from_affine_raw(fp_from_words32(xw), fp_from_words32(yw));
+    const pnt r = pnt_from_affine_raw<MONT>(fp_from_words32(xw), fp_from_words32(yw));
     uint32_t w[32];
 #pragma unroll
     for (int j = 0; j < NL; j++) { w[j] = r.hm.v[j]; w[NL + j] = r.hp.v[j]; w[2 * NL + j] = r.dt.v[j]; }
@@ -84,10 +88,11 @@ __device__ __forceinline__ void prep_points_block(uint32_t blk, uint4* __restric
     }
   }
 }
+template <bool MONT = false>
 __global__ void __launch_bounds__(256) k_prep_points(batch_ptrs in, batch_slabs row_slab, pnt_slot* __restrict__ recs, uint32_t n) {
   __shared__ uint4 lds[256 * 8];                        // 32 KB: first the block's 256 points (16 KB), then its 256 records
   // grid row y converts point buffer y into record slab s = row_slab[y]: slots [s * n, (s + 1) * n)
-  prep_points_block(blockIdx.x, lds, in.p[blockIdx.y], recs + (size_t)row_slab.s[blockIdx.y] * n, n);
+  prep_points_block<MONT>(blockIdx.x, lds, in.p[blockIdx.y], recs + (size_t)row_slab.s[blockIdx.y] * n, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -122,7 +127,10 @@ __device__ __forceinline__ bool digit_bucket(uint32_t stored, uint32_t half, uin
 #endif
 // The body of k_digits and k_digits_ragged: the block's entries of MSM blockIdx.y, whose n scalars start at `scalars`; entries i >= n
 // (up to the row stride nst) are padding and get digit 0.  hist: the block's LDS histogram.
-template <int C>
+// FORM (scalar_form.hpp): what the records hold.  SCALAR_FORM_CANONICAL is the code of every build before the option "scalars_montgomery"
+// existed; the two Montgomery forms decode both scalars of a step in registers, between the load and the addition of `half` -- ~70
+// multiply-accumulates per scalar in a kernel that is bound by memory (one wave per SIMD: registers are no constraint).
+template <int C, int FORM>
 __device__ __forceinline__ void digits_block(const uint4* __restrict__ scalars, const uint32_t n, uint32_t* __restrict__ hist, uint16_t* __restrict__ digits,
                                              const digits_params& prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
   // MSM blockIdx.y of the launch sequence: its digit rows and level-1 counts [y * nw_local, (y + 1) * nw_local)
@@ -162,6 +170,17 @@ __device__ __forceinline__ void digits_block(const uint4* __restrict__ scalars, 
       bad |= (a2.x | a2.y | a2.z | a2.w | b2.x | b2.y | b2.z | b2.w) != 0u;
     }
     uint32_t s[2][10] = {{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, 0u, 0u}, {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, 0u, 0u}};
+    if constexpr (FORM != SCALAR_FORM_CANONICAL) {
+#pragma unroll
+      for (int t = 0; t < 2; t++) {
+        uint32_t k[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) k[j] = s[t][j];
+        scalar_from_montgomery<FORM>(k);
+#pragma unroll
+        for (int j = 0; j < 8; j++) s[t][j] = k[j];
+      }
+    }
 #pragma unroll
     for (int t = 0; t < 2; t++) {
       uint64_t c = 0;
@@ -210,11 +229,11 @@ __device__ __forceinline__ void digits_block(const uint4* __restrict__ scalars, 
   }
 }
 
-template <int C>
+template <int C, int FORM = SCALAR_FORM_CANONICAL>
 __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_ptrs in, uint16_t* __restrict__ digits,
                                                 digits_params prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
   __shared__ uint32_t hist[4096];                        // [local window][partition]: nw_local * P <= 4096 for every plan
-  digits_block<C>(in.p[blockIdx.y], prm.n, hist, digits, prm, err, counts1);      // every MSM of the sequence has prm.n scalars
+  digits_block<C, FORM>(in.p[blockIdx.y], prm.n, hist, digits, prm, err, counts1);      // every MSM of the sequence has prm.n scalars
 }
 
 // RAGGED SEQUENCES (te_msm_run_scalars_batch): up to TE_RAGGED_MAX MSMs of DIFFERENT lengths over prefixes of one bound point set.
@@ -224,12 +243,12 @@ __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_p
 // the kernel arguments (TE_RAGGED_MAX x 12 bytes): a separate kernel, so that k_digits (the headline path) keeps its code.
 #define TE_RAGGED_MAX 64
 struct ragged_tab { uint64_t off[TE_RAGGED_MAX]; uint32_t len[TE_RAGGED_MAX]; };
-template <int C>
+template <int C, int FORM = SCALAR_FORM_CANONICAL>
 __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits_ragged(const uint4* __restrict__ scalars, ragged_tab tab, uint16_t* __restrict__ digits,
                                                        digits_params prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
   __shared__ uint32_t hist[4096];
   const uint32_t m = blockIdx.y;
-  digits_block<C>(scalars + tab.off[m] * prm.sc_stride, tab.len[m], hist, digits, prm, err, counts1);
+  digits_block<C, FORM>(scalars + tab.off[m] * prm.sc_stride, tab.len[m], hist, digits, prm, err, counts1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1561,18 +1580,20 @@ __global__ void __launch_bounds__(1024) k_reduce_tail(tail_params_t<N> prm) {
 // ------------------------------------------------------------------------------------------------
 // K1a for BLS12-377 G1: short-Weierstrass affine (x, y), 48-byte little-endian each -> projective twisted-Edwards record
 // (curve.hpp, pnt_from_sw377), one lane per point; loads and stores are 16 bytes per lane.
+template <bool MONT = false>
 __device__ __forceinline__ void prep_point377(uint32_t i, const uint4* __restrict__ pts, rec_slot<14>* __restrict__ recs) {
   uint4 u[6];
 #pragma unroll
   for (int j = 0; j < 6; j++) u[j] = pts[6 * (size_t)i + j];
   const uint32_t xw[12] = {u[0].x, u[0].y, u[0].z, u[0].w, u[1].x, u[1].y, u[1].z, u[1].w, u[2].x, u[2].y, u[2].z, u[2].w};
   const uint32_t yw[12] = {u[3].x, u[3].y, u[3].z, u[3].w, u[4].x, u[4].y, u[4].z, u[4].w, u[5].x, u[5].y, u[5].z, u[5].w};
-  store_pnt<14>(recs + i, pnt_from_sw377(te377::fq_from_words32(xw), te377::fq_from_words32(yw)));
+  store_pnt<14>(recs + i, pnt_from_sw377<MONT>(te377::fq_from_words32(xw), te377::fq_from_words32(yw)));
 }
+template <bool MONT = false>
 __global__ void __launch_bounds__(256) k_prep_points377(batch_ptrs in, batch_slabs row_slab, rec_slot<14>* __restrict__ recs, uint32_t n) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
-  prep_point377(i, in.p[blockIdx.y], recs + (size_t)row_slab.s[blockIdx.y] * n);
+  prep_point377<MONT>(i, in.p[blockIdx.y], recs + (size_t)row_slab.s[blockIdx.y] * n);
 }
 // Level 1 of the sort and the BLS12-377 record conversion in one launch (k_part_scatter_prep for the other curve): the scatter is
 // bound by its LDS rounds and barriers, the conversion by its eight 14-limb products per point -- back to back they cost 46 + 130 us
@@ -1689,8 +1710,8 @@ struct fb_digit_args {
 // run per row -- 25 KB more LDS per block, a third of the resident blocks: 122 instead of 106 us for 13.6 M entries -- and, on top of it,
 // wave-aggregated ranks by ballots instead of one LDS atomic per entry: 140 us.  The kernel is bound by its occupancy and the latency of
 // its scattered stores, not by the atomics.)
-// one scalar per thread; LDS: cnt[rows] | base[rows] | hist[rows][2][P] (dynamic)
-template <int C>
+// one scalar per thread; LDS: cnt[rows] | base[rows] | hist[rows][2][P] (dynamic).  FORM: as digits_block (Twisted-Edwards curve only)
+template <int C, int FORM = SCALAR_FORM_CANONICAL>
 __global__ void __launch_bounds__(TE_FB_THREADS) k_fb_digits(const uint4* __restrict__ scalars, fb_digit_args a) {
   extern __shared__ uint32_t fl[];
   uint32_t* const cnt = fl; uint32_t* const base = fl + a.rows; uint32_t* const hist = fl + 2u * a.rows;
@@ -1703,7 +1724,15 @@ __global__ void __launch_bounds__(TE_FB_THREADS) k_fb_digits(const uint4* __rest
   {
     const size_t ii = live ? i : 0u;
     const uint4 a0 = scalars[2 * ii], a1 = scalars[2 * ii + 1];
-    const uint32_t raw[10] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, 0u, 0u};
+    uint32_t raw[10] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, 0u, 0u};
+    if constexpr (FORM != SCALAR_FORM_CANONICAL) {
+      uint32_t k[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) k[j] = raw[j];
+      scalar_from_montgomery<FORM>(k);
+#pragma unroll
+      for (int j = 0; j < 8; j++) raw[j] = k[j];
+    }
     uint64_t c = 0;
 #pragma unroll
     for (int j = 0; j < 10; j++) { c += (uint64_t)raw[j] + a.half[j]; s[j] = (uint32_t)c; c >>= 32; }

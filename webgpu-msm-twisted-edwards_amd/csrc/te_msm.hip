@@ -78,6 +78,7 @@ struct plan_t {
   uint32_t S = 0, logS = 0, P = 0;   // level-1 partition: S buckets each, P = B/S partitions per window
   uint32_t packed = 0;               // level-1 entries as one 32-bit word (index | key << 23 | sign << 31): n <= 2^23
   int rec_kind = 0;                  // records k_accumulate gathers: 0 = the curve's own, 1 = affine BLS12-377 (bound point sets)
+  int scalar_mont = 0;               // the scalar records hold k 2^256 mod (the curve's scalar field): option "scalars_montgomery" as it was when the call started
   // fixed-base windows (bound point sets with a per-window table, kernels.hip.hpp k_fb_digits): fb_rb > 0 -- the "windows" of this
   // plan are fb_rb + 1 pseudo-windows (rows) of 2^15 buckets over ONE bucket set; fb_c / fb_W: window bits and windows of the real decomposition
   int fb_rb = 0, fb_c = 0, fb_W = 0;
@@ -246,6 +247,9 @@ struct te_ctx {
   int64_t stat_record_conversions = 0;   // point -> record conversions the MSM launch sequences enqueued (get_option "record_conversions")
   int64_t opt_batch_small_max = 1ll << 15;   // te_msm_run_scalars_batch: MSMs up to this length share launch sequences (option "batch_small_max")
   int64_t stat_batch_sequences = 0;          // launch sequences the last batch call ran (get_option "batch_sequences")
+  int opt_scalars_montgomery = 0;   // scalar records are Montgomery residues k 2^256 mod m, decoded in the digit kernels (csrc/scalar_form.hpp); read when a call
+                                    // starts, on the calling thread -- a ticket keeps the form it was submitted with (plan_t::scalar_mont)
+  int opt_points_montgomery = 0;    // te_msm_bind_points[_device]: coordinates are Montgomery residues x 2^256 mod p / x 2^384 mod q; read at bind time
 };
 
 // A bound point set (include/te_msm.h, "resident bases"): the records of n points on EVERY device of its context, converted
@@ -321,8 +325,11 @@ int auto_window_bits(uint64_t n) {
 int num_windows_for(int c, int signed_digits) { return ((signed_digits ? 255 : 256) + c - 1) / c; }
 
 // whole: every window (a whole MSM: host buffers, tickets of a multi-device context) instead of the device's window shard
-void make_plan(const te_ctx* ctx, const gpu_t& d, uint64_t n, plan_t& p, int force_c = 0, int batch = 1, uint32_t force_seg = 0, bool whole = false) {
+// scalar_form: the form of the scalar records (plan_t::scalar_mont) where the caller fixed it earlier -- the jobs of asynchronous tickets, which
+// run on an upload lane and do not read the option, and the second run of a fixed-base ticket; -1 = option "scalars_montgomery" as it is now
+void make_plan(const te_ctx* ctx, const gpu_t& d, uint64_t n, plan_t& p, int force_c = 0, int batch = 1, uint32_t force_seg = 0, bool whole = false, int scalar_form = -1) {
   p.curve = ctx->opt_curve;
+  p.scalar_mont = scalar_form >= 0 ? scalar_form : ctx->opt_scalars_montgomery;
   p.c = force_c ? force_c : ctx->opt_window_bits ? ctx->opt_window_bits : auto_window_bits(n);
   p.signed_digits = ctx->opt_signed;
   p.W = num_windows_for(p.c, p.signed_digits);
@@ -440,14 +447,25 @@ template <int LO, int HI, typename F> void with_window_bits(int c, F&& f) {
   f(std::integral_constant<int, LO>{});
 }
 
-template <int C> void launch_digits(const te::batch_ptrs& sc, int batch, uint16_t* dg, const te::digits_params& prm, uint32_t* err, uint32_t* counts1, hipStream_t s) {
-  hipLaunchKernelGGL(te::k_digits<C>, dim3((prm.nst + TE_DIG_BLOCK - 1u) / TE_DIG_BLOCK, batch), dim3(TE_DIG_THREADS), 0, s, sc, dg, prm, err, counts1);
+// FORM: te::SCALAR_FORM_* (scalar_form_of below)
+template <int C, int FORM> void launch_digits(const te::batch_ptrs& sc, int batch, uint16_t* dg, const te::digits_params& prm, uint32_t* err, uint32_t* counts1, hipStream_t s) {
+  hipLaunchKernelGGL((te::k_digits<C, FORM>), dim3((prm.nst + TE_DIG_BLOCK - 1u) / TE_DIG_BLOCK, batch), dim3(TE_DIG_THREADS), 0, s, sc, dg, prm, err, counts1);
 }
 static_assert(TE_BATCH_MAX == TE_MSM_MAX_BATCH, "batch tables");
-template <int C> void launch_digits_ragged(const void* sc, const te::ragged_tab& tab, int batch, uint16_t* dg, const te::digits_params& prm, uint32_t* err, uint32_t* counts1, hipStream_t s) {
-  hipLaunchKernelGGL(te::k_digits_ragged<C>, dim3((prm.nst + TE_DIG_BLOCK - 1u) / TE_DIG_BLOCK, batch), dim3(TE_DIG_THREADS), 0, s, static_cast<const uint4*>(sc), tab, dg, prm, err, counts1);
+template <int C, int FORM> void launch_digits_ragged(const void* sc, const te::ragged_tab& tab, int batch, uint16_t* dg, const te::digits_params& prm, uint32_t* err, uint32_t* counts1, hipStream_t s) {
+  hipLaunchKernelGGL((te::k_digits_ragged<C, FORM>), dim3((prm.nst + TE_DIG_BLOCK - 1u) / TE_DIG_BLOCK, batch), dim3(TE_DIG_THREADS), 0, s, static_cast<const uint4*>(sc), tab, dg, prm, err, counts1);
 }
 static_assert(TE_RAGGED_MAX == TE_BATCH_SEQ_MAX && TE_BATCH_SEQ_MAX == TE_MSM_BATCH_SEQ_MAX, "ragged tables");
+// the instantiation of the digit kernels a plan runs: canonical records, or Montgomery residues modulo the scalar field of the plan's curve
+inline int scalar_form_of(const plan_t& p) {
+  return !p.scalar_mont ? te::SCALAR_FORM_CANONICAL : p.curve == TE_MSM_CURVE_BLS12_377_G1 ? te::SCALAR_FORM_377 : te::SCALAR_FORM_TE;
+}
+// f(integral_constant<int, FORM>) for a form of scalar_form_of
+template <typename F> void with_scalar_form(int form, F&& f) {
+  if (form == te::SCALAR_FORM_TE) f(std::integral_constant<int, te::SCALAR_FORM_TE>{});
+  else if (form == te::SCALAR_FORM_377) f(std::integral_constant<int, te::SCALAR_FORM_377>{});
+  else f(std::integral_constant<int, te::SCALAR_FORM_CANONICAL>{});
+}
 
 // One MSM's device work in three parts: the stages before the dominant kernel, k_accumulate (bracketed by timing events),
 // and the stages after it.
@@ -555,8 +573,10 @@ struct msm_launch {
       if (!ragged) for (int m = 0; m < p.batch; m++) sc.p[m] = (const uint4*)scalars_of(m);
       uint16_t* dg = ws.d_digits;
       uint32_t* c1 = ws.d_counts1;
-      if (ragged) with_window_bits<4, 16>(p.c, [&](auto C) { launch_digits_ragged<decltype(C)::value>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); });
-      else with_window_bits<4, 16>(p.c, [&](auto C) { launch_digits<decltype(C)::value>(sc, p.batch, dg, prm, ws.d_err, c1, stream); });
+      with_scalar_form(scalar_form_of(p), [&](auto FORM) {
+        if (ragged) with_window_bits<4, 16>(p.c, [&](auto C) { launch_digits_ragged<decltype(C)::value, decltype(FORM)::value>(d_scalars, *ragged, p.batch, dg, prm, ws.d_err, c1, stream); });
+        else with_window_bits<4, 16>(p.c, [&](auto C) { launch_digits<decltype(C)::value, decltype(FORM)::value>(sc, p.batch, dg, prm, ws.d_err, c1, stream); });
+      });
     }
     const uint32_t cap_w = p.B + (uint32_t)(n / p.seg_len);        // segment ids of one window (see k_part_scatter)
     mark(ST_SCATTER);
@@ -1011,13 +1031,14 @@ struct partial_req {
   const te_bases* bases = nullptr;    // the launch sequence gathers from a bound point set (d_points is not read: no conversion); batch must be 1
   share_mode share = SHARE_NONE;      // the record slab of the call; a shared slab only for device-resident points, without bound bases
   const uint32_t* d_idx = nullptr;    // (with bases) an indexed subset: the n entries gather records d_idx[0 .. n) of the set (device memory of d)
+  int scalar_form = -1;               // make_plan's: -1 = option "scalars_montgomery" as it is now
 };
 int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const partial_req& r) {
   const void* const d_points = r.d_points; const uint64_t n = r.n; hipStream_t const stream = r.stream;
   const int batch = r.batch; const te_bases* const bases = r.bases; const auto* const upload_points = r.upload_points;
   // (the plan is made for the n entries; only the entry form follows the set's count: indexed_plan.hpp)
   const te_indexed::call_plan ip = te_indexed::plan_for(n, r.d_idx ? bases->n : n, ctx->opt_packed);
-  plan_t p; make_plan(ctx, d, ip.plan_n, p, 0, batch, 0, r.whole);
+  plan_t p; make_plan(ctx, d, ip.plan_n, p, 0, batch, 0, r.whole, r.scalar_form);
   if (bases) p.rec_kind = bases->rec_kind;
   if (r.d_idx) p.packed = ip.packed;
   // (a batch shares when all its MSMs name ONE point buffer: the batch then holds one conversion anyway -- slab 0 of msm_launch::slabs())
@@ -1384,10 +1405,11 @@ int host_pieces(const te_ctx* ctx, uint64_t n) {
 // wait_for_pinned: the caller promises its buffers only until this call returns (te_msm_run, te_msm_submit).  Copies from
 // PAGEABLE memory have left the caller's buffer when hipMemcpyAsync returns (the runtime stages them); from pinned or
 // registered memory they are truly asynchronous -- then the call waits for the last piece's upload before it returns.
+// scalar_form: make_plan's (a lane thread passes what its ticket was submitted with).
 int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_points, const uint8_t* src_scalars, uint64_t n, int c, int K,
-                       bool wait_for_pinned = true) {
+                       bool wait_for_pinned = true, int scalar_form = -1) {
   HIP_TRY(ctx, hipSetDevice(d.device));
-  plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true);
+  plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true, scalar_form);
   const curve_sizes sz = sizes_of(pf.curve);
   if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sz.scalar_in)) return rc;
   const bool host_waits = !wait_for_pinned || caller_may_wait_on_host(src_points, src_scalars);
@@ -1407,7 +1429,7 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
   for (int i = 0; i < K; i++) m_max = std::max(m_max, piece_lo(i + 1) - piece_lo(i));
   uint32_t seg_all = 0;
   {
-    plan_t pm; make_plan(ctx, d, m_max, pm, pf.c, 1, 0, true);
+    plan_t pm; make_plan(ctx, d, m_max, pm, pf.c, 1, 0, true, pf.scalar_mont);
     seg_all = pm.seg_len;
     if (int rc = ensure_buffers(ctx, d, ws, m_max, pm)) return rc;        // every buffer at its final size before the first piece
   }
@@ -1445,7 +1467,7 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
   for (int i = 0; i < K; i++) {
     const uint64_t lo = piece_lo(i), hi = piece_lo(i + 1), m = hi - lo;
     if (m == 0) continue;
-    make_plan(ctx, d, m, p, pf.c, 1, seg_all, true);
+    make_plan(ctx, d, m, p, pf.c, 1, seg_all, true, pf.scalar_mont);
     if (int rc = ensure_buffers(ctx, d, ws, m, p)) return rc;              // no reallocation: only the pointers into the zeroed block move
     msm_launch L = L0;
     L.p = p; L.d_points = dpts + lo * sz.point_in; L.d_scalars = dscs + lo * sz.scalar_in; L.n = m; L.onto = !first;
@@ -1493,10 +1515,11 @@ int scalar_pieces(const te_ctx* ctx, uint64_t n) {
 // src_idx (te_msm_run_scalars_indexed*): the slice is n (index, scalar) pairs over a set of idx_count records -- `recs` is the set's FIRST
 // record, every piece carries its slice of both arrays and gathers records idx[j] (msm_launch::idx); idx_pos: position of the slice's
 // first pair in the caller's list.  The entry form follows the set's count, everything else n (indexed_plan.hpp).
+// scalar_form: make_plan's (a lane thread passes what its ticket was submitted with).
 int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* recs, int rec_kind, const uint8_t* src_scalars, uint64_t n, int c, int K,
-                         bool wait_for_pinned = true, const uint32_t* src_idx = nullptr, uint64_t idx_count = 0, uint64_t idx_pos = 0) {
+                         bool wait_for_pinned = true, const uint32_t* src_idx = nullptr, uint64_t idx_count = 0, uint64_t idx_pos = 0, int scalar_form = -1) {
   HIP_TRY(ctx, hipSetDevice(d.device));
-  plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true);
+  plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true, scalar_form);
   pf.rec_kind = rec_kind;
   const curve_sizes sz = sizes_of(pf.curve);
   const size_t rec_bytes = rec_bytes_of(pf.curve, rec_kind);
@@ -1510,7 +1533,7 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
   for (int i = 0; i < K; i++) m_max = std::max(m_max, piece_lo(i + 1) - piece_lo(i));
   uint32_t seg_all = 0;
   {
-    plan_t pm; make_plan(ctx, d, m_max, pm, pf.c, 1, 0, true);
+    plan_t pm; make_plan(ctx, d, m_max, pm, pf.c, 1, 0, true, pf.scalar_mont);
     pm.rec_kind = rec_kind;
     if (src_idx) pm.packed = te_indexed::plan_for(m_max, idx_count, ctx->opt_packed).packed;
     seg_all = pm.seg_len;
@@ -1543,7 +1566,7 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
       if (int rc = lane_wait(ctx, ws, evs[(size_t)i], !wait_for_pinned || caller_may_wait_on_host(src_scalars, src_idx))) return rc;
       stamp("upload awaited", i);
     }
-    make_plan(ctx, d, m, p, pf.c, 1, seg_all, true);
+    make_plan(ctx, d, m, p, pf.c, 1, seg_all, true, pf.scalar_mont);
     p.rec_kind = rec_kind;
     if (src_idx) p.packed = te_indexed::plan_for(m, idx_count, ctx->opt_packed).packed;
     if (int rc = ensure_buffers(ctx, d, ws, m, p, false)) return rc;           // no reallocation: only the pointers into the zeroed block move
@@ -1570,14 +1593,14 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
 // geometry (codes lo + 1, half = 0), general sort entries (the table index needs 24 bits).
 constexpr uint32_t FB_LOBITS = TE_FB_LOBITS;
 int fb_windows_for(int c) { return (255 + c - 1) / c; }
-void make_plan_fb(const te_ctx* ctx, const gpu_t& d, uint64_t n, int fb_c, plan_t& p) {
+void make_plan_fb(const te_ctx* ctx, const gpu_t& d, uint64_t n, int fb_c, plan_t& p, int scalar_form = -1) {
   const int W = fb_windows_for(fb_c);
   const uint32_t rb = 1u << ((uint32_t)fb_c - 1u - FB_LOBITS);
   // a regular row holds (W - 1) n / rb entries for well-spread digits, the extra row the top window's n: capacity for the larger of
   // the two plus a sixteenth (an overflow -- badly skewed scalars -- is detected on the device and falls back to the ordinary windows)
   const uint64_t reg = ((uint64_t)(W - 1) * n + rb - 1) / rb, big = std::max<uint64_t>(reg, n);
   const uint64_t cap = (big + big / 16 + 4096 + 7) & ~(uint64_t)7;
-  make_plan(ctx, d, cap, p, 16, 1, 0, true);           // chunk geometry, segment length and partitions for rows of `cap` entries
+  make_plan(ctx, d, cap, p, 16, 1, 0, true, scalar_form);           // chunk geometry, segment length and partitions for rows of `cap` entries
   p.fb_rb = (int)rb; p.fb_c = fb_c; p.fb_W = W;
   p.signed_digits = 0; p.c = (int)FB_LOBITS; p.W = (int)rb + 1; p.nw = p.nw1 = (int)rb + 1; p.batch = 1; p.w_first = 0; p.w_step = 1;
   p.logB = FB_LOBITS; p.B = 1u << FB_LOBITS;
@@ -1597,16 +1620,17 @@ void make_plan_fb(const te_ctx* ctx, const gpu_t& d, uint64_t n, int fb_c, plan_
   }
 }
 
-template <int C> void launch_fb_digits(const void* d_scalars, const te::fb_digit_args& a, uint32_t n, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL(te::k_fb_digits<C>, dim3((n + TE_FB_THREADS - 1u) / TE_FB_THREADS), dim3(TE_FB_THREADS), lds, st, static_cast<const uint4*>(d_scalars), a);
+template <int C, int FORM> void launch_fb_digits(const void* d_scalars, const te::fb_digit_args& a, uint32_t n, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL((te::k_fb_digits<C, FORM>), dim3((n + TE_FB_THREADS - 1u) / TE_FB_THREADS), dim3(TE_FB_THREADS), lds, st, static_cast<const uint4*>(d_scalars), a);
 }
 
 // An MSM of n scalars (device memory) over the fixed-base table of `bases` on device `d`: the scalars' digits address the table
 // entries (w, idx_base + i) -- idx_base: the first point of this launch inside the bound set (a device's slice of a lone
-// multi-device call).  Rows in the set's own block; the caller ends the sequence with fetch_rows().
-int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const void* d_scalars, uint64_t n, uint64_t idx_base, hipStream_t stream) {
+// multi-device call).  Rows in the set's own block; the caller ends the sequence with fetch_rows().  scalar_form: make_plan's.
+int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const void* d_scalars, uint64_t n, uint64_t idx_base, hipStream_t stream,
+                       int scalar_form = -1) {
   HIP_TRY(ctx, hipSetDevice(d.device));
-  plan_t p; make_plan_fb(ctx, d, n, bases->fb_c, p);
+  plan_t p; make_plan_fb(ctx, d, n, bases->fb_c, p, scalar_form);
   const uint64_t cap = p.nst;
   if ((uint64_t)p.nw * cap >= (1ull << 31) || (uint64_t)bases->fb_W * bases->n >= (1ull << 31))
     return set_err(ctx, TE_MSM_EINVAL, "fixed-base windows: windows x points must stay below 2^31");
@@ -1631,7 +1655,9 @@ int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bas
     a.chunk_len = p.chunk_len; a.CH = p.CH; a.P = p.P; a.logS = p.logS;
     a.digits = ws.d_digits; a.remap = ws.d_fb_remap; a.row_fill = ws.d_fb_fill; a.counts1 = ws.d_counts1; a.err = ws.d_err;
     const size_t lds = (size_t)(2u * a.rows + a.rows * 2u * a.P) * sizeof(uint32_t);
-    with_window_bits<16, 21>(p.fb_c, [&](auto C) { launch_fb_digits<decltype(C)::value>(d_scalars, a, a.n, lds, stream); });
+    // (fixed-base sets exist on the Twisted-Edwards curve only: the one Montgomery form here is modulo L)
+    if (p.scalar_mont) with_window_bits<16, 21>(p.fb_c, [&](auto C) { launch_fb_digits<decltype(C)::value, te::SCALAR_FORM_TE>(d_scalars, a, a.n, lds, stream); });
+    else with_window_bits<16, 21>(p.fb_c, [&](auto C) { launch_fb_digits<decltype(C)::value, te::SCALAR_FORM_CANONICAL>(d_scalars, a, a.n, lds, stream); });
   }
   // the engine's own stages from here on (front_scalars skips k_digits for a fixed-base plan)
   if (int rc = L.front_scalars()) return rc;
@@ -1920,7 +1946,9 @@ struct check_lane {
   }
 };
 
-int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason) {
+// mont: the coordinates are Montgomery residues (option "points_montgomery": te_msm_bind_points*, te_msm_check_points*); every per-call
+// check of an MSM or a multiplication reads canonical coordinates
+int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason, bool mont = false) {
   *bad = -1; *reason = 0;
   if (n == 0) return 0;
   gpu_t& d = ctx->devs[di];
@@ -1937,7 +1965,13 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
     const uint4* p4 = reinterpret_cast<const uint4*>(at);
     HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
     const dim3 grid((m + 255u) / 256u), block(256);
-    if (curve == TE_MSM_CURVE_BLS12_377_G1) {
+    if (mont && curve == TE_MSM_CURVE_BLS12_377_G1) {
+      hipLaunchKernelGGL((te::k_check_form<1, true>), grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL((te::k_check_subgroup<1, true>), grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
+    } else if (mont) {
+      hipLaunchKernelGGL((te::k_check_form<0, true>), grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL((te::k_check_subgroup<0, true>), grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
+    } else if (curve == TE_MSM_CURVE_BLS12_377_G1) {
       hipLaunchKernelGGL(te::k_check_form<1>, grid, block, 0, st, p4, m, d.chk_word);
       if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<1>, grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
     } else {
@@ -1971,14 +2005,17 @@ int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* fir
   return set_err(ctx, TE_MSM_EPOINT, buf);
 }
 // option "check_points" in front of a call: 0 = go on, TE_MSM_EPOINT (noted) or a device error
-int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n) {
+int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont = false) {
   if (!ctx->opt_check_points) return 0;
   int64_t bad = -1; int reason = 0;
-  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points, &bad, &reason);
+  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points, &bad, &reason, mont);
   if (rc == TE_MSM_EPOINT) return note_bad(ctx, kBadPoint, bad, reason);
   return rc;
 }
 
+// te_msm_run_x and te_msm_mul* read canonical scalars only: with option "scalars_montgomery" set they are refused (a silent canonical
+// reading would be a wrong answer)
+const char* const kNoMontgomeryScalars = "option \"scalars_montgomery\" is set: te_msm_run_x and te_msm_mul* take canonical scalars only";
 int check_n(te_ctx* ctx, uint64_t n) { return n >= (1ull << 31) ? set_err(ctx, TE_MSM_EINVAL, "n must be < 2^31") : 0; }
 
 // share: how a single-device call from device-resident points keeps its records (share_mode; x-only points: SHARE_CONVERT)
@@ -2345,11 +2382,11 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
     hand_out_ticket(ctx, t, ticket);
     return 0;
   }
-  const int level = ctx->opt_check_points, curve = ctx->opt_curve;
-  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, points_xy_le, scalars_le, n, c, K, level, curve]() -> int {
+  const int level = ctx->opt_check_points, curve = ctx->opt_curve, form = pf.scalar_mont;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, points_xy_le, scalars_le, n, c, K, level, curve, form]() -> int {
     // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
     if (const int rc = check_ticket(ctx, t.ws, (size_t)t.di, points_xy_le, true, n, curve, level)) return rc;
-    return enqueue_host_slice(ctx, t.d, t.ws, points_xy_le, scalars_le, n, c, K, false);
+    return enqueue_host_slice(ctx, t.d, t.ws, points_xy_le, scalars_le, n, c, K, false, form);
   });
   hand_out_ticket(ctx, t, ticket, nullptr, std::move(job));
   return 0;
@@ -2443,7 +2480,8 @@ void free_bases(te_ctx* ctx, te_bases* b) {
 // The records of the set on device i: raw points -> (temporary) -> records, on a stream of its own; returns when they are there.
 // src on the host: the device's own upload (D devices: D links side by side, one host thread each); src on a device of the
 // context: read in place on its holder, pulled over the peer link elsewhere.
-int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src_is_host, int src_dev) {
+// mont: the raw coordinates are Montgomery residues (option "points_montgomery"): the conversion's other instantiation, the same records.
+int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src_is_host, int src_dev, bool mont) {
   gpu_t& d = ctx->devs[i];
   HIP_TRY(ctx, hipSetDevice(d.device));
   const curve_sizes sz = sizes_of(b->curve);
@@ -2470,13 +2508,16 @@ int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src
   if (b->curve == TE_MSM_CURVE_BLS12_377_G1) {
     te::rec_slot<14>* pr = reinterpret_cast<te::rec_slot<14>*>(recs);
     if (b->rec_kind == 1) { HIP_TRY(ctx, hipMalloc(&proj, (size_t)n * sizeof(te::rec_slot<14>))); pr = static_cast<te::rec_slot<14>*>(proj); }
-    hipLaunchKernelGGL(te::k_prep_points377, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, pr, n32);
+    if (mont) hipLaunchKernelGGL(te::k_prep_points377<true>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, pr, n32);
+    else hipLaunchKernelGGL(te::k_prep_points377<false>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, pr, n32);
     if (b->rec_kind == 1) {
       const uint32_t groups = (n32 + TE_AFF_GROUP - 1u) / TE_AFF_GROUP;
       hipLaunchKernelGGL(te::k_affine377, dim3((groups + 255) / 256), dim3(256), 0, st, pr, reinterpret_cast<te::rec_aff377*>(recs), n32);
     }
+  } else if (mont) {
+    hipLaunchKernelGGL(te::k_prep_points<true>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, reinterpret_cast<te::pnt_slot*>(recs), n32);
   } else {
-    hipLaunchKernelGGL(te::k_prep_points, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, reinterpret_cast<te::pnt_slot*>(recs), n32);
+    hipLaunchKernelGGL(te::k_prep_points<false>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, reinterpret_cast<te::pnt_slot*>(recs), n32);
   }
   if (b->fb_c) {
     // fixed-base windows: table w = the records of 2^(c w) P_i; the extended points travel from window to window by c doublings
@@ -2494,7 +2535,8 @@ int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src
   return 0;
 }
 
-int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_bases** out) {
+// mont: option "points_montgomery" as te_msm_bind_points[_device] found it (te_msm_bind_points_x binds points it recovered itself: canonical)
+int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_bases** out, bool mont = false) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   *out = nullptr;
   if (int rc = check_n(ctx, n)) return rc;
@@ -2510,7 +2552,7 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
   if (n > 0) {                                        // option "check_points": once, here (MSMs over the set never check again)
     size_t ci = 0;
     if (!src_is_host) while (ctx->devs[ci].device != src_dev) ci++;
-    if (int rc = check_call(ctx, ci, src, src_is_host, n)) return rc;
+    if (int rc = check_call(ctx, ci, src, src_is_host, n, mont)) return rc;
   }
   te_bases* b = new te_bases();
   b->ctx = ctx; b->n = n; b->curve = ctx->opt_curve;
@@ -2521,7 +2563,7 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
     if ((uint64_t)b->fb_W * n >= (1ull << 31)) { delete b; return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base: windows x points must stay below 2^31"); }
   }
   b->recs.assign(nd, nullptr);
-  const int rc = n > 0 ? te_sched::on_devices(*ctx, nd, [=](size_t i) { return bind_on_device(ctx, b, i, src, src_is_host, src_dev); }) : 0;
+  const int rc = n > 0 ? te_sched::on_devices(*ctx, nd, [=](size_t i) { return bind_on_device(ctx, b, i, src, src_is_host, src_dev, mont); }) : 0;
   if (rc) { free_bases(ctx, b); delete b; return rc; }
   // a set bound from HOST memory announces tickets from host scalars: the lanes' first concurrent copies (15-30 ms once per process,
   // warm_upload_lanes) happen here, in the call that blocks anyway, not in the first te_msm_submit_scalars -- which the N-API addon
@@ -2534,7 +2576,8 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
 
 // A whole MSM over a fixed-base set from HOST scalars on work set `ws`: all scalars cross PCIe in one copy (the digits of every
 // window address one bucket set: there are no pieces to accumulate onto), then the fixed-base launch sequence and its read-back.
-int enqueue_fixed_base_host(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const uint8_t* src_scalars, uint64_t n, bool wait_for_pinned) {
+int enqueue_fixed_base_host(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const uint8_t* src_scalars, uint64_t n, bool wait_for_pinned,
+                            int scalar_form = -1) {
   HIP_TRY(ctx, hipSetDevice(d.device));
   const curve_sizes sz = sizes_of(bases->curve);
   if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
@@ -2552,7 +2595,7 @@ int enqueue_fixed_base_host(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases
       HIP_TRY(ctx, hipEventSynchronize(ws.ev_copy));
     }
   }
-  if (int rc = enqueue_fixed_base(ctx, d, ws, bases, ws.d_in_scalars, n, 0, ws.stream)) return rc;
+  if (int rc = enqueue_fixed_base(ctx, d, ws, bases, ws.d_in_scalars, n, 0, ws.stream, scalar_form)) return rc;
   return fetch_rows(ctx, ws, ws.stream);
 }
 
@@ -2564,6 +2607,7 @@ int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* base
   ctx->stat_fb_fallbacks++;
   HIP_TRY(ctx, hipSetDevice(d.device));
   partial_req r; r.d_scalars = ws.fb_scalars; r.n = ws.fb_n; r.stream = ws.stream; r.whole = true; r.bases = bases;
+  r.scalar_form = ws.plan.scalar_mont;                 // (a ticket: the form it was submitted with, whatever the option says at its collect)
   if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
@@ -2654,12 +2698,12 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
 
 int te_msm_bind_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, te_bases** out) {
   device_guard restore_callers_device;
-  return bind_common(ctx, points_xy_le, true, n, out);
+  return bind_common(ctx, points_xy_le, true, n, out, ctx && ctx->opt_points_montgomery);
 }
 
 int te_msm_bind_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, te_bases** out) {
   device_guard restore_callers_device;
-  return bind_common(ctx, d_points_xy_le, false, n, out);
+  return bind_common(ctx, d_points_xy_le, false, n, out, ctx && ctx->opt_points_montgomery);
 }
 
 uint64_t te_msm_bases_count(const te_bases* bases) { return bases ? bases->n : 0; }
@@ -2704,10 +2748,10 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
   // pieces shorten ONE MSM's way through the device (its upload hides under its own first pieces); with other tickets in flight on
   // the device the upload hides under THEIR device work, and one piece keeps the sort and the accumulation at full width
   const int c = pf.c, K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, n) : 1;
-  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind;
-  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, bases, recs, kind, scalars_le, n, c, K]() -> int {
-    return bases->fb_c ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, scalars_le, n, false)
-                       : enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, n, c, K, false);
+  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind, form = pf.scalar_mont;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, bases, recs, kind, scalars_le, n, c, K, form]() -> int {
+    return bases->fb_c ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, scalars_le, n, false, form)
+                       : enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, n, c, K, false, nullptr, 0, 0, form);
   });
   hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
@@ -2807,9 +2851,9 @@ int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* 
   plan_t pf; make_plan(ctx, t.d, m, pf, 0, 1, 0, true);
   // (pieces: the rule of te_msm_submit_scalars -- with other tickets in flight the upload hides under their device work)
   const int c = pf.c, K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? te_indexed::pieces(m, ctx->opt_scalar_chunks) : 1;
-  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind; const uint64_t count = bases->n;
-  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, recs, kind, idx, scalars_le, m, c, K, count]() -> int {
-    return enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, m, c, K, false, idx, count, 0);
+  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind, form = pf.scalar_mont; const uint64_t count = bases->n;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, recs, kind, idx, scalars_le, m, c, K, count, form]() -> int {
+    return enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, m, c, K, false, idx, count, 0, form);
   });
   hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
@@ -2901,6 +2945,8 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
   if (!strcmp(key, "share_records")) { ctx->opt_share_records = value == 2 ? 2 : value ? 1 : 0; return 0; }
   if (!strcmp(key, "bind_fixed_base")) { if (value != 0 && (value < 16 || value > 21)) return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base must be 0 or in [16, 21]"); ctx->opt_bind_fixed_base = (int)value; return 0; }
   if (!strcmp(key, "scalar_chunks")) { if (value < 0 || value > 64) return set_err(ctx, TE_MSM_EINVAL, "scalar_chunks out of range"); ctx->opt_scalar_chunks = (int)value; return 0; }
+  if (!strcmp(key, "scalars_montgomery")) { if (value != 0 && value != 1) return set_err(ctx, TE_MSM_EINVAL, "scalars_montgomery must be 0 or 1"); ctx->opt_scalars_montgomery = (int)value; return 0; }
+  if (!strcmp(key, "points_montgomery")) { if (value != 0 && value != 1) return set_err(ctx, TE_MSM_EINVAL, "points_montgomery must be 0 or 1"); ctx->opt_points_montgomery = (int)value; return 0; }
   if (!strcmp(key, "batch_small_max")) { if (value < 0 || value > (1ll << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch_small_max must be in [0, 2^31]"); ctx->opt_batch_small_max = value; return 0; }
   return set_err(ctx, TE_MSM_EINVAL, "unknown option");
 }
@@ -2939,6 +2985,8 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "record_slabs")) { int64_t t = 0; for (const gpu_t& d : ctx->devs) for (const auto& sl : d.slabs) if (sl.d) t++; *value = t; return 0; }
   if (!strcmp(key, "scalar_chunks")) { *value = ctx->opt_scalar_chunks; return 0; }
   if (!strcmp(key, "batch_small_max")) { *value = ctx->opt_batch_small_max; return 0; }
+  if (!strcmp(key, "scalars_montgomery")) { *value = ctx->opt_scalars_montgomery; return 0; }
+  if (!strcmp(key, "points_montgomery")) { *value = ctx->opt_points_montgomery; return 0; }
   if (!strcmp(key, "batch_sequences")) { *value = ctx->stat_batch_sequences; return 0; }
   if (!strcmp(key, "bind_fixed_base")) { *value = ctx->opt_bind_fixed_base; return 0; }
   if (!strcmp(key, "fixed_base_fallbacks")) { *value = ctx->stat_fb_fallbacks; return 0; }
@@ -2969,7 +3017,7 @@ int check_standalone(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n,
   const int di = !src_is_host && n > 0 && ctx->devs.size() > 1
                      ? owner_of(ctx, "te_msm_check_points_device: the points must be resident on a device of the context", {src}) : 0;
   if (di < 0) return di;
-  const int rc = check_points_on(ctx, (size_t)di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why);
+  const int rc = check_points_on(ctx, (size_t)di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why, ctx->opt_points_montgomery != 0);
   if (rc != TE_MSM_EPOINT) return rc;
   return note_bad(ctx, kBadPoint, bad, why, first_bad, reason);
 }
@@ -3093,6 +3141,7 @@ int te_msm_bind_points_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, te_bases*
 int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, uint8_t* out_xy_le) {
   device_guard restore_callers_device;
   if (!ctx || !out_xy_le) return TE_MSM_EINVAL;
+  if (ctx->opt_scalars_montgomery) return set_err(ctx, TE_MSM_EINVAL, kNoMontgomeryScalars);
   if (int rc = from_x_args(ctx, x_le, n, scalars_le)) return rc;
   if (n == 0) return run_common(ctx, x_le, scalars_le, true, 0, out_xy_le);
   dev_tmp pts, sc;
@@ -3117,6 +3166,8 @@ int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
 // temporary is freed before the call returns (dev_tmp).
 namespace {
 constexpr uint64_t kMulPiece = 1ull << 18;
+// te_msm_mul* as te_msm_run_x: canonical scalars only -- refused under the option instead of a silent canonical reading
+int mul_refused(te_ctx* ctx) { return ctx->opt_scalars_montgomery ? set_err(ctx, TE_MSM_EINVAL, kNoMontgomeryScalars) : 0; }
 
 inline te::naf_t shared_naf_of(const uint8_t* k32, int curve) {
   uint32_t k[8];
@@ -3218,18 +3269,21 @@ int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalar
 int te_msm_mul(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le) {
   device_guard restore_callers_device;
   if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = mul_refused(ctx)) return rc;
   return mul_host(ctx, points_xy_le, false, scalars_le, n, shared_scalar != 0, out_points_xy_le);
 }
 
 int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le) {
   device_guard restore_callers_device;
   if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = mul_refused(ctx)) return rc;
   return mul_host(ctx, x_le, true, scalars_le, n, shared_scalar != 0, out_points_xy_le);
 }
 
 int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_scalars_le, uint64_t n, int shared_scalar, void* d_out_points_xy_le) {
   device_guard restore_callers_device;
   if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = mul_refused(ctx)) return rc;
   if (int rc = mul_args(ctx, d_points_xy_le, d_scalars_le, n, d_out_points_xy_le)) return rc;
   if (n == 0) return 0;
   const int owner = owner_of(ctx, "te_msm_mul_device: the points, the scalars and the output must be resident on one device of the context",

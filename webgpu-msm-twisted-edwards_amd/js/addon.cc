@@ -32,6 +32,13 @@
 namespace {
 
 std::atomic<int> g_check_points{0};    // setCheckPoints(level): option "check_points" of every context created from now on
+std::atomic<int> g_scalars_montgomery{0};   // setScalarsMontgomery(flag): option "scalars_montgomery" of every context created from now on
+// what setBases bound: the Buffer, kept alive so that its address cannot become another object's, and the form of its coordinates
+// ({montgomery: true}: option "points_montgomery" for every bind of that buffer; a pool thread binds it again on a new context)
+struct BoundBuffer {
+  napi_ref ref = nullptr;
+  std::atomic<int> montgomery{0};
+} g_bases;
 
 // the engine behind te_promise::protocol (js/promise_protocol.hpp holds the lock protocol itself)
 struct EngineApi {
@@ -54,6 +61,10 @@ struct EngineApi {
       const int orc = te_msm_set_option(*out, "check_points", g_check_points.load());
       if (orc) { te_msm_destroy(*out); *out = nullptr; return orc; }
     }
+    if (rc == 0 && g_scalars_montgomery.load()) {
+      const int orc = te_msm_set_option(*out, "scalars_montgomery", 1);
+      if (orc) { te_msm_destroy(*out); *out = nullptr; return orc; }
+    }
     return rc;
   }
   static void destroy(te_ctx* c) { te_msm_destroy(c); }
@@ -65,13 +76,22 @@ struct EngineApi {
   static int64_t in_flight(te_ctx* c) { int64_t v = 0; te_msm_get_option(c, "in_flight", &v); return v; }
   static int64_t num_devices(te_ctx* c) { int64_t v = 1; te_msm_get_option(c, "num_devices", &v); return v; }
   // resident bases (include/te_msm.h): the opt-in behind setBases(buffer)
-  static int bind(te_ctx* c, const uint8_t* p, uint64_t n, te_bases** out) { return te_msm_bind_points(c, p, n, out); }
+  // (the option is read at bind time: set for the length of this bind and put back -- also when the set is bound again on a new context)
+  static int bind(te_ctx* c, const uint8_t* p, uint64_t n, te_bases** out) {
+    if (!g_bases.montgomery.load()) return te_msm_bind_points(c, p, n, out);
+    int64_t before = 0;
+    int orc = te_msm_get_option(c, "points_montgomery", &before);
+    if (!orc) orc = te_msm_set_option(c, "points_montgomery", 1);
+    if (orc) return orc;
+    const int rc = te_msm_bind_points(c, p, n, out);
+    (void)te_msm_set_option(c, "points_montgomery", before);
+    return rc;
+  }
   static int release(te_ctx* c, te_bases* b) { return te_msm_release_points(c, b); }
   static int run_scalars(te_ctx* c, te_bases* b, const uint8_t* s, uint8_t* out) { return te_msm_run_scalars(c, b, s, out); }
   static int submit_scalars(te_ctx* c, te_bases* b, const uint8_t* s, uint64_t* t) { return te_msm_submit_scalars(c, b, s, t); }
 };
 te_promise::protocol<EngineApi> g_proto;
-napi_ref g_bases_ref = nullptr;       // the Buffer that setBases bound: kept alive, so that its address cannot become another object's
 
 struct Job {
   napi_async_work work = nullptr;
@@ -160,9 +180,25 @@ napi_value SetDevices(napi_env env, napi_callback_info info) {
 // then uploads and decomposes the scalars only.  Every other buffer takes the ordinary path; setBases(null) unbinds.
 // compute_msm's signature (submission.ts:73-78) is untouched; the reference's harness passes one point buffer to six calls per
 // size (submission/miscellaneous/full_benchmarks.ts:63-68,100-105).  Blocks until no promise is pending (like resetContext).
+// setBases(points, {montgomery: true}): the coordinates are a native prover's Montgomery residues, x * 2^256 mod p (include/te_msm.h,
+// option "points_montgomery"); the set, and every result over it, is the same as from canonical coordinates.
 napi_value SetBases(napi_env env, napi_callback_info info) {
-  size_t argc = 1; napi_value argv[1];
+  size_t argc = 2; napi_value argv[2];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool montgomery = false;
+  if (argc >= 2) {
+    napi_valuetype ot = napi_undefined;
+    napi_typeof(env, argv[1], &ot);
+    if (ot == napi_object) {
+      napi_value mv; bool has = false;
+      napi_has_named_property(env, argv[1], "montgomery", &has);
+      if (has && (napi_get_named_property(env, argv[1], "montgomery", &mv) != napi_ok || napi_coerce_to_bool(env, mv, &mv) != napi_ok ||
+                  napi_get_value_bool(env, mv, &montgomery) != napi_ok)) {
+        napi_throw_type_error(env, nullptr, "setBases: options.montgomery is a boolean");
+        return nullptr;
+      }
+    } else if (ot != napi_undefined && ot != napi_null) { napi_throw_type_error(env, nullptr, "setBases(points: Buffer | null, options?: { montgomery?: boolean })"); return nullptr; }
+  }
   napi_valuetype vt = napi_undefined;
   if (argc >= 1) napi_typeof(env, argv[0], &vt);
   bool is_buf = false;
@@ -171,23 +207,26 @@ napi_value SetBases(napi_env env, napi_callback_info info) {
   std::string err;
   if (!is_buf) {
     (void)g_proto.set_bases(nullptr, 0, err);
-    if (g_bases_ref) { napi_delete_reference(env, g_bases_ref); g_bases_ref = nullptr; }
+    if (g_bases.ref) { napi_delete_reference(env, g_bases.ref); g_bases.ref = nullptr; }
+    g_bases.montgomery.store(0);
   } else {
     void* p = nullptr; size_t pl = 0;
     napi_get_buffer_info(env, argv[0], &p, &pl);
     if (pl % 64 != 0) { napi_throw_range_error(env, nullptr, "setBases: points must be 64*n bytes"); return nullptr; }
     napi_ref ref = nullptr;
     napi_create_reference(env, argv[0], 1, &ref);
+    g_bases.montgomery.store(montgomery ? 1 : 0);                     // (Api::bind reads it inside set_bases)
     const int rc = g_proto.set_bases(static_cast<const uint8_t*>(p), pl / 64, err);
-    if (g_bases_ref) napi_delete_reference(env, g_bases_ref);         // the previous buffer is unbound either way
-    g_bases_ref = nullptr;
+    if (g_bases.ref) napi_delete_reference(env, g_bases.ref);         // the previous buffer is unbound either way
+    g_bases.ref = nullptr;
     if (rc) {
+      g_bases.montgomery.store(0);                                    // nothing is bound
       napi_delete_reference(env, ref);
       const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
       napi_throw_error(env, nullptr, m.c_str());
       return nullptr;
     }
-    g_bases_ref = ref;
+    g_bases.ref = ref;
   }
   napi_value u; napi_get_undefined(env, &u); return u;
 }
@@ -381,6 +420,23 @@ napi_value SetCheckPoints(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+// setScalarsMontgomery(flag): the scalar buffers of later calls hold a native prover's Montgomery residues, k * 2^256 mod L (include/te_msm.h,
+// option "scalars_montgomery": decoded on the device, in the digit kernels).  Applies to compute_msm, msmBatch and msmIndexed; scalarMul /
+// scalarMulX take canonical scalars only and throw while it is set.  Takes effect for the next call, like setCheckPoints: the cached
+// context is dropped once no promise is pending (a bound point set is bound again on the new one).
+napi_value SetScalarsMontgomery(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool flag = false;
+  if (argc < 1 || napi_coerce_to_bool(env, argv[0], &argv[0]) != napi_ok || napi_get_value_bool(env, argv[0], &flag) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "setScalarsMontgomery(flag: boolean)");
+    return nullptr;
+  }
+  g_proto.reset();
+  g_scalars_montgomery.store(flag ? 1 : 0);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
 // getStats(): how the promises so far were mapped onto the engine -- tickets submitted from the JavaScript thread / from pool
 // threads, lone calls, jobs over bound bases, and the largest number of tickets seen in flight at a submit
 napi_value GetStats(napi_env env, napi_callback_info) {
@@ -403,7 +459,7 @@ napi_value GetDevices(napi_env env, napi_callback_info) {
 napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
-      {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints},
+      {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints}, {"setScalarsMontgomery", SetScalarsMontgomery},
       {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed}};
   for (const auto& f : fns) {
     napi_value v;

@@ -51,7 +51,13 @@ const getDevices = () => native.getDevices();
 // Opt-in, also outside the reference's interface: setBases(bufferPoints) binds that Buffer once (upload + conversion on every
 // device); compute_msm(bufferPoints, scalars) with THE SAME Buffer object then moves the scalars only.  The harness passes one
 // point buffer to six calls per size (submission/miscellaneous/full_benchmarks.ts:63-68,100-105).  setBases(null) unbinds.
-const setBases = (bufferPoints) => native.setBases(bufferPoints === undefined ? null : bufferPoints);
+// setBases(bufferPoints, { montgomery: true }): the coordinates are a native prover's Montgomery residues (x * 2^256 mod p, what arkworks
+// and snarkVM hold in memory); the bound set and every result over it are the same.
+const setBases = (bufferPoints, options) => native.setBases(bufferPoints === undefined ? null : bufferPoints, options);
+// Opt-in as well: setScalarsMontgomery(true) -- the scalar buffers of later compute_msm / msmBatch / msmIndexed calls hold Montgomery
+// residues k * 2^256 mod L (L: the order of the prime subgroup), decoded on the GPU where the scalars are first read; any 256-bit value
+// stands for its residue.  scalarMul / scalarMulX take canonical scalars only and throw while it is set.
+const setScalarsMontgomery = (flag) => native.setScalarsMontgomery(!!flag);
 const getStats = () => native.getStats();
 // Opt-in as well: setCheckPoints(level) validates the input points of later calls (0 = none, default; 1 = canonical and on the
 // curve; 2 = also in the prime-order subgroup, costly -- best paired with setBases, which then checks the set once).  A call with
@@ -86,4 +92,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed };

@@ -13,7 +13,11 @@ export declare const getDevices: () => number[];
 // Not in the reference: resident bases.  setBases(points) binds that Buffer once (upload + conversion on every device);
 // compute_msm(points, scalars) with the same Buffer object then moves the scalars only (full_benchmarks.ts:63-68,100-105 pass
 // one point buffer to six calls per size).  setBases(null) unbinds.
-export declare const setBases: (bufferPoints: Buffer | null) => void;
+// { montgomery: true }: the coordinates are Montgomery residues x * 2^256 mod p (a native prover's in-memory form); same set, same results.
+export declare const setBases: (bufferPoints: Buffer | null, options?: { montgomery?: boolean }) => void;
+// Not in the reference: the scalar buffers of later compute_msm / msmBatch / msmIndexed calls hold Montgomery residues k * 2^256 mod L,
+// decoded on the GPU (any 256-bit value stands for its residue); scalarMul / scalarMulX throw while it is set.
+export declare const setScalarsMontgomery: (flag: boolean) => void;
 export declare const getStats: () => { submittedInEnter: number; submittedInExecute: number; loneRuns: number; boundJobs: number; maxInFlight: number };
 // Not in the reference: opt-in validation of input points (0 none, 1 canonical + on the curve, 2 + prime-order subgroup); a bad
 // point rejects the call's promise (the message names the index and the reason), setBases throws for a bad set.
