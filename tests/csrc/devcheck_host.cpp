@@ -1,0 +1,18 @@
+// devcheck_host.cpp -- TEST SHIM: the host build of the operation table (devcheck_ops.hpp), a loop over elements per operation.
+// tests/devcheck.py compares the gfx950 build of the same table (devcheck.hip) with it bit for bit.  Not part of the product.
+#include <stddef.h>
+#include "devcheck_ops.hpp"
+
+extern "C" {
+#define X(name, fn, IW, OW)                                                      \
+  int dc_##name(const uint32_t* in, uint32_t* out, uint32_t n) {                 \
+    for (uint32_t i = 0; i < n; i++) fn(in + (size_t)i * IW, out + (size_t)i * OW); \
+    return 0;                                                                    \
+  }
+DC_OPS(X)
+#undef X
+// "name:words in:words out;" for every entry, so the Python side can check its own copy of the word counts
+#define X(name, fn, IW, OW) #name ":" #IW ":" #OW ";"
+const char* dc_table() { return DC_OPS(X); }
+#undef X
+}

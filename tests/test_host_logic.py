@@ -9,6 +9,7 @@ import sys
 
 import pytest
 
+import devcheck
 from oracle.gen_golden import edge_scalars
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -71,17 +72,10 @@ def test_small_constant_product(fpcheck, model):
         assert 0 <= r < P + (P >> 13)                      # below 1.0002 p: offset subtractions with 2p are safe
         assert all(int(out[i]) <= LM for i in range(NL - 1)) and int(out[NL - 1]) < 1 << 22
 
-    edge = [0, 1, P - 1, P, P + 1, 2 * P - 1, 2 * P, (1 << 254) - 1, 1 << 253, (1 << 232) - 1, 1 << 232, (1 << 222) - 1, 1 << 222]
-    for q in range(1, 6100, 97):                           # values where 6042 a crosses a multiple of p
-        for d in (-1, 0, 1):
-            edge.append(max(0, (q * P + K - 1) // K + d))
-    for v in edge:
-        if v < 1 << 254:
-            check(v)
-    for _ in range(20000):
-        check(rnd.randrange(1 << 254))
-    for _ in range(5000):
-        check(rnd.randrange(P + P // 8))                   # the range product outputs live in
+    vals = devcheck.small_product_values(K, n_random=20000, n_product=5000)     # the device tests run a few hundred of the same set
+    assert len(vals) > 25000 and {0, P, 2 * P, (1 << 254) - 1, (P + K - 1) // K} <= set(vals)
+    for v in vals:
+        check(v)
 
 
 def test_mont_mul_values_and_limb_classes(fpcheck, model):
@@ -97,42 +91,29 @@ def test_mont_mul_values_and_limb_classes(fpcheck, model):
         assert r < a * b // R + P + 1                       # value bound every caller relies on
         assert all(int(out[i]) <= LM for i in range(NL - 1))  # class N
 
-    for _ in range(2000):
-        check(list(limbs(rnd.randrange(8 * P))), list(limbs(rnd.randrange(16 * P))))
     # limb-magnitude edge: D-class limbs (2^29 - 1 + largest offset limb) against S-class limbs (2 * (2^29 - 1))
     offs = (ctypes.c_uint32 * 81)()
     fpcheck.fpc_constants(offs)
+    assert [int(offs[9 * 6 + i]) for i in range(9)] == devcheck.FIELDS[9].offset(2)
     max_off = max(int(offs[9 * 6 + i]) for i in range(8))
     d_max, s_max = LM + max_off, 2 * LM
     assert 9 * d_max * s_max + 8 * (1 << 58) + (1 << 36) < (1 << 64)      # the accumulator bound stated in fp.hpp
-    check([d_max] * 8 + [1 << 22], [s_max] * 8 + [1 << 22])
-    check([s_max] * 8 + [1 << 22], [s_max] * 8 + [1 << 22])
-    check([LM] * 8 + [1 << 22], [(1 << 31) - 1] * 8 + [1 << 22])
-    for _ in range(500):
-        check([rnd.randrange(d_max + 1) for _ in range(8)] + [rnd.randrange(1 << 22)],
-              [rnd.randrange(s_max + 1) for _ in range(8)] + [rnd.randrange(1 << 22)])
-    # carry-folded quotient (fp.hpp): columns whose value is 0 or -1 modulo 2^29, zero operands, sparse operands
-    zero, one = [0] * NL, [1] + [0] * (NL - 1)
-    for la in (zero, one, [0, 1] + [0] * 7, [1 << 28] + [0] * 8, [LM] * NL, [0] * 8 + [1 << 22], list(limbs(P)), list(limbs(P - 1)), list(limbs(R % P)), list(limbs(R * R % P))):
-        for lb in (zero, one, [2] + [0] * 8, [LM] * 8 + [1 << 22], list(limbs(P)), list(limbs(P + 1)), list(limbs(R % P)), list(limbs(pow(R, 2, P))), [1 << 30] * 8 + [0]):
-            check(la, lb)
-    for _ in range(300):                                  # a_0 * b_0 = 0 (mod 2^29): column 0 takes q_0 = 2^29
-        la, lb = list(limbs(rnd.randrange(4 * P))), list(limbs(rnd.randrange(4 * P)))
-        la[0] &= ~((1 << rnd.randrange(1, 29)) - 1); lb[0] = (lb[0] << 20) & LM
+    # random values below 8p / 16p; D x S and S x S at their maximum and at random; the carry-folded quotient (fp.hpp): columns whose
+    # value is 0 or -1 modulo 2^29, zero operands, sparse operands; a_0 * b_0 = 0 (mod 2^29), where column 0 takes q_0 = 2^29
+    pairs = devcheck.mont_mul_pairs(9, n_random=2000, n_wide=500, n_col0=300)
+    assert ([d_max] * 8 + [1 << 22], [s_max] * 8 + [1 << 22]) in pairs and ([0] * 9, list(limbs(P))) in pairs and len(pairs) == 2000 + 3 + 500 + 90 + 300
+    for la, lb in pairs:
         check(la, lb)
 
 
 def test_field_helpers(fpcheck, model):
     P, rnd = model.P, random.Random(12)
     out = (ctypes.c_uint32 * NL)()
-    for _ in range(500):
-        ls = [rnd.randrange(1 << 32) for _ in range(8)] + [rnd.randrange(1 << 20)]
+    for ls, x, y, w in devcheck.helper_operands(9, 500):
         fpcheck.fpc_norm(raw(ls), out)
         assert val(out) == val(ls) and all(int(out[i]) <= LM for i in range(8))
-        x, y = rnd.randrange(2 * P), rnd.randrange(2 * P)
         fpcheck.fpc_sub2(limbs(x), limbs(y), out)
         assert val(out) == x - y + 2 * P
-        w = rnd.randrange(1 << 256)
         fpcheck.fpc_from_words32((ctypes.c_uint32 * 8)(*[(w >> (32 * i)) & 0xFFFFFFFF for i in range(8)]), out)
         assert val(out) == w and all(int(out[i]) <= LM for i in range(NL))
 

@@ -95,21 +95,15 @@ def test_device_field_377_on_the_host(fq377check):
     R, Q, L = 1 << (NL * LB), m.Q, fq377check
     rinv, rnd = pow(R, -1, Q), random.Random(1)
     out = (ctypes.c_uint32 * NL)()
-    for _ in range(1500):
-        a, b = rnd.randrange(8 * Q), rnd.randrange(8 * Q)
-        L.f377_mont_mul(limbs(a), limbs(b), out)
-        r = val(out)
+    # random values below 8q; zero / sparse columns of the carry-folded quotient; the widest legal operands (one normalised, the other
+    # with limbs up to 2^30.8) at their maximum and at random; column 0 = 0 (mod 2^29) -- the set the device tests run as well
+    import devcheck
+    pairs = devcheck.mont_mul_pairs(14, n_random=1500, n_wide=100, n_col0=100)
+    assert ([LM] * 13 + [7], [int(2 ** 30.8)] * 13 + [7]) in pairs and (list(limbs(Q)), list(limbs(R * R % Q))) in pairs and len(pairs) == 1500 + 2 + 100 + 108 + 100
+    for la, lb in pairs:
+        L.f377_mont_mul((ctypes.c_uint32 * NL)(*la), (ctypes.c_uint32 * NL)(*lb), out)
+        a, b, r = val(la), val(lb), val(out)
         assert r % Q == a * b * rinv % Q and r < a * b // R + Q + 1 and all(out[i] <= LM for i in range(NL - 1))
-    for a in (0, 1, Q, Q - 1, R % Q, 1 << 29, (1 << 29) - 1, 1 << 377):    # carry-folded quotient: zero / sparse columns
-        for b in (0, 1, 2, Q, Q + 1, R % Q, R * R % Q, (1 << 58) - (1 << 29)):
-            L.f377_mont_mul(limbs(a), limbs(b), out)
-            r = val(out)
-            assert r % Q == a * b * rinv % Q and r < a * b // R + Q + 1 and all(out[i] <= LM for i in range(NL - 1))
-    # widest legal operands: one normalised, the other with limbs up to 2^30.8
-    wide = (ctypes.c_uint32 * NL)(*([int(2 ** 30.8)] * 13 + [7]))
-    norm = (ctypes.c_uint32 * NL)(*([LM] * 13 + [7]))
-    L.f377_mont_mul(norm, wide, out)
-    assert val(out) % Q == val(norm) * val(wide) * rinv % Q
     assert L.f377_overflow_and_reset() == 0
     c = (ctypes.c_uint32 * (14 * NL))()
     L.f377_constants(c)
