@@ -206,3 +206,98 @@ def test_the_comparators_bite(N, dc_host, dc_pools, dc_dec):
         bad[:, :N], bad[:, N:2 * N] = mgood[:, N:2 * N], mgood[:, :N]
         with pytest.raises(AssertionError, match=name + ": element 0 word"):
             dc.compare_bits(name, bad, mgood, minp)
+
+
+# ---- the second table: check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp ------------------------------------------------------------
+def test_the_second_table_builds_and_exports(dc_host, pkg):
+    dc.build()
+    want = "".join("%s:%d:%d;" % (k, v[0], v[1]) for k, v in dc.OPS2.items())
+    assert dc.host_lib2().dc_table().decode() == want
+    cmd = dc.device_build_command(second=True)
+    mk = open(os.path.join(dc.PRODUCT_CSRC, "Makefile")).read()
+    assert "--offload-arch=gfx950" in cmd and "-O3" in cmd and all(f in mk for f in cmd[2:-4]), "built with the product's flags"
+    assert cmd[2:-2] == dc.device_build_command()[2:-2], "both device libraries take the same flags"
+    dev = dc.device_lib2()                              # loads without a GPU
+    assert dev.dc_table().decode() == want
+    assert all(hasattr(dev, "dc_" + name) for name in dc.OPS2)
+    blob = open(dc.DEV2_SO, "rb").read()
+    assert b"gfx950" in blob and b"k_dc_sqrt_ratio_9" in blob and b"k_dc_aff_group_377" in blob
+    text = open(os.path.join(dc.CSRC, "devcheck_ops2.hpp")).read()
+    assert "hip/" not in text and "csrc/scalar_mul.hip.hpp" in text
+    assert not set(dc.OPS) & set(dc.OPS2)
+
+
+@pytest.mark.parametrize("name", list(dc.OPS2))
+def test_the_second_table_against_bigints(name, dc_host, dc_pools, dc_dec):
+    """the host build of every operation of the second table on the operands the device test uses, pinned to Python integers and the
+    bigint models (devcheck.check_table2): zero tests, canonical conversions, inverses, roots of every 2-adic order, word compares, the
+    complete short-Weierstrass formulas with their exceptional pairs, the negating addition against ete_add<9> on (a, +-b), the order
+    chain on the whole curve, the offset recoding, the affine groups with infinity in every position, and the verdicts"""
+    inp = dc.table2_inputs(name)
+    dc.check_table2(name, inp, dc.run_host(name, inp), dc_dec)
+
+
+def test_the_second_table_comparators_bite(dc_host, dc_pools, dc_dec):
+    """outputs a wrong build would give, made from the host build's: a wrong verdict word, the other root, a to_canon output left at
+    value + modulus, a wrong digit, a finite point where infinity belongs, Y kept by the conditional negation -- each rejected by the
+    bigint pin or, where both answers are valid roots, by the bit-for-bit comparison"""
+    P = dc.FIELDS[9].P
+    good = {}
+
+    def outputs(name):
+        if name not in good:
+            inp = dc.table2_inputs(name)
+            good[name] = (inp, dc.run_host(name, inp))
+            dc.check_table2(name, inp, good[name][1], dc_dec)
+        return good[name][0], good[name][1].copy()
+    for name in ("is_zero_9", "is_zero_14", "words_lt_8", "words_lt_12", "check_form_te", "check_form_377_mont", "in_subgroup_te", "in_subgroup_377"):
+        for e in {"in_subgroup_te": (3, 7), "in_subgroup_377": (6, 9)}.get(name, (0, 3)):   # (a subgroup verdict is pinned on curve points only)
+            inp, bad = outputs(name)
+            bad[e, 0] = (int(bad[e, 0]) + 1) % (3 if name.startswith("check_form") else 2)
+            with pytest.raises(AssertionError, match=r"%s: element %d: " % (name, e)):
+                dc.check_table2(name, inp, bad, dc_dec)
+            with pytest.raises(AssertionError, match=r"%s: element %d word 0" % (name, e)):
+                dc.compare_bits(name, bad, good[name][1], inp)
+    # the other root: as good a root for the bigint pin -- only the comparison with the host build's words notices
+    for name, N in (("sqrt_ratio_9", 9), ("sqrt_14", 14)):
+        inp, bad = outputs(name)
+        F = dc.FIELDS[N]
+        e = 5
+        assert dc.unmont(N, bad[e, 1:]) != 0
+        bad[e, 1:] = F.limbs(F.P - F.val(bad[e, 1:]) % F.P)
+        dc.check_table2(name, inp, bad, dc_dec)
+        with pytest.raises(AssertionError, match=r"%s: element %d word 1" % (name, e)):
+            dc.compare_bits(name, bad, good[name][1], inp)
+        bad = good[name][1].copy()                                          # the flag of a non-square
+        e = next(i for i in range(len(bad)) if bad[i, 0] == 0)
+        bad[e, 0] = 1
+        with pytest.raises(AssertionError, match=r"%s: element %d: flag 1" % (name, e)):
+            dc.check_table2(name, inp, bad, dc_dec)
+    # fe_to_canon without its conditional subtraction: value + modulus wherever the input was the larger representative
+    for name, N, nw in (("to_canon_9", 9, 8), ("to_canon_14", 14, 12)):
+        inp, bad = outputs(name)
+        F = dc.FIELDS[N]
+        e = next(i for i in range(len(inp)) if F.val(inp[i]) * F.rinv % F.P + F.P < 1 << (32 * nw))
+        v = sum(int(x) << (32 * i) for i, x in enumerate(bad[e])) + F.P
+        bad[e] = dc.words32(v, nw)
+        with pytest.raises(AssertionError, match=r"%s: element %d: .*it is that \+ the modulus" % (name, e)):
+            dc.check_table2(name, inp, bad, dc_dec)
+    inp, bad = outputs("sm_digits")
+    bad[7, 9 + 64] = np.uint32((int(bad[7, 9 + 64]) + 1) & 0xFFFFFFFF)
+    with pytest.raises(AssertionError, match=r"sm_digits: element 7: "):
+        dc.check_table2("sm_digits", inp, bad, dc_dec)
+    inp, bad = outputs("aff_group_377")
+    cases = dc.aff_cases(1)
+    e = next(i for i, (slots, cnt) in enumerate(cases) if cnt == 8 and dc.sw_pool().pts[slots[0]] is None and dc.sw_pool().pts[slots[1]] is not None)
+    bad[e, :24] = bad[e, 24:48]
+    with pytest.raises(AssertionError, match=r"aff_group_377: element %d: cnt = 8, slot 0 \(infinity\)" % e):
+        dc.check_table2("aff_group_377", inp, bad, dc_dec)
+    inp, bad = outputs("sw_cneg")
+    e = next(i for i in range(len(inp)) if inp[i, 42] == 1 and dc.sw_pool().pts[i // 4] is not None)
+    bad[e] = inp[e, :42]
+    with pytest.raises(AssertionError, match=r"sw_cneg: element %d: " % e):
+        dc.check_table2("sw_cneg", inp, bad, dc_dec)
+    inp, bad = outputs("add_cneg")
+    bad[[2, 3]] = bad[[3, 2]]                                               # O + P and O - P exchanged: the sign ignored
+    with pytest.raises(AssertionError, match=r"add_cneg: element [23]: "):
+        dc.check_table2("add_cneg", inp, bad, dc_dec)

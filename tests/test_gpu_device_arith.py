@@ -197,3 +197,31 @@ def test_reduce_tail_rows(N, dc_dev, dc_dec, dc_pools):
                             want.append(dc.msum(N, [dc.mmul(N, v, dc.msum(N, ps)) for v, ps in M.items() if v]))
                         for slot in range(5):
                             dc_dec.check(op, N, rows[5 * k + slot], want[slot], "%s, window %d, %s" % (what, k, "T" if slot == 0 else "W%d" % (slot - 1)))
+
+
+# ---- the second table: check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp ------------------------------------------------------------
+BLOCK_EDGE_COUNTS = (1, 255, 256, 257)
+
+
+@pytest.mark.parametrize("name", list(dc.OPS2))
+def test_second_table_operations_equal_the_host_build(name, dc_host):
+    """every operation of the second table (tests/csrc/devcheck_ops2.hpp): the gfx950 compilation gives the host compilation's words bit
+    for bit -- on the operation's whole operand set (a few hundred elements, pinned to bigints by tests/test_device_arith_host.py) and on
+    1, 255, 256 and 257 elements of it, rotated so that its first operand, an edge of the contract, sits in the last lane of a full block,
+    alone in a block, and in a part-filled block"""
+    assert dc.device_lib2().dc_table() == dc.host_lib2().dc_table()
+    inp = dc.table2_inputs(name)
+    sets = [("all %d elements" % len(inp), inp)]
+    for n in BLOCK_EDGE_COUNTS:
+        reps = -(-n // len(inp)) + 1
+        rows = np.roll(np.tile(inp, (reps, 1)), n - 1, axis=0)[:n]
+        assert (rows[n - 1] == inp[0]).all()
+        sets.append(("%d elements" % n, rows))
+    failures = []
+    for what, rows in sets:
+        got, want = dc.run_device(name, rows), dc.run_host(name, rows)
+        try:
+            dc.compare_bits("%s, %s" % (name, what), got, want, rows)
+        except AssertionError as e:
+            failures.append(str(e))
+    assert not failures, "\n".join(failures)

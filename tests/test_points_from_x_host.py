@@ -2,6 +2,8 @@
 compiled for the host by tests/csrc/fromxcheck.cpp -- the same functions k_points_from_x runs on gfx950) against the reference's
 getPointFromX known answers and the bigint models, on every class of bad x, and the new names of the C header and the package."""
 import ctypes
+import functools
+import json
 import os
 import random
 import re
@@ -58,62 +60,6 @@ def is_qr(a, p):
     return a % p == 0 or pow(a, (p - 1) // 2, p) == 1
 
 
-# ---- Twisted-Edwards BLS12 ---------------------------------------------------------------------------------------------------------
-def test_reference_point_from_x_kats(fx, kats):
-    assert len(kats["point_from_x"]) == 6
-    for k in kats["point_from_x"]:
-        x, y = int(k["x"]), int(k["y"])
-        assert recover_te(fx, x) == (0, (x, y))
-
-
-def test_recovery_gives_back_subgroup_points(fx):
-    pts = oracle.gen_points(0xF00D, 1000) + oracle.gen_points_random(0xF00E, 1000)
-    for i in range(2000):
-        x, y = m.xy_from_bytes(pts[64 * i:64 * i + 64])
-        assert recover_te(fx, x) == (0, (x, y)), i
-    assert recover_te(fx, 0) == (0, (0, 1))
-    assert recover_te(fx, m.GX) == (0, (m.GX, m.GY))
-
-
-def test_bad_x_reasons(fx):
-    for x in (m.P, m.P + 1, (1 << 256) - 1):
-        assert recover_te(fx, x)[0] == 1, x
-    rng = random.Random(3)
-    nonres = [x for x in (rng.randrange(m.P) for _ in range(40)) if not is_qr(te_y2(x), m.P)][:6]
-    assert len(nonres) >= 3
-    for x in nonres:
-        assert recover_te(fx, x)[0] == 2, x
-    i4 = m.sqrt_mod_p(m.P - 1)
-    T4 = (i4, 0)
-    assert m.on_curve(T4) and m.add(T4, T4) == (0, m.P - 1)
-    assert recover_te(fx, i4)[0] == 3 and recover_te(fx, m.P - i4)[0] == 3       # +-sqrt(-1): y = 0, order 4
-    P = m.xy_from_bytes(oracle.gen_points(21, 1))
-    for T in (T4, m.neg(T4)):                                                     # P + T4, P - T4
-        PT = m.add(P, T)
-        assert m.on_curve(PT) and m.scalar_mul(m.L, PT) != m.ZERO
-        assert recover_te(fx, PT[0])[0] == 3
-
-
-def test_order_two_shift_recovers_the_negated_point(fx):
-    """P + T2 = (-x, -y): its x recovers -P = (-x, y), the point of the subgroup with that x (one chain, Q = T2: take -y)"""
-    for seed in (31, 32, 33):
-        P = m.xy_from_bytes(oracle.gen_points(seed, 1))
-        PT = m.add(P, (0, m.P - 1))
-        assert PT == ((-P[0]) % m.P, (-P[1]) % m.P)
-        assert recover_te(fx, PT[0]) == (0, ((-P[0]) % m.P, P[1]))
-
-
-def test_model_point_from_x_differs_only_outside_the_subgroup(fx):
-    """getPointFromX (oracle.model.point_from_x) agrees wherever a subgroup point exists; on an order-4 coset it returns (x, -y) while
-    the engine reports reason 3"""
-    P = m.xy_from_bytes(oracle.gen_points(41, 1))
-    assert recover_te(fx, P[0]) == (0, m.point_from_x(P[0]))
-    PT = m.add(P, (m.sqrt_mod_p(m.P - 1), 0))
-    assert m.point_from_x(PT[0])[0] == PT[0]                 # the reference answers something ...
-    assert recover_te(fx, PT[0])[0] == 3                     # ... the engine refuses
-
-
-# ---- square roots in both fields --------------------------------------------------------------------------------------------------
 def two_adic_order(a, p):
     t, s = p - 1, 0
     while t % 2 == 0:
@@ -131,6 +77,188 @@ def smallest_nonresidue(p):
     return z
 
 
+def two_adic_radicands(p, per_k=3, seed=17):
+    """(k, r) for every k = 0 .. S (p - 1 = 2^S t): per_k field elements r = zeta_k h^(2^S) whose 2-adic order is exactly k -- r^t has
+    order 2^k -- with zeta_k an odd power of Z^(t 2^(S - k)); k = S are non-squares.  Step i of the uniform root loop takes its
+    `e1 = false` arm exactly where the remaining order reaches i, so the sweep drives every step through both arms; random field
+    elements have order k with probability 2^-(S + 1 - k) and never reach the late steps."""
+    t, S = p - 1, 0
+    while t % 2 == 0:
+        t, S = t // 2, S + 1
+    c = pow(smallest_nonresidue(p), t, p)                  # of order 2^S
+    rnd = random.Random(seed)
+    out = []
+    for k in range(S + 1):
+        for _ in range(per_k):
+            zeta = pow(c, (1 << (S - k)) * (2 * rnd.randrange(1 << 20) + 1), p)
+            r = zeta * pow(rnd.randrange(2, p), 1 << S, p) % p
+            assert two_adic_order(r, p) == (k, S)
+            out.append((k, r))
+    return out
+
+
+# ---- the edge classes of both curves, shared with the GPU tests: (name, x bytes, expected reason code or expected point bytes) ----
+def _te_subgroup_point_of(x, y):
+    """what recovery must answer for the curve point (x, +-y): the root in the subgroup, or reason 3 (neither is: an order-4 coset)"""
+    for cand in (y, (-y) % m.P):
+        if m.scalar_mul(m.L, (x, cand)) == m.ZERO:
+            return m.points_to_bytes([(x, cand)])
+    return 3
+
+
+def te_two_adic_x(k, seed=29):
+    """an x whose y^2 = (1 + x^2) / (1 - d x^2) has exact 2-adic order k < 47: r = zeta_k h^(2^47), x^2 = (r - 1) / (1 + d r), retried
+    until x^2 is a square; returns (x, r, tries)"""
+    p = m.P
+    c = pow(smallest_nonresidue(p), (p - 1) >> 47, p)
+    rnd = random.Random(seed * 64 + k)
+    for tries in range(1, 40):
+        r = pow(c, (1 << (47 - k)) * (2 * rnd.randrange(1 << 20) + 1), p) * pow(rnd.randrange(2, p), 1 << 47, p) % p
+        den = (1 + m.D * r) % p
+        if den == 0 or r == 1:
+            continue
+        x2 = (r - 1) * pow(den, -1, p) % p
+        x = m.sqrt_mod_p(x2)
+        if x is not None:
+            assert te_y2(x) == r and two_adic_order(r, p) == (k, 47)
+            return x, r, tries
+    raise AssertionError("no x for 2-adic order %d" % k)
+
+
+@functools.lru_cache(maxsize=None)
+def te_x_classes():
+    le = lambda v: int(v).to_bytes(32, "little")
+    kats = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_kats.json")))["point_from_x"]
+    out = [("x=0", le(0), m.points_to_bytes([(0, 1)])), ("GX", le(m.GX), m.points_to_bytes([(m.GX, m.GY)]))]
+    out += [("reference kat %d" % i, le(int(k["x"])), m.points_to_bytes([(int(k["x"]), int(k["y"]))])) for i, k in enumerate(kats)]
+    for seed in (31, 32, 33):                              # P + T2 = (-x, -y): its x recovers -P = (-x, y)
+        P = m.xy_from_bytes(oracle.gen_points(seed, 1))
+        PT = m.add(P, (0, m.P - 1))
+        assert PT == ((-P[0]) % m.P, (-P[1]) % m.P)
+        out.append(("x of P+T2 (seed %d)" % seed, le(PT[0]), m.points_to_bytes([((-P[0]) % m.P, P[1])])))
+    i4 = m.sqrt_mod_p(m.P - 1)
+    T4 = (i4, 0)
+    assert m.on_curve(T4) and m.add(T4, T4) == (0, m.P - 1)
+    out += [("+sqrt(-1)", le(i4), 3), ("-sqrt(-1)", le(m.P - i4), 3)]          # y = 0, order 4
+    P = m.xy_from_bytes(oracle.gen_points(21, 1))
+    for name, T in (("x of P+T4", T4), ("x of P-T4", m.neg(T4))):
+        PT = m.add(P, T)
+        assert m.on_curve(PT) and m.scalar_mul(m.L, PT) != m.ZERO
+        out.append((name, le(PT[0]), 3))
+    out += [("x=p", le(m.P), 1), ("x=p+1", le(m.P + 1), 1), ("x=2^256-1", le((1 << 256) - 1), 1)]
+    rng = random.Random(3)
+    nonres = [x for x in (rng.randrange(m.P) for _ in range(40)) if not is_qr(te_y2(x), m.P)][:6]
+    assert len(nonres) >= 3
+    out += [("non-residue %d" % i, le(x), 2) for i, x in enumerate(nonres)]
+    for k in range(47):
+        x, r, tries = te_two_adic_x(k)
+        assert tries <= 12
+        out.append(("y^2 of 2-adic order %d" % k, le(x), _te_subgroup_point_of(x, m.sqrt_mod_p(r))))
+    return out
+
+
+def bls_w_zero_x(s):
+    """the x with s x + s + 1 = 0, where the engine's map to the twisted-Edwards form is undefined (s = 1 / sqrt(3) as the headers hold it)"""
+    assert 3 * s * s % b.Q == 1
+    x = (-1 - pow(s, -1, b.Q)) % b.Q
+    assert (s * x + s + 1) % b.Q == 0 and is_qr(x ** 3 + 1, b.Q), "a root exists: only the map's w = 0 rejects this x"
+    return x
+
+
+RESERVED_BITS = (1, 2, 4, 8, 16, 31)                       # bits 377 .. 381
+
+
+@functools.lru_cache(maxsize=None)
+def bls_x_classes(s):
+    out = []
+    pts = oracle377.gen_points(9, 40) + b.points_to_bytes([b.G])
+    for i in range(len(pts) // 96):
+        x, y = b.xy_from_bytes(pts[96 * i:96 * i + 96])
+        yl, ys = max(y, b.Q - y), min(y, b.Q - y)
+        who = "G" if i == 40 else "point %d" % i
+        out += [(who + " larger root", x377(x, larger=True), b.le48(x) + b.le48(yl)), (who + " smaller root", x377(x, larger=False), b.le48(x) + b.le48(ys)),
+                (who + " its own root", x377(x, larger=y > b.Q - y), b.le48(x) + b.le48(y))]
+    out += [("x=0 smaller root", x377(0), b.le48(0) + b.le48(1)), ("x=0 larger root", x377(0, larger=True), b.le48(0) + b.le48(b.Q - 1))]
+    out += [("x=q-1 (y=0)", x377(b.Q - 1), 2), ("x=q-1 (y=0) larger", x377(b.Q - 1, larger=True), 2)]
+    G = b.G
+    for extra in RESERVED_BITS:
+        out += [("reserved bits %d" % extra, x377(G[0], extra=extra), 1),
+                ("reserved bits %d with both flags" % extra, x377(G[0], larger=True, infinity=True, extra=extra), 1)]
+    out += [("x=q", x377(b.Q), 1), ("x=q+1", x377(b.Q + 1), 1), ("x=2^377-1", x377((1 << 377) - 1), 1)]
+    out += [("infinity flag on GX", x377(G[0], infinity=True), 2), ("infinity flag on x=0", x377(0, infinity=True), 2),
+            ("the bare infinity flag", bytes(47) + b"\x40", 2)]
+    rng = random.Random(8)
+    nonres = [x for x in (rng.randrange(b.Q) for _ in range(40)) if not is_qr(x ** 3 + 1, b.Q)][:6]
+    assert len(nonres) >= 3
+    for i, x in enumerate(nonres):
+        out += [("non-residue %d" % i, x377(x), 2), ("non-residue %d larger" % i, x377(x, larger=True), 2)]
+    xw = bls_w_zero_x(s)
+    out += [("s x + s + 1 = 0", x377(xw), 2), ("s x + s + 1 = 0 larger", x377(xw, larger=True), 2)]
+    return out
+
+
+# ---- Twisted-Edwards BLS12 ---------------------------------------------------------------------------------------------------------
+def test_reference_point_from_x_kats(fx, kats):
+    assert len(kats["point_from_x"]) == 6
+    for k in kats["point_from_x"]:
+        x, y = int(k["x"]), int(k["y"])
+        assert recover_te(fx, x) == (0, (x, y))
+
+
+def test_recovery_gives_back_subgroup_points(fx):
+    pts = oracle.gen_points(0xF00D, 1000) + oracle.gen_points_random(0xF00E, 1000)
+    for i in range(2000):
+        x, y = m.xy_from_bytes(pts[64 * i:64 * i + 64])
+        assert recover_te(fx, x) == (0, (x, y)), i
+    assert recover_te(fx, 0) == (0, (0, 1))
+    assert recover_te(fx, m.GX) == (0, (m.GX, m.GY))
+
+
+def _run_te_class(fx, x32, want):
+    out = ctypes.create_string_buffer(64)
+    r = fx.fx_from_x_te(x32, out)
+    return (r == want) if isinstance(want, int) else (r == 0 and out.raw == want)
+
+
+def test_bad_x_reasons(fx):
+    bad = [(name, x, want) for name, x, want in te_x_classes() if isinstance(want, int)]
+    names = [name for name, _, _ in bad]
+    assert {"x=p", "x=p+1", "x=2^256-1", "+sqrt(-1)", "-sqrt(-1)", "x of P+T4", "x of P-T4"} <= set(names)
+    assert sum(1 for _, _, want in bad if want == 1) == 3 and sum(1 for n in names if n.startswith("non-residue")) >= 3
+    for name, x, want in bad:
+        assert recover_te(fx, int.from_bytes(x, "little"))[0] == want, name
+
+
+def test_order_two_shift_recovers_the_negated_point(fx):
+    """P + T2 = (-x, -y): its x recovers -P = (-x, y), the point of the subgroup with that x (one chain, Q = T2: take -y)"""
+    shifted = [(name, x, want) for name, x, want in te_x_classes() if name.startswith("x of P+T2")]
+    assert len(shifted) == 3
+    for name, x, want in shifted:
+        assert recover_te(fx, int.from_bytes(x, "little")) == (0, m.xy_from_bytes(want)), name
+
+
+def test_every_te_edge_class_and_the_two_adic_sweep_of_y2(fx):
+    """every class the GPU tests feed (te_x_classes), the 47 x whose y^2 has exact 2-adic order 0 .. 46 included: recovered bytes or reason
+    as the bigint model gives them ([L] P decides the root and the order-4 cosets)"""
+    classes = te_x_classes()
+    sweep = [c for c in classes if c[0].startswith("y^2 of 2-adic order")]
+    assert len(sweep) == 47 and len(classes) >= 2 + 6 + 3 + 4 + 3 + 3 + 47
+    assert {want if isinstance(want, int) else 0 for _, _, want in sweep} >= {0, 3}, "the sweep meets both roots' cosets"
+    for name, x, want in classes:
+        assert _run_te_class(fx, x, want), name
+
+
+def test_model_point_from_x_differs_only_outside_the_subgroup(fx):
+    """getPointFromX (oracle.model.point_from_x) agrees wherever a subgroup point exists; on an order-4 coset it returns (x, -y) while
+    the engine reports reason 3"""
+    P = m.xy_from_bytes(oracle.gen_points(41, 1))
+    assert recover_te(fx, P[0]) == (0, m.point_from_x(P[0]))
+    PT = m.add(P, (m.sqrt_mod_p(m.P - 1), 0))
+    assert m.point_from_x(PT[0])[0] == PT[0]                 # the reference answers something ...
+    assert recover_te(fx, PT[0])[0] == 3                     # ... the engine refuses
+
+
+# ---- square roots in both fields --------------------------------------------------------------------------------------------------
 def test_sqrt_ratio_te_matches_the_model(fx):
     p = m.P
     z = smallest_nonresidue(p)
@@ -170,34 +298,52 @@ def test_sqrt_377_matches_the_model(fx):
             assert got * got % q == z * u % q, u
 
 
+def test_sqrt_ratio_te_two_adic_sweep(fx):
+    """every 2-adic order k = 0 .. 47 of u / v, three radicands each: step i of the loop takes both arms"""
+    p, z, rng = m.P, smallest_nonresidue(m.P), random.Random(15)
+    y = ctypes.create_string_buffer(32)
+    for k, r in two_adic_radicands(p):
+        v = rng.randrange(1, p)
+        u = r * v % p
+        qr = fx.fx_sqrt_ratio_te(u.to_bytes(32, "little"), v.to_bytes(32, "little"), y)
+        got = int.from_bytes(y.raw, "little")
+        assert got < p and bool(qr) == (k < 47), k
+        assert got * got % p == (r if qr else z * r % p), k
+
+
+def test_sqrt_377_two_adic_sweep(fx):
+    q, z = b.Q, smallest_nonresidue(b.Q)
+    y = ctypes.create_string_buffer(48)
+    for k, u in two_adic_radicands(q):
+        qr = fx.fx_sqrt_377(u.to_bytes(48, "little"), y)
+        got = int.from_bytes(y.raw, "little")
+        assert got < q and bool(qr) == (k < 46), k
+        assert got * got % q == (u if qr else z * u % q), k
+
+
 # ---- BLS12-377 G1 ---------------------------------------------------------------------------------------------------------------
-def test_bls377_flags_pick_the_root(fx):
-    pts = oracle377.gen_points(9, 40) + b.points_to_bytes([b.G])
-    for i in range(len(pts) // 96):
-        x, y = b.xy_from_bytes(pts[96 * i:96 * i + 96])
-        yl, ys = max(y, b.Q - y), min(y, b.Q - y)
-        assert recover_377(fx, x377(x, larger=True)) == (0, (x, yl)), i
-        assert recover_377(fx, x377(x, larger=False)) == (0, (x, ys)), i
-        assert recover_377(fx, x377(x, larger=y > b.Q - y)) == (0, (x, y)), i
+def _s377(fq377check):
+    from test_oracle_bls377 import _edwards_consts
+    return _edwards_consts(fq377check)[0]
 
 
-def test_bls377_bad_x_reasons(fx):
-    G = b.G
-    for extra in (1, 2, 4, 8, 16, 31):                                             # bits 377 .. 381
-        assert recover_377(fx, x377(G[0], extra=extra))[0] == 1, extra
-        assert recover_377(fx, x377(G[0], larger=True, infinity=True, extra=extra))[0] == 1, extra
-    for x in (b.Q, b.Q + 1, (1 << 377) - 1):
-        assert recover_377(fx, x377(x))[0] == 1, x
-    assert recover_377(fx, x377(G[0], infinity=True))[0] == 2
-    assert recover_377(fx, x377(0, infinity=True))[0] == 2
-    assert recover_377(fx, bytes(47) + b"\x40")[0] == 2                           # the bare infinity flag
-    rng = random.Random(8)
-    nonres = [x for x in (rng.randrange(b.Q) for _ in range(40)) if not is_qr(x ** 3 + 1, b.Q)][:6]
-    assert len(nonres) >= 3
-    for x in nonres:
-        assert recover_377(fx, x377(x))[0] == 2 and recover_377(fx, x377(x, larger=True))[0] == 2
-    assert recover_377(fx, x377(b.Q - 1))[0] == 2 and recover_377(fx, x377(b.Q - 1, larger=True))[0] == 2   # x = -1: y = 0
+def test_bls377_flags_pick_the_root(fx, fq377check):
+    picks = [c for c in bls_x_classes(_s377(fq377check)) if c[0].endswith(" root")]
+    assert len(picks) == 3 * 41 + 2
+    for name, x48, want in picks:
+        assert recover_377(fx, x48) == (0, b.xy_from_bytes(want)), name
     assert recover_377(fx, x377(0)) == (0, (0, 1)) and recover_377(fx, x377(0, larger=True)) == (0, (0, b.Q - 1))
+
+
+def test_bls377_bad_x_reasons(fx, fq377check):
+    bad = [c for c in bls_x_classes(_s377(fq377check)) if isinstance(c[2], int)]
+    names = {name for name, _, _ in bad}
+    assert {"reserved bits %d" % e for e in RESERVED_BITS} | {"reserved bits %d with both flags" % e for e in RESERVED_BITS} <= names
+    assert {"x=q", "x=q+1", "x=2^377-1", "infinity flag on GX", "infinity flag on x=0", "the bare infinity flag", "x=q-1 (y=0)",
+            "x=q-1 (y=0) larger", "s x + s + 1 = 0", "s x + s + 1 = 0 larger"} <= names
+    assert sum(1 for n in names if n.startswith("non-residue")) >= 6
+    for name, x48, want in bad:
+        assert recover_377(fx, x48)[0] == want, name
 
 
 def test_bls377_recovered_points_pass_the_form_check(fx):

@@ -65,6 +65,54 @@ def sqrt_minus_one():
 
 
 EDGE_TE = [0, 1, 2, m.L - 1, m.L, m.L + 1, 4 * m.L, b.R_ORDER, 1 << 255, TOP]
+EDGE_377 = [0, 1, 2, b.R_ORDER - 1, b.R_ORDER, b.R_ORDER + 1, 2 * b.R_ORDER, 1 << 255, TOP, int("01" * 128, 2), int("10" * 128, 2)]
+
+
+def digit_pattern_scalars():
+    """2-bit signed windows take digits -2, -1, 0, 1: a scalar of one repeated window value u gives every digit u - 2 in every position;
+    mixtures and alternations flip the sign from window to window; single bits and 2^256 - 2^i carry through the offset recoding"""
+    ks = [int(format(u, "02b") * 128, 2) for u in range(4)]
+    ks += [int("0110" * 64, 2), int("1001" * 64, 2), int("0011" * 64, 2), int("1100" * 64, 2), int("01" + "10" * 127, 2)]
+    ks += [(1 << i) for i in (0, 1, 2, 3, 127, 254, 255)] + [(1 << 256) - (1 << i) for i in (1, 2, 128)]
+    return ks
+
+
+def te_torsion_points():
+    """(name, point) outside the subgroup: T2 = (0, -1) of order 2, both T4 = (+-sqrt(-1), 0) of order 4, G + T2 (order 2 L), G + T4 (4 L)"""
+    i4 = sqrt_minus_one()
+    t2, t4a, t4b = (0, m.P - 1), (i4, 0), (m.P - i4, 0)
+    g = (m.GX, m.GY)
+    out = [("T2", t2), ("T4", t4a), ("-T4", t4b), ("G+T2", m.add(g, t2)), ("G+T4", m.add(g, t4a))]
+    for _, p in out:
+        assert m.on_curve(p)
+    return out
+
+
+def te_edge_cases(n_subgroup=4):
+    """(name, point bytes, scalar, expected bytes): the cross product of every edge and digit-pattern scalar with subgroup points, O = (0, 1) and
+    the torsion points, from the bigint model -- a few hundred elements, shared with the GPU tests"""
+    pts = [("subgroup point %d" % i, p) for i, p in enumerate(te_points(0xA16, n_subgroup))] + [("O", (0, 1))] + te_torsion_points()
+    ks = [("edge scalar %d" % i, k) for i, k in enumerate(EDGE_TE)] + [("digit pattern %d" % i, k) for i, k in enumerate(digit_pattern_scalars())]
+    return [("%s x %s" % (kn, pn), m.points_to_bytes([p]), k, m.points_to_bytes([m.scalar_mul(k, p)])) for kn, k in ks for pn, p in pts]
+
+
+def bls_edge_cases():
+    """(name, points bytes, scalars, expected bytes) for n = 1, 7, 8, 9, 15, 16, 17, 19 -- every tail shape of the affine groups of 8 -- with the
+    edge scalars in turn and scalars r or 0 placed so that infinity falls on the first slot, the last slot, a middle slot and a whole group"""
+    r = b.R_ORDER
+    out = []
+    for n in (1, 7, 8, 9, 15, 16, 17, 19):
+        raw = oracle377.gen_points(0x3E + n, n)
+        pts = [b.xy_from_bytes(raw[96 * i:96 * i + 96]) for i in range(n)]
+        plans = {"edge scalars": [EDGE_377[(i + n) % len(EDGE_377)] for i in range(n)],
+                 "infinity first": [r if i == 0 else 1000 + i for i in range(n)],
+                 "infinity last": [0 if i == n - 1 else 1000 + i for i in range(n)],
+                 "infinity in the middle": [r if i == n // 2 or i % 8 == 3 else 1000 + i for i in range(n)],
+                 "a whole group at infinity": [(0, r)[i & 1] if i < 8 else 1000 + i for i in range(n)],
+                 "the last group at infinity": [2 * r if i >= 8 * ((n - 1) // 8) else 1000 + i for i in range(n)]}
+        for what, ks in plans.items():
+            out.append(("n = %d, %s" % (n, what), raw, ks, b"".join(b.result_to_bytes(b.scalar_mul(k, p)) for k, p in zip(ks, pts))))
+    return out
 
 
 # ---- Twisted-Edwards BLS12 -----------------------------------------------------------------------------------------------------
@@ -111,9 +159,8 @@ def test_edge_scalars_both_recodings(sm):
 def test_digit_patterns_hit_every_table_entry_and_sign(sm):
     # 2-bit signed windows take digits -2, -1, 0, 1: a scalar of one repeated window value u gives every digit u - 2 in every
     # position; mixtures and alternations flip the sign from window to window
-    ks = [int(format(u, "02b") * 128, 2) for u in range(4)]
-    ks += [int("0110" * 64, 2), int("1001" * 64, 2), int("0011" * 64, 2), int("1100" * 64, 2), int("01" + "10" * 127, 2)]
-    ks += [(1 << i) for i in (0, 1, 2, 3, 127, 254, 255)] + [(1 << 256) - (1 << i) for i in (1, 2, 128)]
+    ks = digit_pattern_scalars()
+    assert len(ks) == 19
     pts = te_points(0xA14, len(ks))
     assert mul_te(sm, pts, ks) == [m.scalar_mul(k, p) for k, p in zip(ks, pts)]
     for k in ks[:4]:
@@ -121,13 +168,7 @@ def test_digit_patterns_hit_every_table_entry_and_sign(sm):
 
 
 def test_points_outside_the_subgroup(sm):
-    i4 = sqrt_minus_one()
-    t2, t4a, t4b = (0, m.P - 1), (i4, 0), (m.P - i4, 0)
-    g = (m.GX, m.GY)
-    g2l = m.add(g, t2)                                 # order 2 L
-    g4l = m.add(g, t4a)                                # order 4 L
-    for p in (t2, t4a, t4b, g2l, g4l):
-        assert m.on_curve(p)
+    t2, t4a, t4b, g2l, g4l = (p for _, p in te_torsion_points())       # g2l of order 2 L, g4l of order 4 L
     assert m.scalar_mul(4, t4a) == (0, 1) and m.scalar_mul(2, t4a) == t2
     assert m.scalar_mul(2 * m.L, g2l) == (0, 1) and m.scalar_mul(m.L, g2l) == t2
     pts = [t2, t4a, t4b, g2l, g4l]
@@ -177,8 +218,8 @@ def test_bls377_random_points_and_scalars(sm):
 
 
 def test_bls377_edge_scalars_and_infinity(sm):
-    r = b.R_ORDER
-    ks = [0, 1, 2, r - 1, r, r + 1, 2 * r, 1 << 255, TOP, int("01" * 128, 2), int("10" * 128, 2)]
+    ks = EDGE_377
+    assert len(ks) == 11 and ks[4] == b.R_ORDER
     raw = oracle377.gen_points(12, len(ks))
     pts = [b.xy_from_bytes(raw[96 * i:96 * i + 96]) for i in range(len(ks))]
     got = mul_377(sm, raw, ks)
@@ -194,6 +235,20 @@ def test_bls377_infinity_among_finite_results_keeps_the_neighbours_right(sm):
     pts = [b.xy_from_bytes(raw[96 * i:96 * i + 96]) for i in range(16)]
     ks = [(b.R_ORDER if i % 3 == 1 else 1000 + i) for i in range(16)]
     assert mul_377(sm, raw, ks) == b"".join(b.result_to_bytes(b.scalar_mul(k, p)) for k, p in zip(ks, pts))
+
+
+def test_the_shared_edge_cases_on_the_host(sm):
+    """the case builders the GPU tests import, through the host build: per-point scalars over the whole cross product, the shared form on one
+    row of it, every BLS12-377 tail shape with infinity at the first, last and middle slots and over whole groups"""
+    cases = te_edge_cases()
+    assert 200 <= len(cases) <= 400
+    pts = [m.xy_from_bytes(c[1]) for c in cases]
+    got = mul_te(sm, pts, [c[2] for c in cases])
+    for c, g in zip(cases, got):
+        assert m.points_to_bytes([g]) == c[3], c[0]
+    for name, raw, ks, want in bls_edge_cases():
+        assert mul_377(sm, raw, ks) == want, name
+        assert want.count(bytes(96)) >= (0 if "edge scalars" in name and len(ks) < 3 else 1), name
 
 
 # ---- the public names -----------------------------------------------------------------------------------------------------------
