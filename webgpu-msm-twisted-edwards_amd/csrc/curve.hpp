@@ -142,43 +142,95 @@ template <int N> TE_HD ete_t<N> ete_close(const fel<N>& E, const fel<N>& H, cons
 // With A' = (Y1-X1)(y2-x2)/2, B' = (Y1+X1)(y2+x2)/2:  E = B'-A' = X1 y2 + Y1 x2,
 // H = B'+A' = Y1 y2 + X1 x2, C = d T1 x2 y2, F = Z1 - C, G = Z1 + C;  (X3,Y3,T3,Z3) = (EF, HG, EH, GF).
 // The record holds -d x2 y2, so the product below is C' = -C and F = Z1 + C' is a SUM, G = Z1 - C' the difference.
-// Limb classes: A' = D x N, B' = S x N, C' = N x (<2^30.6);  E and G are D (differences in offset form), H and F are S.
+//
+// The accumulator enters the addition OPENED: (U, V, Z, T) with U = Y1 - X1 (offset form, + 2p) and V = Y1 + X1, the first operands
+// of A' and B' -- ete_open, 27 limb operations right behind the closing products of the addition before.  In this form the NEGATIVE
+// of the accumulator is cheap: -(X, Y) = (-X, Y) swaps U and V and negates T (ete_uv_neg: 2p - T in offset form), and that is how
+// k_accumulate subtracts a point: Q - P = -((-Q) + P).  A lane keeps a flag "my accumulator stands for its negative", negates the
+// opened accumulator only where an entry's sign differs from the flag, and ALWAYS adds the record as loaded (no pnt_cneg, whose 9
+// subtractions and 27 selects every entry paid).
+// Limb classes: U is D (limbs < 2^30.6), V is S (< 2^30) -- or the other way round behind a negation -- and T is N or, negated,
+// 2p - T with limbs < 2^30 (T is a product output below 1.1p < 2p); each meets a record field, class N ALWAYS (no negated dt any
+// more): D x N, S x N, (< 2^30) x N, the pairings of the addition so far with the wide operand on the accumulator's side.  Every
+// addition closes into fresh product outputs (class N, below 1.1p), so nothing accumulates from one negation to the next, and
+// with 14 limbs the rule "one operand of every product normalised" is met by the record.  E and G are D, H and F are S as before.
 // Values: everything is below 5p before a product and below 1.1p after it; nothing is reduced mod p.
-TE_HD ete ete_madd(const ete& a, const pnt& b) {
-  const fp in1[3] = {fp_sub<2>(a.y, a.x), fp_add(a.y, a.x), a.t}, in2[3] = {b.hm, b.hp, b.dt};
+template <int N> struct ete_uv_t { fel<N> u, v, z, t; };
+template <int N> TE_HD ete_uv_t<N> ete_open(const ete_t<N>& a) {
+  ete_uv_t<N> r;
+  r.u = fe_sub<2>(a.y, a.x); r.v = fe_add(a.y, a.x); r.z = a.z; r.t = a.t;
+  return r;
+}
+// the opened form of -a.  Twice in a row (not what k_accumulate does: an addition stands between two negations) gives u, v and
+// t back limb for limb: 2p - (2p - t) in offset form has no borrow.
+// In place, and on the device the swap is v_swap_b32 by name: written as two assignments the compiler copies U to nine more
+// registers in FRONT of the branch (nine moves that every addition pays, and 168 VGPRs with spills instead of 138).
+template <int N> TE_HD void ete_uv_neg(ete_uv_t<N>& a) {
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_swap_b32 %0, %1" : "+v"(a.u.v[i]), "+v"(a.v.v[i]));
+#else
+    const uint32_t w = a.u.v[i]; a.u.v[i] = a.v.v[i]; a.v.v[i] = w;
+#endif
+  }
+  a.t = fe_neg<2>(a.t);
+}
+// What a lane STORES is the sum itself, never its negative, and always four fresh product outputs (class N, below 1.1p -- the form
+// the buckets and seg_out have always had; 2p - X carried into class N would be a value up to 2p, whose top limb the offset of the
+// next fe_sub<2> does not cover).  The negation rides on the segment's LAST addition instead: (X3, Y3, T3, Z3) = (E F, H G, E H, G F),
+// so -(X3, Y3) = (-X3 : Y3 : Z3 : -T3) is the same closing with -E = A' - B' in the place of E = B' - A'.  SGN = true variants of the
+// additions and segment starts below take that choice per lane (`neg`): the operands of the one subtraction are selected under a
+// mask, 2 N selects, once or twice per segment; E has the same class and range either way (A' and B' are both class N below 1.1p).
+template <bool SGN, int N> TE_HD fel<N> fe_diff(const fel<N>& b, const fel<N>& a, bool neg) {          // b - a, or a - b where neg
+  if constexpr (!SGN) return fe_sub<2>(b, a);
+  else {
+    const uint32_t m = neg ? 0xffffffffu : 0u;
+    fel<N> hi, lo;
+#pragma unroll
+    for (int i = 0; i < N; i++) { hi.v[i] = mask_select(m, a.v[i], b.v[i]); lo.v[i] = mask_select(m, b.v[i], a.v[i]); }
+    return fe_sub<2>(hi, lo);
+  }
+}
+template <bool SGN = false> TE_HD ete ete_madd_raw(const ete_uv_t<9>& a, const pnt& b, bool neg = false) {
+  const fp in1[3] = {a.u, a.v, a.t}, in2[3] = {b.hm, b.hp, b.dt};
   fp abc[3];
   mont_mul_x<3>(in1, in2, abc);
   const fp &A = abc[0], &B = abc[1], &Cn = abc[2];
-  return ete_close<9>(fp_sub<2>(B, A), fp_add(B, A), fp_add(a.z, Cn), fp_sub<2>(a.z, Cn));
+  return ete_close<9>(fe_diff<SGN, 9>(B, A, neg), fp_add(B, A), fp_add(a.z, Cn), fp_sub<2>(a.z, Cn));
 }
 // The same with a projective record: D' = Z1 z2 takes the place of Z1 -- 8 products.
-TE_HD ete_t<14> ete_madd(const ete_t<14>& a, const pnt_t<14>& b) {
-  const fel<14> in1[4] = {fe_sub<2>(a.y, a.x), fe_add(a.y, a.x), a.t, a.z}, in2[4] = {b.hm, b.hp, b.dt, b.z};
+template <bool SGN = false> TE_HD ete_t<14> ete_madd_raw(const ete_uv_t<14>& a, const pnt_t<14>& b, bool neg = false) {
+  const fel<14> in1[4] = {a.u, a.v, a.t, a.z}, in2[4] = {b.hm, b.hp, b.dt, b.z};
   fel<14> p[4];
   fe_mul_x<4>(in1, in2, p);
   const fel<14> &A = p[0], &B = p[1], &Cn = p[2], &D = p[3];
-  return ete_close<14>(fe_sub<2>(B, A), fe_add(B, A), fe_add(D, Cn), fe_sub<2>(D, Cn));
+  return ete_close<14>(fe_diff<SGN, 14>(B, A, neg), fe_add(B, A), fe_add(D, Cn), fe_sub<2>(D, Cn));
 }
-
 // BLS12-377 with an AFFINE record (bound bases): the 7-product form of the other curve under the 14-limb rule -- one operand of
-// every product normalised: the record's coordinates are (a negated dt has limbs < 2^30.6 and meets T1, class N), E and G are
-// normalised by ete_close; F = Z1 + C' is a sum of two product outputs (limbs < 2^30), H likewise.
-TE_HD ete_t<14> ete_madd(const ete_t<14>& a, const pnt_aff377& b) {
-  const fel<14> in1[3] = {fe_sub<2>(a.y, a.x), fe_add(a.y, a.x), a.t}, in2[3] = {b.hm, b.hp, b.dt};
+// every product normalised: the record's coordinates are, E and G are normalised by ete_close; F = Z1 + C' is a sum of two product
+// outputs (limbs < 2^30), H likewise.
+template <bool SGN = false> TE_HD ete_t<14> ete_madd_raw(const ete_uv_t<14>& a, const pnt_aff377& b, bool neg = false) {
+  const fel<14> in1[3] = {a.u, a.v, a.t}, in2[3] = {b.hm, b.hp, b.dt};
   fel<14> p[3];
   fe_mul_x<3>(in1, in2, p);
   const fel<14> &A = p[0], &B = p[1], &Cn = p[2];
-  return ete_close<14>(fe_sub<2>(B, A), fe_add(B, A), fe_add(a.z, Cn), fe_sub<2>(a.z, Cn));
+  return ete_close<14>(fe_diff<SGN, 14>(B, A, neg), fe_add(B, A), fe_add(a.z, Cn), fe_sub<2>(a.z, Cn));
 }
+// acc + b from the closed form (X : Y : Z : T); b may be a record negated by pnt_cneg (its dt then has limbs < 2^30.6 and meets T1,
+// class N)
+TE_HD ete ete_madd(const ete& a, const pnt& b) { return ete_madd_raw(ete_open<9>(a), b); }
+TE_HD ete_t<14> ete_madd(const ete_t<14>& a, const pnt_t<14>& b) { return ete_madd_raw(ete_open<14>(a), b); }
+TE_HD ete_t<14> ete_madd(const ete_t<14>& a, const pnt_aff377& b) { return ete_madd_raw(ete_open<14>(a), b); }
 
 // neutral element + b without the products whose result is known: with (X1 : Y1 : Z1 : T1) = (0 : 1 : 1 : 0) the mixed addition
 // has A' = hm, B' = hp, C' = 0, D' = z2, i.e. (X3, Y3, T3, Z3) = (E z2, H z2, E H, z2^2) with E = hp - hm, H = hp + hm: three
 // products for an affine record (z2 = 1: E and H only pass through a product by one to become class N below 2p), four for a
 // projective one, instead of 7 / 8.  k_accumulate starts a segment of ONE entry with this step, and every segment of projective
 // records (ete_from_pair below); k_fb_ext_from_recs converts whole point sets with it.
-TE_HD ete ete_from_pnt(const pnt& b) {
+template <bool SGN = false> TE_HD ete ete_from_pnt(const pnt& b, bool neg = false) {
   const fp one = fp_R1();
-  const fp E = fp_sub<2>(b.hp, b.hm), H = fp_add(b.hp, b.hm);
+  const fp E = fe_diff<SGN, 9>(b.hp, b.hm, neg), H = fp_add(b.hp, b.hm);
   const fp l[3] = {E, H, E}, rr[3] = {one, one, H};
   fp o[3];
   mont_mul_x<3>(l, rr, o);
@@ -186,8 +238,8 @@ TE_HD ete ete_from_pnt(const pnt& b) {
   r.x = o[0]; r.y = o[1]; r.t = o[2]; r.z = one;
   return r;
 }
-TE_HD ete_t<14> ete_from_pnt(const pnt_t<14>& b) {
-  const fel<14> En = fe_norm(fe_sub<2>(b.hp, b.hm)), H = fe_add(b.hp, b.hm);
+template <bool SGN = false> TE_HD ete_t<14> ete_from_pnt(const pnt_t<14>& b, bool neg = false) {
+  const fel<14> En = fe_norm(fe_diff<SGN, 14>(b.hp, b.hm, neg)), H = fe_add(b.hp, b.hm);
   const fel<14> l[4] = {En, H, En, b.z}, rr[4] = {b.z, b.z, H, b.z};
   fel<14> o[4];
   fe_mul_x<4>(l, rr, o);
@@ -196,9 +248,9 @@ TE_HD ete_t<14> ete_from_pnt(const pnt_t<14>& b) {
   return r;
 }
 
-TE_HD ete_t<14> ete_from_pnt(const pnt_aff377& b) {          // z2 = 1: (E, H, E H, 1), three products
+template <bool SGN = false> TE_HD ete_t<14> ete_from_pnt(const pnt_aff377& b, bool neg = false) {          // z2 = 1: (E, H, E H, 1), three products
   const fel<14> one = fe_one<14>();
-  const fel<14> En = fe_norm(fe_sub<2>(b.hp, b.hm)), H = fe_add(b.hp, b.hm);
+  const fel<14> En = fe_norm(fe_diff<SGN, 14>(b.hp, b.hm, neg)), H = fe_add(b.hp, b.hm);
   const fel<14> l[3] = {En, H, En}, rr[3] = {one, one, H};
   fel<14> o[3];
   fe_mul_x<3>(l, rr, o);
@@ -219,33 +271,35 @@ TE_HD ete_t<14> ete_from_pnt(const pnt_aff377& b) {          // z2 = 1: (E, H, E
 // (the pairing of pnt_from_affine_raw); 2 hm1 and 2 hp1 are S and meet the class-N hm2, hp2; T1 (N) meets dt2 (N, or limbs < 2^30.6
 // when b is negated); 1 is class N, so F is S and G is D as in ete_madd, and ete_close sees what it sees there.  Output: class N.
 // Values: E < 3.1p, H < 2.2p, T1 < 1.02p; 2 hm1, 2 hp1 < 2.2p; A', B', C' < 1.02p; E3, G < 3.1p, H3, F < 2.1p; outputs < 1.02p.
-TE_HD ete ete_from_pair(const pnt& a, const pnt& b) {
+template <bool SGN = false> TE_HD ete ete_from_pair(const pnt& a, const pnt& b, bool neg = false) {
   const fp one = fp_R1();
   const fp T1 = mont_mul(fp_add(a.hp, a.hm), fp_sub<2>(a.hp, a.hm));
   const fp in1[3] = {fp_add(a.hm, a.hm), fp_add(a.hp, a.hp), T1}, in2[3] = {b.hm, b.hp, b.dt};
   fp abc[3];
   mont_mul_x<3>(in1, in2, abc);
   const fp &A = abc[0], &B = abc[1], &Cn = abc[2];
-  return ete_close<9>(fp_sub<2>(B, A), fp_add(B, A), fp_add(one, Cn), fp_sub<2>(one, Cn));
+  return ete_close<9>(fe_diff<SGN, 9>(B, A, neg), fp_add(B, A), fp_add(one, Cn), fp_sub<2>(one, Cn));
 }
 // The same for the affine BLS12-377 record under the 14-limb rule (one operand of every product normalised): E is normalised before
 // it meets H (as in ete_from_pnt); the second record's fields are class N (a negated dt, limbs < 2^30.6, meets T1, class N) and meet
 // the sums 2 hm1, 2 hp1 (limbs < 2^30); ete_close normalises E3 and G.  Values as above with q for p.
-TE_HD ete_t<14> ete_from_pair(const pnt_aff377& a, const pnt_aff377& b) {
+template <bool SGN = false> TE_HD ete_t<14> ete_from_pair(const pnt_aff377& a, const pnt_aff377& b, bool neg = false) {
   const fel<14> one = fe_one<14>();
   const fel<14> T1 = fe_mul(fe_add(a.hp, a.hm), fe_norm(fe_sub<2>(a.hp, a.hm)));
   const fel<14> in1[3] = {fe_add(a.hm, a.hm), fe_add(a.hp, a.hp), T1}, in2[3] = {b.hm, b.hp, b.dt};
   fel<14> p[3];
   fe_mul_x<3>(in1, in2, p);
   const fel<14> &A = p[0], &B = p[1], &Cn = p[2];
-  return ete_close<14>(fe_sub<2>(B, A), fe_add(B, A), fe_add(one, Cn), fe_sub<2>(one, Cn));
+  return ete_close<14>(fe_diff<SGN, 14>(B, A, neg), fe_add(B, A), fe_add(one, Cn), fe_sub<2>(one, Cn));
 }
 // The projective BLS12-377 record keeps the rule it had, 4 + 8 products.  With z1 != 1 the shortcut does not exist: Y1 - X1 of the
 // converted point is 2 hm1 z1, a product in its own right, and forming the addition from the two records directly (A' = hm1 hm2,
 // B' = hp1 hp2, D' = z1 z2) leaves C' = d T1 T2 to be had from dt1 dt2 = d^2 T1 T2 -- a product by 1/d, and one by 1/2 to put D' on
 // the records' common scale: 6 + 4 against 12, for a record kind that only per-call BLS12-377 MSMs use (bound point sets gather the
 // affine record above), with two constants and a limb-bound analysis of their own.  Not taken.
-TE_HD ete_t<14> ete_from_pair(const pnt_t<14>& a, const pnt_t<14>& b) { return ete_madd(ete_from_pnt(a), b); }
+template <bool SGN = false> TE_HD ete_t<14> ete_from_pair(const pnt_t<14>& a, const pnt_t<14>& b, bool neg = false) {
+  return ete_madd_raw<SGN>(ete_open<14>(ete_from_pnt(a)), b, neg);
+}
 
 // Full addition a + b of two accumulators (add-2008-hwcd-3 shape, k = 2d), 9 products.
 // One operand of the opening product of two differences and F are normalised, so that no product sees two wide operands:

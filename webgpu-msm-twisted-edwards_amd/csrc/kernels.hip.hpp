@@ -738,10 +738,12 @@ struct l2_args {
 // alias them: the plan runs between the count and the placement)
 #define TE_L2A_LDS_WORDS (3u * 256u + 32u + TE_L2_LIST)
 static_assert(sizeof(plan_lds) <= TE_L2_LIST * 4u, "the plan's LDS fits into the list area");
+static_assert(TE_L2_CAP < 65536u, "k_l2_local counts a bucket's positive and negative entries in the halves of one word");
 // grid (P + X, nw), block 256: see "level 2" above
 template <bool PK>
 __global__ void __launch_bounds__(256, TE_L2_WAVES) k_l2_local(l2_args a) {
   __shared__ uint32_t lds[TE_L2A_LDS_WORDS];
+  // off_s: two cursors per bucket, [0, 256) for its positive entries and [256, 512) for its negative ones (see the placement)
   uint32_t* const cnt_s = lds; uint32_t* const off_s = lds + 256; uint32_t* const sm = lds + 768; uint32_t* const pj = lds + 768 + 17;
   uint32_t* const list = lds + 768 + 32;
   plan_lds& PL = *reinterpret_cast<plan_lds*>(list);
@@ -769,10 +771,12 @@ __global__ void __launch_bounds__(256, TE_L2_WAVES) k_l2_local(l2_args a) {
     uint32_t kv[8], iv[8]; piece_group<PK>(r, c, kv, iv);
     const uint32_t e0 = ((uint32_t)c * 256u + t) * 8u;
 #pragma unroll
-    for (int e = 0; e < 8; e++) { const uint32_t pos = e0 + (uint32_t)e; if (pos >= head && pos < total) atomicAdd(&cnt_s[kv[e] & 0x7fffu], 1u); }
+    for (int e = 0; e < 8; e++) { const uint32_t pos = e0 + (uint32_t)e; if (pos >= head && pos < total) atomicAdd(&cnt_s[kv[e] & 0x7fffu], 1u << ((kv[e] >> 15) << 4)); }
   }
   __syncthreads();
-  const uint32_t c0 = cnt_s[t];
+  // one LDS word counts a bucket's positive entries in its low half and its negative ones in its high half (a piece has at most
+  // TE_L2_CAP < 2^16 entries): the same one atomic per entry, and the number of positive entries is known before the placement
+  const uint32_t c_pos = cnt_s[t] & 0xffffu, c0 = c_pos + (cnt_s[t] >> 16);
   const size_t gb = (size_t)k * g.B + (size_t)p * g.S + t;        // bucket t of the partition (t < S)
   if (!single) {
     // a piece of a multi-piece partition: counts to memory, the block that counts the last piece plans the partition
@@ -788,7 +792,9 @@ __global__ void __launch_bounds__(256, TE_L2_WAVES) k_l2_local(l2_args a) {
   if (t < g.S) a.bucket_count[gb] = c0;
   const uint32_t ex = seg_plan_block(p, k, c0, g, a.pa, PL, pb, cntp, sbp);
   if (t < g.S) a.pa.bucket_cursor[gb] = pb + ex + c0;   // "everything placed" (the arrival counter of k_seg_combine_all starts from there)
-  off_s[t] = ex;                                        // next free LDS slot of bucket t
+  // A bucket's positive entries are placed in front of its negative ones (any order inside a bucket is a correct sort): k_accumulate
+  // carries an entry's sign in its accumulator and pays for every CHANGE of sign along a segment -- at most one this way.
+  off_s[t] = ex; off_s[256u + t] = ex + c_pos;          // next free LDS slot of bucket t, by sign
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < 5; c++) {
@@ -797,7 +803,7 @@ __global__ void __launch_bounds__(256, TE_L2_WAVES) k_l2_local(l2_args a) {
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       const uint32_t pos = e0 + (uint32_t)e;
-      if (pos >= head && pos < total) list[atomicAdd(&off_s[kv[e] & 0x7fffu], 1u)] = iv[e] | ((kv[e] >> 15) << 31);
+      if (pos >= head && pos < total) list[atomicAdd(&off_s[(kv[e] & 0x7fffu) + ((kv[e] >> 15) << 8)], 1u)] = iv[e] | ((kv[e] >> 15) << 31);
     }
   }
   __syncthreads();
@@ -1113,6 +1119,13 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves
   // onto: the buckets already hold the sums of earlier pieces of the same MSM (te_msm_run uploads and processes large host
   // buffers in pieces): the first part of every bucket continues from that value instead of the neutral element
   ete_t<N> acc = (onto && part == 0u) ? load_ete<N>(buckets + g) : ete_identity_t<N>();
+  // SIGN STATE: `flipped` says that acc stands for the NEGATIVE of the segment's sum so far.  An entry is added as the record that was
+  // loaded, whatever its sign: Q - P = -((-Q) + P), so where an entry's sign differs from the flag the lane negates its accumulator
+  // (ete_uv_neg on the opened form: U <-> V, T -> 2p - T) and flips the flag -- inside a branch that a wave skips when none of its
+  // lanes changes sign -- instead of negating every record under a select (pnt_cneg: 9 v_sub_u32 + 27 v_bitop3_b32 per entry,
+  // needed or not).  k_l2_local places a bucket's positive entries first, so a lane changes sign at most once per segment
+  // (the pieces of over-long partitions keep arrival order: more flips, same sums).
+  bool flipped = false;
   if (cnt) {
     // Software pipeline: while the addition of entry j runs, the record of entry j+1 is in flight and the index of entry
     // j+2 is read from the LDS strip below -- nothing that is loaded in an iteration is waited for in the same iteration
@@ -1126,20 +1139,25 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves
     P cur = RT::load(recs, e);
     if (!(onto && part == 0u)) {
       // the segment starts a sum -- everywhere except where it continues a bucket: its first two entries are added as records
-      // (ete_from_pair: 1 + 7 products, not the 3 + 7 of a conversion and an addition), a single entry is converted (3 products)
-      const P first = pnt_cneg(cur, (e >> 31) != 0u);
+      // (ete_from_pair: 1 + 7 products, not the 3 + 7 of a conversion and an addition), a single entry is converted (3 products).
+      // The first entry's sign becomes the flag; the second record is negated only if its sign differs from the first's (once per
+      // segment: pnt_cneg stays for that).  A segment that continues a bucket starts unflipped: the bucket holds the sum itself.
+      // A segment that ends here (cnt <= 2) closes into its true sign at once (curve.hpp, SGN: the last addition of a segment does).
+      flipped = (e >> 31) != 0u;
+      const bool ends = cnt <= 2u;
       if (cnt >= 2u) {
-        const P second = pnt_cneg(RT::load(recs, e_n), (e_n >> 31) != 0u);
+        const P second = pnt_cneg(RT::load(recs, e_n), ((e_n ^ e) >> 31) != 0u);
         e = e_2; e_n = e_3;
         // entry 2 is in flight while the pair is added.  cnt = 2 has none and gathers entry 1 again (e_2 is clamped to `last`), as
         // the tail below gathers the record at hand again where entry j+1 does not exist: seven loads that hit the cache and are not
         // used, once per segment at most.  Under `if (cnt > 2)` / `if (two)` the loads join a path with seven outstanding and one
         // with none, and the listing pays for it: 138 -> 166 VGPRs for N = 9, two spilled registers in k_accumulate<14, 0>
+        const P first = cur;
         cur = RT::load(recs, e);
-        acc = ete_from_pair(first, second);
+        acc = ete_from_pair<true>(first, second, ends && flipped);
         j0 = 2;
       } else {
-        acc = ete_from_pnt(first);
+        acc = ete_from_pnt<true>(cur, flipped);
         j0 = 1;                                            // = cnt: the loop below does not run
       }
     }
@@ -1159,35 +1177,55 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(1, 256), amdgpu_waves
       }
     };
     if (((j0 + 2u) & (TE_IDX_STRIP - 1u)) != 0u) refill((j0 + 2u) & ~(TE_IDX_STRIP - 1u));
+    // the accumulator travels through the loop OPENED (curve.hpp ete_open: U = Y - X, V = Y + X formed right behind the closing
+    // products -- the 27 limb operations at the head of ete_madd, in the same place of the instruction stream), so that a sign
+    // change costs a swap of U and V and one negation; the last addition of the segment leaves the closed form, in its true sign, for the store
+    ete_uv_t<N> uv = ete_open<N>(acc);
+    auto sign_to = [&](uint32_t entry) {                   // make the flag agree with the entry's sign
+      const bool s = (entry >> 31) != 0u;
+      if (s != flipped) { ete_uv_neg<N>(uv); flipped = s; }
+    };
     // Two additions per pass over two named records, each loaded while the other is added: a single `cur` / `nxt` pair had to be
     // rotated (cur = nxt) behind every addition, 26 v_mov_b64 per 64 points.  A pass runs while entry j+2 exists, so both of its
     // loads are unconditional: a load under a lane mask joins a path with seven loads outstanding and one with none, and the wait
     // for the OTHER record behind that join can only be vmcnt(0) -- the latency of the load just issued, exposed in every pass.
     // j is even wherever a pass runs (j0 is 0 or 2; j0 = 1 comes with cnt = 1), so only its first half can meet a strip boundary,
     // and the indices of entries j+2 and j+3 sit side by side in the strip: one 8-byte LDS read per pass.
-    P rec_b;
-    uint32_t j = j0;
-    for (; j + 2u < cnt; j += 2u) {
-      const uint32_t pn = j + 2u;
-      if ((pn & (TE_IDX_STRIP - 1u)) == 0u) refill(pn);
-      const uint2 e_nn = *reinterpret_cast<const uint2*>(strip + (pn & (TE_IDX_STRIP - 1u)));
-      rec_b = RT::load(recs, e_n);
-      acc = ete_madd(acc, pnt_cneg(cur, (e >> 31) != 0u));
-      // nothing of the second addition moves in front of this line: left free, the scheduler starts its sign selection ~300
-      // instructions before the first addition's last product, and the wait for rec_b with it (1 065 instead of 1 420 instructions
-      // behind the loads)
-      __builtin_amdgcn_sched_barrier(0);
-      cur = RT::load(recs, e_nn.x);
-      acc = ete_madd(acc, pnt_cneg(rec_b, (e_n >> 31) != 0u));
-      e = e_nn.x; e_n = e_nn.y;
-    }
-    if (j < cnt) {                                         // the last one or two entries; `cur` holds entry j
-      const bool two = j + 1u < cnt;
-      rec_b = RT::load(recs, two ? e_n : e);               // (no entry j+1: the record at hand again, not used -- see the pair start)
-      acc = ete_madd(acc, pnt_cneg(cur, (e >> 31) != 0u));
-      if (two) acc = ete_madd(acc, pnt_cneg(rec_b, (e_n >> 31) != 0u));
+    // (All of it under `j0 < cnt`, the tail unconditional behind the loop -- a pass leaves j < cnt: with the tail under a test of
+    // its own the compiler has to keep the closed accumulator of the segment start alive across the loop beside the opened one.)
+    if (j0 < cnt) {
+      P rec_b;
+      uint32_t j = j0;
+      for (; j + 2u < cnt; j += 2u) {
+        const uint32_t pn = j + 2u;
+        if ((pn & (TE_IDX_STRIP - 1u)) == 0u) refill(pn);
+        const uint2 e_nn = *reinterpret_cast<const uint2*>(strip + (pn & (TE_IDX_STRIP - 1u)));
+        rec_b = RT::load(recs, e_n);
+        sign_to(e);
+        uv = ete_open<N>(ete_madd_raw(uv, cur));
+        // nothing of the second addition moves in front of this line: left free, the scheduler starts the second addition's work ~300
+        // instructions before the first addition's last product, and the wait for rec_b with it (1 065 instead of 1 420 instructions
+        // behind the loads)
+        __builtin_amdgcn_sched_barrier(0);
+        cur = RT::load(recs, e_nn.x);
+        sign_to(e_n);
+        uv = ete_open<N>(ete_madd_raw(uv, rec_b));
+        e = e_nn.x; e_n = e_nn.y;
+      }
+      {                                                      // the last one or two entries; `cur` holds entry j
+        const bool two = j + 1u < cnt;
+        rec_b = RT::load(recs, two ? e_n : e);               // (no entry j+1: the record at hand again, not used -- see the pair start)
+        sign_to(e);
+        acc = ete_madd_raw<true>(uv, cur, !two && flipped);
+        if (two) {
+          uv = ete_open<N>(acc);
+          sign_to(e_n);
+          acc = ete_madd_raw<true>(uv, rec_b, flipped);
+        }
+      }
     }
   }
+  // what is stored is the sum itself, four product outputs as ever: the segment's last addition closed into the true sign
   const bool whole = bucket_count[g] <= seg_len;
   store_ete<N>(whole ? buckets + g : seg_out + sgm, acc);
   if (clk && (uint32_t)__lane_id() == (uint32_t)__ffsll((long long)__ballot(1)) - 1u) {
