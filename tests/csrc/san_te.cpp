@@ -15,6 +15,33 @@ extern "C" int ora_msm_naive(const uint8_t* points_xy_le, const uint8_t* scalars
 static int fails = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { fails++; printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } while (0)
 
+// k p by plain double-and-add over the unified addition
+static te_host::Pt mul_plain(te_host::Pt p, uint64_t k, const te_host::Fe& k2d) {
+  te_host::Pt acc = te_host::identity();
+  for (; k; k >>= 1) { if (k & 1) acc = te_host::padd(acc, p, k2d); p = te_host::padd(p, p, k2d); }
+  return acc;
+}
+// what the fixed-base tail must give for `rows` rows [T | W0 | W1 | W2 | W3] of 2^bucket_bits buckets (all-zero rows are absent):
+//   sum_r (T_r + sum_k 2^(w_0 + .. + w_{k-1}) W_{k,r}) + 2^bucket_bits sum_{r < rb} r T_r,  term by term
+static void fixed_base_plain(const uint8_t* partials, int rows, int rb, int bucket_bits, uint8_t out[64]) {
+  using namespace te_host;
+  const Fe k2d = tail_k2d();
+  Pt acc = identity();
+  for (int r = 0; r < rows; r++) {
+    const uint8_t* row = partials + (size_t)r * TE_TAIL_ROW_BYTES;
+    if (all_zero_bytes(row, TE_TAIL_ROW_BYTES)) continue;
+    const Pt T = load_point(row);
+    acc = padd(acc, T, k2d);
+    int sh = 0;
+    for (int k = 0; k < 4; k++) {
+      acc = padd(acc, mul_plain(load_point(row + (size_t)(1 + k) * TE_TAIL_POINT_BYTES), 1ull << sh, k2d), k2d);
+      sh += (bucket_bits + 3 - k) / 4;
+    }
+    if (r < rb) acc = padd(acc, mul_plain(T, (uint64_t)r << bucket_bits, k2d), k2d);
+  }
+  affine_out(acc, out);
+}
+
 int main() {
   CHECK(te_host::tail_selftest(), "host tail self-test");
   // (window sizes up to 10 bits: the stage emulation adds up 5 W 2^(c-1) points per call, under the sanitizer)
@@ -79,6 +106,28 @@ int main() {
       for (int w = 0; w < W; w++) te_host::merge_window_rows(ptrs.data(), ns, w, merged.data(), present.data());
       te_host::horner_to_affine_points(merged.data(), present.data(), c, c - 1, W, out);
       CHECK(memcmp(out, want, 64) == 0, "point shards (merged) n=%llu c=%d S=%d", (unsigned long long)n, c, S);
+    }
+    // the fixed-base tail (te_host::fixed_base_with) in both accumulator forms: the first rb + 1 of these rows read as rb regular rows
+    // and the extra one, whole and with a row absent (row 0, a middle one, the extra one), against the sum formed term by term
+    for (int rb : {1, 2, 4, 8, 16}) {
+      std::vector<int> absents = {-1, 0, rb};
+      if (rb / 2 > 0) absents.push_back(rb / 2);
+      for (int absent : absents) {
+        std::vector<uint8_t> fb(rows.begin(), rows.begin() + (size_t)(rb + 1) * 720);
+        if (absent >= 0) memset(&fb[(size_t)absent * 720], 0, 720);
+        uint8_t plain[64];
+        fixed_base_plain(fb.data(), rb + 1, rb, c - 1, plain);
+        te_host::fixed_base_with<te_host::ScalarAcc>(fb.data(), rb + 1, rb, c - 1, out);
+        CHECK(memcmp(out, plain, 64) == 0, "fixed-base tail, scalar accumulator n=%llu c=%d rb=%d absent=%d", (unsigned long long)n, c, rb, absent);
+#if defined(__x86_64__)
+        if (te_host::have_ifma()) {
+          te_host::fixed_base_with<te_host::IfmaAcc>(fb.data(), rb + 1, rb, c - 1, out);
+          CHECK(memcmp(out, plain, 64) == 0, "fixed-base tail, IFMA accumulator n=%llu c=%d rb=%d absent=%d", (unsigned long long)n, c, rb, absent);
+        }
+#endif
+        te_host::fixed_base_to_affine(fb.data(), rb + 1, rb, c - 1, out);
+        CHECK(memcmp(out, plain, 64) == 0, "fixed-base tail n=%llu c=%d rb=%d absent=%d", (unsigned long long)n, c, rb, absent);
+      }
     }
     CHECK(fpc_bound_violations() == 0, "limb bounds n=%llu c=%d", (unsigned long long)n, c);
     printf("ok n=%llu c=%d\n", (unsigned long long)n, c);

@@ -41,6 +41,7 @@
 #include "host_sched.hpp"
 #include "batch_plan.hpp"
 #include "indexed_plan.hpp"
+#include "fb_plan.hpp"
 
 namespace {
 
@@ -1592,32 +1593,23 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
 // The sort / accumulation / reduction see fb_rb + 1 pseudo-windows ("rows") of 2^15 buckets and `cap` entries each: an unsigned
 // geometry (codes lo + 1, half = 0), general sort entries (the table index needs 24 bits).
 constexpr uint32_t FB_LOBITS = TE_FB_LOBITS;
-int fb_windows_for(int c) { return (255 + c - 1) / c; }
-void make_plan_fb(const te_ctx* ctx, const gpu_t& d, uint64_t n, int fb_c, plan_t& p, int scalar_form = -1) {
-  const int W = fb_windows_for(fb_c);
-  const uint32_t rb = 1u << ((uint32_t)fb_c - 1u - FB_LOBITS);
-  // a regular row holds (W - 1) n / rb entries for well-spread digits, the extra row the top window's n: capacity for the larger of
-  // the two plus a sixteenth (an overflow -- badly skewed scalars -- is detected on the device and falls back to the ordinary windows)
-  const uint64_t reg = ((uint64_t)(W - 1) * n + rb - 1) / rb, big = std::max<uint64_t>(reg, n);
-  const uint64_t cap = (big + big / 16 + 4096 + 7) & ~(uint64_t)7;
-  make_plan(ctx, d, cap, p, 16, 1, 0, true, scalar_form);           // chunk geometry, segment length and partitions for rows of `cap` entries
-  p.fb_rb = (int)rb; p.fb_c = fb_c; p.fb_W = W;
-  p.signed_digits = 0; p.c = (int)FB_LOBITS; p.W = (int)rb + 1; p.nw = p.nw1 = (int)rb + 1; p.batch = 1; p.w_first = 0; p.w_step = 1;
+int fb_windows_for(int c) { return te_fb::windows_for(c); }
+// (the arithmetic -- rows, capacity, chunks, default segment length -- is te_fb::make_geometry, fb_plan.hpp; returned for the caller's
+// refusal, `half` and the digit kernel's LDS size)
+te_fb::geometry make_plan_fb(const te_ctx* ctx, const gpu_t& d, uint64_t n, int fb_c, plan_t& p, int scalar_form = -1) {
+  const te_fb::geometry g = te_fb::make_geometry(n, fb_c, TE_SCATTER_BLOCKS, TE_SCATTER_MINCHUNK);
+  make_plan(ctx, d, g.cap, p, 16, 1, 0, true, scalar_form);         // curve, scalar form, options for rows of `cap` entries
+  p.fb_rb = (int)g.rb; p.fb_c = fb_c; p.fb_W = g.W;
+  p.signed_digits = 0; p.c = (int)FB_LOBITS; p.W = (int)g.rows; p.nw = p.nw1 = (int)g.rows; p.batch = 1; p.w_first = 0; p.w_step = 1;
   p.logB = FB_LOBITS; p.B = 1u << FB_LOBITS;
   for (int k = 0; k < 4; k++) p.dw[k] = (p.logB + 3u - (uint32_t)k) / 4u;
-  p.S = 256u; p.P = p.B / p.S; p.logS = 8u;
+  p.S = g.S; p.P = g.P; p.logS = g.logS;
   p.packed = 0; p.rec_kind = 0;
-  // chunks per row: as make_plan, for the row count of this plan
-  uint32_t ch = TE_SCATTER_BLOCKS / (uint32_t)p.nw; if (ch < 1) ch = 1; if (ch > 256) ch = 256;
-  const uint32_t by_n = (uint32_t)((cap + TE_SCATTER_MINCHUNK - 1) / TE_SCATTER_MINCHUNK); if (ch > by_n) ch = by_n ? by_n : 1;
-  p.nst = (uint32_t)cap;
-  p.chunk_len = ((p.nst + ch - 1) / ch + 4095u) & ~4095u;
-  p.CH = (p.nst + p.chunk_len - 1) / p.chunk_len;
-  if (!ctx->opt_seg_len) {                              // twice the mean bucket size of the ONE bucket set, as a power of two in [16, 64]
-    const uint64_t a = (2ull * (uint64_t)W * n + ((uint64_t)rb << FB_LOBITS) - 1) / ((uint64_t)rb << FB_LOBITS); uint64_t s2 = 16;
-    while (s2 < a && s2 < 64) s2 <<= 1;
-    p.seg_len = (uint32_t)s2;
-  }
+  p.nst = (uint32_t)g.cap;
+  p.chunk_len = g.chunk_len;
+  p.CH = g.CH;
+  if (!ctx->opt_seg_len) p.seg_len = g.seg_len;
+  return g;
 }
 
 template <int C, int FORM> void launch_fb_digits(const void* d_scalars, const te::fb_digit_args& a, uint32_t n, size_t lds, hipStream_t st) {
@@ -1630,9 +1622,9 @@ template <int C, int FORM> void launch_fb_digits(const void* d_scalars, const te
 int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const void* d_scalars, uint64_t n, uint64_t idx_base, hipStream_t stream,
                        int scalar_form = -1) {
   HIP_TRY(ctx, hipSetDevice(d.device));
-  plan_t p; make_plan_fb(ctx, d, n, bases->fb_c, p, scalar_form);
+  plan_t p; const te_fb::geometry g = make_plan_fb(ctx, d, n, bases->fb_c, p, scalar_form);
   const uint64_t cap = p.nst;
-  if ((uint64_t)p.nw * cap >= (1ull << 31) || (uint64_t)bases->fb_W * bases->n >= (1ull << 31))
+  if (te_fb::msm_refused(g, bases->n))
     return set_err(ctx, TE_MSM_EINVAL, "fixed-base windows: windows x points must stay below 2^31");
   if (int rc = ensure_buffers(ctx, d, ws, cap, p, false)) return rc;
   msm_launch L(ctx, ws, p, cap, stream);
@@ -1649,12 +1641,12 @@ int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bas
   L.mark(ST_DIGITS);
   {
     te::fb_digit_args a; memset(&a, 0, sizeof a);
-    for (int w = 0; w < p.fb_W; w++) { const int bit = w * p.fb_c + p.fb_c - 1; if (bit < 320) a.half[bit >> 5] |= 1u << (bit & 31); }
+    memcpy(a.half, g.half, sizeof a.half);
     a.n = (uint32_t)n; a.idx_base = (uint32_t)idx_base; a.n_table = (uint32_t)bases->n; a.W = (uint32_t)p.fb_W;
     a.rows = (uint32_t)p.nw; a.rb = (uint32_t)p.fb_rb; a.cap = (uint32_t)cap;
     a.chunk_len = p.chunk_len; a.CH = p.CH; a.P = p.P; a.logS = p.logS;
     a.digits = ws.d_digits; a.remap = ws.d_fb_remap; a.row_fill = ws.d_fb_fill; a.counts1 = ws.d_counts1; a.err = ws.d_err;
-    const size_t lds = (size_t)(2u * a.rows + a.rows * 2u * a.P) * sizeof(uint32_t);
+    const size_t lds = g.lds_bytes;
     // (fixed-base sets exist on the Twisted-Edwards curve only: the one Montgomery form here is modulo L)
     if (p.scalar_mont) with_window_bits<16, 21>(p.fb_c, [&](auto C) { launch_fb_digits<decltype(C)::value, te::SCALAR_FORM_TE>(d_scalars, a, a.n, lds, stream); });
     else with_window_bits<16, 21>(p.fb_c, [&](auto C) { launch_fb_digits<decltype(C)::value, te::SCALAR_FORM_CANONICAL>(d_scalars, a, a.n, lds, stream); });
@@ -2560,7 +2552,7 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
   b->rec_bytes = rec_bytes_of(b->curve, b->rec_kind);
   if (ctx->opt_bind_fixed_base && b->curve == TE_MSM_CURVE_TE_BLS12 && n > 0) {
     b->fb_c = ctx->opt_bind_fixed_base; b->fb_W = fb_windows_for(b->fb_c);
-    if ((uint64_t)b->fb_W * n >= (1ull << 31)) { delete b; return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base: windows x points must stay below 2^31"); }
+    if (te_fb::bind_refused(b->fb_c, n)) { delete b; return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base: windows x points must stay below 2^31"); }
   }
   b->recs.assign(nd, nullptr);
   const int rc = n > 0 ? te_sched::on_devices(*ctx, nd, [=](size_t i) { return bind_on_device(ctx, b, i, src, src_is_host, src_dev, mont); }) : 0;
