@@ -56,7 +56,7 @@ struct fake_ctx {
 };
 int set_err(fake_ctx* c, int code, const char* msg) { std::lock_guard<std::mutex> lk(c->err_mu); c->err = msg; return code; }
 
-// upload + enqueue of one whole MSM on work set ws of device d (csrc/te_msm.hip: enqueue_host_slice): reads the CALLER's
+// upload + enqueue of one whole MSM on work set ws of device d (csrc/te_msm.hip: enqueue_host_pieces): reads the CALLER's
 // buffers on the calling thread, then the device works on the staged copy
 int enqueue_host(fake_ctx* c, fake_dev& d, fake_set& ws, const uint8_t* points, const uint8_t* scalars, uint64_t n) {
   if (c->fail_next_upload.exchange(0)) return set_err(c, FK_EDEVICE, "hipMemcpyAsync failed (injected)");

@@ -114,7 +114,7 @@ def test_ragged_sizes_pieces_and_digit_forms(pkg, ora, n):
         with pkg.MsmContext(ids) as c:
             c.set_option("host_shard_min", 16)
             b = c.bind_points(pts)
-            for chunks in (0, 1, 2, 3, 5):
+            for chunks in (0, 1, 2, 3, 5, 10):
                 c.set_option("scalar_chunks", chunks)
                 assert c.run_scalars(b, sc) == want, (ids, chunks)
                 t = c.submit_scalars(b, sc)

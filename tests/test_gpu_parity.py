@@ -838,6 +838,14 @@ def test_host_buffers_in_pieces(pkg, model, ora):
         for k in (1, 2, 3, 8, 0):
             c.set_option("host_chunks", k)
             assert c.run(pts, sc) == exp, k
+        # from ten pieces on the integer boundaries differ from the retired floating-point ones (piece 7 of n = 90 starts at 63, not
+        # 62); as many pieces as points: one point per piece, every one after the first added onto the buckets
+        for k, m in ((10, 90), (22, 22)):
+            c.set_option("host_chunks", k)
+            pm, sm = pts[:64 * m], sc[:32 * m]
+            want = ora.msm(pm, sm, threads=8)
+            assert c.run(pm, sm) == want, (k, m)
+            assert c.collect(c.submit_async(pm, sm)) == want, (k, m)
         c.set_option("host_chunks", 4)
         c.set_option("window_bits", 16)
         bad = bytearray(sc)

@@ -75,6 +75,27 @@ def test_pieces_tile_the_pairs(ip):
             assert sum(sizes) == m and min(sizes) >= 1 and max(sizes) - min(sizes) <= 1
 
 
+def test_piece_boundaries_equal_the_retired_floating_rule_up_to_nine_pieces(ip):
+    """Host-point MSMs used to cut their pieces at (uint64_t)((double)n * ((double)i / K)); now every host-buffer form cuts at piece_lo.
+    Python's int(float(n) * (i / K)) is that rule in the same double arithmetic.  Up to nine pieces -- the engine picks 1 to 3 -- the two
+    agree; from ten pieces on (option "host_chunks" only) they may differ by one point, and the old rule could leave a piece empty."""
+    r = random.Random(0x9137)
+    for K in range(1, 10):
+        ns = set(range(K, 4097))
+        for e in range(12, 31):
+            ns.update(((1 << e) - 1, 1 << e, (1 << e) + 1))
+        for base in (1 << 17, 3 << 18, (1 << 31) - 1):
+            ns.update((base - 1, base, base + 1))
+        ns.update(K * r.randrange(1, ((1 << 31) - 1) // K + 1) for _ in range(2000))
+        for n in ns:
+            for i in range(K + 1):
+                assert ip.ip_piece_lo(n, K, i) == int(float(n) * (i / K)), (n, K, i)
+    # the two known differences beyond nine pieces (DESIGN.md, host-buffer pieces)
+    assert int(float(90) * (7 / 10)) == 62 and ip.ip_piece_lo(90, 10, 7) == 63
+    assert int(float(22) * (15 / 22)) == 14 and ip.ip_piece_lo(22, 22, 15) == 15
+    assert int(float(22) * (14 / 22)) == 14, "the retired rule's empty piece"
+
+
 def test_device_slices_tile_the_pairs(ip):
     r = random.Random(6)
     ms = list(M_VALUES[1:]) + [r.randint(1, 1 << 18) for _ in range(300)]

@@ -13,16 +13,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#ifndef TE_HD
-#define TE_HD __host__ __device__ __forceinline__
-#endif
-#else
-#ifndef TE_HD
-#define TE_HD inline
-#endif
-#endif
+#include "plan_arith.hpp"      // TE_HD; the chunks of a row and the default segment length, shared with make_plan
 
 namespace te_fb {
 
@@ -55,19 +46,11 @@ TE_HD geometry make_geometry(uint64_t n, int c, uint32_t scatter_blocks = 1024u,
   g.reg = ((uint64_t)(g.W - 1) * n + g.rb - 1) / g.rb;
   const uint64_t big = g.reg > n ? g.reg : n;
   g.cap = (big + big / 16 + 4096 + 7) & ~(uint64_t)7;
-  // chunks per row: as make_plan, for the row count of this plan
-  uint32_t ch = scatter_blocks / g.rows; if (ch < 1) ch = 1; if (ch > 256) ch = 256;
-  const uint32_t by_n = (uint32_t)((g.cap + min_chunk - 1) / min_chunk); if (ch > by_n) ch = by_n ? by_n : 1;
-  g.chunks = ch;
-  const uint32_t nst = (uint32_t)g.cap;
-  g.chunk_len = ((nst + ch - 1) / ch + 4095u) & ~4095u;
-  g.CH = (nst + g.chunk_len - 1) / g.chunk_len;
+  // chunks per row: make_plan's rule for rows of `cap` entries (cap is a multiple of 8: the row stride is cap itself)
+  const te_plan::chunking k = te_plan::chunks_for(g.rows, g.cap, scatter_blocks, min_chunk);
+  g.chunks = k.asked; g.chunk_len = k.chunk_len; g.CH = k.CH;
   g.S = 256u; g.P = (1u << kLoBits) / g.S; g.logS = 8u;
-  {
-    const uint64_t a = (2ull * (uint64_t)g.W * n + ((uint64_t)g.rb << kLoBits) - 1) / ((uint64_t)g.rb << kLoBits); uint64_t s2 = 16;
-    while (s2 < a && s2 < 64) s2 <<= 1;
-    g.seg_len = (uint32_t)s2;
-  }
+  g.seg_len = te_plan::default_seg_len((uint64_t)g.W * n, (uint64_t)g.rb << kLoBits);     // W n entries over the ONE bucket set
   for (int j = 0; j < 10; j++) g.half[j] = 0u;
   for (int w = 0; w < g.W; w++) { const int bit = w * c + c - 1; if (bit < 320) g.half[bit >> 5] |= 1u << (bit & 31); }
   g.lds_bytes = (size_t)(2u * g.rows + g.rows * 2u * g.P) * sizeof(uint32_t);

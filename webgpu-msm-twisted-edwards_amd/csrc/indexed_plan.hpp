@@ -15,7 +15,8 @@ namespace te_indexed {
 
 constexpr uint64_t kPackedIndexLimit = 1ull << 23;     // records a packed entry can address (kernels.hip.hpp, sort_geom::packed)
 
-// What the engine's planner (te_msm.hip, make_plan) is given for one launch sequence of `entries` pairs
+// What the engine's planner (te_msm.hip: make_plan calls this with plan_req::idx_count; a call that is not indexed is its own set,
+// count = entries) takes for one launch sequence of `entries` pairs
 struct call_plan {
   uint64_t plan_n;     // the "n" every size of the plan derives from: the entries of the sequence
   uint32_t packed;     // level-1 entries as one word: option "packed_sort" and count <= 2^23, whatever m is
@@ -24,14 +25,15 @@ inline call_plan plan_for(uint64_t entries, uint64_t count, int opt_packed) {
   return call_plan{entries, (opt_packed && count <= kPackedIndexLimit) ? 1u : 0u};
 }
 
-// pieces the pairs of one device are uploaded and processed in (option "scalar_chunks", else from m: the thresholds of
-// te_msm_run_scalars); never more pieces than pairs, never fewer than one
+// pieces the scalars (or pairs) of one device are uploaded and processed in over a bound point set, indexed or not (te_msm.hip,
+// scalar_pieces): option "scalar_chunks", else from m; never more pieces than pairs, never fewer than one
 inline int pieces(uint64_t m, int opt_scalar_chunks) {
   int K = opt_scalar_chunks ? opt_scalar_chunks : (m >= (3ull << 18) ? 3 : m >= (1ull << 18) ? 2 : 1);
   if ((uint64_t)K > m) K = (int)m;
   return K < 1 ? 1 : K;
 }
-// first pair of piece i of K (i >= K: m): the pieces tile [0, m) and differ by at most one pair
+// first pair of piece i of K (i >= K: m): the pieces tile [0, m) and differ by at most one pair.  The one boundary rule of every
+// host-buffer form (te_msm.hip, enqueue_host_pieces), host points included
 inline uint64_t piece_lo(uint64_t m, int K, int i) {
   return i >= K ? m : (uint64_t)(((unsigned __int128)m * (unsigned)i) / (unsigned)K);
 }

@@ -41,6 +41,7 @@
 #include "host_sched.hpp"
 #include "batch_plan.hpp"
 #include "indexed_plan.hpp"
+#include "plan_arith.hpp"
 #include "fb_plan.hpp"
 
 namespace {
@@ -325,41 +326,50 @@ int auto_window_bits(uint64_t n) {
 // (miscellaneous/utils.ts:80-83) -- with c * W = 255 that is every scalar from 2^254 - 2^240 up (all of them >= 2 p).
 int num_windows_for(int c, int signed_digits) { return ((signed_digits ? 255 : 256) + c - 1) / c; }
 
-// whole: every window (a whole MSM: host buffers, tickets of a multi-device context) instead of the device's window shard
-// scalar_form: the form of the scalar records (plan_t::scalar_mont) where the caller fixed it earlier -- the jobs of asynchronous tickets, which
-// run on an upload lane and do not read the option, and the second run of a fixed-base ticket; -1 = option "scalars_montgomery" as it is now
-void make_plan(const te_ctx* ctx, const gpu_t& d, uint64_t n, plan_t& p, int force_c = 0, int batch = 1, uint32_t force_seg = 0, bool whole = false, int scalar_form = -1) {
-  p.curve = ctx->opt_curve;
-  p.scalar_mont = scalar_form >= 0 ? scalar_form : ctx->opt_scalars_montgomery;
-  p.c = force_c ? force_c : ctx->opt_window_bits ? ctx->opt_window_bits : auto_window_bits(n);
-  p.signed_digits = ctx->opt_signed;
-  p.W = num_windows_for(p.c, p.signed_digits);
-  p.w_first = whole ? 0 : d.w_first; p.w_step = whole ? 1 : d.w_step;
-  p.nw = 0;
-  for (int w = p.w_first; w < p.W; w += p.w_step) p.nw++;
-  p.nw1 = p.nw; p.batch = batch; p.nw *= batch;
-  p.logB = (uint32_t)(p.signed_digits ? p.c - 1 : p.c); p.B = 1u << p.logB;
-  for (int k = 0; k < 4; k++) p.dw[k] = (p.logB + 3u - (uint32_t)k) / 4u;       // 15 -> 4,4,4,3
+// What a plan is asked for.  Only n is always needed; plan_whole() / plan_shard() below start the two common requests.
+struct plan_req {
+  uint64_t n = 0;                // entries of the launch sequence: every size of the plan derives from it
+  bool whole = false;            // every window (a whole MSM: host buffers, tickets of a multi-device context) instead of the device's window shard
+  int force_c = 0;               // window bits; 0 = option "window_bits", else from n
+  int batch = 1;                 // MSMs that share the launch sequence
+  uint32_t force_seg = 0;        // segment length; 0 = option "segment_len", else from n (the pieces of one host-buffer MSM share the largest piece's)
+  // the form of the scalar records (plan_t::scalar_mont) where the caller fixed it earlier -- the jobs of asynchronous tickets, which run on an
+  // upload lane and do not read the option, and the second run of a fixed-base ticket; -1 = option "scalars_montgomery" as it is now
+  int scalar_form = -1;
+  int rec_kind = 0;              // records k_accumulate gathers (plan_t::rec_kind): a bound point set's form
+  uint64_t idx_count = 0;        // an indexed call: records of the bound set -- the entry form follows the SET (indexed_plan.hpp); 0 = not indexed
+};
+inline plan_req plan_shard(uint64_t n) { plan_req q; q.n = n; return q; }
+inline plan_req plan_whole(uint64_t n) { plan_req q; q.n = n; q.whole = true; return q; }
+
 #ifndef TE_SCATTER_BLOCKS
 #define TE_SCATTER_BLOCKS 1024u       // measured at n = 2^20: 512 blocks 81.8 us, 1024 80.3, 2048 98.4, 4096 264 (every block sums P x CH counts)
 #endif
-  uint32_t ch = p.nw > 0 ? TE_SCATTER_BLOCKS / (uint32_t)p.nw : 1u;     // ~4 blocks of 512 threads per CU in k_part_scatter
-  if (ch < 1) ch = 1;
-  if (ch > 256) ch = 256;
 #ifndef TE_SCATTER_MINCHUNK
 #define TE_SCATTER_MINCHUNK 4096u      // one tile (8192: k_part_scatter_prep 12.1 -> 10.7 us at n = 2^16, equal from 2^18 on)
 #endif
-  const uint32_t by_n = (uint32_t)((n + TE_SCATTER_MINCHUNK - 1) / TE_SCATTER_MINCHUNK);      // at least one tile of digits per chunk
-  if (ch > by_n) ch = by_n ? by_n : 1;
-  p.nst = (uint32_t)((n + 7) & ~(uint64_t)7);
-  p.chunk_len = (uint32_t)((p.nst + ch - 1) / ch);
-  p.chunk_len = (p.chunk_len + 4095u) & ~4095u;               // whole 4096-entry tiles
-  ch = (p.nst + p.chunk_len - 1) / p.chunk_len;
-  p.CH = ch;
+plan_t make_plan(const te_ctx* ctx, const gpu_t& d, const plan_req& q) {
+  plan_t p;
+  const uint64_t n = q.n;
+  p.curve = ctx->opt_curve;
+  p.scalar_mont = q.scalar_form >= 0 ? q.scalar_form : ctx->opt_scalars_montgomery;
+  p.rec_kind = q.rec_kind;
+  p.c = q.force_c ? q.force_c : ctx->opt_window_bits ? ctx->opt_window_bits : auto_window_bits(n);
+  p.signed_digits = ctx->opt_signed;
+  p.W = num_windows_for(p.c, p.signed_digits);
+  p.w_first = q.whole ? 0 : d.w_first; p.w_step = q.whole ? 1 : d.w_step;
+  p.nw = 0;
+  for (int w = p.w_first; w < p.W; w += p.w_step) p.nw++;
+  p.nw1 = p.nw; p.batch = q.batch; p.nw *= q.batch;
+  p.logB = (uint32_t)(p.signed_digits ? p.c - 1 : p.c); p.B = 1u << p.logB;
+  for (int k = 0; k < 4; k++) p.dw[k] = (p.logB + 3u - (uint32_t)k) / 4u;       // 15 -> 4,4,4,3
+  // level-1 chunks per window: ~4 blocks of 512 threads per CU in k_part_scatter, at least one tile of digits per chunk (plan_arith.hpp)
+  const te_plan::chunking k = te_plan::chunks_for((uint32_t)p.nw, n, TE_SCATTER_BLOCKS, TE_SCATTER_MINCHUNK);
+  p.nst = k.nst; p.chunk_len = k.chunk_len; p.CH = k.CH;
   // level-1 partition = S consecutive buckets of one window
   p.S = p.B < 256u ? p.B : 256u;
-  if (force_seg) {
-    p.seg_len = force_seg;               // the pieces of one host-buffer MSM share the geometry (and the buffers) of the largest
+  if (q.force_seg) {
+    p.seg_len = q.force_seg;
   } else if (ctx->opt_seg_len) {
     p.seg_len = (uint32_t)ctx->opt_seg_len;
   } else {
@@ -368,14 +378,14 @@ void make_plan(const te_ctx* ctx, const gpu_t& d, uint64_t n, plan_t& p, int for
     // VALU-bound whole, at smaller n the whole shrinks and long segments set the kernel's duration -- measured latency of
     // one MSM (profiles/r03_segment_len_sweep.txt): 2^16 0.366 -> 0.346 ms, 2^17 0.466 -> 0.410, 2^18 0.582 -> 0.53-0.54
     // with 16 / 16 / 16-32 instead of 64; 2^19 equal at 32; 2^20 1.23 (64) against 1.32 (32).
-    uint64_t a = (2 * n + p.B - 1) / p.B, s2 = 16;
-    while (s2 < a && s2 < 64) s2 <<= 1;
-    p.seg_len = (uint32_t)s2;
+    p.seg_len = te_plan::default_seg_len(n, p.B);
   }
   p.P = p.B / p.S; p.logS = ilog2(p.S);
-  // 4 bytes per level-1 entry instead of 6 (-32 MB written and -32 MB read per 2^20-point MSM) where the index fits 23 bits;
-  // option "packed_sort" = 0 (env TE_MSM_PACKED=0): the general form (A/B measurements, tests; what larger n uses)
-  p.packed = (ctx->opt_packed && n <= (1ull << 23)) ? 1u : 0u;
+  // 4 bytes per level-1 entry instead of 6 (-32 MB written and -32 MB read per 2^20-point MSM) where the index fits 23 bits -- the
+  // index of an indexed call is a record of the SET; option "packed_sort" = 0 (env TE_MSM_PACKED=0): the general form (A/B
+  // measurements, tests; what larger n uses)
+  p.packed = te_indexed::plan_for(n, q.idx_count ? q.idx_count : n, ctx->opt_packed).packed;
+  return p;
 }
 
 // room for need_elems elements: never shrinks, the contents do NOT survive a growth, a need of 0 still allocates (16 bytes)
@@ -1028,20 +1038,20 @@ struct partial_req {
   hipStream_t stream = nullptr;
   const std::function<int(hipStream_t)>* upload_points = nullptr;   // enqueues the host-to-device copy of the points on the given (side) stream
   int batch = 1;
-  bool whole = false;                 // every window instead of the device's window shard (make_plan)
+  bool whole = false;                 // every window instead of the device's window shard (plan_req)
   const te_bases* bases = nullptr;    // the launch sequence gathers from a bound point set (d_points is not read: no conversion); batch must be 1
   share_mode share = SHARE_NONE;      // the record slab of the call; a shared slab only for device-resident points, without bound bases
   const uint32_t* d_idx = nullptr;    // (with bases) an indexed subset: the n entries gather records d_idx[0 .. n) of the set (device memory of d)
-  int scalar_form = -1;               // make_plan's: -1 = option "scalars_montgomery" as it is now
+  int scalar_form = -1;               // plan_req's: -1 = option "scalars_montgomery" as it is now
 };
 int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const partial_req& r) {
   const void* const d_points = r.d_points; const uint64_t n = r.n; hipStream_t const stream = r.stream;
   const int batch = r.batch; const te_bases* const bases = r.bases; const auto* const upload_points = r.upload_points;
   // (the plan is made for the n entries; only the entry form follows the set's count: indexed_plan.hpp)
-  const te_indexed::call_plan ip = te_indexed::plan_for(n, r.d_idx ? bases->n : n, ctx->opt_packed);
-  plan_t p; make_plan(ctx, d, ip.plan_n, p, 0, batch, 0, r.whole, r.scalar_form);
-  if (bases) p.rec_kind = bases->rec_kind;
-  if (r.d_idx) p.packed = ip.packed;
+  plan_req q; q.n = n; q.batch = batch; q.whole = r.whole; q.scalar_form = r.scalar_form;
+  if (bases) q.rec_kind = bases->rec_kind;
+  if (r.d_idx) q.idx_count = bases->n;
+  const plan_t p = make_plan(ctx, d, q);
   // (a batch shares when all its MSMs name ONE point buffer: the batch then holds one conversion anyway -- slab 0 of msm_launch::slabs())
   const void* share_src = d_points;
   if (batch > 1 && d_points) { share_src = static_cast<const void* const*>(d_points)[0]; for (int m = 1; m < batch; m++) if (static_cast<const void* const*>(d_points)[m] != share_src) share_src = nullptr; }
@@ -1398,25 +1408,50 @@ int host_pieces(const te_ctx* ctx, uint64_t n) {
   return K < 1 ? 1 : K;
 }
 
-// A host-buffer MSM (or one device's slice of it) on work set `ws` of device `d`: the buffers are uploaded and processed in K
-// pieces -- while piece i is on the GPU, piece i+1 crosses PCIe -- whose additions land on the SAME buckets, one reduction at
-// the end, flag + rows on their way to the set's pinned block when the call returns.  Window bits are forced to c (the slices
-// of a point-sharded MSM must agree on the geometry of their rows).  Does not wait: the caller synchronises ws.ev_result.
-// All windows, whatever the device's window shard says (host buffers always are whole MSMs or point slices of one).
-// wait_for_pinned: the caller promises its buffers only until this call returns (te_msm_run, te_msm_submit).  Copies from
-// PAGEABLE memory have left the caller's buffer when hipMemcpyAsync returns (the runtime stages them); from pinned or
-// registered memory they are truly asynchronous -- then the call waits for the last piece's upload before it returns.
-// scalar_form: make_plan's (a lane thread passes what its ticket was submitted with).
-int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_points, const uint8_t* src_scalars, uint64_t n, int c, int K,
-                       bool wait_for_pinned = true, int scalar_form = -1) {
+// pieces the scalars of a bound point set are uploaded and processed in on ONE device (option "scalar_chunks", else from n)
+int scalar_pieces(const te_ctx* ctx, uint64_t n) { return te_indexed::pieces(n, ctx->opt_scalar_chunks); }
+
+// One MSM from HOST buffers (or one device's slice of it) on work set `ws` of device `d`, in one of two forms:
+//   host points and scalars (`points`): both are uploaded, the points converted into the set's own record slab;
+//   host scalars over a BOUND point set (`recs`, rec_kind: the form of the records): only the scalars travel.  `recs` are the records
+//     of the slice's first point on this device -- or, with `idx` (te_msm_run_scalars_indexed*), the set's FIRST record: the slice is n
+//     (index, scalar) pairs over a set of idx_count records, every piece carries its slice of both arrays and gathers records idx[j]
+//     (msm_launch::idx); idx_pos: position of the slice's first pair in the caller's list.  The entry form follows the set's count,
+//     everything else n (indexed_plan.hpp).
+// The buffers are uploaded and processed in K pieces -- while piece i is on the GPU, piece i+1 crosses PCIe -- whose additions land on
+// the SAME buckets, one reduction at the end, flag + rows on their way to the set's pinned block when the call returns.  Window bits
+// are forced to c (the slices of a sharded MSM must agree on the geometry of their rows).  Does not wait: the caller synchronises
+// ws.ev_result.  All windows, whatever the device's window shard says (host buffers always are whole MSMs or slices of one).
+struct host_slice_req {
+  const uint8_t* points = nullptr;      // host points -- or bound records:
+  const uint8_t* recs = nullptr; int rec_kind = 0;
+  const uint8_t* scalars = nullptr;     // host scalars
+  uint64_t n = 0; int c = 0, K = 1;
+  // the caller promises its buffers only until this call returns (te_msm_run*, te_msm_submit).  Copies from PAGEABLE memory have left
+  // the caller's buffer when hipMemcpyAsync returns (the runtime stages them); from pinned or registered memory they are truly
+  // asynchronous -- then the call waits for the last piece's upload before it returns.  false: a lane thread enqueues a ticket
+  bool wait_for_pinned = true;
+  const uint32_t* idx = nullptr; uint64_t idx_count = 0, idx_pos = 0;
+  int scalar_form = -1;                 // plan_req's (a lane thread passes what its ticket was submitted with)
+};
+int enqueue_host_pieces(te_ctx* ctx, gpu_t& d, workset_t& ws, const host_slice_req& r) {
   HIP_TRY(ctx, hipSetDevice(d.device));
-  plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true, scalar_form);
+  const uint64_t n = r.n;
+  const bool bound = r.points == nullptr;
+  // what the plans of the whole slice and of every piece share; the pieces keep the slice's window bits and scalar form
+  plan_req q = plan_whole(n); q.force_c = r.c; q.scalar_form = r.scalar_form;
+  if (bound) { q.rec_kind = r.rec_kind; if (r.idx) q.idx_count = r.idx_count; }
+  const plan_t pf = make_plan(ctx, d, q);
+  q.force_c = pf.c; q.scalar_form = pf.scalar_mont;
   const curve_sizes sz = sizes_of(pf.curve);
-  if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sz.scalar_in)) return rc;
-  const bool host_waits = !wait_for_pinned || caller_may_wait_on_host(src_points, src_scalars);
+  const size_t rec_bytes = rec_bytes_of(pf.curve, pf.rec_kind);
+  if (int rc = ensure_staging(ctx, ws, bound ? 0 : n * sz.point_in, n * sz.scalar_in)) return rc;
+  if (r.idx) { if (int rc = make_room(ctx, ws.d_in_idx, (size_t)n)) return rc; }
+  const bool pinned_source = r.wait_for_pinned && !caller_may_wait_on_host(r.scalars, bound ? static_cast<const void*>(r.idx) : r.points);
+  const bool host_waits = !pinned_source;
   uint8_t* dpts = static_cast<uint8_t*>(ws.d_in_points);
   uint8_t* dscs = static_cast<uint8_t*>(ws.d_in_scalars);
-  // Pieces of n / K points: piece i crosses PCIe on the side stream while piece i-1 is converted and ACCUMULATED ONTO THE SAME
+  // Pieces of n / K entries: piece i crosses PCIe on the side stream while piece i-1 is (converted and) ACCUMULATED ONTO THE SAME
   // BUCKETS on the main stream; one bucket reduction at the end.  (The first version ran every piece as a complete MSM with
   // its own reduction of all W x 2^(c-1) buckets: K reductions, which made more than four pieces a loss.)  Pageable copies
   // return once the data has left the caller's buffer, so the host alternates between staging a piece and enqueueing the
@@ -1424,159 +1459,84 @@ int enqueue_host_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* src_
   // Measured (n = 2^20, tools/host_path.py, TE_MSM_TRACE_HOST=1, profiles/r03_host_buffer_path.txt): three equal pieces 2.48 ms,
   // two 2.56, four 2.59 (the device falls behind the uploads: every piece pays a sort and ~10 launches on a fraction of the
   // points), falling piece sizes 2.51-2.56 (profiles/r06_host_split_experiment.txt: equal thirds confirmed); the link alone needs 1.85 ms.
-  // Equal pieces, in floating point (the integer n i / K of enqueue_scalar_slice differs by one point for some n)
-  auto piece_lo = [&](int i) -> uint64_t { return i >= K ? n : (uint64_t)((double)n * ((double)i / K)); };     // first point of piece i
+  int K = r.K < 1 ? 1 : r.K;
+  if ((uint64_t)K > n) K = (int)n;                                         // no piece is empty: the last one ends the sequence
+  auto piece_lo = [&](int i) -> uint64_t { return te_indexed::piece_lo(n, K, i); };     // first entry of piece i
   uint64_t m_max = 0;
   for (int i = 0; i < K; i++) m_max = std::max(m_max, piece_lo(i + 1) - piece_lo(i));
-  uint32_t seg_all = 0;
   {
-    plan_t pm; make_plan(ctx, d, m_max, pm, pf.c, 1, 0, true, pf.scalar_mont);
-    seg_all = pm.seg_len;
-    if (int rc = ensure_buffers(ctx, d, ws, m_max, pm)) return rc;        // every buffer at its final size before the first piece
+    q.n = m_max;
+    const plan_t pm = make_plan(ctx, d, q);
+    q.force_seg = pm.seg_len;                                              // the pieces share the geometry (and the buffers) of the largest
+    if (int rc = ensure_buffers(ctx, d, ws, m_max, pm, !bound)) return rc;    // every buffer at its final size before the first piece
   }
   // what every piece's launch shares; the piece sets its plan, its inputs and `onto`
   msm_launch L0(ctx, ws, pf, n, ws.stream);
   L0.d_partials_out = ws.d_partials; L0.own_rows = true;
-  if (int rc = begin_sequence(d, L0, ws.d_recs)) return rc;          // a host-buffer MSM converts into the set's own slab
-  if (int rc = copy_stream_behind_previous(ctx, ws)) return rc;
+  if (int rc = begin_sequence(d, L0, bound ? nullptr : ws.d_recs.p)) return rc;     // host points are converted into the set's own slab
+  if (int rc = copy_stream_behind_previous(ctx, ws)) return rc;            // the staging area may still be read by the set's previous MSM
+  // host stamps of every piece (stderr), one line format per form: tools/stamp_summary.py and tools/trace_point_shards.py parse them.
+  // (host points: index of the device in the context's list / its HIP id; the absolute time tells the threads of one call apart from the next call's)
   const bool tr = getenv("TE_MSM_TRACE_HOST") != nullptr;
   const auto t00 = std::chrono::steady_clock::now();
-  // (index of the device in the context's list / its HIP id; the absolute time tells the threads of one call apart from the next call's)
   auto stamp = [&](const char* what, int i) {
     if (!tr) return;
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[te_msm_run dev %d/%d] %8.1f us  %s %d   (t = %.1f us)\n", (int)(&d - ctx->devs.data()), d.device,
-            std::chrono::duration<double, std::micro>(now - t00).count(), what, i, std::chrono::duration<double, std::micro>(now.time_since_epoch()).count());
+    const double us = std::chrono::duration<double, std::micro>(now - t00).count();
+    if (bound) fprintf(stderr, "[scalar slice ws %d] %8.1f us  %s %d\n", (int)(&ws - d.ws), us, what, i);
+    else fprintf(stderr, "[te_msm_run dev %d/%d] %8.1f us  %s %d   (t = %.1f us)\n", (int)(&d - ctx->devs.data()), d.device, us, what, i,
+                 std::chrono::duration<double, std::micro>(now.time_since_epoch()).count());
   };
   std::vector<hipEvent_t>& evs = ws.piece_events;
   while ((int)evs.size() < K + 1) { hipEvent_t e; HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming)); evs.push_back(e); }
-  plan_t p;
-  bool first = true;
-  int last_piece = K - 1;
-  while (last_piece > 0 && piece_lo(last_piece) == piece_lo(last_piece + 1)) last_piece--;       // empty tail pieces
-  // ALL scalars first, in one copy (a third of the bytes): every extra pageable copy call costs ~43 us of pipeline drain
-  // (six calls for three pieces ended at 2.02 ms where one pair of calls takes 1.85), and with the scalars there the sort
-  // of piece i + 1 is enqueued behind piece i's accumulation and runs while piece i + 1's points are still crossing PCIe.
-  // (Twisted-Edwards only: there the link is the bottleneck.  BLS12-377 -- 144 MB to upload, but 2.0 ms of accumulation -- is
-  // bound by the device, which must not sit idle while 48 MB of scalar records arrive: piece by piece, 4.1 against 4.7 ms.)
-  const bool scalars_first = pf.curve == TE_MSM_CURVE_TE_BLS12;
+  auto upload_scalars = [&](uint64_t lo, uint64_t m) -> int {
+    return upload(ctx, ws, dscs + lo * sz.scalar_in, r.scalars + lo * sz.scalar_in, m * sz.scalar_in, ws.copy_stream);
+  };
+  // Host points on Twisted-Edwards: ALL scalars first, in one copy (a third of the bytes): every extra pageable copy call costs ~43 us
+  // of pipeline drain (six calls for three pieces ended at 2.02 ms where one pair of calls takes 1.85), and with the scalars there the
+  // sort of piece i + 1 is enqueued behind piece i's accumulation and runs while piece i + 1's points are still crossing PCIe.
+  // (There the link is the bottleneck.  BLS12-377 -- 144 MB to upload, but 2.0 ms of accumulation -- is bound by the device, which
+  // must not sit idle while 48 MB of scalar records arrive: piece by piece, 4.1 against 4.7 ms.)
+  const bool scalars_first = !bound && pf.curve == TE_MSM_CURVE_TE_BLS12;
   if (scalars_first) {
-    if (int rc = upload(ctx, ws, dscs, src_scalars, n * sz.scalar_in, ws.copy_stream)) return rc;
-    if (int rc = lane_wait(ctx, ws, evs[K], host_waits)) return rc;
+    if (int rc = upload_scalars(0, n)) return rc;
+    if (int rc = lane_wait(ctx, ws, evs[(size_t)K], host_waits)) return rc;
     stamp("scalars staged", -1);
   }
-  for (int i = 0; i < K; i++) {
-    const uint64_t lo = piece_lo(i), hi = piece_lo(i + 1), m = hi - lo;
-    if (m == 0) continue;
-    make_plan(ctx, d, m, p, pf.c, 1, seg_all, true, pf.scalar_mont);
-    if (int rc = ensure_buffers(ctx, d, ws, m, p)) return rc;              // no reallocation: only the pointers into the zeroed block move
-    msm_launch L = L0;
-    L.p = p; L.d_points = dpts + lo * sz.point_in; L.d_scalars = dscs + lo * sz.scalar_in; L.n = m; L.onto = !first;
-    first = false;
-    if (!scalars_first) {
-      if (int rc = upload(ctx, ws, dscs + lo * sz.scalar_in, src_scalars + lo * sz.scalar_in, m * sz.scalar_in, ws.copy_stream)) return rc;
-      if (int rc = lane_wait(ctx, ws, evs[K], host_waits)) return rc;
-      stamp("scalars staged", i);
-    }
-    if (int rc = L.front_scalars()) return rc;                             // digits, sort and schedule run while the piece's points cross PCIe
-    stamp("scalar stages enqueued", i);
-    if (int rc = upload(ctx, ws, dpts + lo * sz.point_in, src_points + lo * sz.point_in, m * sz.point_in, ws.copy_stream)) return rc;
-    stamp("points staged", i);
-    if (int rc = lane_wait(ctx, ws, evs[i], host_waits)) return rc;
-    if (int rc = L.front_points()) return rc;
-    if (int rc = L.accumulate()) return rc;
-    if (int rc = L.combine()) return rc;
-    if (i == last_piece) { if (int rc = L.reduce()) return rc; }
-    stamp("piece enqueued", i);
-  }
-  note_sequence(d, ws, p, piece_lo(last_piece + 1) - piece_lo(last_piece), ws.stream, 0);
-  if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
-  HIP_TRY(ctx, hipGetLastError());
-  if (wait_for_pinned && !ctx->opt_host_staging && (host_memory_is_pinned(src_points) || host_memory_is_pinned(src_scalars))) {
-    // everything on the copy stream is ordered: the last recorded upload event covers the scalars and every piece
-    HIP_TRY(ctx, hipEventSynchronize(evs[(size_t)last_piece]));
-    stamp("pinned source: uploads awaited", -1);
-  }
-  return 0;
-}
-
-// pieces the scalars of a bound point set are uploaded and processed in on ONE device (option "scalar_chunks", else from n)
-int scalar_pieces(const te_ctx* ctx, uint64_t n) {
-  int K = ctx->opt_scalar_chunks ? ctx->opt_scalar_chunks : (n >= (3ull << 18) ? 3 : n >= (1ull << 18) ? 2 : 1);
-  if ((uint64_t)K > n) K = (int)n;
-  return K < 1 ? 1 : K;
-}
-
-// An MSM over a BOUND point set from host scalars (or one device's slice of it) on work set `ws` of device `d`: enqueue_host_slice
-// without the points.  `recs` are the records of the slice's first point on this device (rec_kind: their form).  The scalars
-// travel in K pieces on the set's copy stream -- piece i + 1 crosses PCIe while piece i is decomposed, sorted and accumulated
-// ONTO THE SAME BUCKETS on the main stream (its records are at recs + lo * record bytes) --, one bucket reduction at the end,
-// flag + rows on their way to the set's pinned block when the call returns.  Does not wait: the caller synchronises ws.ev_result.
-// All windows, window bits forced to c.  wait_for_pinned: as enqueue_host_slice.
-// src_idx (te_msm_run_scalars_indexed*): the slice is n (index, scalar) pairs over a set of idx_count records -- `recs` is the set's FIRST
-// record, every piece carries its slice of both arrays and gathers records idx[j] (msm_launch::idx); idx_pos: position of the slice's
-// first pair in the caller's list.  The entry form follows the set's count, everything else n (indexed_plan.hpp).
-// scalar_form: make_plan's (a lane thread passes what its ticket was submitted with).
-int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* recs, int rec_kind, const uint8_t* src_scalars, uint64_t n, int c, int K,
-                         bool wait_for_pinned = true, const uint32_t* src_idx = nullptr, uint64_t idx_count = 0, uint64_t idx_pos = 0, int scalar_form = -1) {
-  HIP_TRY(ctx, hipSetDevice(d.device));
-  plan_t pf; make_plan(ctx, d, n, pf, c, 1, 0, true, scalar_form);
-  pf.rec_kind = rec_kind;
-  const curve_sizes sz = sizes_of(pf.curve);
-  const size_t rec_bytes = rec_bytes_of(pf.curve, rec_kind);
-  if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
-  if (src_idx) { if (int rc = make_room(ctx, ws.d_in_idx, (size_t)n)) return rc; }
-  uint8_t* dscs = static_cast<uint8_t*>(ws.d_in_scalars);
-  if (K < 1) K = 1;
-  if ((uint64_t)K > n) K = (int)n;
-  auto piece_lo = [&](int i) -> uint64_t { return te_indexed::piece_lo(n, K, i); };
-  uint64_t m_max = 0;
-  for (int i = 0; i < K; i++) m_max = std::max(m_max, piece_lo(i + 1) - piece_lo(i));
-  uint32_t seg_all = 0;
-  {
-    plan_t pm; make_plan(ctx, d, m_max, pm, pf.c, 1, 0, true, pf.scalar_mont);
-    pm.rec_kind = rec_kind;
-    if (src_idx) pm.packed = te_indexed::plan_for(m_max, idx_count, ctx->opt_packed).packed;
-    seg_all = pm.seg_len;
-    if (int rc = ensure_buffers(ctx, d, ws, m_max, pm, false)) return rc;      // every buffer at its final size before the first piece
-  }
-  // what every piece's launch shares; the piece sets its plan, its inputs and `onto`
-  msm_launch L0(ctx, ws, pf, n, ws.stream);
-  L0.d_partials_out = ws.d_partials; L0.own_rows = true;
-  if (int rc = begin_sequence(d, L0, nullptr)) return rc;
-  if (int rc = copy_stream_behind_previous(ctx, ws)) return rc;                 // the staging area may still be read by the set's previous MSM
-  std::vector<hipEvent_t>& evs = ws.piece_events;
-  while ((int)evs.size() < K + 1) { hipEvent_t e; HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming)); evs.push_back(e); }
   plan_t p;
-  bool first = true;
-  static const bool tr = getenv("TE_MSM_TRACE_HOST") != nullptr;          // host stamps of every piece (stderr)
-  const auto t00 = std::chrono::steady_clock::now();
-  auto stamp = [&](const char* what, int i) {
-    if (tr) fprintf(stderr, "[scalar slice ws %d] %8.1f us  %s %d\n", (int)(&ws - d.ws), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t00).count(), what, i);
-  };
   for (int i = 0; i < K; i++) {
     const uint64_t lo = piece_lo(i), m = piece_lo(i + 1) - lo;
-    if (m == 0) continue;
-    {
+    if (bound) {
       std::unique_lock<std::mutex> link(*d.scalar_link, std::defer_lock);
-      if (!wait_for_pinned) link.lock();                                        // (a lane thread: see gpu_t::scalar_link)
+      if (!r.wait_for_pinned) link.lock();                                   // (a lane thread: see gpu_t::scalar_link)
       stamp("upload begins", i);
-      if (src_idx) { if (int rc = upload(ctx, ws, ws.d_in_idx + lo, reinterpret_cast<const uint8_t*>(src_idx + lo), m * sizeof(uint32_t), ws.copy_stream)) return rc; }
-      if (int rc = upload(ctx, ws, dscs + lo * sz.scalar_in, src_scalars + lo * sz.scalar_in, m * sz.scalar_in, ws.copy_stream)) return rc;
+      if (r.idx) { if (int rc = upload(ctx, ws, ws.d_in_idx + lo, reinterpret_cast<const uint8_t*>(r.idx + lo), m * sizeof(uint32_t), ws.copy_stream)) return rc; }
+      if (int rc = upload_scalars(lo, m)) return rc;
       stamp("upload call returned", i);
-      if (int rc = lane_wait(ctx, ws, evs[(size_t)i], !wait_for_pinned || caller_may_wait_on_host(src_scalars, src_idx))) return rc;
+      if (int rc = lane_wait(ctx, ws, evs[(size_t)i], host_waits)) return rc;
       stamp("upload awaited", i);
     }
-    make_plan(ctx, d, m, p, pf.c, 1, seg_all, true, pf.scalar_mont);
-    p.rec_kind = rec_kind;
-    if (src_idx) p.packed = te_indexed::plan_for(m, idx_count, ctx->opt_packed).packed;
-    if (int rc = ensure_buffers(ctx, d, ws, m, p, false)) return rc;           // no reallocation: only the pointers into the zeroed block move
+    q.n = m;
+    p = make_plan(ctx, d, q);
+    if (int rc = ensure_buffers(ctx, d, ws, m, p, !bound)) return rc;        // no reallocation: only the pointers into the zeroed block move
     msm_launch L = L0;
-    L.p = p; L.d_scalars = dscs + lo * sz.scalar_in; L.n = m; L.onto = !first;
-    L.bound = src_idx ? recs : recs + lo * rec_bytes;
-    if (src_idx) { L.idx = ws.d_in_idx + lo; L.idx_count = (uint32_t)idx_count; L.idx_pos = (uint32_t)(idx_pos + lo); }
-    first = false;
-    if (int rc = L.front_scalars()) return rc;
+    L.p = p; L.d_scalars = dscs + lo * sz.scalar_in; L.n = m; L.onto = i > 0;
+    if (!bound) L.d_points = dpts + lo * sz.point_in;
+    else if (!r.idx) L.bound = r.recs + lo * rec_bytes;
+    else { L.bound = r.recs; L.idx = ws.d_in_idx + lo; L.idx_count = (uint32_t)r.idx_count; L.idx_pos = (uint32_t)(r.idx_pos + lo); }
+    if (!bound && !scalars_first) {
+      if (int rc = upload_scalars(lo, m)) return rc;
+      if (int rc = lane_wait(ctx, ws, evs[(size_t)K], host_waits)) return rc;
+      stamp("scalars staged", i);
+    }
+    if (int rc = L.front_scalars()) return rc;                               // host points: digits, sort and schedule run while the piece's points cross PCIe
+    if (!bound) {
+      stamp("scalar stages enqueued", i);
+      if (int rc = upload(ctx, ws, dpts + lo * sz.point_in, r.points + lo * sz.point_in, m * sz.point_in, ws.copy_stream)) return rc;
+      stamp("points staged", i);
+      if (int rc = lane_wait(ctx, ws, evs[(size_t)i], host_waits)) return rc;
+      if (int rc = L.front_points()) return rc;
+    }
     if (int rc = L.accumulate()) return rc;
     if (int rc = L.combine()) return rc;
     if (i == K - 1) { if (int rc = L.reduce()) return rc; }
@@ -1585,7 +1545,11 @@ int enqueue_scalar_slice(te_ctx* ctx, gpu_t& d, workset_t& ws, const uint8_t* re
   note_sequence(d, ws, p, piece_lo(K) - piece_lo(K - 1), ws.stream, 0);
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipGetLastError());
-  if (wait_for_pinned && !ctx->opt_host_staging && (host_memory_is_pinned(src_scalars) || (src_idx && host_memory_is_pinned(src_idx)))) HIP_TRY(ctx, hipEventSynchronize(evs[(size_t)K - 1]));
+  if (pinned_source && !ctx->opt_host_staging) {
+    // everything on the copy stream is ordered: the last recorded upload event covers the scalars and every piece
+    HIP_TRY(ctx, hipEventSynchronize(evs[(size_t)K - 1]));
+    if (!bound) stamp("pinned source: uploads awaited", -1);
+  }
   return 0;
 }
 
@@ -1598,7 +1562,8 @@ int fb_windows_for(int c) { return te_fb::windows_for(c); }
 // refusal, `half` and the digit kernel's LDS size)
 te_fb::geometry make_plan_fb(const te_ctx* ctx, const gpu_t& d, uint64_t n, int fb_c, plan_t& p, int scalar_form = -1) {
   const te_fb::geometry g = te_fb::make_geometry(n, fb_c, TE_SCATTER_BLOCKS, TE_SCATTER_MINCHUNK);
-  make_plan(ctx, d, g.cap, p, 16, 1, 0, true, scalar_form);         // curve, scalar form, options for rows of `cap` entries
+  plan_req q = plan_whole(g.cap); q.force_c = 16; q.scalar_form = scalar_form;
+  p = make_plan(ctx, d, q);                                         // curve, scalar form, options for rows of `cap` entries
   p.fb_rb = (int)g.rb; p.fb_c = fb_c; p.fb_W = g.W;
   p.signed_digits = 0; p.c = (int)FB_LOBITS; p.W = (int)g.rows; p.nw = p.nw1 = (int)g.rows; p.batch = 1; p.w_first = 0; p.w_step = 1;
   p.logB = FB_LOBITS; p.B = 1u << FB_LOBITS;
@@ -1618,7 +1583,7 @@ template <int C, int FORM> void launch_fb_digits(const void* d_scalars, const te
 
 // An MSM of n scalars (device memory) over the fixed-base table of `bases` on device `d`: the scalars' digits address the table
 // entries (w, idx_base + i) -- idx_base: the first point of this launch inside the bound set (a device's slice of a lone
-// multi-device call).  Rows in the set's own block; the caller ends the sequence with fetch_rows().  scalar_form: make_plan's.
+// multi-device call).  Rows in the set's own block; the caller ends the sequence with fetch_rows().  scalar_form: plan_req's.
 int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const void* d_scalars, uint64_t n, uint64_t idx_base, hipStream_t stream,
                        int scalar_form = -1) {
   HIP_TRY(ctx, hipSetDevice(d.device));
@@ -1717,12 +1682,13 @@ int settle_status(te_ctx* ctx, const workset_t& ws, bool entries_of_failed = tru
   return 0;
 }
 
-// te_msm_run for a large MSM on one device: enqueue_host_slice on a free work set, wait, host tail
+// te_msm_run for a large MSM on one device: enqueue_host_pieces on a free work set, wait, host tail
 int run_host_chunked(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_scalars, uint64_t n, int K, uint8_t out[64]) {
   gpu_t& d = ctx->devs[0];
   workset_t& ws = d.ws[0];
-  plan_t pf; make_plan(ctx, d, n, pf, 0, 1, 0, true);
-  if (int rc = enqueue_host_slice(ctx, d, ws, src_points, src_scalars, n, pf.c, K)) return rc;
+  const plan_t pf = make_plan(ctx, d, plan_whole(n));
+  host_slice_req r; r.points = src_points; r.scalars = src_scalars; r.n = n; r.c = pf.c; r.K = K;
+  if (int rc = enqueue_host_pieces(ctx, d, ws, r)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
   if (int rc = settle_status(ctx, ws)) return rc;
   fold_rows(pf, ws.h_partials, out);
@@ -1731,7 +1697,7 @@ int run_host_chunked(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
 
 // te_msm_run on a context of D > 1 devices: POINT sharding.  Points and scalars are cut into contiguous slices, one per
 // device; one host thread per device stages its slice over that device's own PCIe link (pageable copies block the thread
-// that issues them) and runs ALL windows on its n/D points (enqueue_host_slice, itself in pieces for large slices); the D x W
+// that issues them) and runs ALL windows on its n/D points (enqueue_host_pieces, itself in pieces for large slices); the D x W
 // rows are linear in the bucket contents, so the host tail folds their sum (horner_to_affine_multi).  Every device pays the
 // reduction of all W x B buckets -- which is why device-resident inputs (te_msm_run_device, one process per GPU) shard
 // the WINDOWS instead -- but on this boundary the cost is the link: 1.85 of 2.47 ms at n = 2^20 on one device.  The window size
@@ -1750,9 +1716,9 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
   size_t D = src_idx ? te_indexed::devices_for(n, nd, per_min) : (size_t)std::min<uint64_t>(nd, std::max<uint64_t>(1, n / per_min));
   const uint64_t per = (n + D - 1) / D;
   auto slice_lo = [&](size_t i) -> uint64_t { return src_idx ? te_indexed::slice_lo(n, D, i) : std::min<uint64_t>(n, per * i); };
-  plan_t p0; make_plan(ctx, ctx->devs[0], per, p0, 0, 1, 0, true);     // geometry of every slice's rows (window bits from the slice size)
+  const plan_t p0 = make_plan(ctx, ctx->devs[0], plan_whole(per));     // geometry of every slice's rows (window bits from the slice size)
   const curve_sizes sz = sizes_of(p0.curve);
-  const int K = src_idx ? te_indexed::pieces(per, ctx->opt_scalar_chunks) : bases ? scalar_pieces(ctx, per) : host_pieces(ctx, per);
+  const int K = bases ? scalar_pieces(ctx, per) : host_pieces(ctx, per);
   std::vector<int> wsel;
   if (int rc = free_sets(ctx, D, wsel)) return rc;
   auto slice = [&](size_t i) -> int {
@@ -1760,13 +1726,11 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
     gpu_t& d = ctx->devs[i];
     if (hi == lo) return 0;
     workset_t& ws = d.ws[wsel[i]];
-    if (src_idx) {
-      if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[i], bases->rec_kind, src_scalars + lo * sz.scalar_in, hi - lo, p0.c, K, true, src_idx + lo, bases->n, lo)) return rc;
-    } else if (bases) {
-      if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[i] + lo * bases->rec_bytes, bases->rec_kind, src_scalars + lo * sz.scalar_in, hi - lo, p0.c, K)) return rc;
-    } else {
-      if (int rc = enqueue_host_slice(ctx, d, ws, src_points + lo * sz.point_in, src_scalars + lo * sz.scalar_in, hi - lo, p0.c, K)) return rc;
-    }
+    host_slice_req r; r.scalars = src_scalars + lo * sz.scalar_in; r.n = hi - lo; r.c = p0.c; r.K = K;
+    if (!bases) r.points = src_points + lo * sz.point_in;
+    else if (!src_idx) { r.recs = bases->recs[i] + lo * bases->rec_bytes; r.rec_kind = bases->rec_kind; }
+    else { r.recs = bases->recs[i]; r.rec_kind = bases->rec_kind; r.idx = src_idx + lo; r.idx_count = bases->n; r.idx_pos = lo; }
+    if (int rc = enqueue_host_pieces(ctx, d, ws, r)) return rc;
     HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
     return 0;
   };
@@ -1850,7 +1814,7 @@ int settle_window_shards(te_ctx* ctx, const std::vector<int>& wsel, const plan_t
 // (One physical GPU named several times -- the only form a one-GPU box can run -- makes every copy a device-to-device copy.)
 int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* src_scalars, uint64_t n, uint8_t* out) {
   const size_t nd = ctx->devs.size();
-  plan_t p0; make_plan(ctx, ctx->devs[0], n, p0);
+  const plan_t p0 = make_plan(ctx, ctx->devs[0], plan_shard(n));
   const curve_sizes sz = sizes_of(p0.curve);
   std::vector<int> wsel;
   if (int rc = free_sets(ctx, nd, wsel)) return rc;
@@ -2032,7 +1996,7 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
   }
   const int wsel = lone_set(ctx, d, ctx->opt_workset);
   if (wsel < 0) return wsel;
-  plan_t p0; make_plan(ctx, d, n, p0);
+  const plan_t p0 = make_plan(ctx, d, plan_shard(n));
   const curve_sizes sz = sizes_of(p0.curve);
   workset_t& ws = d.ws[wsel];
   HIP_TRY(ctx, hipSetDevice(d.device));
@@ -2366,19 +2330,21 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
   std::optional<ticket_set> taken;
   if (int rc = take_free_workset(ctx, -1, false, taken)) return rc;
   const ticket_set& t = *taken;
-  plan_t pf; make_plan(ctx, t.d, n, pf, 0, 1, 0, true);
-  const int c = pf.c, K = host_pieces(ctx, n);               // the plan's window bits and pieces are fixed here
+  const plan_t pf = make_plan(ctx, t.d, plan_whole(n));
+  host_slice_req r; r.points = points_xy_le; r.scalars = scalars_le; r.n = n;
+  r.c = pf.c; r.K = host_pieces(ctx, n);                     // the plan's window bits and pieces are fixed here
   if (!async) {
     if (int rc; ticket_ends_at_check(ctx, t, (size_t)t.di, points_xy_le, true, n, ticket, &rc)) return rc;
-    if (int rc = enqueue_host_slice(ctx, t.d, t.ws, points_xy_le, scalars_le, n, c, K, true)) return rc;
+    if (int rc = enqueue_host_pieces(ctx, t.d, t.ws, r)) return rc;
     hand_out_ticket(ctx, t, ticket);
     return 0;
   }
-  const int level = ctx->opt_check_points, curve = ctx->opt_curve, form = pf.scalar_mont;
-  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, points_xy_le, scalars_le, n, c, K, level, curve, form]() -> int {
+  const int level = ctx->opt_check_points, curve = ctx->opt_curve;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, r, level, curve]() -> int {
     // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
-    if (const int rc = check_ticket(ctx, t.ws, (size_t)t.di, points_xy_le, true, n, curve, level)) return rc;
-    return enqueue_host_slice(ctx, t.d, t.ws, points_xy_le, scalars_le, n, c, K, false, form);
+    if (const int rc = check_ticket(ctx, t.ws, (size_t)t.di, r.points, true, r.n, curve, level)) return rc;
+    return enqueue_host_pieces(ctx, t.d, t.ws, r);
   });
   hand_out_ticket(ctx, t, ticket, nullptr, std::move(job));
   return 0;
@@ -2612,7 +2578,7 @@ int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* base
 // from its own copy of the bound records.  One host thread per device enqueues its copy, its share and its read-back.
 int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_scalars, uint64_t n, uint8_t* out) {
   const size_t nd = ctx->devs.size();
-  plan_t p0; make_plan(ctx, ctx->devs[0], n, p0);
+  const plan_t p0 = make_plan(ctx, ctx->devs[0], plan_shard(n));
   const int owner = owner_of(ctx, "te_msm_run_scalars_device: the scalars must be resident on a device of the context", {d_scalars});
   if (owner < 0) return owner;
   const int src_dev = ctx->devs[(size_t)owner].device;
@@ -2658,7 +2624,7 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
   if (wsel < 0) return wsel;
   workset_t& ws = d.ws[wsel];
   HIP_TRY(ctx, hipSetDevice(d.device));
-  plan_t p0; make_plan(ctx, d, n, p0);
+  const plan_t p0 = make_plan(ctx, d, plan_shard(n));
   const curve_sizes sz = sizes_of(p0.curve);
   const bool fb = bases->fb_c && (ctx->devs.size() > 1 || d.w_step == 1);      // (a window-sharded single-device context keeps the ordinary windows)
   if (fb) {
@@ -2666,7 +2632,9 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
     else { if (int rc = enqueue_fixed_base(ctx, d, ws, bases, src, n, 0, ws.stream)) return rc; if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc; }
   } else if (src_is_host && !ctx->opt_profile && d.w_step == 1) {
     // whole MSM, no stage timing: the scalars in pieces
-    if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[di], bases->rec_kind, static_cast<const uint8_t*>(src), n, p0.c, scalar_pieces(ctx, n))) return rc;
+    host_slice_req r; r.recs = bases->recs[di]; r.rec_kind = bases->rec_kind; r.scalars = static_cast<const uint8_t*>(src); r.n = n;
+    r.c = p0.c; r.K = scalar_pieces(ctx, n);
+    if (int rc = enqueue_host_pieces(ctx, d, ws, r)) return rc;
   } else {
     const void* ds = src;
     if (src_is_host) {
@@ -2736,14 +2704,14 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
   std::optional<ticket_set> taken;
   if (int rc = take_free_workset(ctx, -1, false, taken)) return rc;
   const ticket_set& t = *taken;
-  plan_t pf; make_plan(ctx, t.d, n, pf, 0, 1, 0, true);
+  const plan_t pf = make_plan(ctx, t.d, plan_whole(n));
   // pieces shorten ONE MSM's way through the device (its upload hides under its own first pieces); with other tickets in flight on
   // the device the upload hides under THEIR device work, and one piece keeps the sort and the accumulation at full width
-  const int c = pf.c, K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, n) : 1;
-  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind, form = pf.scalar_mont;
-  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, bases, recs, kind, scalars_le, n, c, K, form]() -> int {
-    return bases->fb_c ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, scalars_le, n, false, form)
-                       : enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, n, c, K, false, nullptr, 0, 0, form);
+  host_slice_req r; r.recs = bases->recs[(size_t)t.di]; r.rec_kind = bases->rec_kind; r.scalars = scalars_le; r.n = n;
+  r.c = pf.c; r.K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, n) : 1;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, bases, r]() -> int {
+    return bases->fb_c ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, r.scalars, r.n, false, r.scalar_form) : enqueue_host_pieces(ctx, t.d, t.ws, r);
   });
   hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
@@ -2810,9 +2778,10 @@ int run_indexed_common(te_ctx* ctx, te_bases* bases, const void* idx, const void
   workset_t& ws = d.ws[wsel];
   HIP_TRY(ctx, hipSetDevice(d.device));
   if (src_is_host) {
-    plan_t p0; make_plan(ctx, d, m, p0, 0, 1, 0, true);
-    if (int rc = enqueue_scalar_slice(ctx, d, ws, bases->recs[(size_t)owner], bases->rec_kind, static_cast<const uint8_t*>(src), m, p0.c,
-                                      te_indexed::pieces(m, ctx->opt_scalar_chunks), true, static_cast<const uint32_t*>(idx), bases->n, 0)) return rc;
+    host_slice_req r; r.recs = bases->recs[(size_t)owner]; r.rec_kind = bases->rec_kind; r.scalars = static_cast<const uint8_t*>(src); r.n = m;
+    r.c = make_plan(ctx, d, plan_whole(m)).c; r.K = scalar_pieces(ctx, m);
+    r.idx = static_cast<const uint32_t*>(idx); r.idx_count = bases->n;
+    if (int rc = enqueue_host_pieces(ctx, d, ws, r)) return rc;
   } else {
     partial_req r; r.d_scalars = src; r.n = m; r.stream = ws.stream; r.whole = true; r.bases = bases; r.d_idx = static_cast<const uint32_t*>(idx);
     if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
@@ -2840,13 +2809,13 @@ int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* 
   std::optional<ticket_set> taken;
   if (int rc = take_free_workset(ctx, -1, false, taken)) return rc;
   const ticket_set& t = *taken;
-  plan_t pf; make_plan(ctx, t.d, m, pf, 0, 1, 0, true);
+  const plan_t pf = make_plan(ctx, t.d, plan_whole(m));
+  host_slice_req r; r.recs = bases->recs[(size_t)t.di]; r.rec_kind = bases->rec_kind; r.scalars = scalars_le; r.n = m;
   // (pieces: the rule of te_msm_submit_scalars -- with other tickets in flight the upload hides under their device work)
-  const int c = pf.c, K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? te_indexed::pieces(m, ctx->opt_scalar_chunks) : 1;
-  const uint8_t* recs = bases->recs[(size_t)t.di]; const int kind = bases->rec_kind, form = pf.scalar_mont; const uint64_t count = bases->n;
-  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, recs, kind, idx, scalars_le, m, c, K, count, form]() -> int {
-    return enqueue_scalar_slice(ctx, t.d, t.ws, recs, kind, scalars_le, m, c, K, false, idx, count, 0, form);
-  });
+  r.c = pf.c; r.K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, m) : 1;
+  r.idx = idx; r.idx_count = bases->n;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont;
+  te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, r]() -> int { return enqueue_host_pieces(ctx, t.d, t.ws, r); });
   hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
 }
@@ -3297,7 +3266,7 @@ int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_sca
 namespace {
 // what one MSM adds to a ragged sequence whose largest length is n (ensure_buffers' sizes, per MSM; te_batch::make_plan's budget)
 void batch_cost(const te_ctx* ctx, uint64_t n, te_batch::msm_cost& c) {
-  plan_t p; make_plan(ctx, ctx->devs[0], n, p, 0, 1, 0, true);
+  const plan_t p = make_plan(ctx, ctx->devs[0], plan_whole(n));
   const curve_sizes sz = sizes_of(p.curve);
   c.windows = (uint64_t)p.W; c.stride = p.nst;
   const uint64_t cells = c.windows * c.stride, wb = c.windows * p.B, segs = wb + c.windows * (n / p.seg_len);
@@ -3416,8 +3385,8 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
   for (const te_batch::sequence& s : P.seqs) {
     batch_seq_run r; r.s = &s;
     const size_t di = src_is_host ? (size_t)s.device : holder;
-    make_plan(ctx, ctx->devs[di], s.n_max, r.p, 0, (int)s.msms.size(), 0, true);
-    r.p.rec_kind = bases->rec_kind;
+    plan_req q = plan_whole(s.n_max); q.batch = (int)s.msms.size(); q.rec_kind = bases->rec_kind;
+    r.p = make_plan(ctx, ctx->devs[di], q);
     runs[(size_t)s.device].push_back(r);
   }
   // the scalars on each device that runs sequences: device form -- in place; host form -- one device: the caller's packed buffer,
@@ -3508,7 +3477,7 @@ int te_msm_set_window_shard(te_ctx* ctx, int first, int step) {
 
 int te_msm_plan(te_ctx* ctx, uint64_t n, int* window_bits, int* num_windows) {
   if (!ctx) return TE_MSM_EINVAL;
-  plan_t p; make_plan(ctx, ctx->devs[0], n ? n : 1, p);
+  const plan_t p = make_plan(ctx, ctx->devs[0], plan_shard(n ? n : 1));
   if (window_bits) *window_bits = p.c;
   if (num_windows) *num_windows = p.W;
   return 0;
