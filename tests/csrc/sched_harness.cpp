@@ -6,7 +6,7 @@
 // merge (csrc/host_tail.hpp: te_host::merge_window_rows, as the multi-device te_msm_run uses it).  What is faked is the GPU:
 // a "device" is a thread that computes an MSM's partial rows with the device arithmetic compiled for the host
 // (fpc_partial_rows, tests/csrc/fpcheck.cpp) and then signals an event, the way a stream signals ev_result.
-// The fake engine below makes the calls into te_sched:: that csrc/te_msm.hip makes, in its order: fk_submit is submit_host with
+// The fake engine below makes the calls into te_sched:: that csrc/tickets.hip makes, in its order: fk_submit is submit_host with
 // take_free_workset, post_to_lane (clear job_err, pick the lane, post, keep a failure's text: lane_status) and hand_out_ticket written
 // out; fk_ticket_wait and fk_collect are te_msm_ticket_wait and te_msm_collect (find, await_job, the result's event, retire, status).  Built with -fsanitize=thread by tests/sanitize/Makefile; any report fails the run.
 // SURVEY.md section 5 "race detection / sanitizers" (the reference is single-threaded JavaScript).
@@ -134,7 +134,7 @@ int fk_collect(fake_ctx* c, uint64_t ticket, uint8_t out[64]) {
   te_host::horner_to_affine(ws.rows.data(), WBITS, WBITS - 1, NWIN, out);
   return 0;
 }
-// the lone call on several devices (csrc/te_msm.hip: run_host_sharded): point slices, one host thread per device, the sets' rows
+// the lone call on several devices (csrc/run.hip: run_host_sharded): point slices, one host thread per device, the sets' rows
 // merged window by window BY THOSE THREADS (distinct elements of merged[] / present[]), one fold
 int fk_run(fake_ctx* c, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out[64]) {
   if (n == 0) { memset(out, 0, 64); out[32] = 1; return 0; }

@@ -19,7 +19,7 @@ from oracle.gen_golden import make_inputs
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PIECE = 1 << 18                      # host x-coordinates cross the link in pieces of 2^18 (te_msm.hip, kCheckPiece)
+PIECE = 1 << 18                      # host x-coordinates cross the link in pieces of 2^18 (points.hip, kCheckPiece)
 
 
 def _dev(buf):

@@ -312,6 +312,17 @@ def test_abi_exports_every_declared_symbol(pkg):
     assert len(syms) >= 14
     for s in syms:
         assert hasattr(L, s), f"{s} declared in include/te_msm.h but not exported"
+    # ... and nothing else: the functions the library defines for the dynamic linker are exactly the declared ones, beside the kernels'
+    # launch stubs (te::__device_stub__*).  An engine internal exported under a plain name (tmp_alloc, pick_device, owner_of ...) could
+    # be pre-empted by any other object of the host process that defines the name.
+    import shutil
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    if not nm:
+        pytest.skip("nm is not installed")
+    out = subprocess.run([nm, "-D", "--defined-only", pkg.library_path()], stdout=subprocess.PIPE, check=True, universal_newlines=True).stdout
+    text = [l.split()[-1] for l in out.splitlines() if len(l.split()) >= 3 and l.split()[-2] == "T"]
+    exported = sorted(s for s in text if "__device_stub__" not in s)
+    assert exported == syms, {"exported, not declared": sorted(set(exported) - set(syms)), "declared, not exported": sorted(set(syms) - set(exported))}
 
 
 def test_library_has_gfx950_code_object(pkg):

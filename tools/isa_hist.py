@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Instruction-class histogram of one kernel in the gfx950 ISA listing (`make -C csrc asm`).
+"""Instruction-class histogram of one kernel in the gfx950 ISA listing (`make -C csrc asm`: the kernels of csrc/te_msm.hip, i.e. the MSM stages
+and the queue probe; the check, x-recovery and scalar-multiplication kernels are compiled in csrc/points.hip and are not in it).
 
 usage: tools/isa_hist.py <listing.s> <kernel-substring> [--loop]
   --loop   restrict to the hottest loop: the first loop of the kernel that holds at least one field product

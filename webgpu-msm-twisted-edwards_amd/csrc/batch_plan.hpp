@@ -33,7 +33,7 @@ struct limits {
   uint64_t seq_bytes = 1ull << 30;      // scratch budget of one sequence
 };
 
-// What ONE MSM adds to a sequence whose largest length is n, under the engine's plan for n (te_msm.hip, batch_cost)
+// What ONE MSM adds to a sequence whose largest length is n, under the engine's plan for n (bases.hip, batch_cost)
 struct msm_cost {
   uint64_t bytes = 0;        // scratch bytes
   uint64_t windows = 1;      // windows of its decomposition

@@ -56,7 +56,7 @@ TE_HD geometry make_geometry(uint64_t n, int c, uint32_t scatter_blocks = 1024u,
   g.lds_bytes = (size_t)(2u * g.rows + g.rows * 2u * g.P) * sizeof(uint32_t);
   return g;
 }
-// the two refusals "windows x points must stay below 2^31", as te_msm_bind_points and enqueue_fixed_base (te_msm.hip) call them: of a
+// the two refusals "windows x points must stay below 2^31", as te_msm_bind_points (bases.hip) and enqueue_fixed_base (te_msm.hip) call them: of a
 // bind, and of an MSM over the set
 TE_HD bool bind_refused(int c, uint64_t n_table) { return (uint64_t)windows_for(c) * n_table >= (1ull << 31); }
 TE_HD bool msm_refused(const geometry& g, uint64_t n_table) { return (uint64_t)g.rows * g.cap >= (1ull << 31) || (uint64_t)g.W * n_table >= (1ull << 31); }

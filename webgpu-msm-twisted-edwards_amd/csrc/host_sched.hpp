@@ -1,7 +1,7 @@
 // host_sched.hpp -- the parts of the engine's host side that involve more than one thread: the per-device host thread (a
 // FIFO of jobs) and the bookkeeping of MSMs in flight (tickets on work sets, which device the next one goes to).
 //
-// No HIP in here.  te_msm.hip builds the C-ABI's submit / ticket_wait / collect on these pieces, and
+// No HIP in here.  tickets.hip builds the C-ABI's submit / ticket_wait / collect on these pieces, and
 // tests/csrc/sched_harness.cpp drives the SAME code under ThreadSanitizer with a stand-in for the device (SURVEY.md
 // section 5, "race detection / sanitizers"; the reference is single-threaded JavaScript and has no counterpart --
 // its async call convention is ui/Benchmark.tsx:32, multi-device its README's future work, README.md:551).
@@ -117,7 +117,7 @@ inline int pick_device(const int* in_flight, int n_dev, int sets_per_dev, int pr
 //   ctx.last_dev           int, the device the previous ticket went to
 //   ctx.workers[i]         std::unique_ptr<worker_t>, device i's host thread (the lone call's slices and shares)
 //   ctx.lanes, ctx.next_lane   the upload lanes of asynchronous tickets, see next_lane_of
-// te_msm.hip instantiates these with te_ctx / gpu_t / workset_t, tests/csrc/sched_harness.cpp with a stand-in device.
+// The engine (engine.hpp) instantiates these with te_ctx / gpu_t / workset_t, tests/csrc/sched_harness.cpp with a stand-in device.
 // Except for find_ticket and await_job -- which only read, with acquire loads, and may run on any thread -- everything here
 // runs under the caller's serialisation of the context.
 

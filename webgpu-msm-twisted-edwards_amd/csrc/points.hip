@@ -1,0 +1,408 @@
+// points.hip -- what the library does with points beside MSMs: validation (option "check_points", te_msm_check_points*), x-only
+// points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x) and batch scalar multiplication (te_msm_mul*).  The one unit
+// that includes the kernels of check.hip.hpp, from_x.hip.hpp and scalar_mul.hip.hpp.
+#include "engine.hpp"
+#include "check.hip.hpp"
+#include "from_x.hip.hpp"
+#include "scalar_mul.hip.hpp"
+
+using namespace te_eng;
+
+namespace te_eng {
+
+namespace {
+// ---- input-point validation (option "check_points", te_msm_check_points*; kernels in check.hip.hpp) ----------------------------
+// Runs on device devs[di] in front of whatever the call does with the points, and waits for its verdict: a point that fails must
+// stop the call before an MSM result exists.  Device-resident points are checked where they lie (one launch per check); host points
+// cross PCIe in pieces of kCheckPiece through the device's own buffer -- the same bytes the MSM uploads again afterwards: checking is
+// opt-in and priced in the header.  The report word takes the lowest failing index of a launch (check_code); pieces run in order,
+// so the first piece that reports holds the lowest index of the whole buffer.
+constexpr uint64_t kCheckPiece = 1ull << 18;
+
+// The check lane of a device (its stream, report word and pinned host word: check_points_on, recover_on, mul_on), held while this
+// lives: chk_mu locked, the device made current, the three created on first use.  rc: 0, or the HIP error (noted) that left it unusable.
+struct check_lane {
+  gpu_t& d;
+  std::lock_guard<std::mutex> lk;
+  const int rc;
+  check_lane(te_ctx* ctx, gpu_t& dev) : d(dev), lk(*dev.chk_mu), rc(open(ctx, dev)) {}
+  hipStream_t stream() const { return d.chk_stream; }
+  // the report word on the host: 0, or TE_MSM_EPOINT and the lowest failing index among the m points it covers (check_decode)
+  int verdict(te_ctx* ctx, uint64_t m, int64_t* bad, int* reason) {
+    HIP_TRY(ctx, hipMemcpyAsync(d.chk_host, d.chk_word, sizeof(unsigned long long), hipMemcpyDeviceToHost, d.chk_stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d.chk_stream));
+    if (!*d.chk_host) return 0;
+    te::check_decode(*d.chk_host, m, bad, reason);
+    return TE_MSM_EPOINT;
+  }
+ private:
+  static int open(te_ctx* ctx, gpu_t& d) {
+    HIP_TRY(ctx, hipSetDevice(d.device));
+    if (!d.chk_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.chk_stream, hipStreamNonBlocking));
+    if (!d.chk_word) HIP_TRY(ctx, hipMalloc(&d.chk_word, sizeof(unsigned long long)));
+    if (!d.chk_host) HIP_TRY(ctx, hipHostMalloc(&d.chk_host, sizeof(unsigned long long), hipHostMallocDefault));
+    return 0;
+  }
+};
+
+// te_msm_run_x and te_msm_mul* read canonical scalars only: with option "scalars_montgomery" set they are refused (a silent canonical
+// reading would be a wrong answer)
+const char* const kNoMontgomeryScalars = "option \"scalars_montgomery\" is set: te_msm_run_x and te_msm_mul* take canonical scalars only";
+int check_standalone(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, int level, int64_t* first_bad, int* reason) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  int64_t bad = -1; int why = 0;
+  if (first_bad) *first_bad = -1;
+  if (reason) *reason = 0;
+  if (level != 1 && level != 2) return set_err(ctx, TE_MSM_EINVAL, "te_msm_check_points: level must be 1 or 2");
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n > 0 && !src) return set_err(ctx, TE_MSM_EINVAL, "null point buffer");
+  const int di = !src_is_host && n > 0 && ctx->devs.size() > 1
+                     ? owner_of(ctx, "te_msm_check_points_device: the points must be resident on a device of the context", {src}) : 0;
+  if (di < 0) return di;
+  const int rc = check_points_on(ctx, (size_t)di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why, ctx->opt_points_montgomery != 0);
+  if (rc != TE_MSM_EPOINT) return rc;
+  return note_bad(ctx, kBadPoint, bad, why, first_bad, reason);
+}
+
+// ---- x-only points (te_msm_points_from_x[_device], te_msm_bind_points_x, te_msm_run_x; kernels in from_x.hip.hpp) ----------------
+// Recovery runs on device devs[di] into a buffer of the call's own, and the call waits for the verdict: on a failure nothing reaches
+// the caller's output and no MSM runs.  Host x-coordinates cross PCIe in pieces of kCheckPiece through a staging buffer, on the
+// check stream of the device (one stream: a piece's copy waits for the previous piece's kernel); every piece reports into one word
+// over the whole buffer, so the lowest failing index wins without a wait per piece.  The temporary buffers are freed before the call
+// returns (dev_tmp): nothing is cached, nothing counts in "device_bytes".
+
+inline size_t x_bytes_of(int curve) { return curve == TE_MSM_CURVE_BLS12_377_G1 ? TE_MSM_X_BYTES_BLS12_377 : TE_MSM_X_BYTES; }
+
+// n x-coordinates at src (host, or memory of devs[di]) -> n points in d_pts (memory of devs[di]); then, when dst is given and every x
+// passed, the points are copied to dst (host or device memory) before the lock is released
+int recover_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, void* d_pts, void* dst, bool dst_is_host,
+               int64_t* bad, int* reason) {
+  *bad = -1; *reason = 0;
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const int curve = ctx->opt_curve;
+  const size_t xb = x_bytes_of(curve), pb = sizes_of(curve).point_in;
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
+  dev_tmp stage;
+  if (src_is_host) { if (int rc = tmp_alloc(ctx, d, stage, piece * xb)) return rc; }
+  hipStream_t st = lane.stream();
+  HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint8_t* at = static_cast<const uint8_t*>(src) + off * xb;
+    if (src_is_host) { HIP_TRY(ctx, hipMemcpyAsync(stage.p, at, (size_t)m * xb, hipMemcpyHostToDevice, st)); at = static_cast<const uint8_t*>(stage.p); }
+    const uint4* x4 = reinterpret_cast<const uint4*>(at);
+    uint4* o4 = reinterpret_cast<uint4*>(static_cast<uint8_t*>(d_pts) + off * pb);
+    const dim3 grid((m + 255u) / 256u), block(256);
+    if (curve == TE_MSM_CURVE_BLS12_377_G1) hipLaunchKernelGGL(te::k_points_from_x<1>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::kRootExp377, te::kNaf377Order);
+    else hipLaunchKernelGGL(te::k_points_from_x<0>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::kRootExpTe, te::kNafTeOrder);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if (int rc = lane.verdict(ctx, n, bad, reason)) return rc;
+  if (dst) {
+    HIP_TRY(ctx, hipMemcpyAsync(dst, d_pts, n * pb, dst_is_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+  }
+  return 0;
+}
+// host x -> points of the first device in t (allocated here): 0, TE_MSM_EPOINT (noted) or a device error
+int recover_host_to_first(te_ctx* ctx, const uint8_t* x_le, uint64_t n, dev_tmp& t) {
+  if (int rc = tmp_alloc(ctx, ctx->devs[0], t, n * sizes_of(ctx->opt_curve).point_in)) return rc;
+  int64_t bad = -1; int why = 0;
+  const int rc = recover_on(ctx, 0, x_le, true, n, t.p, nullptr, false, &bad, &why);
+  if (rc == TE_MSM_EPOINT) return note_bad(ctx, kBadX, bad, why);
+  return rc;
+}
+int from_x_args(te_ctx* ctx, const void* x, uint64_t n, const void* out) {
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n > 0 && (!x || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  return 0;
+}
+// te_msm_points_from_x (buffers on the host: recovery on the first device) and te_msm_points_from_x_device (on the device that holds them)
+int points_from_x_common(te_ctx* ctx, const void* x, bool on_host, uint64_t n, void* out, int64_t* first_bad, int* reason) {
+  if (!ctx) return TE_MSM_EINVAL;
+  if (first_bad) *first_bad = -1;
+  if (reason) *reason = 0;
+  if (int rc = from_x_args(ctx, x, n, out)) return rc;
+  if (n == 0) return 0;
+  const int di = on_host ? 0 : owner_of(ctx, "te_msm_points_from_x_device: x and the output must be resident on one device of the context", {x, out});
+  if (di < 0) return di;
+  dev_tmp pts;
+  if (int rc = tmp_alloc(ctx, ctx->devs[(size_t)di], pts, n * sizes_of(ctx->opt_curve).point_in)) return rc;
+  int64_t bad = -1; int why = 0;
+  const int rc = recover_on(ctx, (size_t)di, x, on_host, n, pts.p, out, on_host, &bad, &why);
+  if (rc != TE_MSM_EPOINT) return rc;
+  return note_bad(ctx, kBadX, bad, why, first_bad, reason);
+}
+
+// ---- batch scalar multiplication (te_msm_mul[_device], te_msm_mul_x; kernels in scalar_mul.hip.hpp) ------------------------------
+// Host buffers: contiguous slices over the context's devices, one host thread per device (on_devices), as te_msm_run's point slices.
+// Every slice is staged whole on its device -- points (or x), scalars and results -- checked (recovery, option "check_points"),
+// multiplied, and copied out only when no slice reported a bad point: on a failure `out` is untouched.  The chain writes projective
+// results of a piece of kMulPiece points into a buffer of the call's own; the affine pass turns them into the wire format.  Every
+// temporary is freed before the call returns (dev_tmp).
+constexpr uint64_t kMulPiece = 1ull << 18;
+// te_msm_mul* as te_msm_run_x: canonical scalars only -- refused under the option instead of a silent canonical reading
+int mul_refused(te_ctx* ctx) { return ctx->opt_scalars_montgomery ? set_err(ctx, TE_MSM_EINVAL, kNoMontgomeryScalars) : 0; }
+
+inline te::naf_t shared_naf_of(const uint8_t* k32, int curve) {
+  uint32_t k[8];
+  memcpy(k, k32, 32);
+  return te::sm_shared_naf(k, curve);
+}
+// n points and scalars (memory of devs[di]) -> n affine results at d_out (memory of devs[di]); returns when they are there
+int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t n, bool shared, const te::naf_t& kn, void* d_out) {
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const int curve = ctx->opt_curve;
+  const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1;
+  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in;
+  const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  const uint64_t piece = std::min(n, kMulPiece);
+  dev_tmp proj;
+  if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
+  hipStream_t st = lane.stream();
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint4* p4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_pts) + off * pb);
+    const uint4* s4 = shared ? nullptr : reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_sc) + off * sb);
+    uint4* j4 = static_cast<uint4*>(proj.p);
+    uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
+    const dim3 grid((m + 255u) / 256u), block(256), agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP));
+    if (bls) {
+      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<1, true>), grid, block, 0, st, p4, s4, m, j4, kn);
+      else hipLaunchKernelGGL((te::k_scalar_mul<1, false>), grid, block, 0, st, p4, s4, m, j4, kn);
+      hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExp377);
+    } else {
+      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<0, true>), grid, block, 0, st, p4, s4, m, j4, kn);
+      else hipLaunchKernelGGL((te::k_scalar_mul<0, false>), grid, block, 0, st, p4, s4, m, j4, kn);
+      hipLaunchKernelGGL(te::k_scalar_mul_affine<0>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExpTe);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+int mul_args(te_ctx* ctx, const void* pts, const void* sc, uint64_t n, const void* out) {
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n > 0 && (!pts || !sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  return 0;
+}
+// te_msm_mul (x_only = false) and te_msm_mul_x (true): host buffers, sliced over the devices
+int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalars_le, uint64_t n, bool shared, uint8_t* out) {
+  if (int rc = mul_args(ctx, src, scalars_le, n, out)) return rc;
+  if (n == 0) return 0;
+  const int curve = ctx->opt_curve, level = ctx->opt_check_points;
+  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in, ib = x_only ? x_bytes_of(curve) : pb;
+  const te::naf_t kn = shared ? shared_naf_of(scalars_le, curve) : te::naf_t{};
+  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
+  const uint64_t per = (n + D - 1) / D;
+  struct slice_t { dev_tmp pts, sc, res; int64_t bad = -1; int why = 0; bool from_x = false; };
+  std::vector<slice_t> sl(D);
+  auto stage = [&](size_t i) -> int {                             // upload, recover, check, multiply: everything but the copy out
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    gpu_t& d = ctx->devs[i];
+    slice_t& s = sl[i];
+    if (int rc = tmp_alloc(ctx, d, s.pts, m * pb)) return rc;
+    if (int rc = tmp_alloc(ctx, d, s.res, m * pb)) return rc;
+    if (!shared) {
+      if (int rc = tmp_alloc(ctx, d, s.sc, m * sb)) return rc;
+      HIP_TRY(ctx, hipMemcpy(s.sc.p, scalars_le + lo * sb, m * sb, hipMemcpyHostToDevice));
+    }
+    if (x_only) {
+      const int rc = recover_on(ctx, i, src + lo * ib, true, m, s.pts.p, nullptr, false, &s.bad, &s.why);
+      if (rc == TE_MSM_EPOINT) { s.from_x = true; return 0; }
+      if (rc) return rc;
+    } else {
+      HIP_TRY(ctx, hipMemcpy(s.pts.p, src + lo * ib, m * pb, hipMemcpyHostToDevice));
+    }
+    if (level) {
+      const int rc = check_points_on(ctx, i, s.pts.p, false, m, curve, level, &s.bad, &s.why);
+      if (rc == TE_MSM_EPOINT) return 0;
+      if (rc) return rc;
+    }
+    return mul_on(ctx, i, s.pts.p, s.sc.p, m, shared, kn, s.res.p);
+  };
+  auto copy_out = [&](size_t i) -> int {
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
+    HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].res.p, m * pb, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
+  for (size_t i = 0; i < D; i++) {                                // slices in order: the first that reports holds the lowest index
+    if (sl[i].bad < 0) continue;
+    return note_bad(ctx, sl[i].from_x ? kBadX : kBadPoint, (int64_t)(per * i) + sl[i].bad, sl[i].why);
+  }
+  return te_sched::on_devices(*ctx, D, copy_out);
+}
+}  // namespace
+
+// mont: the coordinates are Montgomery residues (option "points_montgomery": te_msm_bind_points*, te_msm_check_points*); every per-call
+// check of an MSM or a multiplication reads canonical coordinates
+int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason, bool mont) {
+  *bad = -1; *reason = 0;
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  const size_t pb = sizes_of(curve).point_in;
+  const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
+  if (src_is_host) { if (int rc = make_room(ctx, d.chk_pts, piece * pb)) return rc; }
+  hipStream_t st = lane.stream();
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint8_t* at = static_cast<const uint8_t*>(src) + off * pb;
+    if (src_is_host) { HIP_TRY(ctx, hipMemcpyAsync(d.chk_pts, at, (size_t)m * pb, hipMemcpyHostToDevice, st)); at = d.chk_pts; }
+    const uint4* p4 = reinterpret_cast<const uint4*>(at);
+    HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
+    const dim3 grid((m + 255u) / 256u), block(256);
+    if (mont && curve == TE_MSM_CURVE_BLS12_377_G1) {
+      hipLaunchKernelGGL((te::k_check_form<1, true>), grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL((te::k_check_subgroup<1, true>), grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
+    } else if (mont) {
+      hipLaunchKernelGGL((te::k_check_form<0, true>), grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL((te::k_check_subgroup<0, true>), grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
+    } else if (curve == TE_MSM_CURVE_BLS12_377_G1) {
+      hipLaunchKernelGGL(te::k_check_form<1>, grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<1>, grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
+    } else {
+      hipLaunchKernelGGL(te::k_check_form<0>, grid, block, 0, st, p4, m, d.chk_word);
+      if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<0>, grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    int64_t i = -1;
+    const int rc = lane.verdict(ctx, m, &i, reason);
+    if (rc == TE_MSM_EPOINT) *bad = (int64_t)off + i;
+    if (rc) return rc;
+  }
+  return 0;
+}
+// A failed check (kBadPoint) or recovery (kBadX, x-only points) as the outcome of a call: the failure is remembered for get_option
+// ("bad_point_index" / "bad_point_reason"), described in the error text and written to the caller's outputs where given.
+int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* first_bad, int* reason_out) {
+  ctx->bad_point_index = index; ctx->bad_point_reason = reason;
+  if (first_bad) *first_bad = index;
+  if (reason_out) *reason_out = reason;
+  char buf[256];
+  if (kind == kBadPoint)
+    snprintf(buf, sizeof buf, "input point %lld failed the check of option \"check_points\": %s", (long long)index,
+             reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical coordinate" : reason == TE_MSM_POINT_OFF_CURVE ? "not on the curve (or map undefined)" : "not in the prime-order subgroup");
+  else
+    snprintf(buf, sizeof buf, "x-coordinate %lld has no point (reason %d): %s", (long long)index, reason,
+             reason == TE_MSM_POINT_NONCANONICAL ? "non-canonical (x >= modulus, or reserved flag bits set)"
+             : reason == TE_MSM_POINT_OFF_CURVE ? "no point on the curve has this x (or the point at infinity / map undefined)"
+                                                : "no point of the prime-order subgroup has this x");
+  return set_err(ctx, TE_MSM_EPOINT, buf);
+}
+// option "check_points" in front of a call: 0 = go on, TE_MSM_EPOINT (noted) or a device error
+int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont) {
+  if (!ctx->opt_check_points) return 0;
+  int64_t bad = -1; int reason = 0;
+  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points, &bad, &reason, mont);
+  if (rc == TE_MSM_EPOINT) return note_bad(ctx, kBadPoint, bad, reason);
+  return rc;
+}
+
+int tmp_alloc(te_ctx* ctx, gpu_t& d, dev_tmp& t, size_t bytes) {
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  HIP_TRY(ctx, hipMalloc(&t.p, bytes ? bytes : 16));
+  t.dev = d.device;
+  return 0;
+}
+
+}  // namespace te_eng
+
+extern "C" {
+
+int te_msm_check_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason) {
+  return check_standalone(ctx, points_xy_le, true, n, level, first_bad, reason);
+}
+int te_msm_check_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, int level, int64_t* first_bad, int* reason) {
+  return check_standalone(ctx, d_points_xy_le, false, n, level, first_bad, reason);
+}
+
+int te_msm_points_from_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_points_xy_le, int64_t* first_bad, int* reason) {
+  device_guard restore_callers_device;
+  return points_from_x_common(ctx, x_le, true, n, out_points_xy_le, first_bad, reason);
+}
+
+int te_msm_points_from_x_device(te_ctx* ctx, const void* d_x_le, uint64_t n, void* d_out_points_xy_le, int64_t* first_bad, int* reason) {
+  device_guard restore_callers_device;
+  return points_from_x_common(ctx, d_x_le, false, n, d_out_points_xy_le, first_bad, reason);
+}
+
+int te_msm_bind_points_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, te_bases** out) {
+  device_guard restore_callers_device;
+  if (!ctx || !out) return TE_MSM_EINVAL;
+  *out = nullptr;
+  if (int rc = from_x_args(ctx, x_le, n, out)) return rc;
+  if (n == 0) return bind_common(ctx, x_le, true, 0, out);
+  dev_tmp pts;
+  if (int rc = recover_host_to_first(ctx, x_le, n, pts)) return rc;
+  return bind_common(ctx, pts.p, false, n, out);                 // as te_msm_bind_points_device (conversion on every device, check_points)
+}
+
+int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx || !out_xy_le) return TE_MSM_EINVAL;
+  if (ctx->opt_scalars_montgomery) return set_err(ctx, TE_MSM_EINVAL, kNoMontgomeryScalars);
+  if (int rc = from_x_args(ctx, x_le, n, scalars_le)) return rc;
+  if (n == 0) return run_common(ctx, x_le, scalars_le, true, 0, out_xy_le);
+  dev_tmp pts, sc;
+  if (int rc = recover_host_to_first(ctx, x_le, n, pts)) return rc;
+  gpu_t& d = ctx->devs[0];
+  const size_t sbytes = n * sizes_of(ctx->opt_curve).scalar_in;
+  if (int rc = tmp_alloc(ctx, d, sc, sbytes)) return rc;
+  {
+    check_lane lane(ctx, d);
+    if (lane.rc) return lane.rc;
+    HIP_TRY(ctx, hipMemcpyAsync(sc.p, scalars_le, sbytes, hipMemcpyHostToDevice, lane.stream()));
+    HIP_TRY(ctx, hipStreamSynchronize(lane.stream()));
+  }
+  return run_common(ctx, pts.p, sc.p, false, n, out_xy_le, SHARE_CONVERT);   // as te_msm_run_device (window shards, check_points, TE_MSM_ESCALAR)
+}
+
+int te_msm_mul(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = mul_refused(ctx)) return rc;
+  return mul_host(ctx, points_xy_le, false, scalars_le, n, shared_scalar != 0, out_points_xy_le);
+}
+
+int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = mul_refused(ctx)) return rc;
+  return mul_host(ctx, x_le, true, scalars_le, n, shared_scalar != 0, out_points_xy_le);
+}
+
+int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_scalars_le, uint64_t n, int shared_scalar, void* d_out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = mul_refused(ctx)) return rc;
+  if (int rc = mul_args(ctx, d_points_xy_le, d_scalars_le, n, d_out_points_xy_le)) return rc;
+  if (n == 0) return 0;
+  const int owner = owner_of(ctx, "te_msm_mul_device: the points, the scalars and the output must be resident on one device of the context",
+                             {d_points_xy_le, d_scalars_le, d_out_points_xy_le});
+  if (owner < 0) return owner;
+  gpu_t& d = ctx->devs[(size_t)owner];
+  te::naf_t kn = {};
+  if (shared_scalar) {                                            // the NAF is built here: the scalar's first 32 bytes come back
+    uint8_t k[32];
+    HIP_TRY(ctx, hipSetDevice(d.device));
+    HIP_TRY(ctx, hipMemcpy(k, d_scalars_le, 32, hipMemcpyDeviceToHost));
+    kn = shared_naf_of(k, ctx->opt_curve);
+  }
+  if (int rc = check_call(ctx, (size_t)owner, d_points_xy_le, false, n)) return rc;
+  return mul_on(ctx, (size_t)owner, d_points_xy_le, d_scalars_le, n, shared_scalar != 0, kn, d_out_points_xy_le);
+}
+
+}  // extern "C"
