@@ -349,6 +349,46 @@ int te_msm_mul(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars_
 int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_scalars_le, uint64_t n, int shared_scalar, void* d_out_points_xy_le);
 int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, uint64_t n, int shared_scalar, uint8_t* out_points_xy_le);
 
+/* ---- fixed-base batch scalar multiplication -----------------------------------------------------------------------------------
+ * out[i] = [k_i] P for ONE point P bound in advance and n scalars: arkworks' FixedBase::msm / batch_mul ([tau^i] G of an SRS, [sk_i] G
+ * of many addresses, Pedersen generators).  te_msm_bind_base tabulates [j 2^(W i)] P once (i < M = ceil(257 / W), j = 0 .. 2^(W-1);
+ * W = option "mul_base_window", 4..12, default 12, read at bind time), on EVERY device of the context; [k] P is then one table
+ * look-up and one mixed addition per window -- no doublings (csrc/mul_base.hip.hpp).
+ * te_msm_bind_base: one point in host memory, wire format (64 / 96 bytes), canonical -- option "points_montgomery" is NOT read.  The
+ *   curve is option "curve" at bind time; a later call under the other curve, or with a released handle, is TE_MSM_EINVAL with the
+ *   output untouched.  Twisted-Edwards: any point of the curve, cofactor part included.  BLS12-377: P must lie in G1.  Option
+ *   "check_points" (1, 2) applies to the point: a failure is TE_MSM_EPOINT with "bad_point_index" 0 and its reason, no handle is made
+ *   and nothing stays bound.  The table, M (2^(W-1) + 1) entries of 128 bytes a device (0.54 MB at W = 8, 1.7 MB at W = 10, 5.8 MB at
+ *   W = 12), is held until te_msm_release_base or te_msm_destroy; it is the only resident memory (read-only options "mul_bases_bound",
+ *   "mul_base_bytes": handles bound, bytes held on all devices -- not counted in "bases_bound" / "bases_bytes").
+ * te_msm_mul_base[_device]: exactly [k_i] P for every k_i below 2^256, with no reduction of k_i that could be wrong for the input.
+ *   Scalars: the MSM's records (32 bytes; BLS12-377: 48-byte records whose bytes 32..47 are not read).  Option "scalars_montgomery" is
+ *   read when a call starts: with it set a record holds a and the call uses k = a 2^-256 mod m (m = L or r as for the MSMs), decoded
+ *   in registers -- a native prover's &[Fr] of powers of tau goes in as it is (te_msm_mul* keep refusing the option).
+ *   Output: as te_msm_mul -- canonical affine x || y; the Twisted-Edwards identity is (0, 1), BLS12-377 infinity 96 zero bytes.
+ *   n = 0 is a no-op.  Host form: contiguous slices of the scalars over the context's devices, one host thread per device; results are
+ *   staged and copied out only when every slice succeeded.  Device form: the scalars and the output on one device of the context
+ *   (else TE_MSM_EINVAL); returns with d_out complete.  Every call leaves the calling thread's current device as it found it and
+ *   frees its temporaries before it returns.
+ * te_msm_base_read (stage verification, as te_msm_bases_read): entries [first, first + count) of window `window` on one device,
+ *   at most cap bytes; returns the bytes written, *entry_bytes (optional) receives 128.  An entry is [j 2^(W window)] P, j its index in
+ *   the window: Twisted-Edwards hm | hp | dt of 9 words each (te_msm_bases_read's record; entry 0 is the record of (0, 1));
+ *   BLS12-377 affine short-Weierstrass x | y of 14 words each in the engine's Montgomery form (entry 0 holds x = y = 0 mod q and is never added).
+ * COST (MI355X, device buffers, three alternating rounds, lowest .. highest; tools/mul_base_cost.py, profiles/mul_base_cost.txt), per call
+ *   of 2^20 scalars against te_msm_mul_device over the point replicated:
+ *     Twisted-Edwards  20.9 .. 21.1 ms replicated;  bound: W = 6 3.01 .. 3.10, W = 8 2.56 .. 2.57, W = 10 2.24 .. 2.28, W = 12 2.08 .. 2.10 ms
+ *     BLS12-377        72.0 .. 72.3 ms replicated;  bound: W = 6 11.5 .. 11.7, W = 8 9.59 .. 9.71, W = 10 8.33 .. 8.47, W = 12 7.66 .. 7.75 ms
+ *   W = 12 is lowest in every round at every size measured (2^10 .. 2^20), hence the default.  Of a W = 12 call the affine pass
+ *   (k_scalar_mul_affine, unchanged) is 0.82 of 1.9 ms / 3.5 of 7.5 ms kernel time.  The bind took 1.7 .. 2.8 ms (Twisted-Edwards) and
+ *   5.2 .. 7.5 ms (BLS12-377) per table on one device, W = 6 .. 12. */
+typedef struct te_base te_base;
+int te_msm_bind_base(te_ctx* ctx, const uint8_t* point_xy_le, te_base** out);
+int te_msm_release_base(te_ctx* ctx, te_base* base);
+int te_msm_mul_base(te_ctx* ctx, te_base* base, const uint8_t* scalars_le, uint64_t n, uint8_t* out_points_xy_le);
+int te_msm_mul_base_device(te_ctx* ctx, te_base* base, const void* d_scalars_le, uint64_t n, void* d_out_points_xy_le);
+int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uint32_t window, uint32_t first, uint32_t count, void* dst, uint64_t cap,
+                         int* entry_bytes);
+
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "scalars_montgomery" 0 (default) = scalar records hold the integers themselves (the wire format above); 1 = every scalar record holds
  *                   a = k * 2^256 mod m and the MSM uses k = a * 2^-256 mod m, where m is the scalar field of the curve in force:
@@ -435,6 +475,9 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *                   in; 0 = from n (default), 1 = whole.  The result does not depend on it.
  *   "batch_small_max" te_msm_run_scalars_batch*: MSMs of at most this many points share launch sequences, longer ones run alone
  *                   (default 32768; 0 = every MSM alone).  The result does not depend on it.  Read-only "batch_sequences": see there.
+ *   "mul_base_window" W in [4, 12] (default 12, the fastest measured): window bits of the table te_msm_bind_base builds, see "fixed-base batch scalar
+ *                   multiplication" above.  Read at bind time; a handle keeps the W it was bound with.  Read-only "mul_bases_bound",
+ *                   "mul_base_bytes": see there.
  *   read-only:      "num_devices", "segment_len_used", "peer_copies" / "peer_bytes" (hipMemcpyPeerAsync calls a multi-device
  *                   context issued, and the bytes they moved), "entries_accumulated" (non-zero window digits of the MSM whose
  *                   result was fetched last, counted on the device: the points k_accumulate gathered -- all windows of this

@@ -11,6 +11,7 @@ There is no CPU fallback anywhere in this package: without libtemsm.so and a HIP
 point raises.
 """
 from .binding import (  # noqa: F401
+    Base,
     Bases,
     MsmContext,
     MsmError,

@@ -200,6 +200,19 @@ def _lib() -> ctypes.CDLL:
         L.te_msm_mul_device.restype = ci
         L.te_msm_mul_x.argtypes = [vp, cp, cp, u64, ci, cp]
         L.te_msm_mul_x.restype = ci
+        # (a library TE_MSM_LIB names for an A/B against an OLDER build -- tools/mul_base_cost.py --parent-lib -- has no fixed-base entry
+        # points: there they stay undeclared and MsmContext.bind_base raises AttributeError; the in-tree library must have them)
+        if not os.environ.get("TE_MSM_LIB") or hasattr(L, "te_msm_bind_base"):
+            L.te_msm_bind_base.argtypes = [vp, cp, ctypes.POINTER(vp)]
+            L.te_msm_bind_base.restype = ci
+            L.te_msm_release_base.argtypes = [vp, vp]
+            L.te_msm_release_base.restype = ci
+            L.te_msm_mul_base.argtypes = [vp, vp, cp, u64, cp]
+            L.te_msm_mul_base.restype = ci
+            L.te_msm_mul_base_device.argtypes = [vp, vp, vp, u64, vp]
+            L.te_msm_mul_base_device.restype = ci
+            L.te_msm_base_read.argtypes = [vp, vp, ci, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, u64, ctypes.POINTER(ci)]
+            L.te_msm_base_read.restype = ctypes.c_int64
         _LIB = L
     return _LIB
 
@@ -462,6 +475,43 @@ class MsmContext:
         self._check(self._L.te_msm_mul_x(self._h, bytes(xs), bytes(scalars), n, int(shared), out))
         return out.raw[:self._sizes[0] * n]
 
+    # ---- fixed-base batch scalar multiplication (include/te_msm.h): one point bound, [k_i] P for many scalars
+    def bind_base(self, point: bytes) -> "Base":
+        """te_msm_bind_base: tabulates one point (64 / 96 bytes, canonical) on every device of the context -- option "mul_base_window"
+        (4..12, default 8) as it is now; option "check_points" applies to the point"""
+        pb = self._sizes[0]
+        if len(point) != pb:
+            raise MsmError(-1, f"the point must be {pb} bytes")
+        h = ctypes.c_void_p()
+        self._check(self._L.te_msm_bind_base(self._h, bytes(point), ctypes.byref(h)))
+        return Base(self, h, self.curve, self.get_option("mul_base_window"))
+
+    def release_base(self, base: "Base"):
+        self._check(self._L.te_msm_release_base(self._h, base._h))
+        base._h = None
+
+    def mul_base(self, base: "Base", scalars: bytes) -> bytes:
+        """te_msm_mul_base: n scalar records (32 / 48 bytes; Montgomery residues under option "scalars_montgomery") -> n points [k_i] P,
+        canonical affine x || y as mul() writes them"""
+        pb, sb = self._sizes[0], self._sizes[1]
+        if len(scalars) % sb:
+            raise MsmError(-1, f"scalars must be {sb}*n bytes")
+        n = len(scalars) // sb
+        out = ctypes.create_string_buffer(max(1, pb * n))
+        self._check(self._L.te_msm_mul_base(self._h, base._h, bytes(scalars), n, out))
+        return out.raw[:pb * n]
+
+    def mul_base_device(self, base: "Base", d_scalars: int, n: int, d_out: int):
+        """te_msm_mul_base_device: the same between buffers on one device of the context"""
+        self._check(self._L.te_msm_mul_base_device(self._h, base._h, d_scalars, n, d_out))
+
+    def base_read(self, base: "Base", window: int, first: int, count: int, device_index: int = 0):
+        """(entry bytes, raw entries [first, first + count) of one window of the table on one device) -- te_msm_base_read"""
+        eb = ctypes.c_int(0)
+        buf = ctypes.create_string_buffer(max(1, count * 128))
+        got = self._check(self._L.te_msm_base_read(self._h, base._h, device_index, window, first, count, buf, count * 128, ctypes.byref(eb)))
+        return eb.value, buf.raw[:got]
+
     def bases_read(self, bases: "Bases", first: int, count: int, device_index: int = 0):
         """(record bytes, raw records [first, first + count) of the bound set on one device) -- te_msm_bases_read"""
         rb = ctypes.c_int(0)
@@ -657,6 +707,18 @@ class Bases:
     def release(self):
         if self._h is not None and getattr(self._ctx, "_h", None):
             self._ctx.release_points(self)
+        self._h = None
+
+
+class Base:
+    """A bound point of one MsmContext (te_base): the table of fixed-base scalar multiplication on every device of the context."""
+
+    def __init__(self, ctx: MsmContext, handle, curve: int, window: int):
+        self._ctx, self._h, self.curve, self.window = ctx, handle, curve, window
+
+    def release(self):
+        if self._h is not None and getattr(self._ctx, "_h", None):
+            self._ctx.release_base(self)
         self._h = None
 
 

@@ -78,6 +78,7 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
   if (!strcmp(key, "scalar_chunks")) { if (value < 0 || value > 64) return set_err(ctx, TE_MSM_EINVAL, "scalar_chunks out of range"); ctx->opt_scalar_chunks = (int)value; return 0; }
   if (!strcmp(key, "scalars_montgomery")) { if (value != 0 && value != 1) return set_err(ctx, TE_MSM_EINVAL, "scalars_montgomery must be 0 or 1"); ctx->opt_scalars_montgomery = (int)value; return 0; }
   if (!strcmp(key, "points_montgomery")) { if (value != 0 && value != 1) return set_err(ctx, TE_MSM_EINVAL, "points_montgomery must be 0 or 1"); ctx->opt_points_montgomery = (int)value; return 0; }
+  if (!strcmp(key, "mul_base_window")) { if (value < 4 || value > 12) return set_err(ctx, TE_MSM_EINVAL, "mul_base_window must be in [4, 12]"); ctx->opt_mul_base_window = (int)value; return 0; }
   if (!strcmp(key, "batch_small_max")) { if (value < 0 || value > (1ll << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch_small_max must be in [0, 2^31]"); ctx->opt_batch_small_max = value; return 0; }
   return set_err(ctx, TE_MSM_EINVAL, "unknown option");
 }
@@ -123,6 +124,9 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "fixed_base_fallbacks")) { *value = ctx->stat_fb_fallbacks; return 0; }
   if (!strcmp(key, "bases_bound")) { *value = (int64_t)ctx->bases.size(); return 0; }
   if (!strcmp(key, "bases_bytes")) { int64_t t = 0; for (const te_bases* b : ctx->bases) for (const uint8_t* r : b->recs) if (r) t += (int64_t)(b->n * b->rec_bytes) * (b->fb_c ? b->fb_W : 1); *value = t; return 0; }
+  if (!strcmp(key, "mul_base_window")) { *value = ctx->opt_mul_base_window; return 0; }
+  if (!strcmp(key, "mul_bases_bound")) { *value = (int64_t)ctx->mul_bases.size(); return 0; }
+  if (!strcmp(key, "mul_base_bytes")) { int64_t t = 0; for (const te_base* b : ctx->mul_bases) for (const uint8_t* r : b->tab) if (r) t += (int64_t)b->bytes(); *value = t; return 0; }
   if (!strcmp(key, "in_flight")) { int64_t t = 0; for (const gpu_t& d : ctx->devs) t += d.in_flight; *value = t; return 0; }
   if (!strcmp(key, "device_bytes")) {      drain_workers(ctx);      // device memory this context holds in work-set buffers (te_msm_trim gives it back)
     int64_t tot = 0;

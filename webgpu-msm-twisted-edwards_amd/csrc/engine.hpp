@@ -7,7 +7,7 @@
 //              run.hip      te_msm_init / destroy, the lone calls te_msm_run[_device], how a call's status is settled
 //              tickets.hip  te_msm_submit* / ticket_wait / collect
 //              bases.hip    bound point sets: bind, scalars-only, indexed and batched MSMs
-//              points.hip   point checks, x-only points, batch scalar multiplication
+//              points.hip   point checks, x-only points, batch scalar multiplication (per point, and over one bound point)
 //              abi.hip      the rest of the C-ABI: options, trim, building blocks, host tails, debug reads
 // Everything in here has hidden visibility; a function only one unit calls is file-local there.  The library exports the C-ABI of
 // include/te_msm.h and nothing else of the engine.
@@ -251,6 +251,8 @@ struct te_ctx {
   int opt_scalars_montgomery = 0;   // scalar records are Montgomery residues k 2^256 mod m, decoded in the digit kernels (csrc/scalar_form.hpp); read when a call
                                     // starts, on the calling thread -- a ticket keeps the form it was submitted with (plan_t::scalar_mont)
   int opt_points_montgomery = 0;    // te_msm_bind_points[_device]: coordinates are Montgomery residues x 2^256 mod p / x 2^384 mod q; read at bind time
+  std::vector<te_base*> mul_bases;  // the bound points of fixed-base scalar multiplication (te_msm_bind_base), freed by te_msm_release_base / te_msm_destroy
+  int opt_mul_base_window = 12;     // te_msm_bind_base: window bits W of the table, 4..12 (option "mul_base_window"; 12 measured fastest at every size: DESIGN.md section 17); read at bind time
 };
 
 // A bound point set (include/te_msm.h, "resident bases"): the records of n points on EVERY device of its context, converted
@@ -263,6 +265,17 @@ struct te_bases {
   std::vector<uint8_t*> recs;    // recs[i]: n records in the memory of ctx->devs[i]
   int fb_c = 0, fb_W = 0;        // fixed-base windows: recs[i] holds fb_W tables of n records, table w = records of 2^(fb_c w) P_i (table 0 = the ordinary records)
   int in_flight = 0;             // tickets not collected that gather from it (the set cannot be released under them)
+};
+
+// A bound point of fixed-base batch scalar multiplication (include/te_msm.h, te_msm_bind_base; csrc/mul_base.hip.hpp): the table
+// [j 2^(W i)] P, i < M, j <= 2^(W-1), in 128-byte entries on EVERY device of its context, built once.
+struct te_base {
+  te_ctx* ctx = nullptr;
+  int curve = TE_MSM_CURVE_TE_BLS12;
+  int W = 0, M = 0;              // window bits, windows
+  uint32_t per = 0;              // entries of a window: 2^(W-1) + 1
+  std::vector<uint8_t*> tab;     // tab[i]: M * per entries in the memory of ctx->devs[i]
+  size_t bytes() const { return (size_t)M * per * 128; }
 };
 
 namespace te_eng {
@@ -440,6 +453,7 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
 int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* first_bad = nullptr, int* reason_out = nullptr);
 int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont = false);
 int tmp_alloc(te_ctx* ctx, gpu_t& d, dev_tmp& t, size_t bytes);
+void free_mul_base(te_ctx* ctx, te_base* b);
 
 // An asynchronous ticket: `enqueue` (the upload and the launches of one whole MSM; 0 or an error already noted) runs on an upload lane
 // of the ticket's device, and the call returns at once -- D of them keep D links busy.  The job's status, and the error text of a failure,

@@ -1,10 +1,12 @@
 // points.hip -- what the library does with points beside MSMs: validation (option "check_points", te_msm_check_points*), x-only
-// points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x) and batch scalar multiplication (te_msm_mul*).  The one unit
-// that includes the kernels of check.hip.hpp, from_x.hip.hpp and scalar_mul.hip.hpp.
+// points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x), batch scalar multiplication (te_msm_mul*) and its fixed-base form
+// over one bound point (te_msm_bind_base, te_msm_mul_base*).  The one unit that includes the kernels of check.hip.hpp, from_x.hip.hpp,
+// scalar_mul.hip.hpp and mul_base.hip.hpp.
 #include "engine.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
 #include "scalar_mul.hip.hpp"
+#include "mul_base.hip.hpp"
 
 using namespace te_eng;
 
@@ -243,7 +245,121 @@ int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalar
   }
   return te_sched::on_devices(*ctx, D, copy_out);
 }
+
+// ---- fixed-base batch scalar multiplication (te_msm_bind_base, te_msm_mul_base[_device]; kernels in mul_base.hip.hpp) ---------------
+// The bind makes the table's scalars j 2^(W i) mod (4 L | r) on the host and runs te_msm_mul's own chain (mul_on) over the point
+// replicated, on every device; k_mul_base_entries turns the affine results into entries.  A call is mul_on's shape with k_mul_base in the
+// chain's place: pieces of kMulPiece scalars into a projective buffer of the call's own, then the affine pass.  The table is the only
+// memory that outlives a call.
+const char* const kBadBase = "not a bound point of this context (released, or bound to another context)";
+const char* const kBaseCurve = "the point was bound under another curve than the one selected now (option \"curve\")";
+int check_base(te_ctx* ctx, const te_base* b) {
+  if (!b || std::find(ctx->mul_bases.begin(), ctx->mul_bases.end(), b) == ctx->mul_bases.end()) return set_err(ctx, TE_MSM_EINVAL, kBadBase);
+  if (b->curve != ctx->opt_curve) return set_err(ctx, TE_MSM_EINVAL, kBaseCurve);
+  return 0;
+}
+// the table of b on device devs[i]: pts / sc hold the point replicated and the scalar records of its entries (host memory)
+int base_table_on(te_ctx* ctx, te_base* b, size_t i, const uint8_t* pts, const uint8_t* sc, const te::mb_geom& g) {
+  gpu_t& d = ctx->devs[i];
+  const bool bls = b->curve == TE_MSM_CURVE_BLS12_377_G1;
+  const size_t pb = sizes_of(b->curve).point_in, sb = sizes_of(b->curve).scalar_in;
+  HIP_TRY(ctx, hipSetDevice(d.device));
+  HIP_TRY(ctx, hipMalloc((void**)&b->tab[i], b->bytes()));                 // (freed by the caller on failure: free_mul_base)
+  dev_tmp d_pts, d_sc, d_aff;
+  if (int rc = tmp_alloc(ctx, d, d_pts, g.entries * pb)) return rc;
+  if (int rc = tmp_alloc(ctx, d, d_sc, g.entries * sb)) return rc;
+  if (int rc = tmp_alloc(ctx, d, d_aff, g.entries * pb)) return rc;
+  HIP_TRY(ctx, hipMemcpy(d_pts.p, pts, g.entries * pb, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(d_sc.p, sc, g.entries * sb, hipMemcpyHostToDevice));
+  if (int rc = mul_on(ctx, i, d_pts.p, d_sc.p, g.entries, false, te::naf_t{}, d_aff.p)) return rc;
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  const dim3 grid((g.entries + 255u) / 256u), block(256);
+  const uint4* a4 = static_cast<const uint4*>(d_aff.p);
+  uint4* t4 = reinterpret_cast<uint4*>(b->tab[i]);
+  if (bls) hipLaunchKernelGGL(te::k_mul_base_entries<1>, grid, block, 0, lane.stream(), a4, g.entries, t4);
+  else hipLaunchKernelGGL(te::k_mul_base_entries<0>, grid, block, 0, lane.stream(), a4, g.entries, t4);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(lane.stream()));
+  return 0;
+}
+// n scalar records (memory of devs[di]; mont: Montgomery residues) -> n affine results at d_out (memory of devs[di]); returns when they are there
+int mul_base_on(te_ctx* ctx, size_t di, const te_base* b, const void* d_sc, uint64_t n, bool mont, void* d_out) {
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const bool bls = b->curve == TE_MSM_CURVE_BLS12_377_G1;
+  const size_t pb = sizes_of(b->curve).point_in, sb = sizes_of(b->curve).scalar_in;
+  const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
+  const te::mb_geom g = te::mb_geometry(b->W);
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  const uint64_t piece = std::min(n, kMulPiece);
+  dev_tmp proj;
+  if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
+  hipStream_t st = lane.stream();
+  const uint4* t4 = reinterpret_cast<const uint4*>(b->tab[di]);
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint4* s4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_sc) + off * sb);
+    uint4* j4 = static_cast<uint4*>(proj.p);
+    uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
+    const dim3 grid((m + 255u) / 256u), block(256), agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP));
+    if (bls) {
+      if (mont) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_377>), grid, block, 0, st, t4, s4, m, j4, g);
+      else hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_CANONICAL>), grid, block, 0, st, t4, s4, m, j4, g);
+      hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExp377);
+    } else {
+      if (mont) hipLaunchKernelGGL((te::k_mul_base<0, te::SCALAR_FORM_TE>), grid, block, 0, st, t4, s4, m, j4, g);
+      else hipLaunchKernelGGL((te::k_mul_base<0, te::SCALAR_FORM_CANONICAL>), grid, block, 0, st, t4, s4, m, j4, g);
+      hipLaunchKernelGGL(te::k_scalar_mul_affine<0>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExpTe);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+// what every te_msm_mul_base* call checks first; *go = false: nothing to do (n = 0)
+int mul_base_args(te_ctx* ctx, const te_base* b, const void* sc, uint64_t n, const void* out, bool* go) {
+  *go = false;
+  if (int rc = check_base(ctx, b)) return rc;
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n > 0 && (!sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  *go = n > 0;
+  return 0;
+}
+// te_msm_mul_base: host scalars sliced over the devices, as mul_host
+int mul_base_host(te_ctx* ctx, const te_base* b, const uint8_t* scalars_le, uint64_t n, uint8_t* out) {
+  const bool mont = ctx->opt_scalars_montgomery != 0;
+  const size_t pb = sizes_of(b->curve).point_in, sb = sizes_of(b->curve).scalar_in;
+  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
+  const uint64_t per = (n + D - 1) / D;
+  struct slice_t { dev_tmp sc, res; };
+  std::vector<slice_t> sl(D);
+  auto stage = [&](size_t i) -> int {                             // upload and multiply: everything but the copy out
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    gpu_t& d = ctx->devs[i];
+    if (int rc = tmp_alloc(ctx, d, sl[i].sc, m * sb)) return rc;
+    if (int rc = tmp_alloc(ctx, d, sl[i].res, m * pb)) return rc;
+    HIP_TRY(ctx, hipMemcpy(sl[i].sc.p, scalars_le + lo * sb, m * sb, hipMemcpyHostToDevice));
+    return mul_base_on(ctx, i, b, sl[i].sc.p, m, mont, sl[i].res.p);
+  };
+  auto copy_out = [&](size_t i) -> int {
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
+    HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].res.p, m * pb, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
+  return te_sched::on_devices(*ctx, D, copy_out);
+}
 }  // namespace
+
+void free_mul_base(te_ctx* ctx, te_base* b) {
+  for (size_t i = 0; i < b->tab.size() && i < ctx->devs.size(); i++)
+    if (b->tab[i]) { (void)hipSetDevice(ctx->devs[i].device); (void)hipFree(b->tab[i]); b->tab[i] = nullptr; }
+}
 
 // mont: the coordinates are Montgomery residues (option "points_montgomery": te_msm_bind_points*, te_msm_check_points*); every per-call
 // check of an MSM or a multiplication reads canonical coordinates
@@ -403,6 +519,84 @@ int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_sca
   }
   if (int rc = check_call(ctx, (size_t)owner, d_points_xy_le, false, n)) return rc;
   return mul_on(ctx, (size_t)owner, d_points_xy_le, d_scalars_le, n, shared_scalar != 0, kn, d_out_points_xy_le);
+}
+
+int te_msm_bind_base(te_ctx* ctx, const uint8_t* point_xy_le, te_base** out) {
+  device_guard restore_callers_device;
+  if (!ctx || !out) return TE_MSM_EINVAL;
+  *out = nullptr;
+  if (!point_xy_le) return set_err(ctx, TE_MSM_EINVAL, "null point");
+  const int curve = ctx->opt_curve;
+  if (ctx->opt_check_points) {                                      // (canonical coordinates: "points_montgomery" is not read here)
+    int64_t bad = -1; int why = 0;
+    const int rc = check_points_on(ctx, 0, point_xy_le, true, 1, curve, ctx->opt_check_points, &bad, &why);
+    if (rc == TE_MSM_EPOINT) return note_bad(ctx, kBadPoint, 0, why);
+    if (rc) return rc;
+  }
+  const te::mb_geom g = te::mb_geometry(ctx->opt_mul_base_window);
+  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in;
+  std::vector<uint32_t> words((size_t)g.entries * 8);
+  te::mb_table_scalars(curve == TE_MSM_CURVE_BLS12_377_G1 ? 1 : 0, g, words.data());
+  std::vector<uint8_t> sc((size_t)g.entries * sb, 0), pts((size_t)g.entries * pb);
+  for (uint32_t e = 0; e < g.entries; e++) {
+    memcpy(&sc[(size_t)e * sb], &words[(size_t)e * 8], 32);
+    memcpy(&pts[(size_t)e * pb], point_xy_le, pb);
+  }
+  te_base* b = new te_base;
+  b->ctx = ctx; b->curve = curve; b->W = g.W; b->M = g.M; b->per = g.H + 1u;
+  const size_t nd = ctx->devs.size();
+  b->tab.assign(nd, nullptr);
+  const int rc = te_sched::on_devices(*ctx, nd, [&](size_t i) { return base_table_on(ctx, b, i, pts.data(), sc.data(), g); });
+  if (rc) { free_mul_base(ctx, b); delete b; return rc; }
+  ctx->mul_bases.push_back(b);
+  *out = b;
+  return 0;
+}
+
+int te_msm_release_base(te_ctx* ctx, te_base* base) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  const auto at = std::find(ctx->mul_bases.begin(), ctx->mul_bases.end(), base);
+  if (!base || at == ctx->mul_bases.end()) return set_err(ctx, TE_MSM_EINVAL, kBadBase);
+  free_mul_base(ctx, base);                                         // (every call over it has returned: they are synchronous)
+  ctx->mul_bases.erase(at);
+  delete base;
+  return 0;
+}
+
+int te_msm_mul_base(te_ctx* ctx, te_base* base, const uint8_t* scalars_le, uint64_t n, uint8_t* out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  bool go = false;
+  if (int rc = mul_base_args(ctx, base, scalars_le, n, out_points_xy_le, &go)) return rc;
+  return go ? mul_base_host(ctx, base, scalars_le, n, out_points_xy_le) : 0;
+}
+
+int te_msm_mul_base_device(te_ctx* ctx, te_base* base, const void* d_scalars_le, uint64_t n, void* d_out_points_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  bool go = false;
+  if (int rc = mul_base_args(ctx, base, d_scalars_le, n, d_out_points_xy_le, &go)) return rc;
+  if (!go) return 0;
+  const int owner = owner_of(ctx, "te_msm_mul_base_device: the scalars and the output must be resident on one device of the context", {d_scalars_le, d_out_points_xy_le});
+  if (owner < 0) return owner;
+  return mul_base_on(ctx, (size_t)owner, base, d_scalars_le, n, ctx->opt_scalars_montgomery != 0, d_out_points_xy_le);
+}
+
+int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uint32_t window, uint32_t first, uint32_t count, void* dst, uint64_t cap,
+                         int* entry_bytes) {
+  device_guard restore_callers_device;
+  if (!ctx || !dst) return TE_MSM_EINVAL;
+  if (!base || std::find(ctx->mul_bases.begin(), ctx->mul_bases.end(), base) == ctx->mul_bases.end()) return set_err(ctx, TE_MSM_EINVAL, kBadBase);
+  if (device_index < 0 || (size_t)device_index >= ctx->devs.size() || window >= (uint32_t)base->M || first > base->per || count > base->per - first)
+    return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
+  if (entry_bytes) *entry_bytes = 128;
+  uint64_t bytes = (uint64_t)count * 128;
+  if (bytes > cap) bytes = cap;
+  if (!bytes) return 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->devs[(size_t)device_index].device));
+  HIP_TRY(ctx, hipMemcpy(dst, base->tab[(size_t)device_index] + ((size_t)window * base->per + first) * 128, bytes, hipMemcpyDeviceToHost));
+  return (int64_t)bytes;
 }
 
 }  // extern "C"

@@ -416,6 +416,7 @@ void te_msm_destroy(te_ctx* ctx) {
       if (b->recs[i]) { (void)hipSetDevice(ctx->devs[i].device); (void)hipFree(b->recs[i]); }
     delete b;
   }
+  for (te_base* b : ctx->mul_bases) { free_mul_base(ctx, b); delete b; }   // ... and the bound points of te_msm_bind_base
   delete ctx;
 }
 

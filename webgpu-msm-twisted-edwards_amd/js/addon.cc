@@ -402,6 +402,83 @@ napi_value MsmIndexed(napi_env env, napi_callback_info info) {
 napi_value ScalarMul(napi_env env, napi_callback_info info) { return MulCommon(env, info, false); }
 napi_value ScalarMulX(napi_env env, napi_callback_info info) { return MulCommon(env, info, true); }
 
+// setBase(point: Buffer) and scalarMulBase(scalars: Buffer): Buffer -- fixed-base batch scalar multiplication (include/te_msm.h,
+// te_msm_bind_base / te_msm_mul_base): one 64-byte point bound once, then n x 32-byte little-endian scalars -> n x 64-byte points
+// [k_i] P (the identity as (0, 1)).  Twisted-Edwards curve only, like the rest of the addon; run like scalarMul.  The addon keeps the
+// point: a context that replaces the cached one (setDevices, setCheckPoints, ...) binds it again at the next scalarMulBase.  The addon
+// is the only one to bind points on its context, so "no point bound there" is the read-only option "mul_bases_bound" = 0.  A bad
+// point (setCheckPoints) throws as scalarMul does, with .index 0; setScalarsMontgomery applies to the scalars.
+uint8_t g_base_point[TE_MSM_POINT_BYTES];
+bool g_have_base = false;
+te_base* g_base = nullptr;      // the handle on the cached context (stale once that context is gone: see bound_base)
+
+int bound_base(te_ctx* c, bool rebind) {
+  int64_t bound = 0;
+  (void)te_msm_get_option(c, "mul_bases_bound", &bound);
+  if (bound && rebind) { (void)te_msm_release_base(c, g_base); bound = 0; }
+  if (!bound) { g_base = nullptr; return te_msm_bind_base(c, g_base_point, &g_base); }
+  return 0;
+}
+napi_value throw_te_error(napi_env env, int rc, const std::string& err, int64_t bad, int64_t reason) {
+  const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+  napi_value msg, errv;
+  napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+  napi_create_error(env, nullptr, msg, &errv);
+  if (rc == TE_MSM_EPOINT) {
+    napi_value iv, rv;
+    napi_create_int64(env, bad, &iv); napi_create_int32(env, (int32_t)reason, &rv);
+    napi_set_named_property(env, errv, "index", iv); napi_set_named_property(env, errv, "reason", rv);
+  }
+  napi_throw(env, errv);
+  return nullptr;
+}
+napi_value SetBase(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool b0 = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &b0);
+  if (!b0) { napi_throw_type_error(env, nullptr, "setBase(point: Buffer)"); return nullptr; }
+  void* p = nullptr; size_t pl = 0;
+  napi_get_buffer_info(env, argv[0], &p, &pl);
+  if (pl != TE_MSM_POINT_BYTES) { napi_throw_range_error(env, nullptr, "setBase: the point must be 64 bytes"); return nullptr; }
+  memcpy(g_base_point, p, TE_MSM_POINT_BYTES);
+  g_have_base = true;
+  int64_t bad = -1, reason = 0;
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    const int r = bound_base(c, true);
+    if (r == TE_MSM_EPOINT) { (void)te_msm_get_option(c, "bad_point_index", &bad); (void)te_msm_get_option(c, "bad_point_reason", &reason); }
+    return r;
+  }, err);
+  if (rc) { g_have_base = false; return throw_te_error(env, rc, err, bad, reason); }
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+napi_value ScalarMulBase(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool b0 = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &b0);
+  if (!b0) { napi_throw_type_error(env, nullptr, "scalarMulBase(scalars: Buffer)"); return nullptr; }
+  if (!g_have_base) { napi_throw_error(env, nullptr, "scalarMulBase: no point bound (setBase)"); return nullptr; }
+  void* s = nullptr; size_t sl = 0;
+  napi_get_buffer_info(env, argv[0], &s, &sl);
+  if (sl % TE_MSM_SCALAR_BYTES != 0) { napi_throw_range_error(env, nullptr, "scalarMulBase: scalars must be 32*n bytes"); return nullptr; }
+  const uint64_t n = sl / TE_MSM_SCALAR_BYTES;
+  std::vector<uint8_t> out((size_t)n * TE_MSM_POINT_BYTES);
+  int64_t bad = -1, reason = 0;
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    int r = bound_base(c, false);
+    if (!r) r = te_msm_mul_base(c, g_base, static_cast<const uint8_t*>(s), n, out.data());
+    if (r == TE_MSM_EPOINT) { (void)te_msm_get_option(c, "bad_point_index", &bad); (void)te_msm_get_option(c, "bad_point_reason", &reason); }
+    return r;
+  }, err);
+  if (rc) return throw_te_error(env, rc, err, bad, reason);
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
+  return buf;
+}
+
 // setCheckPoints(level): opt-in validation of the input points (include/te_msm.h, option "check_points"): 0 = none (default),
 // 1 = canonical and on the curve, 2 = also in the prime-order subgroup (costly: about 3 000 field products per point).  A call whose
 // points fail rejects its promise with an Error that names the lowest failing index and the reason; setBases then throws for a bad
@@ -460,7 +537,8 @@ napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
       {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints}, {"setScalarsMontgomery", SetScalarsMontgomery},
-      {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed}};
+      {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed},
+      {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

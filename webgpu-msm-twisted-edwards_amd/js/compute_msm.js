@@ -72,6 +72,11 @@ const pointsFromX = (xs) => native.pointsFromX(xs);
 // bad point or x throws an Error naming the lowest failing index and the reason (also as .index / .reason).
 const scalarMul = (points, scalars) => native.scalarMul(points, scalars);
 const scalarMulX = (xs, scalars) => native.scalarMulX(xs, scalars);
+// Fixed-base batch scalar multiplication: setBase(point) binds one 64-byte point (its table is built once, and again on a context that
+// replaces the cached one); scalarMulBase(scalars) returns the n points [k_i] P as a 64n-byte Buffer -- scalarMul over the point
+// replicated, without the doublings.  setScalarsMontgomery applies to these scalars.
+const setBase = (point) => native.setBase(point);
+const scalarMulBase = (scalars) => native.scalarMulBase(scalars);
 
 // Outside the reference's interface too: msmBatch(scalarBuffers) runs one MSM per Buffer over the set bound by setBases -- MSM m over
 // its first scalarBuffers[m].length / 32 points (a prover's commitments to polynomials of different degrees against one SRS) -- and
@@ -92,4 +97,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase };

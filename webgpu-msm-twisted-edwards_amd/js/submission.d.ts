@@ -29,6 +29,10 @@ export declare const pointsFromX: (xs: Buffer) => Buffer;
 // x-only points (bulkGroupScalarMul).  One 32-byte scalar is shared by all points; a bad point or x throws (error.index / error.reason).
 export declare const scalarMul: (points: Buffer, scalars: Buffer) => Buffer;
 export declare const scalarMulX: (xs: Buffer, scalars: Buffer) => Buffer;
+// Not in the reference: fixed-base batch scalar multiplication.  setBase binds one 64-byte point (a table built once); scalarMulBase
+// returns [k_i] P for n 32-byte scalars as a 64n-byte points Buffer.  setScalarsMontgomery applies to these scalars.
+export declare const setBase: (point: Buffer) => void;
+export declare const scalarMulBase: (scalars: Buffer) => Buffer;
 // Not in the reference: batched MSMs over prefixes of the set bound by setBases; MSM m runs over the first scalarBuffers[m].length / 32
 // points.  Results in input order, in compute_msm's form; throws without setBases or for a buffer longer than the set.
 export declare const msmBatch: (scalarBuffers: Buffer[]) => { x: bigint; y: bigint }[];
