@@ -15,8 +15,19 @@
  *   result : x[32 B LE] || y[32 B LE], canonical affine  ( == result.toAffine(), submission.ts:412 )
  * A NATIVE PROVER'S FORM (arkworks, snarkVM: a field element is a = k * 2^256 mod m in four u64 limbs -- in memory a 32-byte little-endian
  * integer -- six limbs and 2^384 for the BLS12-377 base field): options "scalars_montgomery" and "points_montgomery" below make the engine
- * read exactly those bytes, the scalars on every MSM call and the points at te_msm_bind_points*.  Record sizes do not change; results are
- * always canonical.
+ * read exactly those bytes, the scalars on every MSM call and the points at te_msm_bind_points*.  Those two options do not change
+ * record sizes; results are always canonical.
+ * A NATIVE PROVER'S SCALAR RECORD: on BLS12-377 G1 the wire format below is a 48-byte record per scalar, a native prover's `Fr` or
+ * `BigInt<4>` is 32 bytes.  Option "scalar_record_bytes" = 32 makes every scalar buffer of a BLS12-377 call n x 32 bytes, so that
+ * `&[Fr]` (with "scalars_montgomery" = 1) or `&[BigInt<4>]` (without) goes in as it is: no repacking on the CPU, a third fewer bytes
+ * over the link.  The 32-byte layout is pinned as written here (four little-endian u64 limbs, least significant first, no padding);
+ * it was not checked against the arkworks sources.
+ * A NATIVE PROVER'S POINT RECORD: te_msm_bind_points[_device] and te_msm_check_points[_device] take packed x || y by default.  Option
+ * "point_stride" makes point i start at byte i * stride, and on BLS12-377 G1 option "point_infinity_flag" reads the byte at offset 96 of
+ * every record as "this is the point at infinity".  Together "points_montgomery" = 1, "point_stride" = 104, "point_infinity_flag" = 1 and
+ * "scalar_record_bytes" = 32 are meant to be `&[G1Affine]` and `&[Fr]` of arkworks 0.4 on a 64-bit little-endian host, G1Affine being
+ * x[48] | y[48] | infinity: bool | 7 bytes of padding = 104 bytes.  That struct layout is pinned as written here; it was not checked
+ * against the arkworks sources.
  *
  * All functions return 0 on success or a negative TE_MSM_E* code; te_msm_last_error() gives text.
  * A context is not thread-safe: serialise the calls on one context (the one exception is te_msm_ticket_wait).
@@ -51,7 +62,7 @@ typedef struct te_ctx te_ctx;
 /* Groups (option "curve").  0: the Twisted-Edwards BLS12 curve of the competition (default; everything above).
  * 1: BLS12-377 G1, y^2 = x^3 + 1 over the 377-bit base field (README.md:57-73, BASELINE config 5): points are
  * n x (x || y) with 48-byte little-endian coordinates (96 bytes), scalars n x 48-byte little-endian records holding
- * values below 2^256 (README.md:325-331), the result is x || y in 96 bytes (the point at infinity as 96 zero bytes) --
+ * values below 2^256 (README.md:325-331) -- or, under option "scalar_record_bytes" = 32, n x 32-byte records --, the result is x || y in 96 bytes (the point at infinity as 96 zero bytes) --
  * `out_xy_le` of te_msm_run / run_device / collect must then hold TE_MSM_RESULT_BYTES_MAX bytes.  Inputs must lie in G1 (the
  * subgroup of prime order r, as the harness generates them): the engine works in the curve's twisted-Edwards form, whose
  * map from y^2 = x^3 + 1 is undefined at the points of order 2 and 4.  As on the other curve, with "check_points" = 0 a
@@ -204,7 +215,8 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
  * set.  te_msm_run_scalars* needs a scalar for every point of the set (a shorter polynomial pays for zero padding), and every MSM is a
  * launch sequence of its own with a latency-bound reduction tail.  These two calls take the whole list:
  *   MSM m = sum_{i < lens[m]} k_{m,i} P_i over the bound set's points.  scalars_le is PACKED: MSM m's lens[m] scalar records start at
- *   record sum_{j<m} lens[j]; the record format is the MSM's own (32 bytes Twisted-Edwards, 48-byte records for BLS12-377).  out receives
+ *   record sum_{j<m} lens[j]; the record format is the MSM's own (32 bytes Twisted-Edwards; BLS12-377: 48-byte records, or 32 under option
+ *   "scalar_record_bytes").  out receives
  *   `count` results in input order, each encoded as te_msm_run_scalars encodes its result (64 / 96 bytes; the Twisted-Edwards identity as
  *   (0, 1), the BLS12-377 point at infinity as zeros).  lens[m] == 0 gives the identity; count == 0 does nothing.
  *   TE_MSM_EINVAL, out untouched: lens[m] > te_msm_bases_count(bases); a null pointer (lens, out, or the scalars while some lens[m] > 0);
@@ -234,7 +246,7 @@ int te_msm_run_scalars_batch_device(te_ctx* ctx, te_bases* bases, int count, con
  * scalars: 32 bytes per BOUND point over PCIe, a digit pass and a sort over n entries, a plan made for n.  These calls take the pairs:
  *   result = sum_{j < m} k_j P_{idx[j]}.  idx: m little-endian u32, each below te_msm_bases_count(bases), in any order, repeats allowed
  *   (the sum is defined either way); scalars_le: m scalar records in the MSM's own format (32 bytes Twisted-Edwards, 48-byte records for
- *   BLS12-377).  m may exceed the set's size and is bounded as n of te_msm_run (m < 2^31).  The result is encoded as te_msm_run_scalars_batch
+ *   BLS12-377 unless option "scalar_record_bytes" says 32).  m may exceed the set's size and is bounded as n of te_msm_run (m < 2^31).  The result is encoded as te_msm_run_scalars_batch
  *   encodes it (64 / 96 bytes); m == 0 gives the identity.
  *   How it runs (csrc/indexed_plan.hpp): entry j's scalar is record j of the CALL, so the digit pass, the sort and the
  *   schedule run over m entries, and window bits, digit form and segment length follow the options with m standing for n.  The sort's first
@@ -329,7 +341,8 @@ int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  * Address.group_scalar_mul) and FieldMath.multiply (utils/FieldMath.ts:71-84).  The curve is option "curve".
  * Points: the wire format above (64 / 96 bytes); te_msm_mul_x takes x-only points in te_msm_points_from_x's format and recovers them
  *   first (on the device, no host round trip).  Scalars: the MSM's format -- 32-byte little-endian (Twisted-Edwards), 48-byte records
- *   holding values below 2^256 (BLS12-377; bytes 32..47 are not read).  shared_scalar != 0: scalars_le holds ONE scalar, used for all
+ *   holding values below 2^256 (BLS12-377; bytes 32..47 are not read), 32-byte records there under option "scalar_record_bytes" = 32.
+ *   shared_scalar != 0: scalars_le holds ONE scalar, used for all
  *   n points (one account scalar applied to many group values).
  * The result is exactly [k] P for every k below 2^256, with no reduction of k that could be wrong for the input:
  *   Twisted-Edwards: any point of the curve, cofactor part included (the group law is complete on the whole curve; a shared scalar is
@@ -362,7 +375,8 @@ int te_msm_mul_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
  *   W = 12), is held until te_msm_release_base or te_msm_destroy; it is the only resident memory (read-only options "mul_bases_bound",
  *   "mul_base_bytes": handles bound, bytes held on all devices -- not counted in "bases_bound" / "bases_bytes").
  * te_msm_mul_base[_device]: exactly [k_i] P for every k_i below 2^256, with no reduction of k_i that could be wrong for the input.
- *   Scalars: the MSM's records (32 bytes; BLS12-377: 48-byte records whose bytes 32..47 are not read).  Option "scalars_montgomery" is
+ *   Scalars: the MSM's records (32 bytes; BLS12-377: 48-byte records whose bytes 32..47 are not read, or 32-byte records under option
+ *   "scalar_record_bytes" = 32, read when the call starts; the bind does not read that option).  Option "scalars_montgomery" is
  *   read when a call starts: with it set a record holds a and the call uses k = a 2^-256 mod m (m = L or r as for the MSMs), decoded
  *   in registers -- a native prover's &[Fr] of powers of tau goes in as it is (te_msm_mul* keep refusing the option).
  *   Output: as te_msm_mul -- canonical affine x || y; the Twisted-Edwards identity is (0, 1), BLS12-377 infinity 96 zero bytes.
@@ -396,7 +410,7 @@ int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uin
  *                     TE_MSM_CURVE_BLS12_377_G1  r = 8444461749428370424248824938781546531375899335154063827935233455917409239041
  *                   ANY 256-bit a is accepted and stands for its residue; the decoded k is canonical (< m), so under the option signed digits
  *                   never return TE_MSM_ESCALAR on the Twisted-Edwards curve, and on BLS12-377 only for a non-zero byte 32..47 of a 48-byte
- *                   record (the value is in bytes 0..31, as always).  The reduction runs where the scalars are first read, in the digit
+ *                   record (the value is in bytes 0..31, as always; a 32-byte record -- "scalar_record_bytes" -- then holds just a).  The reduction runs where the scalars are first read, in the digit
  *                   kernels (csrc/scalar_form.hpp: 8 rounds over 32-bit words, ~70 multiply-accumulates a scalar, in registers): no pass
  *                   over the scalars of its own, nothing for the caller to convert.  Read when a call STARTS, by: te_msm_run[_device],
  *                   te_msm_submit / _async / _device, te_msm_run_scalars[_device], te_msm_submit_scalars[_device],
@@ -407,6 +421,48 @@ int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uin
  *                   output untouched (a silent canonical reading would be a wrong answer).
  *                   COST: not measured yet.  tools/montgomery_inputs.py times the option on against off and the CPU pass it takes off
  *                   the caller; until its output is filed, take the option as a convenience of unknown cost.
+ *   "scalar_record_bytes" 0 (default) = the curve's own scalar record: 32 bytes on the Twisted-Edwards curve, 48 on BLS12-377 G1.  32 on BLS12-377:
+ *                   EVERY scalar buffer of a call is n x 32 bytes little-endian -- where the 48-byte record held a value in bytes 0..31 and
+ *                   zeros above, there is now just the value.  48 on BLS12-377 and 32 on the Twisted-Edwards curve are the defaults spelled
+ *                   out; any other value is TE_MSM_EINVAL here.  48 on the Twisted-Edwards curve is TE_MSM_EINVAL when a call starts, its
+ *                   output untouched (option "curve" may change after this one was set).  Read when a call STARTS, by every entry point
+ *                   that reads "scalars_montgomery" (above) and by te_msm_run_x, te_msm_mul[_device], te_msm_mul_x and
+ *                   te_msm_mul_base[_device].  It sizes every buffer the call reads: host uploads and their pieces ("host_chunks",
+ *                   "scalar_chunks"), the packed buffer of te_msm_run_scalars_batch* (MSM m starts at record sum lens[j], in records of
+ *                   this size), the pairs of the indexed calls, peer copies and the "peer_bytes" they count.  A ticket keeps the size it was
+ *                   submitted with, as it keeps its scalar form: changing the option affects later calls only.  Composes with
+ *                   "scalars_montgomery".  Unchanged: TE_MSM_ESCALAR under signed digits from about 2^254 - 2^240 up (exactly: from
+ *                   2^(cW) - sum_w 2^(cw + c - 1), which at 17 windows of 15 bits is 2^254 - 2^239 - 2^224 - ...);
+ *                   te_msm_bind_base builds its table from records of its own and does not read the option; te_msm_synth_inputs_bls12_377
+ *                   writes 48-byte records.  The digit kernels take the record size at run time; te_msm_mul* and te_msm_mul_base* run
+ *                   another instantiation of their kernels; the existing ones keep their code (profiles/native_layout_isa.txt).
+ *                   MEASURED (MI355X, n = 2^20 over a bound set, scalars from host memory; profiles/native_layout_cost.txt): the lone
+ *                   te_msm_run_scalars call 2.49-2.57 ms with 32-byte records against 2.61-2.67 ms with 48-byte ones, an MSM with four
+ *                   tickets in flight 2.10-2.11 against 2.21-2.22 ms.
+ *   "point_stride"  0 (default) = packed points; else the bytes from one point record to the next: point i starts at byte i * stride, x and y
+ *                   are its first 2 x 32 / 2 x 48 bytes, and the bytes behind the pair (and the flag byte, below) are never interpreted.
+ *                   A multiple of 8 from the pair size (64 / 96) up to 128, else TE_MSM_EINVAL here -- 128 because a block stages its 256
+ *                   records through 32 KB of LDS (csrc/strided.hip.hpp); arkworks' G1Affine is 104.  Read at BIND time, like
+ *                   "points_montgomery", by te_msm_bind_points[_device] and te_msm_check_points[_device], on both curves; a stride below
+ *                   the pair size of the curve in force then is TE_MSM_EINVAL with no handle.  Device pointers of the _device forms must
+ *                   be 8-byte aligned while a stride is set (TE_MSM_EINVAL otherwise); nothing issues a 16-byte load from the caller's
+ *                   buffer.  Host points travel whole at the bind (n * stride bytes) and in pieces cut at record boundaries in the
+ *                   checks.  The records of a set bound at a stride are those of the same points bound packed, bit for bit, so every
+ *                   MSM over the set (ordinary, batch, indexed, tickets, fixed-base windows) is unchanged; multi-device contexts convert
+ *                   on every device.  te_msm_bind_points_x, te_msm_bind_base and the per-call point paths (te_msm_run*, te_msm_submit*,
+ *                   te_msm_partial_device*, te_msm_mul*) do NOT read it.  The packed path keeps its kernels and their code.
+ *   "point_infinity_flag" 0 (default) or 1; BLS12-377 G1 only; read at bind time with "point_stride".  With 1 the byte at offset 96 of every
+ *                   record is a flag, so the stride must be at least 104 (else the bind is TE_MSM_EINVAL; on the Twisted-Edwards curve a
+ *                   bind or check with the option set is TE_MSM_EINVAL: (0, 1) is an ordinary input there).  A flagged record is the point
+ *                   at infinity: its x and y bytes are not looked at (arkworks stores zeros there; the engine does not care) and its
+ *                   record is the neutral element of the twisted-Edwards form, which the additions take as an ordinary operand: in every
+ *                   MSM over the set it contributes nothing, whatever its scalar or digit sign; an MSM whose contributing points are all
+ *                   flagged returns 96 zero bytes.  With "check_points" 1 or 2 at the bind, and in te_msm_check_points* while the option is
+ *                   set, a record whose flag byte is 1 passes both levels and a flag byte other than 0 or 1 is
+ *                   TE_MSM_POINT_NONCANONICAL at its index (lowest index first, as for every other failure); with "check_points" = 0 any
+ *                   non-zero flag byte means infinity.
+ *                   MEASURED (MI355X, 2^20 points from host memory; profiles/native_layout_cost.txt): the bind of arkworks' image (stride 104, flag
+ *                   option, Montgomery coordinates) 4.11-4.13 ms against 3.92-3.95 ms for packed canonical points.
  *   "points_montgomery" 0 (default); 1 = te_msm_bind_points[_device] read coordinates as Montgomery residues: x * 2^256 mod p in 32 bytes
  *                   (Twisted-Edwards), x * 2^384 mod q in 48 bytes (BLS12-377).  Read at BIND time, like "bind_affine": the conversion
  *                   kernels take another constant in their first products, no more arithmetic; the records, and every MSM over the set

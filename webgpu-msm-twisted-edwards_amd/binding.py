@@ -229,8 +229,10 @@ class MsmContext:
             raise MsmError(rc, L.te_msm_last_error(None).decode())
         self._h = h
         self._L = L
-        self._sizes = (64, 32, 64)          # point, scalar, result bytes of the selected curve
+        self._sizes = (64, 32, 64)          # point, scalar, result bytes of the selected curve and scalar record (_resize)
         self.curve = CURVE_TE_BLS12
+        self._scalar_record_bytes = 0       # option "scalar_record_bytes" as set_option left it (0 = the curve's own record)
+        self._point_stride = 0              # option "point_stride" as set_option left it (0 = packed x || y)
         self._held = {}                     # ticket -> the buffers of an asynchronous submit (alive until collected)
 
     def close(self):
@@ -267,7 +269,7 @@ class MsmContext:
     def check_points(self, points: bytes, level: int = 1):
         """te_msm_check_points: None when every point passes, else (lowest failing index, POINT_* reason).  level 1: canonical
         and on the curve; 2: also in the prime-order subgroup (costly: meant for a point set that is used many times)."""
-        pb = self._sizes[0]
+        pb = self._point_stride or self._sizes[0]         # option "point_stride" while it is set: n follows the stride
         if len(points) % pb:
             raise MsmError(-1, f"points must be {pb}*n bytes")
         bad, why = ctypes.c_int64(), ctypes.c_int()
@@ -284,8 +286,18 @@ class MsmContext:
     def set_option(self, key: str, value: int):
         self._check(self._L.te_msm_set_option(self._h, key.encode(), int(value)))
         if key == "curve":
-            self._sizes = (96, 48, 96) if int(value) == CURVE_BLS12_377_G1 else (64, 32, 64)
             self.curve = int(value)
+        elif key == "scalar_record_bytes":
+            self._scalar_record_bytes = int(value)
+        elif key == "point_stride":
+            self._point_stride = int(value)
+        self._resize()
+
+    def _resize(self):
+        """_sizes is the one place that knows the byte sizes: the scalar record is option "scalar_record_bytes" where it is set (32 on
+        BLS12-377: a native prover's records), else the curve's own.  (48 on the Twisted-Edwards curve: the engine refuses the call.)"""
+        pb, sb, rb = (96, 48, 96) if self.curve == CURVE_BLS12_377_G1 else (64, 32, 64)
+        self._sizes = (pb, self._scalar_record_bytes or sb, rb)
 
     @property
     def row_bytes(self) -> int:
@@ -308,7 +320,7 @@ class MsmContext:
     # ---- whole MSM
     def run(self, points: bytes, scalars: bytes) -> bytes:
         """Host buffers in the reference's wire format -> affine result x || y, little-endian (64 bytes; 96 for
-        BLS12-377 G1, whose points are 96 and scalar records 48 bytes)."""
+        BLS12-377 G1, whose points are 96 and scalar records 48 bytes -- 32 under option "scalar_record_bytes" = 32)."""
         pb, sb, rb = self._sizes
         n = len(scalars) // sb
         if len(scalars) != sb * n or len(points) != pb * n:
@@ -365,40 +377,46 @@ class MsmContext:
         self._check(self._L.te_msm_ticket_wait(self._h, ticket))
 
     # ---- resident bases: points bound once, scalars per call (te_msm_bind_points ...)
-    def _bind(self, montgomery: bool, call) -> ctypes.c_void_p:
+    def _bind(self, montgomery: bool, call, stride: int = 0, infinity_flag: bool = False) -> ctypes.c_void_p:
         """One bind call.  montgomery=True: option "points_montgomery" (read at bind time) is 1 for that call and put back afterwards.
         False asks for nothing: the option stays as set_option left it, so the keyword can switch the form on for one set but not off
-        on a context whose option is 1 -- set_option("points_montgomery", 0) does that."""
+        on a context whose option is 1 -- set_option("points_montgomery", 0) does that.  stride / infinity_flag: options "point_stride"
+        and "point_infinity_flag" in the same way."""
         h = ctypes.c_void_p()
-        if not montgomery:
-            self._check(call(ctypes.byref(h)))
-            return h
-        before = self.get_option("points_montgomery")
-        self.set_option("points_montgomery", 1)
+        want = [(k, v) for k, v in (("points_montgomery", 1 if montgomery else 0), ("point_stride", int(stride)),
+                                    ("point_infinity_flag", 1 if infinity_flag else 0)) if v]
+        before = [(k, self.get_option(k)) for k, _ in want]
         try:
+            for k, v in want:
+                self.set_option(k, v)
             self._check(call(ctypes.byref(h)))
         finally:
-            self.set_option("points_montgomery", before)
+            for k, v in before:
+                self.set_option(k, v)
         return h
 
-    def bind_points(self, points: bytes, montgomery: bool = False) -> "Bases":
+    def bind_points(self, points: bytes, montgomery: bool = False, stride: int = 0, infinity_flag: bool = False) -> "Bases":
         """Uploads the points once, converts them to records on every device of the context and keeps only the records
         (te_msm_bind_points).  The harness hands the same point buffer to compute_msm for every run of a size
         (submission/miscellaneous/full_benchmarks.ts:63-68,100-105).
         montgomery=True: the coordinates are a native prover's Montgomery residues (x * 2^256 mod p in 32 bytes; BLS12-377: x * 2^384
         mod q in 48) -- option "points_montgomery" = 1 for this call; False leaves the option as set_option left it.  The records, and every
-        MSM over the set, are the same either way.  (The scalars' counterpart is the option "scalars_montgomery" alone: set_option.)"""
-        pb = self._sizes[0]
+        MSM over the set, are the same either way.  (The scalars' counterpart is the option "scalars_montgomery" alone: set_option.)
+        stride: point i starts at byte i * stride (a multiple of 8 from the size of x || y up to 128; 0 = as set_option left "point_stride",
+        packed by default) -- option "point_stride" for this call.  infinity_flag=True (BLS12-377, stride >= 104): the byte at offset 96 of
+        a record flags the point at infinity -- option "point_infinity_flag" for this call.  Together with montgomery=True and stride=104
+        the buffer is meant to be arkworks' &[G1Affine]."""
+        pb = int(stride) or self._point_stride or self._sizes[0]
         n = len(points) // pb
         if len(points) != pb * n:
             raise MsmError(-1, f"points must be {pb}*n bytes")
         points = bytes(points)
-        h = self._bind(montgomery, lambda out: self._L.te_msm_bind_points(self._h, points, n, out))
+        h = self._bind(montgomery, lambda out: self._L.te_msm_bind_points(self._h, points, n, out), stride, infinity_flag)
         return Bases(self, h, n, self.curve)
 
-    def bind_points_device(self, d_points: int, n: int, montgomery: bool = False) -> "Bases":
-        """te_msm_bind_points_device; montgomery: as bind_points"""
-        h = self._bind(montgomery, lambda out: self._L.te_msm_bind_points_device(self._h, d_points, n, out))
+    def bind_points_device(self, d_points: int, n: int, montgomery: bool = False, stride: int = 0, infinity_flag: bool = False) -> "Bases":
+        """te_msm_bind_points_device; montgomery, stride, infinity_flag: as bind_points (the buffer 8-byte aligned under a stride)"""
+        h = self._bind(montgomery, lambda out: self._L.te_msm_bind_points_device(self._h, d_points, n, out), stride, infinity_flag)
         return Bases(self, h, n, self.curve)
 
     # ---- x-only points (include/te_msm.h "x-only points"): y recovered on the device; a bad x raises MsmError(EPOINT) with .index / .reason

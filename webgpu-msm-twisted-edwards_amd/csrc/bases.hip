@@ -25,20 +25,22 @@ void free_bases(te_ctx* ctx, te_bases* b) {
 
 // A whole MSM over a fixed-base set from HOST scalars on work set `ws`: all scalars cross PCIe in one copy (the digits of every
 // window address one bucket set: there are no pieces to accumulate onto), then the fixed-base launch sequence and its read-back.
+// (Fixed-base sets exist on the Twisted-Edwards curve only, whose one scalar record is the curve's own: option "scalar_record_bytes"
+// changes nothing here, and k_fb_digits reads 32-byte records.)
 int enqueue_fixed_base_host(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases, const uint8_t* src_scalars, uint64_t n, bool wait_for_pinned,
                             int scalar_form = -1) {
   HIP_TRY(ctx, hipSetDevice(d.device));
-  const curve_sizes sz = sizes_of(bases->curve);
-  if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
+  const size_t sb = sizes_of(bases->curve).scalar_in;
+  if (int rc = ensure_staging(ctx, ws, 0, n * sb)) return rc;
   if (int rc = wait_behind_previous(ctx, ws)) return rc;
   if (!wait_for_pinned) {
     // an asynchronous ticket: the lane thread waits for the upload itself (lane_wait), no wait enters the work set's stream
     if (ws.used) HIP_TRY(ctx, hipEventSynchronize(ws.ev_done));
     if (int rc = need_copy_stream(ctx, ws)) return rc;
-    if (int rc = upload(ctx, ws, ws.d_in_scalars, src_scalars, n * sz.scalar_in, ws.copy_stream)) return rc;
+    if (int rc = upload(ctx, ws, ws.d_in_scalars, src_scalars, n * sb, ws.copy_stream)) return rc;
     if (int rc = lane_wait(ctx, ws, ws.ev_copy, true)) return rc;
   } else {
-    if (int rc = upload(ctx, ws, ws.d_in_scalars, src_scalars, n * sz.scalar_in, ws.stream)) return rc;
+    if (int rc = upload(ctx, ws, ws.d_in_scalars, src_scalars, n * sb, ws.stream)) return rc;
     if (wait_for_pinned && !ctx->opt_host_staging && host_memory_is_pinned(src_scalars)) {
       HIP_TRY(ctx, hipEventRecord(ws.ev_copy, ws.stream));
       HIP_TRY(ctx, hipEventSynchronize(ws.ev_copy));
@@ -65,8 +67,8 @@ int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_sc
     gpu_t& d = ctx->devs[i]; workset_t& ws = d.ws[wsel[i]];
     HIP_TRY(ctx, hipSetDevice(d.device));
     device_inputs in; in.scalars = d_scalars;
-    if (must_pull(ctx, d, src_dev)) { if (int rc = pull_inputs(ctx, d, ws, src_dev, n, in, moved[i])) return rc; }
-    partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = ws.stream; r.bases = bases;
+    if (must_pull(ctx, d, src_dev)) { if (int rc = pull_inputs(ctx, d, ws, src_dev, n, (size_t)p0.sc_bytes, in, moved[i])) return rc; }
+    partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = ws.stream; r.bases = bases; r.scalar_bytes = p0.sc_bytes;
     if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
@@ -78,6 +80,7 @@ int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_sc
 int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_is_host, uint8_t* out) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   if (int rc = check_bases(ctx, bases)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   const uint64_t n = bases->n;
   if (n == 0) { write_identity(ctx->opt_curve, out); return 0; }
   if (!src) return set_err(ctx, TE_MSM_EINVAL, "null scalar buffer");
@@ -101,7 +104,7 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
   workset_t& ws = d.ws[wsel];
   HIP_TRY(ctx, hipSetDevice(d.device));
   const plan_t p0 = make_plan(ctx, d, plan_shard(n));
-  const curve_sizes sz = sizes_of(p0.curve);
+  const size_t sb = (size_t)p0.sc_bytes;
   const bool fb = bases->fb_c && (ctx->devs.size() > 1 || d.w_step == 1);      // (a window-sharded single-device context keeps the ordinary windows)
   if (fb) {
     if (src_is_host) { if (int rc = enqueue_fixed_base_host(ctx, d, ws, bases, static_cast<const uint8_t*>(src), n, true)) return rc; }
@@ -114,9 +117,9 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
   } else {
     const void* ds = src;
     if (src_is_host) {
-      if (int rc = ensure_staging(ctx, ws, 0, n * sz.scalar_in)) return rc;
+      if (int rc = ensure_staging(ctx, ws, 0, n * sb)) return rc;
       if (int rc = wait_behind_previous(ctx, ws)) return rc;
-      if (int rc = upload(ctx, ws, ws.d_in_scalars, static_cast<const uint8_t*>(src), n * sz.scalar_in, ws.stream)) return rc;
+      if (int rc = upload(ctx, ws, ws.d_in_scalars, static_cast<const uint8_t*>(src), n * sb, ws.stream)) return rc;
       ds = ws.d_in_scalars;
     }
     partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.bases = bases;
@@ -136,6 +139,7 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
 int indexed_args(te_ctx* ctx, const te_bases* bases, const void* idx, const void* scalars, uint64_t m) {
   if (int rc = check_bases(ctx, bases)) return rc;
   if (int rc = check_n(ctx, m)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_EINVAL, "indexed MSMs are whole MSMs: reset the window shard first");
   if (m > 0 && (!idx || !scalars)) return set_err(ctx, TE_MSM_EINVAL, "null index or scalar buffer");
   if (m > 0 && bases->n == 0) { ctx->bad_index_position = 0; return set_err(ctx, TE_MSM_EINVAL, "the bound point set is empty: no index is below its count"); }
@@ -196,6 +200,7 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
   if (!ctx) return TE_MSM_EINVAL;
   drain_workers(ctx);
   if (int rc = check_bases(ctx, bases)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   // (the window shards of a multi-device context are the engine's own, for its lone calls: a batch runs whole MSMs on every device)
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_EINVAL, "batched MSMs compute whole MSMs: reset the window shard first");
   if (count < 0) return set_err(ctx, TE_MSM_EINVAL, "count must be >= 0");
@@ -209,6 +214,7 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
   }
   if (total && !src) return set_err(ctx, TE_MSM_EINVAL, "null scalar buffer");
   const curve_sizes sz = sizes_of(ctx->opt_curve);
+  const size_t sb = scalar_bytes_now(ctx);               // the packed buffer: off[m] in records of this size (the sequences' plans carry it: sc_bytes)
   const int owner = !src_is_host && total && ctx->devs.size() > 1
                         ? owner_of(ctx, "te_msm_run_scalars_batch_device: the scalars must be resident on a device of the context", {src}) : 0;
   if (owner < 0) return owner;
@@ -238,8 +244,8 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
     gpu_t& d = ctx->devs[i];
     if (nd == 1) {
       offs[i] = off;
-      if (int rc = tmp_alloc(ctx, d, tmp[i], total * sz.scalar_in)) return rc;
-      HIP_TRY(ctx, hipMemcpy(tmp[i].p, src, total * sz.scalar_in, hipMemcpyHostToDevice));
+      if (int rc = tmp_alloc(ctx, d, tmp[i], total * sb)) return rc;
+      HIP_TRY(ctx, hipMemcpy(tmp[i].p, src, total * sb, hipMemcpyHostToDevice));
     } else {
       offs[i].assign((size_t)count, 0);
       std::vector<uint32_t> mine;
@@ -247,8 +253,8 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
       std::sort(mine.begin(), mine.end());
       uint64_t here = 0;
       for (uint32_t m : mine) { offs[i][m] = here; here += lens[m]; }
-      std::vector<uint8_t> pack((size_t)(here * sz.scalar_in));
-      for (uint32_t m : mine) memcpy(&pack[(size_t)(offs[i][m] * sz.scalar_in)], static_cast<const uint8_t*>(src) + off[m] * sz.scalar_in, (size_t)(lens[m] * sz.scalar_in));
+      std::vector<uint8_t> pack((size_t)(here * sb));
+      for (uint32_t m : mine) memcpy(&pack[(size_t)(offs[i][m] * sb)], static_cast<const uint8_t*>(src) + off[m] * sb, (size_t)(lens[m] * sb));
       if (int rc = tmp_alloc(ctx, d, tmp[i], pack.size())) return rc;
       HIP_TRY(ctx, hipMemcpy(tmp[i].p, pack.data(), pack.size(), hipMemcpyHostToDevice));
     }
@@ -295,10 +301,11 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
 }  // namespace
 
 // mont: option "points_montgomery" as te_msm_bind_points[_device] found it (te_msm_bind_points_x binds points it recovered itself: canonical)
-int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_bases** out, bool mont) {
+int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_bases** out, bool mont, point_layout lay) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   *out = nullptr;
   if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_layout(ctx, lay, src, src_is_host)) return rc;
   if (n > 0 && !src) return set_err(ctx, TE_MSM_EINVAL, "null point buffer");
   drain_workers(ctx);
   const size_t nd = ctx->devs.size();
@@ -311,7 +318,7 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
   if (n > 0) {                                        // option "check_points": once, here (MSMs over the set never check again)
     size_t ci = 0;
     if (!src_is_host) while (ctx->devs[ci].device != src_dev) ci++;
-    if (int rc = check_call(ctx, ci, src, src_is_host, n, mont)) return rc;
+    if (int rc = check_call(ctx, ci, src, src_is_host, n, mont, lay)) return rc;
   }
   te_bases* b = new te_bases();
   b->ctx = ctx; b->n = n; b->curve = ctx->opt_curve;
@@ -322,7 +329,7 @@ int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_b
     if (te_fb::bind_refused(b->fb_c, n)) { delete b; return set_err(ctx, TE_MSM_EINVAL, "bind_fixed_base: windows x points must stay below 2^31"); }
   }
   b->recs.assign(nd, nullptr);
-  const int rc = n > 0 ? te_sched::on_devices(*ctx, nd, [=](size_t i) { return bind_on_device(ctx, b, i, src, src_is_host, src_dev, mont); }) : 0;
+  const int rc = n > 0 ? te_sched::on_devices(*ctx, nd, [=](size_t i) { return bind_on_device(ctx, b, i, src, src_is_host, src_dev, mont, lay); }) : 0;
   if (rc) { free_bases(ctx, b); delete b; return rc; }
   // a set bound from HOST memory announces tickets from host scalars: the lanes' first concurrent copies (15-30 ms once per process,
   // warm_upload_lanes) happen here, in the call that blocks anyway, not in the first te_msm_submit_scalars -- which the N-API addon
@@ -341,7 +348,7 @@ int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* base
   ctx->stat_fb_fallbacks++;
   HIP_TRY(ctx, hipSetDevice(d.device));
   partial_req r; r.d_scalars = ws.fb_scalars; r.n = ws.fb_n; r.stream = ws.stream; r.whole = true; r.bases = bases;
-  r.scalar_form = ws.plan.scalar_mont;                 // (a ticket: the form it was submitted with, whatever the option says at its collect)
+  r.scalar_form = ws.plan.scalar_mont; r.scalar_bytes = ws.plan.sc_bytes;   // (a ticket: the form and size it was submitted with, whatever the options say at its collect)
   if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
@@ -354,12 +361,12 @@ extern "C" {
 
 int te_msm_bind_points(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, te_bases** out) {
   device_guard restore_callers_device;
-  return bind_common(ctx, points_xy_le, true, n, out, ctx && ctx->opt_points_montgomery);
+  return bind_common(ctx, points_xy_le, true, n, out, ctx && ctx->opt_points_montgomery, ctx ? layout_now(ctx) : point_layout{});
 }
 
 int te_msm_bind_points_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, te_bases** out) {
   device_guard restore_callers_device;
-  return bind_common(ctx, d_points_xy_le, false, n, out, ctx && ctx->opt_points_montgomery);
+  return bind_common(ctx, d_points_xy_le, false, n, out, ctx && ctx->opt_points_montgomery, ctx ? layout_now(ctx) : point_layout{});
 }
 
 uint64_t te_msm_bases_count(const te_bases* bases) { return bases ? bases->n : 0; }
@@ -394,6 +401,7 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (int rc = check_bases(ctx, bases)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   const uint64_t n = bases->n;
   if (!scalars_le || n == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty point set has no tickets: te_msm_run_scalars returns the identity)");
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_submit_scalars computes whole MSMs: reset the window shard first");
@@ -405,7 +413,7 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
   // the device the upload hides under THEIR device work, and one piece keeps the sort and the accumulation at full width
   host_slice_req r; r.recs = bases->recs[(size_t)t.di]; r.rec_kind = bases->rec_kind; r.scalars = scalars_le; r.n = n;
   r.c = pf.c; r.K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, n) : 1;
-  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes;
   te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, bases, r]() -> int {
     return bases->fb_c ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, r.scalars, r.n, false, r.scalar_form) : enqueue_host_pieces(ctx, t.d, t.ws, r);
   });
@@ -417,6 +425,7 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (int rc = check_bases(ctx, bases)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   const uint64_t n = bases->n;
   if (!d_scalars_le || n == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty point set has no tickets: te_msm_run_scalars_device returns the identity)");
   const bool multi = ctx->devs.size() > 1;
@@ -426,7 +435,7 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
   if (int rc = take_free_workset(ctx, owner, true, taken)) return rc;
   const ticket_set& t = *taken;
   device_inputs in; in.scalars = d_scalars_le;
-  if (int rc = pull_for_ticket(ctx, t, owner, n, in)) return rc;
+  if (int rc = pull_for_ticket(ctx, t, owner, n, scalar_bytes_now(ctx), in)) return rc;
   if (bases->fb_c && (multi || t.d.w_step == 1)) { if (int rc = enqueue_fixed_base(ctx, t.d, t.ws, bases, in.scalars, n, 0, t.ws.stream)) return rc; }
   else {
     partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = t.ws.stream; r.whole = multi; r.bases = bases;
@@ -460,7 +469,7 @@ int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* 
   // (pieces: the rule of te_msm_submit_scalars -- with other tickets in flight the upload hides under their device work)
   r.c = pf.c; r.K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, m) : 1;
   r.idx = idx; r.idx_count = bases->n;
-  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes;
   te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, r]() -> int { return enqueue_host_pieces(ctx, t.d, t.ws, r); });
   hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
@@ -477,7 +486,7 @@ int te_msm_submit_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const voi
   if (int rc = take_free_workset(ctx, owner, true, taken)) return rc;
   const ticket_set& t = *taken;
   device_inputs in; in.scalars = d_scalars_le; in.idx = static_cast<const uint32_t*>(d_idx);
-  if (int rc = pull_for_ticket(ctx, t, owner, m, in)) return rc;
+  if (int rc = pull_for_ticket(ctx, t, owner, m, scalar_bytes_now(ctx), in)) return rc;
   partial_req r; r.d_scalars = in.scalars; r.n = m; r.stream = t.ws.stream; r.whole = true; r.bases = bases; r.d_idx = in.idx;
   if (int rc = enqueue_partial(ctx, t.d, t.ws, r)) return rc;
   if (int rc = fetch_rows(ctx, t.ws, t.ws.stream)) return rc;

@@ -20,6 +20,7 @@
 //     so such a point is rejected, which is right: it is not in G1.
 #pragma once
 #include "curve.hpp"
+#include "strided.hip.hpp"
 
 namespace te {
 
@@ -273,6 +274,38 @@ template <int CURVE, bool MONT = false> __global__ __launch_bounds__(256) void k
   if constexpr (CURVE == 1) in = in_subgroup_377<MONT>(w, k);
   else in = in_subgroup_te<MONT>(w, k);
   if (!in) atomicMax(word, (unsigned long long)check_code(n, i, 3));
+}
+// The same two checks over records at a stride (options "point_stride" / "point_infinity_flag"; strided.hip.hpp): the block's tile through
+// LDS, then the packed kernels' verdict per lane.  flag (BLS12-377): a record whose flag byte is 1 is the point at infinity and passes both
+// levels without its coordinates being looked at; a flag byte other than 0 or 1 is TE_MSM_POINT_NONCANONICAL at its index.
+template <int CURVE, bool MONT = false> __global__ __launch_bounds__(256) void k_check_form_strided(const uint64_t* __restrict__ src, uint32_t stride, uint32_t flag, uint32_t n,
+                                                                                                    unsigned long long* word) {
+  __shared__ uint64_t tile[TE_STRIDE_TILE * TE_STRIDE_MAX / 8u];
+  strided_stage(tile, src, blockIdx.x, n, stride);
+  const uint32_t t = threadIdx.x, i = blockIdx.x * TE_STRIDE_TILE + t;
+  if (i >= n) return;
+  constexpr int PW = CURVE == 1 ? 24 : 16;
+  uint32_t w[PW];
+  const uint32_t fb = strided_pick<PW>(tile, t, stride, w, CURVE == 1 && flag != 0u);
+  int reason;
+  if constexpr (CURVE == 1) reason = check_form_377<MONT>(w);
+  else reason = check_form_te<MONT>(w);
+  if (fb) reason = fb == 1u ? 0 : 1;
+  if (reason) atomicMax(word, (unsigned long long)check_code(n, i, reason));
+}
+template <int CURVE, bool MONT = false> __global__ __launch_bounds__(256) void k_check_subgroup_strided(const uint64_t* __restrict__ src, uint32_t stride, uint32_t flag, uint32_t n,
+                                                                                                        unsigned long long* word, naf_t k) {
+  __shared__ uint64_t tile[TE_STRIDE_TILE * TE_STRIDE_MAX / 8u];
+  strided_stage(tile, src, blockIdx.x, n, stride);
+  const uint32_t t = threadIdx.x, i = blockIdx.x * TE_STRIDE_TILE + t;
+  if (i >= n) return;
+  constexpr int PW = CURVE == 1 ? 24 : 16;
+  uint32_t w[PW];
+  const uint32_t fb = strided_pick<PW>(tile, t, stride, w, CURVE == 1 && flag != 0u);
+  bool in;
+  if constexpr (CURVE == 1) in = in_subgroup_377<MONT>(w, k);
+  else in = in_subgroup_te<MONT>(w, k);
+  if (!in && !fb) atomicMax(word, (unsigned long long)check_code(n, i, 3));      // (a flagged record: the form check has spoken)
 }
 #endif
 

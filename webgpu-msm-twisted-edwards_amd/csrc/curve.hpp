@@ -125,6 +125,17 @@ template <bool MONT = false> TE_HD pnt_t<14> pnt_from_sw377(const fel<14>& x, co
   return r;
 }
 
+// The neutral element (X : Y : Z : T) = (0 : 1 : 1 : 0) as a record of the form above (times 2: hm = Y - X, hp = Y + X, dt = -2 d T,
+// z = 2 Z): (1, 1, 0, 2) in Montgomery form -- what a point flagged "at infinity" converts to (option "point_infinity_flag").  Its affine
+// record is (hm / z, hp / z, dt / z) = (1/2, 1/2, 0): k_affine377's shared inversion handles it like any other record (z = 2 is a unit).
+TE_HD pnt_t<14> pnt_identity377() {
+  pnt_t<14> r;
+  r.hm = r.hp = fe_one<14>();
+  r.dt = fe_zero<14>();
+  r.z = fe_norm(fe_add(fe_one<14>(), fe_one<14>()));
+  return r;
+}
+
 // the four closing products of every addition: (X3, Y3, T3, Z3) = (E F, H G, E H, G F) with E, G differences (offset form)
 // and H, F sums.  N = 9: every product is "difference x sum", 9 * 2^30.6 * 2^30 + 8 * 2^58 = 0.9 * 2^64: nothing is
 // normalised.  N = 14: one operand of every product must be normalised -- E and G are.

@@ -79,6 +79,7 @@ struct plan_t {
   uint32_t packed = 0;               // level-1 entries as one 32-bit word (index | key << 23 | sign << 31): n <= 2^23
   int rec_kind = 0;                  // records k_accumulate gathers: 0 = the curve's own, 1 = affine BLS12-377 (bound point sets)
   int scalar_mont = 0;               // the scalar records hold k 2^256 mod (the curve's scalar field): option "scalars_montgomery" as it was when the call started
+  int sc_bytes = 0;                  // bytes of one scalar record, 32 or 48: option "scalar_record_bytes" as it was when the call started (scalar_bytes_now)
   // fixed-base windows (bound point sets with a per-window table, kernels.hip.hpp k_fb_digits): fb_rb > 0 -- the "windows" of this
   // plan are fb_rb + 1 pseudo-windows (rows) of 2^15 buckets over ONE bucket set; fb_c / fb_W: window bits and windows of the real decomposition
   int fb_rb = 0, fb_c = 0, fb_W = 0;
@@ -252,6 +253,10 @@ struct te_ctx {
                                     // starts, on the calling thread -- a ticket keeps the form it was submitted with (plan_t::scalar_mont)
   int opt_points_montgomery = 0;    // te_msm_bind_points[_device]: coordinates are Montgomery residues x 2^256 mod p / x 2^384 mod q; read at bind time
   std::vector<te_base*> mul_bases;  // the bound points of fixed-base scalar multiplication (te_msm_bind_base), freed by te_msm_release_base / te_msm_destroy
+  int opt_scalar_record_bytes = 0;  // bytes of one scalar record: 0 = the curve's own (32 / 48), 32 = BLS12-377 scalars as a native prover holds them; read when a call
+                                    // starts, on the calling thread -- a ticket keeps the size it was submitted with (plan_t::sc_bytes)
+  int opt_point_stride = 0;         // te_msm_bind_points[_device], te_msm_check_points[_device]: bytes from one point record to the next, 0 = packed x || y; read at bind time
+  int opt_point_infinity_flag = 0;  // ... BLS12-377: the byte at offset 96 of every record flags the point at infinity (needs a stride >= 104); read at bind time
   int opt_mul_base_window = 12;     // te_msm_bind_base: window bits W of the table, 4..12 (option "mul_base_window"; 12 measured fastest at every size: DESIGN.md section 17); read at bind time
 };
 
@@ -293,6 +298,17 @@ namespace te_eng {
 
 inline int set_err(te_ctx* ctx, int code, const char* msg) { std::lock_guard<std::mutex> lk(ctx->err_mu); ctx->err = msg; return code; }
 
+// Bytes of one scalar record of a call that starts NOW (option "scalar_record_bytes"; 0 = the curve's own record).  Every buffer size and
+// piece offset of the call's scalars, and the stride its kernels read them at, come from this value -- never from sizes_of().scalar_in.
+inline size_t scalar_bytes_now(const te_ctx* ctx) { return ctx->opt_scalar_record_bytes ? (size_t)ctx->opt_scalar_record_bytes : sizes_of(ctx->opt_curve).scalar_in; }
+// ... and what every entry point that reads scalars asks first: the Twisted-Edwards curve has no 48-byte record (the curve option may have
+// changed after this one was set).  0 = go on
+inline int check_scalar_record(te_ctx* ctx) {
+  if (ctx->opt_scalar_record_bytes == 48 && ctx->opt_curve != TE_MSM_CURVE_BLS12_377_G1)
+    return set_err(ctx, TE_MSM_EINVAL, "option \"scalar_record_bytes\" is 48: the Twisted-Edwards curve has 32-byte scalar records only");
+  return 0;
+}
+
 // The engine selects devices with hipSetDevice, which is state of the CALLING thread: every entry point that may do so puts the
 // caller's device back when it returns.  (A host that shares the thread with another HIP user -- PyTorch in bench.py's rank 0,
 // which opens all N devices in its own process -- would otherwise find its "current device" moved to wherever the last ticket
@@ -305,6 +321,14 @@ struct device_guard {
   device_guard& operator=(const device_guard&) = delete;
 };
 
+// How the points of a bind or a standalone check lie in the caller's buffer (options "point_stride" / "point_infinity_flag" as the call
+// found them; csrc/strided.hip.hpp).  The per-call point paths and te_msm_bind_points_x pass the default: packed, no flag.
+struct point_layout {
+  uint32_t stride = 0; bool flag = false;
+  size_t bytes(int curve) const { return stride ? stride : sizes_of(curve).point_in; }      // from one point to the next
+};
+constexpr uint32_t kPointStrideMax = 128;      // TE_STRIDE_MAX: a block's tile of 256 records fits 32 KB of LDS
+
 // What a plan is asked for.  Only n is always needed; plan_whole() / plan_shard() below start the two common requests.
 struct plan_req {
   uint64_t n = 0;                // entries of the launch sequence: every size of the plan derives from it
@@ -315,6 +339,7 @@ struct plan_req {
   // the form of the scalar records (plan_t::scalar_mont) where the caller fixed it earlier -- the jobs of asynchronous tickets, which run on an
   // upload lane and do not read the option, and the second run of a fixed-base ticket; -1 = option "scalars_montgomery" as it is now
   int scalar_form = -1;
+  int scalar_bytes = 0;          // ... and their size (plan_t::sc_bytes), fixed by the same callers; 0 = option "scalar_record_bytes" as it is now
   int rec_kind = 0;              // records k_accumulate gathers (plan_t::rec_kind): a bound point set's form
   uint64_t idx_count = 0;        // an indexed call: records of the bound set -- the entry form follows the SET (indexed_plan.hpp); 0 = not indexed
 };
@@ -349,6 +374,7 @@ struct partial_req {
   share_mode share = SHARE_NONE;      // the record slab of the call; a shared slab only for device-resident points, without bound bases
   const uint32_t* d_idx = nullptr;    // (with bases) an indexed subset: the n entries gather records d_idx[0 .. n) of the set (device memory of d)
   int scalar_form = -1;               // plan_req's: -1 = option "scalars_montgomery" as it is now
+  int scalar_bytes = 0;               // plan_req's: 0 = option "scalar_record_bytes" as it is now
 };
 
 // Device-resident inputs of a call, and the peer pull that brings them from the memory of device src_dev into the staging area of a
@@ -368,6 +394,7 @@ struct host_slice_req {
   bool wait_for_pinned = true;
   const uint32_t* idx = nullptr; uint64_t idx_count = 0, idx_pos = 0;
   int scalar_form = -1;                 // plan_req's (a lane thread passes what its ticket was submitted with)
+  int scalar_bytes = 0;                 // plan_req's (likewise)
 };
 
 const char* const kFinalCarry = "final carry is 1: a scalar does not fit the signed window decomposition";
@@ -413,11 +440,11 @@ int enqueue_fixed_base(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bas
                        int scalar_form = -1);
 int run_batch_on_device(te_ctx* ctx, size_t di, const te_bases* bases, const void* d_sc, const std::vector<uint64_t>& off, const uint64_t* lens,
                         std::vector<batch_seq_run>& runs, bool* carry, int64_t* entries);
-int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src_is_host, int src_dev, bool mont);
+int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src_is_host, int src_dev, bool mont, point_layout lay);
 int ensure_staging(te_ctx* ctx, workset_t& ws, size_t bytes_points, size_t bytes_scalars);
 int wait_behind_previous(te_ctx* ctx, workset_t& ws);
 bool must_pull(const te_ctx* ctx, const gpu_t& d, int src_dev);
-int pull_inputs(te_ctx* ctx, const gpu_t& d, workset_t& ws, int src_dev, uint64_t n, device_inputs& in, peer_traffic& moved);
+int pull_inputs(te_ctx* ctx, const gpu_t& d, workset_t& ws, int src_dev, uint64_t n, size_t scalar_bytes, device_inputs& in, peer_traffic& moved);
 void note_peer_traffic(te_ctx* ctx, const peer_traffic& moved);
 bool host_memory_is_pinned(const void* p);
 int upload(te_ctx* ctx, workset_t& ws, void* dst, const uint8_t* src, size_t bytes, hipStream_t stream);
@@ -443,15 +470,18 @@ int take_free_workset(te_ctx* ctx, int prefer, bool probe, std::optional<ticket_
 int lane_status(te_ctx* ctx, workset_t& ws, int rc);
 void hand_out_ticket(te_ctx* ctx, const ticket_set& t, uint64_t* ticket, te_bases* bound = nullptr, te_sched::job_ref job = nullptr);
 int owner_of(te_ctx* ctx, const char* msg, std::initializer_list<const void*> ptrs);
-int pull_for_ticket(te_ctx* ctx, const ticket_set& t, int owner, uint64_t n, device_inputs& in, bool* pulled = nullptr);
+int pull_for_ticket(te_ctx* ctx, const ticket_set& t, int owner, uint64_t n, size_t scalar_bytes, device_inputs& in, bool* pulled = nullptr);
 void warm_upload_lanes(te_ctx* ctx);
 // bases.hip
-int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_bases** out, bool mont = false);
+int bind_common(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n, te_bases** out, bool mont = false, point_layout lay = {});
 int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* bases);
 // points.hip
-int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason, bool mont = false);
+int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason, bool mont = false,
+                    point_layout lay = {});
+int check_layout(te_ctx* ctx, const point_layout& lay, const void* src, bool src_is_host);
+point_layout layout_now(const te_ctx* ctx);
 int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* first_bad = nullptr, int* reason_out = nullptr);
-int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont = false);
+int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont = false, point_layout lay = {});
 int tmp_alloc(te_ctx* ctx, gpu_t& d, dev_tmp& t, size_t bytes);
 void free_mul_base(te_ctx* ctx, te_base* b);
 

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "curve.hpp"
 #include "scalar_form.hpp"
+#include "strided.hip.hpp"
 
 namespace te {
 
@@ -1633,6 +1634,40 @@ __global__ void __launch_bounds__(256) k_prep_points377(batch_ptrs in, batch_sla
   if (i >= n) return;
   prep_point377<MONT>(i, in.p[blockIdx.y], recs + (size_t)row_slab.s[blockIdx.y] * n);
 }
+// The bind-time conversions over records at a stride (options "point_stride" / "point_infinity_flag"; strided.hip.hpp says how the
+// block's tile is read).  One lane per point, 256-thread blocks, the packed kernels' arithmetic and record layout: a set bound at a
+// stride holds the records of the same points bound packed, bit for bit.  flag: the byte at offset 96 of a BLS12-377 record, non-zero =
+// the point at infinity -- its coordinates are not looked at and its record is the neutral element's (pnt_identity377).  The records
+// are stored per lane (16-byte pieces at the slot stride): the slow pattern the packed Twisted-Edwards kernel avoids, accepted here --
+// once per bound set, and the tile owns the block's LDS.
+template <bool MONT = false>
+__global__ void __launch_bounds__(256) k_prep_points377_strided(const uint64_t* __restrict__ src, uint32_t stride, uint32_t flag, rec_slot<14>* __restrict__ recs, uint32_t n) {
+  __shared__ uint64_t tile[TE_STRIDE_TILE * TE_STRIDE_MAX / 8u];
+  strided_stage(tile, src, blockIdx.x, n, stride);
+  const uint32_t t = threadIdx.x, i = blockIdx.x * TE_STRIDE_TILE + t;
+  if (i >= n) return;
+  uint32_t w[24];
+  const uint32_t inf = strided_pick<24>(tile, t, stride, w, flag != 0u);
+  uint32_t xw[12], yw[12];
+#pragma unroll
+  for (int j = 0; j < 12; j++) { xw[j] = w[j]; yw[j] = w[12 + j]; }
+  const pnt_t<14> conv = pnt_from_sw377<MONT>(te377::fq_from_words32(xw), te377::fq_from_words32(yw));
+  store_pnt<14>(recs + i, inf ? pnt_identity377() : conv);
+}
+template <bool MONT = false>
+__global__ void __launch_bounds__(256) k_prep_points_strided(const uint64_t* __restrict__ src, uint32_t stride, rec_slot<9>* __restrict__ recs, uint32_t n) {
+  __shared__ uint64_t tile[TE_STRIDE_TILE * TE_STRIDE_MAX / 8u];
+  strided_stage(tile, src, blockIdx.x, n, stride);
+  const uint32_t t = threadIdx.x, i = blockIdx.x * TE_STRIDE_TILE + t;
+  if (i >= n) return;
+  uint32_t w[16];
+  (void)strided_pick<16>(tile, t, stride, w, false);
+  uint32_t xw[8], yw[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) { xw[j] = w[j]; yw[j] = w[8 + j]; }
+  store_pnt<9>(recs + i, pnt_from_affine_raw<MONT>(fp_from_words32(xw), fp_from_words32(yw)));
+}
+
 // Level 1 of the sort and the BLS12-377 record conversion in one launch (k_part_scatter_prep for the other curve): the scatter is
 // bound by its LDS rounds and barriers, the conversion by its eight 14-limb products per point -- back to back they cost 46 + 130 us
 // of one MSM's critical path.  1-D grid, the two kinds of blocks interleaved evenly; a conversion block converts 512 points (one

@@ -189,12 +189,12 @@ struct mb_device_table {
     for (int j = 0; j < MB_ENTRY_WORDS / 4; j++) { const uint4 v = e[j]; w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w; }
   }
 };
-// one lane per scalar of a piece of m; no early exit inside the window loop
-template <int CURVE, int FORM> __global__ __launch_bounds__(256) void k_mul_base(const uint4* __restrict__ table, const uint4* __restrict__ sc, uint32_t m,
+// one lane per scalar of a piece of m; no early exit inside the window loop.  SQ: 16-byte words of a scalar record, as k_scalar_mul's
+template <int CURVE, int FORM, int SQ = (CURVE == 1 ? 3 : 2)> __global__ __launch_bounds__(256) void k_mul_base(const uint4* __restrict__ table, const uint4* __restrict__ sc, uint32_t m,
                                                                                  uint4* __restrict__ proj, mb_geom g) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
-  constexpr int JQ = sm_sizes<CURVE>::JW / 4, SQ = CURVE == 1 ? 3 : 2;
+  constexpr int JQ = sm_sizes<CURVE>::JW / 4;
   uint32_t k[8];
 #pragma unroll
   for (int j = 0; j < 2; j++) { const uint4 v = sc[(size_t)i * SQ + j]; k[4 * j] = v.x; k[4 * j + 1] = v.y; k[4 * j + 2] = v.z; k[4 * j + 3] = v.w; }

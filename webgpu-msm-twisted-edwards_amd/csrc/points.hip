@@ -62,7 +62,9 @@ int check_standalone(te_ctx* ctx, const void* src, bool src_is_host, uint64_t n,
   const int di = !src_is_host && n > 0 && ctx->devs.size() > 1
                      ? owner_of(ctx, "te_msm_check_points_device: the points must be resident on a device of the context", {src}) : 0;
   if (di < 0) return di;
-  const int rc = check_points_on(ctx, (size_t)di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why, ctx->opt_points_montgomery != 0);
+  const point_layout lay = layout_now(ctx);
+  if (int rc = check_layout(ctx, lay, src, src_is_host)) return rc;
+  const int rc = check_points_on(ctx, (size_t)di, src, src_is_host, n, ctx->opt_curve, level, &bad, &why, ctx->opt_points_montgomery != 0, lay);
   if (rc != TE_MSM_EPOINT) return rc;
   return note_bad(ctx, kBadPoint, bad, why, first_bad, reason);
 }
@@ -155,13 +157,14 @@ inline te::naf_t shared_naf_of(const uint8_t* k32, int curve) {
   memcpy(k, k32, 32);
   return te::sm_shared_naf(k, curve);
 }
-// n points and scalars (memory of devs[di]) -> n affine results at d_out (memory of devs[di]); returns when they are there
-int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t n, bool shared, const te::naf_t& kn, void* d_out) {
+// n points and scalars (memory of devs[di]) -> n affine results at d_out (memory of devs[di]); returns when they are there.
+// sb: bytes of one scalar record -- the call's (scalar_bytes_now), or the curve's own for the records te_msm_bind_base makes itself
+int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t n, bool shared, const te::naf_t& kn, void* d_out, size_t sb) {
   if (n == 0) return 0;
   gpu_t& d = ctx->devs[di];
   const int curve = ctx->opt_curve;
   const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1;
-  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in;
+  const size_t pb = sizes_of(curve).point_in;
   const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
   check_lane lane(ctx, d);
   if (lane.rc) return lane.rc;
@@ -177,7 +180,8 @@ int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t
     uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
     const dim3 grid((m + 255u) / 256u), block(256), agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP));
     if (bls) {
-      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<1, true>), grid, block, 0, st, p4, s4, m, j4, kn);
+      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<1, true>), grid, block, 0, st, p4, s4, m, j4, kn);     // (reads no record: the NAF)
+      else if (sb == 32) hipLaunchKernelGGL((te::k_scalar_mul<1, false, 2>), grid, block, 0, st, p4, s4, m, j4, kn);
       else hipLaunchKernelGGL((te::k_scalar_mul<1, false>), grid, block, 0, st, p4, s4, m, j4, kn);
       hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExp377);
     } else {
@@ -192,6 +196,7 @@ int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t
 }
 int mul_args(te_ctx* ctx, const void* pts, const void* sc, uint64_t n, const void* out) {
   if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   if (n > 0 && (!pts || !sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   return 0;
 }
@@ -200,7 +205,7 @@ int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalar
   if (int rc = mul_args(ctx, src, scalars_le, n, out)) return rc;
   if (n == 0) return 0;
   const int curve = ctx->opt_curve, level = ctx->opt_check_points;
-  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in, ib = x_only ? x_bytes_of(curve) : pb;
+  const size_t pb = sizes_of(curve).point_in, sb = scalar_bytes_now(ctx), ib = x_only ? x_bytes_of(curve) : pb;
   const te::naf_t kn = shared ? shared_naf_of(scalars_le, curve) : te::naf_t{};
   const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
   const uint64_t per = (n + D - 1) / D;
@@ -229,7 +234,7 @@ int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalar
       if (rc == TE_MSM_EPOINT) return 0;
       if (rc) return rc;
     }
-    return mul_on(ctx, i, s.pts.p, s.sc.p, m, shared, kn, s.res.p);
+    return mul_on(ctx, i, s.pts.p, s.sc.p, m, shared, kn, s.res.p, sb);
   };
   auto copy_out = [&](size_t i) -> int {
     const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
@@ -271,7 +276,7 @@ int base_table_on(te_ctx* ctx, te_base* b, size_t i, const uint8_t* pts, const u
   if (int rc = tmp_alloc(ctx, d, d_aff, g.entries * pb)) return rc;
   HIP_TRY(ctx, hipMemcpy(d_pts.p, pts, g.entries * pb, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(d_sc.p, sc, g.entries * sb, hipMemcpyHostToDevice));
-  if (int rc = mul_on(ctx, i, d_pts.p, d_sc.p, g.entries, false, te::naf_t{}, d_aff.p)) return rc;
+  if (int rc = mul_on(ctx, i, d_pts.p, d_sc.p, g.entries, false, te::naf_t{}, d_aff.p, sb)) return rc;
   check_lane lane(ctx, d);
   if (lane.rc) return lane.rc;
   const dim3 grid((g.entries + 255u) / 256u), block(256);
@@ -283,12 +288,12 @@ int base_table_on(te_ctx* ctx, te_base* b, size_t i, const uint8_t* pts, const u
   HIP_TRY(ctx, hipStreamSynchronize(lane.stream()));
   return 0;
 }
-// n scalar records (memory of devs[di]; mont: Montgomery residues) -> n affine results at d_out (memory of devs[di]); returns when they are there
-int mul_base_on(te_ctx* ctx, size_t di, const te_base* b, const void* d_sc, uint64_t n, bool mont, void* d_out) {
+// n scalar records of sb bytes (memory of devs[di]; mont: Montgomery residues) -> n affine results at d_out (memory of devs[di]); returns when they are there
+int mul_base_on(te_ctx* ctx, size_t di, const te_base* b, const void* d_sc, uint64_t n, bool mont, void* d_out, size_t sb) {
   if (n == 0) return 0;
   gpu_t& d = ctx->devs[di];
   const bool bls = b->curve == TE_MSM_CURVE_BLS12_377_G1;
-  const size_t pb = sizes_of(b->curve).point_in, sb = sizes_of(b->curve).scalar_in;
+  const size_t pb = sizes_of(b->curve).point_in;
   const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
   const te::mb_geom g = te::mb_geometry(b->W);
   check_lane lane(ctx, d);
@@ -305,7 +310,9 @@ int mul_base_on(te_ctx* ctx, size_t di, const te_base* b, const void* d_sc, uint
     uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
     const dim3 grid((m + 255u) / 256u), block(256), agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP));
     if (bls) {
-      if (mont) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_377>), grid, block, 0, st, t4, s4, m, j4, g);
+      if (sb == 32 && mont) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_377, 2>), grid, block, 0, st, t4, s4, m, j4, g);
+      else if (sb == 32) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_CANONICAL, 2>), grid, block, 0, st, t4, s4, m, j4, g);
+      else if (mont) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_377>), grid, block, 0, st, t4, s4, m, j4, g);
       else hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_CANONICAL>), grid, block, 0, st, t4, s4, m, j4, g);
       hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExp377);
     } else {
@@ -323,6 +330,7 @@ int mul_base_args(te_ctx* ctx, const te_base* b, const void* sc, uint64_t n, con
   *go = false;
   if (int rc = check_base(ctx, b)) return rc;
   if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   if (n > 0 && (!sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   *go = n > 0;
   return 0;
@@ -330,7 +338,7 @@ int mul_base_args(te_ctx* ctx, const te_base* b, const void* sc, uint64_t n, con
 // te_msm_mul_base: host scalars sliced over the devices, as mul_host
 int mul_base_host(te_ctx* ctx, const te_base* b, const uint8_t* scalars_le, uint64_t n, uint8_t* out) {
   const bool mont = ctx->opt_scalars_montgomery != 0;
-  const size_t pb = sizes_of(b->curve).point_in, sb = sizes_of(b->curve).scalar_in;
+  const size_t pb = sizes_of(b->curve).point_in, sb = scalar_bytes_now(ctx);
   const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
   const uint64_t per = (n + D - 1) / D;
   struct slice_t { dev_tmp sc, res; };
@@ -342,7 +350,7 @@ int mul_base_host(te_ctx* ctx, const te_base* b, const uint8_t* scalars_le, uint
     if (int rc = tmp_alloc(ctx, d, sl[i].sc, m * sb)) return rc;
     if (int rc = tmp_alloc(ctx, d, sl[i].res, m * pb)) return rc;
     HIP_TRY(ctx, hipMemcpy(sl[i].sc.p, scalars_le + lo * sb, m * sb, hipMemcpyHostToDevice));
-    return mul_base_on(ctx, i, b, sl[i].sc.p, m, mont, sl[i].res.p);
+    return mul_base_on(ctx, i, b, sl[i].sc.p, m, mont, sl[i].res.p, sb);
   };
   auto copy_out = [&](size_t i) -> int {
     const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
@@ -363,13 +371,25 @@ void free_mul_base(te_ctx* ctx, te_base* b) {
 
 // mont: the coordinates are Montgomery residues (option "points_montgomery": te_msm_bind_points*, te_msm_check_points*); every per-call
 // check of an MSM or a multiplication reads canonical coordinates
-int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason, bool mont) {
+// lay: the records' stride and flag byte (te_msm_bind_points*, te_msm_check_points*): the strided kernels, pieces cut at record boundaries
+point_layout layout_now(const te_ctx* ctx) { point_layout l; l.stride = (uint32_t)ctx->opt_point_stride; l.flag = ctx->opt_point_infinity_flag != 0; return l; }
+// what a bind or a standalone check refuses before it reads a point: a stride below the pair size of the curve in force, the flag on the
+// Twisted-Edwards curve ((0, 1) is an ordinary input there) or without room for its byte, a device buffer that is not 8-byte aligned
+int check_layout(te_ctx* ctx, const point_layout& lay, const void* src, bool src_is_host) {
+  const bool bls = ctx->opt_curve == TE_MSM_CURVE_BLS12_377_G1;
+  if (lay.flag && !bls) return set_err(ctx, TE_MSM_EINVAL, "option \"point_infinity_flag\" is set: BLS12-377 G1 only (the Twisted-Edwards neutral element (0, 1) is an ordinary point)");
+  if (lay.flag && lay.stride < 104) return set_err(ctx, TE_MSM_EINVAL, "option \"point_infinity_flag\" needs \"point_stride\" >= 104: the flag is the byte at offset 96");
+  if (lay.stride && lay.stride < sizes_of(ctx->opt_curve).point_in) return set_err(ctx, TE_MSM_EINVAL, "option \"point_stride\" is below the size of x || y on this curve");
+  if (lay.stride && !src_is_host && (reinterpret_cast<uintptr_t>(src) & 7u)) return set_err(ctx, TE_MSM_EINVAL, "with \"point_stride\" set, a device point buffer must be 8-byte aligned");
+  return 0;
+}
+int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, int curve, int level, int64_t* bad, int* reason, bool mont, point_layout lay) {
   *bad = -1; *reason = 0;
   if (n == 0) return 0;
   gpu_t& d = ctx->devs[di];
   check_lane lane(ctx, d);
   if (lane.rc) return lane.rc;
-  const size_t pb = sizes_of(curve).point_in;
+  const size_t pb = lay.bytes(curve);
   const uint64_t piece = src_is_host ? std::min(n, kCheckPiece) : n;
   if (src_is_host) { if (int rc = make_room(ctx, d.chk_pts, piece * pb)) return rc; }
   hipStream_t st = lane.stream();
@@ -380,7 +400,21 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
     const uint4* p4 = reinterpret_cast<const uint4*>(at);
     HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
     const dim3 grid((m + 255u) / 256u), block(256);
-    if (mont && curve == TE_MSM_CURVE_BLS12_377_G1) {
+    if (lay.stride) {
+      const uint64_t* p8 = reinterpret_cast<const uint64_t*>(at);
+      const uint32_t sd = lay.stride, fl = lay.flag ? 1u : 0u;
+      const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1;
+      if (bls && mont) hipLaunchKernelGGL((te::k_check_form_strided<1, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
+      else if (bls) hipLaunchKernelGGL((te::k_check_form_strided<1, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
+      else if (mont) hipLaunchKernelGGL((te::k_check_form_strided<0, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
+      else hipLaunchKernelGGL((te::k_check_form_strided<0, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
+      if (level >= 2) {
+        if (bls && mont) hipLaunchKernelGGL((te::k_check_subgroup_strided<1, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNaf377Order);
+        else if (bls) hipLaunchKernelGGL((te::k_check_subgroup_strided<1, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNaf377Order);
+        else if (mont) hipLaunchKernelGGL((te::k_check_subgroup_strided<0, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNafTeOrder);
+        else hipLaunchKernelGGL((te::k_check_subgroup_strided<0, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNafTeOrder);
+      }
+    } else if (mont && curve == TE_MSM_CURVE_BLS12_377_G1) {
       hipLaunchKernelGGL((te::k_check_form<1, true>), grid, block, 0, st, p4, m, d.chk_word);
       if (level >= 2) hipLaunchKernelGGL((te::k_check_subgroup<1, true>), grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
     } else if (mont) {
@@ -419,10 +453,10 @@ int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* fir
   return set_err(ctx, TE_MSM_EPOINT, buf);
 }
 // option "check_points" in front of a call: 0 = go on, TE_MSM_EPOINT (noted) or a device error
-int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont) {
+int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont, point_layout lay) {
   if (!ctx->opt_check_points) return 0;
   int64_t bad = -1; int reason = 0;
-  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points, &bad, &reason, mont);
+  const int rc = check_points_on(ctx, di, src, src_is_host, n, ctx->opt_curve, ctx->opt_check_points, &bad, &reason, mont, lay);
   if (rc == TE_MSM_EPOINT) return note_bad(ctx, kBadPoint, bad, reason);
   return rc;
 }
@@ -470,12 +504,13 @@ int te_msm_run_x(te_ctx* ctx, const uint8_t* x_le, const uint8_t* scalars_le, ui
   device_guard restore_callers_device;
   if (!ctx || !out_xy_le) return TE_MSM_EINVAL;
   if (ctx->opt_scalars_montgomery) return set_err(ctx, TE_MSM_EINVAL, kNoMontgomeryScalars);
+  if (int rc = check_scalar_record(ctx)) return rc;
   if (int rc = from_x_args(ctx, x_le, n, scalars_le)) return rc;
   if (n == 0) return run_common(ctx, x_le, scalars_le, true, 0, out_xy_le);
   dev_tmp pts, sc;
   if (int rc = recover_host_to_first(ctx, x_le, n, pts)) return rc;
   gpu_t& d = ctx->devs[0];
-  const size_t sbytes = n * sizes_of(ctx->opt_curve).scalar_in;
+  const size_t sbytes = n * scalar_bytes_now(ctx);
   if (int rc = tmp_alloc(ctx, d, sc, sbytes)) return rc;
   {
     check_lane lane(ctx, d);
@@ -518,7 +553,7 @@ int te_msm_mul_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_sca
     kn = shared_naf_of(k, ctx->opt_curve);
   }
   if (int rc = check_call(ctx, (size_t)owner, d_points_xy_le, false, n)) return rc;
-  return mul_on(ctx, (size_t)owner, d_points_xy_le, d_scalars_le, n, shared_scalar != 0, kn, d_out_points_xy_le);
+  return mul_on(ctx, (size_t)owner, d_points_xy_le, d_scalars_le, n, shared_scalar != 0, kn, d_out_points_xy_le, scalar_bytes_now(ctx));
 }
 
 int te_msm_bind_base(te_ctx* ctx, const uint8_t* point_xy_le, te_base** out) {
@@ -534,7 +569,7 @@ int te_msm_bind_base(te_ctx* ctx, const uint8_t* point_xy_le, te_base** out) {
     if (rc) return rc;
   }
   const te::mb_geom g = te::mb_geometry(ctx->opt_mul_base_window);
-  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in;
+  const size_t pb = sizes_of(curve).point_in, sb = sizes_of(curve).scalar_in;     // (the table's scalars are records of the bind's own: the curve's, whatever "scalar_record_bytes" says)
   std::vector<uint32_t> words((size_t)g.entries * 8);
   te::mb_table_scalars(curve == TE_MSM_CURVE_BLS12_377_G1 ? 1 : 0, g, words.data());
   std::vector<uint8_t> sc((size_t)g.entries * sb, 0), pts((size_t)g.entries * pb);
@@ -580,7 +615,7 @@ int te_msm_mul_base_device(te_ctx* ctx, te_base* base, const void* d_scalars_le,
   if (!go) return 0;
   const int owner = owner_of(ctx, "te_msm_mul_base_device: the scalars and the output must be resident on one device of the context", {d_scalars_le, d_out_points_xy_le});
   if (owner < 0) return owner;
-  return mul_base_on(ctx, (size_t)owner, base, d_scalars_le, n, ctx->opt_scalars_montgomery != 0, d_out_points_xy_le);
+  return mul_base_on(ctx, (size_t)owner, base, d_scalars_le, n, ctx->opt_scalars_montgomery != 0, d_out_points_xy_le, scalar_bytes_now(ctx));
 }
 
 int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uint32_t window, uint32_t first, uint32_t count, void* dst, uint64_t cap,

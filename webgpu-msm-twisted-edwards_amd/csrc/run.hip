@@ -51,6 +51,7 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
   const size_t nd = ctx->devs.size();
   const plan_t p0 = make_plan(ctx, ctx->devs[0], plan_shard(n));
   const curve_sizes sz = sizes_of(p0.curve);
+  const size_t sb = (size_t)p0.sc_bytes;
   std::vector<int> wsel;
   if (int rc = free_sets(ctx, nd, wsel)) return rc;
   const int src_dev = ctx->devs[0].device;
@@ -61,13 +62,13 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
   for (size_t i = 1; i < nd; i++) {
     gpu_t& d = ctx->devs[i]; workset_t& ws = d.ws[wsel[i]];
     HIP_TRY(ctx, hipSetDevice(d.device));
-    if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sz.scalar_in)) return rc;
+    if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sb)) return rc;
     if (int rc = wait_behind_previous(ctx, ws)) return rc;
     const uint64_t lo = lo_of(i), m = lo_of(i + 1) - lo;
     if (m) {
       HIP_TRY(ctx, hipMemcpyPeerAsync(static_cast<uint8_t*>(ws.d_in_points) + lo * sz.point_in, d.device, sp + lo * sz.point_in, src_dev, m * sz.point_in, ws.stream));
-      HIP_TRY(ctx, hipMemcpyPeerAsync(static_cast<uint8_t*>(ws.d_in_scalars) + lo * sz.scalar_in, d.device, ss + lo * sz.scalar_in, src_dev, m * sz.scalar_in, ws.stream));
-      ctx->stat_peer_copies += 2; ctx->stat_peer_bytes += (int64_t)(m * (sz.point_in + sz.scalar_in));
+      HIP_TRY(ctx, hipMemcpyPeerAsync(static_cast<uint8_t*>(ws.d_in_scalars) + lo * sb, d.device, ss + lo * sb, src_dev, m * sb, ws.stream));
+      ctx->stat_peer_copies += 2; ctx->stat_peer_bytes += (int64_t)(m * (sz.point_in + sb));
     }
     HIP_TRY(ctx, hipEventRecord(ws.ev_copy, ws.stream));
   }
@@ -87,12 +88,12 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
         const uint8_t* fs = j == 0 ? ss : static_cast<const uint8_t*>(ows.d_in_scalars);
         if (j > 0) HIP_TRY(ctx, hipStreamWaitEvent(ws.stream, ows.ev_copy, 0));
         HIP_TRY(ctx, hipMemcpyPeerAsync(static_cast<uint8_t*>(ws.d_in_points) + lo * sz.point_in, d.device, fp + lo * sz.point_in, o.device, m * sz.point_in, ws.stream));
-        HIP_TRY(ctx, hipMemcpyPeerAsync(static_cast<uint8_t*>(ws.d_in_scalars) + lo * sz.scalar_in, d.device, fs + lo * sz.scalar_in, o.device, m * sz.scalar_in, ws.stream));
-        copies[i] += 2; bytes[i] += (int64_t)(m * (sz.point_in + sz.scalar_in));
+        HIP_TRY(ctx, hipMemcpyPeerAsync(static_cast<uint8_t*>(ws.d_in_scalars) + lo * sb, d.device, fs + lo * sb, o.device, m * sb, ws.stream));
+        copies[i] += 2; bytes[i] += (int64_t)(m * (sz.point_in + sb));
       }
       dp = ws.d_in_points; ds = ws.d_in_scalars;
     }
-    partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream;
+    partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.scalar_bytes = p0.sc_bytes;
     if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
@@ -215,7 +216,7 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
     gpu_t& d = ctx->devs[i];
     if (hi == lo) return 0;
     workset_t& ws = d.ws[wsel[i]];
-    host_slice_req r; r.scalars = src_scalars + lo * sz.scalar_in; r.n = hi - lo; r.c = p0.c; r.K = K;
+    host_slice_req r; r.scalars = src_scalars + lo * (size_t)p0.sc_bytes; r.n = hi - lo; r.c = p0.c; r.K = K; r.scalar_bytes = p0.sc_bytes;
     if (!bases) r.points = src_points + lo * sz.point_in;
     else if (!src_idx) { r.recs = bases->recs[i] + lo * bases->rec_bytes; r.rec_kind = bases->rec_kind; }
     else { r.recs = bases->recs[i]; r.rec_kind = bases->rec_kind; r.idx = src_idx + lo; r.idx_count = bases->n; r.idx_pos = lo; }
@@ -296,6 +297,7 @@ int check_n(te_ctx* ctx, uint64_t n) { return n >= (1ull << 31) ? set_err(ctx, T
 int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, bool src_is_host, uint64_t n, uint8_t out[64], share_mode share) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_scalar_record(ctx)) return rc;
   if (n == 0) { write_identity(ctx->opt_curve, out); return 0; }
   if (!src_points || !src_scalars) return set_err(ctx, TE_MSM_EINVAL, "null input buffer");
   // (device-resident inputs live on the first device: a multi-device call checks them there, before the scatter)
@@ -316,14 +318,15 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
   if (wsel < 0) return wsel;
   const plan_t p0 = make_plan(ctx, d, plan_shard(n));
   const curve_sizes sz = sizes_of(p0.curve);
+  const size_t sb = (size_t)p0.sc_bytes;
   workset_t& ws = d.ws[wsel];
   HIP_TRY(ctx, hipSetDevice(d.device));
   const void *dp = src_points, *ds = src_scalars;
   if (src_is_host) {
-    if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sz.scalar_in)) return rc;
+    if (int rc = ensure_staging(ctx, ws, n * sz.point_in, n * sb)) return rc;
     // scalars first; the points follow from inside enqueue_partial (pageable copies return when the data has left
     // the caller's buffer, so the scalar-only stages enqueued in between run while the points are still in flight)
-    if (int rc = upload(ctx, ws, ws.d_in_scalars, static_cast<const uint8_t*>(src_scalars), n * sz.scalar_in, ws.stream)) return rc;
+    if (int rc = upload(ctx, ws, ws.d_in_scalars, static_cast<const uint8_t*>(src_scalars), n * sb, ws.stream)) return rc;
     dp = ws.d_in_points; ds = ws.d_in_scalars;
   }
   const std::function<int(hipStream_t)> upload_points = [&](hipStream_t side) -> int {

@@ -295,11 +295,13 @@ template <int CURVE> TE_HD void sm_affine_group(const uint32_t* proj, uint32_t c
 #if defined(__HIPCC__)
 // one lane per point of a piece of m points; the scalars are per point (sc[i]) or one (SHARED: kn, the NAF).  No early exit inside the
 // chain: a wave's instructions are uniform.
-template <int CURVE, bool SHARED> __global__ __launch_bounds__(256) void k_scalar_mul(const uint4* __restrict__ pts, const uint4* __restrict__ sc,
+// SQ: 16-byte words of a scalar record -- the curve's own unless named: 2 on BLS12-377 reads 32-byte records (option "scalar_record_bytes";
+// the shared-scalar form reads no record).  Lane i < m reads words [i SQ, i SQ + 2): the record's first 32 bytes, inside m records of 16 SQ.
+template <int CURVE, bool SHARED, int SQ = (CURVE == 1 ? 3 : 2)> __global__ __launch_bounds__(256) void k_scalar_mul(const uint4* __restrict__ pts, const uint4* __restrict__ sc,
                                                                                      uint32_t m, uint4* __restrict__ proj, naf_t kn) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
-  constexpr int PQ = sm_sizes<CURVE>::PW / 4, JQ = sm_sizes<CURVE>::JW / 4, SQ = CURVE == 1 ? 3 : 2;   // 16-byte words of a point / slot / scalar
+  constexpr int PQ = sm_sizes<CURVE>::PW / 4, JQ = sm_sizes<CURVE>::JW / 4;                           // 16-byte words of a point / slot
   uint32_t w[4 * PQ], k[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll
   for (int j = 0; j < PQ; j++) { const uint4 v = pts[(size_t)i * PQ + j]; w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w; }

@@ -76,6 +76,7 @@ plan_t make_plan(const te_ctx* ctx, const gpu_t& d, const plan_req& q) {
   const uint64_t n = q.n;
   p.curve = ctx->opt_curve;
   p.scalar_mont = q.scalar_form >= 0 ? q.scalar_form : ctx->opt_scalars_montgomery;
+  p.sc_bytes = q.scalar_bytes ? q.scalar_bytes : (int)scalar_bytes_now(ctx);
   p.rec_kind = q.rec_kind;
   p.c = q.force_c ? q.force_c : ctx->opt_window_bits ? ctx->opt_window_bits : auto_window_bits(n);
   p.signed_digits = ctx->opt_signed;
@@ -289,7 +290,7 @@ struct msm_launch {
       te::digits_params prm; memset(&prm, 0, sizeof prm);
       if (p.signed_digits) for (int w = 0; w < p.W; w++) { const int bit = w * p.c + p.c - 1; if (bit < 320) prm.half[bit >> 5] |= 1u << (bit & 31); }
       prm.zero_digit = p.signed_digits ? 1u << (p.c - 1) : 0u;
-      prm.sc_stride = (uint32_t)(sizes_of(p.curve).scalar_in / 16);
+      prm.sc_stride = (uint32_t)p.sc_bytes / 16u;
       prm.n = n32; prm.nst = p.nst; prm.num_windows = p.W; prm.w_first = p.w_first; prm.w_step = p.w_step; prm.nw_local = p.nw1;
       prm.half_code = sg.half; prm.logS = p.logS; prm.P = p.P; prm.CH = p.CH; prm.chunk_len = p.chunk_len;
       // one launch over the MSMs of the sequence: MSM m (blockIdx.y) fills digit rows and level-1 counts [m * nw1, (m + 1) * nw1)
@@ -761,7 +762,7 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const partial_req& r) 
   const void* const d_points = r.d_points; const uint64_t n = r.n; hipStream_t const stream = r.stream;
   const int batch = r.batch; const te_bases* const bases = r.bases; const auto* const upload_points = r.upload_points;
   // (the plan is made for the n entries; only the entry form follows the set's count: indexed_plan.hpp)
-  plan_req q; q.n = n; q.batch = batch; q.whole = r.whole; q.scalar_form = r.scalar_form;
+  plan_req q; q.n = n; q.batch = batch; q.whole = r.whole; q.scalar_form = r.scalar_form; q.scalar_bytes = r.scalar_bytes;
   if (bases) q.rec_kind = bases->rec_kind;
   if (r.d_idx) q.idx_count = bases->n;
   const plan_t p = make_plan(ctx, d, q);
@@ -881,8 +882,8 @@ void free_workset_buffers(workset_t& ws) {      // the big device buffers of a w
   ws.used = false;
 }
 
-// device copies of a host-buffer call's inputs, in bytes of the call's curve (64 + 32 per point for the Twisted-Edwards
-// wire format, 96 + 48 for BLS12-377)
+// device copies of a host-buffer call's inputs, in bytes of the call's curve and scalar record (64 + 32 per point for the Twisted-Edwards
+// wire format, 96 + 48 for BLS12-377 -- 96 + 32 under option "scalar_record_bytes" = 32)
 int ensure_staging(te_ctx* ctx, workset_t& ws, size_t bytes_points, size_t bytes_scalars) {
   if (int rc = make_room(ctx, ws.d_in_points, bytes_points)) return rc;
   return make_room(ctx, ws.d_in_scalars, bytes_scalars);
@@ -898,16 +899,16 @@ int wait_behind_previous(te_ctx* ctx, workset_t& ws) {
 bool must_pull(const te_ctx* ctx, const gpu_t& d, int src_dev) { return ctx->devs.size() > 1 && (d.device != src_dev || ctx->opt_stage_device_inputs); }
 // The n entries of `in` over the peer link, on the set's stream; `in` then names the staging area.  moved: what was copied -- the caller
 // adds it to the context's counters (plain integers: run_bound_window_shards pulls from one host thread per device and adds after the join).
-int pull_inputs(te_ctx* ctx, const gpu_t& d, workset_t& ws, int src_dev, uint64_t n, device_inputs& in, peer_traffic& moved) {
+int pull_inputs(te_ctx* ctx, const gpu_t& d, workset_t& ws, int src_dev, uint64_t n, size_t scalar_bytes, device_inputs& in, peer_traffic& moved) {
   const curve_sizes sz = sizes_of(ctx->opt_curve);
   if (in.idx) { if (int rc = make_room(ctx, ws.d_in_idx, (size_t)n)) return rc; }
-  if (int rc = ensure_staging(ctx, ws, in.points ? n * sz.point_in : 0, n * sz.scalar_in)) return rc;
+  if (int rc = ensure_staging(ctx, ws, in.points ? n * sz.point_in : 0, n * scalar_bytes)) return rc;
   if (int rc = wait_behind_previous(ctx, ws)) return rc;
-  HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, in.scalars, src_dev, n * sz.scalar_in, ws.stream));
+  HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_scalars, d.device, in.scalars, src_dev, n * scalar_bytes, ws.stream));
   if (in.points) HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_points, d.device, in.points, src_dev, n * sz.point_in, ws.stream));
   if (in.idx) HIP_TRY(ctx, hipMemcpyPeerAsync(ws.d_in_idx, d.device, in.idx, src_dev, n * sizeof(uint32_t), ws.stream));
   moved.copies += 1 + (in.points != nullptr) + (in.idx != nullptr);
-  moved.bytes += (int64_t)(n * (sz.scalar_in + (in.points ? sz.point_in : 0) + (in.idx ? sizeof(uint32_t) : 0)));
+  moved.bytes += (int64_t)(n * (scalar_bytes + (in.points ? sz.point_in : 0) + (in.idx ? sizeof(uint32_t) : 0)));
   in.scalars = ws.d_in_scalars;
   if (in.points) in.points = ws.d_in_points;
   if (in.idx) in.idx = ws.d_in_idx;
@@ -1091,13 +1092,14 @@ int enqueue_host_pieces(te_ctx* ctx, gpu_t& d, workset_t& ws, const host_slice_r
   const uint64_t n = r.n;
   const bool bound = r.points == nullptr;
   // what the plans of the whole slice and of every piece share; the pieces keep the slice's window bits and scalar form
-  plan_req q = plan_whole(n); q.force_c = r.c; q.scalar_form = r.scalar_form;
+  plan_req q = plan_whole(n); q.force_c = r.c; q.scalar_form = r.scalar_form; q.scalar_bytes = r.scalar_bytes;
   if (bound) { q.rec_kind = r.rec_kind; if (r.idx) q.idx_count = r.idx_count; }
   const plan_t pf = make_plan(ctx, d, q);
-  q.force_c = pf.c; q.scalar_form = pf.scalar_mont;
+  q.force_c = pf.c; q.scalar_form = pf.scalar_mont; q.scalar_bytes = pf.sc_bytes;
   const curve_sizes sz = sizes_of(pf.curve);
+  const size_t sb = (size_t)pf.sc_bytes;                                   // the call's scalar record: every size and piece offset below
   const size_t rec_bytes = rec_bytes_of(pf.curve, pf.rec_kind);
-  if (int rc = ensure_staging(ctx, ws, bound ? 0 : n * sz.point_in, n * sz.scalar_in)) return rc;
+  if (int rc = ensure_staging(ctx, ws, bound ? 0 : n * sz.point_in, n * sb)) return rc;
   if (r.idx) { if (int rc = make_room(ctx, ws.d_in_idx, (size_t)n)) return rc; }
   const bool pinned_source = r.wait_for_pinned && !caller_may_wait_on_host(r.scalars, bound ? static_cast<const void*>(r.idx) : r.points);
   const bool host_waits = !pinned_source;
@@ -1142,7 +1144,7 @@ int enqueue_host_pieces(te_ctx* ctx, gpu_t& d, workset_t& ws, const host_slice_r
   std::vector<hipEvent_t>& evs = ws.piece_events;
   while ((int)evs.size() < K + 1) { hipEvent_t e; HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming)); evs.push_back(e); }
   auto upload_scalars = [&](uint64_t lo, uint64_t m) -> int {
-    return upload(ctx, ws, dscs + lo * sz.scalar_in, r.scalars + lo * sz.scalar_in, m * sz.scalar_in, ws.copy_stream);
+    return upload(ctx, ws, dscs + lo * sb, r.scalars + lo * sb, m * sb, ws.copy_stream);
   };
   // Host points on Twisted-Edwards: ALL scalars first, in one copy (a third of the bytes): every extra pageable copy call costs ~43 us
   // of pipeline drain (six calls for three pieces ended at 2.02 ms where one pair of calls takes 1.85), and with the scalars there the
@@ -1172,7 +1174,7 @@ int enqueue_host_pieces(te_ctx* ctx, gpu_t& d, workset_t& ws, const host_slice_r
     p = make_plan(ctx, d, q);
     if (int rc = ensure_buffers(ctx, d, ws, m, p, !bound)) return rc;        // no reallocation: only the pointers into the zeroed block move
     msm_launch L = L0;
-    L.p = p; L.d_scalars = dscs + lo * sz.scalar_in; L.n = m; L.onto = i > 0;
+    L.p = p; L.d_scalars = dscs + lo * sb; L.n = m; L.onto = i > 0;
     if (!bound) L.d_points = dpts + lo * sz.point_in;
     else if (!r.idx) L.bound = r.recs + lo * rec_bytes;
     else { L.bound = r.recs; L.idx = ws.d_in_idx + lo; L.idx_count = (uint32_t)r.idx_count; L.idx_pos = (uint32_t)(r.idx_pos + lo); }
@@ -1359,10 +1361,11 @@ int run_batch_on_device(te_ctx* ctx, size_t di, const te_bases* bases, const voi
 // src on the host: the device's own upload (D devices: D links side by side, one host thread each); src on a device of the
 // context: read in place on its holder, pulled over the peer link elsewhere.
 // mont: the raw coordinates are Montgomery residues (option "points_montgomery"): the conversion's other instantiation, the same records.
-int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src_is_host, int src_dev, bool mont) {
+// lay: the points' stride and flag byte (options "point_stride" / "point_infinity_flag"): the strided conversions, the same records.
+int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src_is_host, int src_dev, bool mont, point_layout lay) {
   gpu_t& d = ctx->devs[i];
   HIP_TRY(ctx, hipSetDevice(d.device));
-  const curve_sizes sz = sizes_of(b->curve);
+  const size_t in_bytes = lay.bytes(b->curve);                             // from one point to the next in the caller's buffer
   const uint64_t n = b->n;
   uint8_t* recs = nullptr; void* raw = nullptr; void* proj = nullptr; hipStream_t st = nullptr;
   struct cleanup_t { void*& raw; void*& proj; hipStream_t& st; ~cleanup_t() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } if (raw) (void)hipFree(raw); if (proj) (void)hipFree(proj); } } cleanup{raw, proj, st};
@@ -1371,13 +1374,13 @@ int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src
   HIP_TRY(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   const void* pts = src;
   if (src_is_host) {
-    HIP_TRY(ctx, hipMalloc(&raw, (size_t)n * sz.point_in));
-    HIP_TRY(ctx, hipMemcpyAsync(raw, src, (size_t)n * sz.point_in, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMalloc(&raw, (size_t)n * in_bytes));
+    HIP_TRY(ctx, hipMemcpyAsync(raw, src, (size_t)n * in_bytes, hipMemcpyHostToDevice, st));
     pts = raw;
   } else if (src_dev != d.device || ctx->opt_stage_device_inputs) {
-    HIP_TRY(ctx, hipMalloc(&raw, (size_t)n * sz.point_in));
-    HIP_TRY(ctx, hipMemcpyPeerAsync(raw, d.device, src, src_dev, (size_t)n * sz.point_in, st));
-    { std::lock_guard<std::mutex> lk(ctx->err_mu); ctx->stat_peer_copies += 1; ctx->stat_peer_bytes += (int64_t)(n * sz.point_in); }
+    HIP_TRY(ctx, hipMalloc(&raw, (size_t)n * in_bytes));
+    HIP_TRY(ctx, hipMemcpyPeerAsync(raw, d.device, src, src_dev, (size_t)n * in_bytes, st));
+    { std::lock_guard<std::mutex> lk(ctx->err_mu); ctx->stat_peer_copies += 1; ctx->stat_peer_bytes += (int64_t)(n * in_bytes); }
     pts = raw;
   }
   const uint32_t n32 = (uint32_t)n;
@@ -1386,12 +1389,20 @@ int bind_on_device(te_ctx* ctx, te_bases* b, size_t i, const void* src, bool src
   if (b->curve == TE_MSM_CURVE_BLS12_377_G1) {
     te::rec_slot<14>* pr = reinterpret_cast<te::rec_slot<14>*>(recs);
     if (b->rec_kind == 1) { HIP_TRY(ctx, hipMalloc(&proj, (size_t)n * sizeof(te::rec_slot<14>))); pr = static_cast<te::rec_slot<14>*>(proj); }
-    if (mont) hipLaunchKernelGGL(te::k_prep_points377<true>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, pr, n32);
+    const uint64_t* p8 = static_cast<const uint64_t*>(pts);
+    if (lay.stride && mont) hipLaunchKernelGGL(te::k_prep_points377_strided<true>, dim3((n32 + 255) / 256), dim3(256), 0, st, p8, lay.stride, lay.flag ? 1u : 0u, pr, n32);
+    else if (lay.stride) hipLaunchKernelGGL(te::k_prep_points377_strided<false>, dim3((n32 + 255) / 256), dim3(256), 0, st, p8, lay.stride, lay.flag ? 1u : 0u, pr, n32);
+    else if (mont) hipLaunchKernelGGL(te::k_prep_points377<true>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, pr, n32);
     else hipLaunchKernelGGL(te::k_prep_points377<false>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, pr, n32);
     if (b->rec_kind == 1) {
       const uint32_t groups = (n32 + TE_AFF_GROUP - 1u) / TE_AFF_GROUP;
       hipLaunchKernelGGL(te::k_affine377, dim3((groups + 255) / 256), dim3(256), 0, st, pr, reinterpret_cast<te::rec_aff377*>(recs), n32);
     }
+  } else if (lay.stride) {
+    const uint64_t* p8 = static_cast<const uint64_t*>(pts);
+    te::rec_slot<9>* pr = reinterpret_cast<te::rec_slot<9>*>(recs);
+    if (mont) hipLaunchKernelGGL(te::k_prep_points_strided<true>, dim3((n32 + 255) / 256), dim3(256), 0, st, p8, lay.stride, pr, n32);
+    else hipLaunchKernelGGL(te::k_prep_points_strided<false>, dim3((n32 + 255) / 256), dim3(256), 0, st, p8, lay.stride, pr, n32);
   } else if (mont) {
     hipLaunchKernelGGL(te::k_prep_points<true>, dim3((n32 + 255) / 256, 1), dim3(256), 0, st, tab, row_slab, reinterpret_cast<te::pnt_slot*>(recs), n32);
   } else {

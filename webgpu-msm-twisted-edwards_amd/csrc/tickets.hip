@@ -59,6 +59,7 @@ const char* const kNoTicket = "no such ticket in flight (already collected, or n
 int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars_le, uint64_t n, uint64_t* ticket, bool async) {
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (!points_xy_le || !scalars_le || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
+  if (int rc = check_scalar_record(ctx)) return rc;
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_submit computes whole MSMs: reset the window shard first");
   std::optional<ticket_set> taken;
   if (int rc = take_free_workset(ctx, -1, false, taken)) return rc;
@@ -73,7 +74,7 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
     return 0;
   }
   const int level = ctx->opt_check_points, curve = ctx->opt_curve;
-  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes;
   te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, r, level, curve]() -> int {
     // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
     if (const int rc = check_ticket(ctx, t.ws, (size_t)t.di, r.points, true, r.n, curve, level)) return rc;
@@ -135,13 +136,13 @@ int owner_of(te_ctx* ctx, const char* msg, std::initializer_list<const void*> pt
 }
 // The device-resident inputs of a ticket (on device `owner` of the context), where its launch sequence reads them: in place, or -- the
 // ticket went to another device -- pulled into its set's staging area and counted.  pulled: which of the two.
-int pull_for_ticket(te_ctx* ctx, const ticket_set& t, int owner, uint64_t n, device_inputs& in, bool* pulled) {
+int pull_for_ticket(te_ctx* ctx, const ticket_set& t, int owner, uint64_t n, size_t scalar_bytes, device_inputs& in, bool* pulled) {
   const int src_dev = ctx->devs[(size_t)owner].device;
   const bool pull = must_pull(ctx, t.d, src_dev);
   if (pulled) *pulled = pull;
   if (!pull) return 0;
   peer_traffic moved;
-  if (int rc = pull_inputs(ctx, t.d, t.ws, src_dev, n, in, moved)) return rc;
+  if (int rc = pull_inputs(ctx, t.d, t.ws, src_dev, n, scalar_bytes, in, moved)) return rc;
   note_peer_traffic(ctx, moved);
   return 0;
 }
@@ -208,6 +209,7 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (!d_points_xy_le || !d_scalars_le || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
+  if (int rc = check_scalar_record(ctx)) return rc;
   const bool multi = ctx->devs.size() > 1;
   // several devices: the inputs may live on any of them; the ticket goes to the least loaded one and pulls them over xGMI
   const int owner = multi ? owner_of(ctx, "te_msm_submit_device: points and scalars must be resident on one device of the context", {d_points_xy_le, d_scalars_le}) : 0;
@@ -223,7 +225,7 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
   HIP_TRY(ctx, hipSetDevice(t.d.device));
   device_inputs in; in.scalars = d_scalars_le; in.points = d_points_xy_le;
   bool pull = false;
-  if (int rc = pull_for_ticket(ctx, t, owner, n, in, &pull)) return rc;
+  if (int rc = pull_for_ticket(ctx, t, owner, n, scalar_bytes_now(ctx), in, &pull)) return rc;
   // a single-device context keeps its window shard (te_msm_set_window_shard); on several devices a ticket is a whole MSM
   partial_req r; r.d_points = in.points; r.d_scalars = in.scalars; r.n = n; r.stream = t.ws.stream; r.whole = multi; r.share = pull ? SHARE_NONE : SHARE_RUN;
   if (int rc = enqueue_partial(ctx, t.d, t.ws, r)) return rc;

@@ -33,11 +33,15 @@ namespace {
 
 std::atomic<int> g_check_points{0};    // setCheckPoints(level): option "check_points" of every context created from now on
 std::atomic<int> g_scalars_montgomery{0};   // setScalarsMontgomery(flag): option "scalars_montgomery" of every context created from now on
+std::atomic<int> g_scalar_record_bytes{0};  // setScalarRecordBytes(n): option "scalar_record_bytes" of every context created from now on
 // what setBases bound: the Buffer, kept alive so that its address cannot become another object's, and the form of its coordinates
-// ({montgomery: true}: option "points_montgomery" for every bind of that buffer; a pool thread binds it again on a new context)
+// ({montgomery: true}: option "points_montgomery" for every bind of that buffer; a pool thread binds it again on a new context;
+// {stride, infinityFlag}: options "point_stride" / "point_infinity_flag", remembered and applied in the same way)
 struct BoundBuffer {
   napi_ref ref = nullptr;
   std::atomic<int> montgomery{0};
+  std::atomic<int> stride{0};
+  std::atomic<int> infinity_flag{0};
 } g_bases;
 
 // the engine behind te_promise::protocol (js/promise_protocol.hpp holds the lock protocol itself)
@@ -65,6 +69,10 @@ struct EngineApi {
       const int orc = te_msm_set_option(*out, "scalars_montgomery", 1);
       if (orc) { te_msm_destroy(*out); *out = nullptr; return orc; }
     }
+    if (rc == 0 && g_scalar_record_bytes.load()) {
+      const int orc = te_msm_set_option(*out, "scalar_record_bytes", g_scalar_record_bytes.load());
+      if (orc) { te_msm_destroy(*out); *out = nullptr; return orc; }
+    }
     return rc;
   }
   static void destroy(te_ctx* c) { te_msm_destroy(c); }
@@ -78,13 +86,19 @@ struct EngineApi {
   // resident bases (include/te_msm.h): the opt-in behind setBases(buffer)
   // (the option is read at bind time: set for the length of this bind and put back -- also when the set is bound again on a new context)
   static int bind(te_ctx* c, const uint8_t* p, uint64_t n, te_bases** out) {
-    if (!g_bases.montgomery.load()) return te_msm_bind_points(c, p, n, out);
-    int64_t before = 0;
-    int orc = te_msm_get_option(c, "points_montgomery", &before);
-    if (!orc) orc = te_msm_set_option(c, "points_montgomery", 1);
-    if (orc) return orc;
-    const int rc = te_msm_bind_points(c, p, n, out);
-    (void)te_msm_set_option(c, "points_montgomery", before);
+    const struct { const char* key; int64_t want; } opts[3] = {{"points_montgomery", g_bases.montgomery.load()}, {"point_stride", g_bases.stride.load()},
+                                                               {"point_infinity_flag", g_bases.infinity_flag.load()}};
+    int64_t before[3] = {0, 0, 0};
+    bool was_set[3] = {false, false, false};                 // only an option this bind changed is put back
+    int orc = 0;
+    for (int i = 0; i < 3 && !orc; i++) {
+      if (!opts[i].want) continue;
+      orc = te_msm_get_option(c, opts[i].key, &before[i]);
+      if (!orc) orc = te_msm_set_option(c, opts[i].key, opts[i].want);
+      was_set[i] = !orc;
+    }
+    const int rc = orc ? orc : te_msm_bind_points(c, p, n, out);
+    for (int i = 0; i < 3; i++) if (was_set[i]) (void)te_msm_set_option(c, opts[i].key, before[i]);
     return rc;
   }
   static int release(te_ctx* c, te_bases* b) { return te_msm_release_points(c, b); }
@@ -130,7 +144,13 @@ napi_value MsmNative(napi_env env, napi_callback_info info) {
   void *p = nullptr, *s = nullptr; size_t pl = 0, sl = 0;
   napi_get_buffer_info(env, argv[0], &p, &pl);
   napi_get_buffer_info(env, argv[1], &s, &sl);
-  if (sl % 32 != 0 || pl != 2 * sl) {
+  // (the buffer setBases bound at a stride is stride*n bytes: it is recognised by identity and its points are not read again)
+  bool bound_at_stride = false;
+  if (g_bases.ref && g_bases.stride.load() && pl == (size_t)g_bases.stride.load() * (sl / 32)) {
+    napi_value bound = nullptr;
+    if (napi_get_reference_value(env, g_bases.ref, &bound) == napi_ok && bound) napi_strict_equals(env, bound, argv[0], &bound_at_stride);
+  }
+  if (sl % 32 != 0 || (pl != 2 * sl && !bound_at_stride)) {
     napi_throw_range_error(env, nullptr, "points must be 64*n bytes and scalars 32*n bytes");
     return nullptr;
   }
@@ -182,10 +202,13 @@ napi_value SetDevices(napi_env env, napi_callback_info info) {
 // size (submission/miscellaneous/full_benchmarks.ts:63-68,100-105).  Blocks until no promise is pending (like resetContext).
 // setBases(points, {montgomery: true}): the coordinates are a native prover's Montgomery residues, x * 2^256 mod p (include/te_msm.h,
 // option "points_montgomery"); the set, and every result over it, is the same as from canonical coordinates.
+// {stride: s}: point i starts at byte i * s of the buffer (option "point_stride"); {infinityFlag: true}: option "point_infinity_flag",
+// BLS12-377 only -- on the curve this addon runs the engine refuses the bind (te_msm error -1).  All three are remembered with the buffer.
 napi_value SetBases(napi_env env, napi_callback_info info) {
   size_t argc = 2; napi_value argv[2];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
-  bool montgomery = false;
+  bool montgomery = false, infinity_flag = false;
+  int32_t stride = 0;
   if (argc >= 2) {
     napi_valuetype ot = napi_undefined;
     napi_typeof(env, argv[1], &ot);
@@ -197,7 +220,21 @@ napi_value SetBases(napi_env env, napi_callback_info info) {
         napi_throw_type_error(env, nullptr, "setBases: options.montgomery is a boolean");
         return nullptr;
       }
-    } else if (ot != napi_undefined && ot != napi_null) { napi_throw_type_error(env, nullptr, "setBases(points: Buffer | null, options?: { montgomery?: boolean })"); return nullptr; }
+      has = false;
+      napi_has_named_property(env, argv[1], "infinityFlag", &has);
+      if (has && (napi_get_named_property(env, argv[1], "infinityFlag", &mv) != napi_ok || napi_coerce_to_bool(env, mv, &mv) != napi_ok ||
+                  napi_get_value_bool(env, mv, &infinity_flag) != napi_ok)) {
+        napi_throw_type_error(env, nullptr, "setBases: options.infinityFlag is a boolean");
+        return nullptr;
+      }
+      has = false;
+      napi_has_named_property(env, argv[1], "stride", &has);
+      if (has && (napi_get_named_property(env, argv[1], "stride", &mv) != napi_ok || napi_get_value_int32(env, mv, &stride) != napi_ok ||
+                  (stride != 0 && (stride % 8 != 0 || stride < 64 || stride > 128)))) {
+        napi_throw_type_error(env, nullptr, "setBases: options.stride is 0 or a multiple of 8 in [64, 128]");
+        return nullptr;
+      }
+    } else if (ot != napi_undefined && ot != napi_null) { napi_throw_type_error(env, nullptr, "setBases(points: Buffer | null, options?: { montgomery?: boolean, stride?: number, infinityFlag?: boolean })"); return nullptr; }
   }
   napi_valuetype vt = napi_undefined;
   if (argc >= 1) napi_typeof(env, argv[0], &vt);
@@ -208,19 +245,21 @@ napi_value SetBases(napi_env env, napi_callback_info info) {
   if (!is_buf) {
     (void)g_proto.set_bases(nullptr, 0, err);
     if (g_bases.ref) { napi_delete_reference(env, g_bases.ref); g_bases.ref = nullptr; }
-    g_bases.montgomery.store(0);
+    g_bases.montgomery.store(0); g_bases.stride.store(0); g_bases.infinity_flag.store(0);
   } else {
     void* p = nullptr; size_t pl = 0;
     napi_get_buffer_info(env, argv[0], &p, &pl);
-    if (pl % 64 != 0) { napi_throw_range_error(env, nullptr, "setBases: points must be 64*n bytes"); return nullptr; }
+    const size_t rec = stride ? (size_t)stride : 64;                  // from one point to the next
+    if (pl % rec != 0) { napi_throw_range_error(env, nullptr, "setBases: points must be 64*n bytes (stride*n with options.stride)"); return nullptr; }
     napi_ref ref = nullptr;
     napi_create_reference(env, argv[0], 1, &ref);
-    g_bases.montgomery.store(montgomery ? 1 : 0);                     // (Api::bind reads it inside set_bases)
-    const int rc = g_proto.set_bases(static_cast<const uint8_t*>(p), pl / 64, err);
+    g_bases.montgomery.store(montgomery ? 1 : 0);                     // (Api::bind reads them inside set_bases)
+    g_bases.stride.store(stride); g_bases.infinity_flag.store(infinity_flag ? 1 : 0);
+    const int rc = g_proto.set_bases(static_cast<const uint8_t*>(p), pl / rec, err);
     if (g_bases.ref) napi_delete_reference(env, g_bases.ref);         // the previous buffer is unbound either way
     g_bases.ref = nullptr;
     if (rc) {
-      g_bases.montgomery.store(0);                                    // nothing is bound
+      g_bases.montgomery.store(0); g_bases.stride.store(0); g_bases.infinity_flag.store(0);      // nothing is bound
       napi_delete_reference(env, ref);
       const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
       napi_throw_error(env, nullptr, m.c_str());
@@ -514,6 +553,22 @@ napi_value SetScalarsMontgomery(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+// setScalarRecordBytes(n): option "scalar_record_bytes" (include/te_msm.h) for the next call, like setScalarsMontgomery: 0 = the curve's own
+// record, 32 or 48 spelled out.  The addon runs the Twisted-Edwards curve, whose one record is 32 bytes: 0 and 32 change nothing, and under
+// 48 every call that reads scalars rejects with the engine's TE_MSM_EINVAL -- the switch is here so that the addon names every input option.
+napi_value SetScalarRecordBytes(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  int32_t n = -1;
+  if (argc < 1 || napi_get_value_int32(env, argv[0], &n) != napi_ok || (n != 0 && n != 32 && n != 48)) {
+    napi_throw_type_error(env, nullptr, "setScalarRecordBytes(n: 0 | 32 | 48)");
+    return nullptr;
+  }
+  g_proto.reset();
+  g_scalar_record_bytes.store(n);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
 // getStats(): how the promises so far were mapped onto the engine -- tickets submitted from the JavaScript thread / from pool
 // threads, lone calls, jobs over bound bases, and the largest number of tickets seen in flight at a submit
 napi_value GetStats(napi_env env, napi_callback_info) {
@@ -537,6 +592,7 @@ napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
       {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints}, {"setScalarsMontgomery", SetScalarsMontgomery},
+      {"setScalarRecordBytes", SetScalarRecordBytes},
       {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed},
       {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase}};
   for (const auto& f : fns) {

@@ -58,6 +58,9 @@ const setBases = (bufferPoints, options) => native.setBases(bufferPoints === und
 // residues k * 2^256 mod L (L: the order of the prime subgroup), decoded on the GPU where the scalars are first read; any 256-bit value
 // stands for its residue.  scalarMul / scalarMulX take canonical scalars only and throw while it is set.
 const setScalarsMontgomery = (flag) => native.setScalarsMontgomery(!!flag);
+// setScalarRecordBytes(n): the engine's option "scalar_record_bytes" for later calls (0 = the curve's own record; 32 and 48 spelled out).
+// On the Twisted-Edwards curve the addon runs, 0 and 32 are the same thing and 48 makes every call that reads scalars reject.
+const setScalarRecordBytes = (n) => native.setScalarRecordBytes(n);
 const getStats = () => native.getStats();
 // Opt-in as well: setCheckPoints(level) validates the input points of later calls (0 = none, default; 1 = canonical and on the
 // curve; 2 = also in the prime-order subgroup, costly -- best paired with setBases, which then checks the set once).  A call with
@@ -97,4 +100,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase };

@@ -14,10 +14,15 @@ export declare const getDevices: () => number[];
 // compute_msm(points, scalars) with the same Buffer object then moves the scalars only (full_benchmarks.ts:63-68,100-105 pass
 // one point buffer to six calls per size).  setBases(null) unbinds.
 // { montgomery: true }: the coordinates are Montgomery residues x * 2^256 mod p (a native prover's in-memory form); same set, same results.
-export declare const setBases: (bufferPoints: Buffer | null, options?: { montgomery?: boolean }) => void;
+// { stride: s }: point i starts at byte i * s (a multiple of 8 in [64, 128]; bytes behind x || y are not interpreted).  { infinityFlag: true } is
+// the engine's BLS12-377 option "point_infinity_flag": on this addon's curve setBases throws (te_msm error -1).  All are remembered per buffer.
+export declare const setBases: (bufferPoints: Buffer | null, options?: { montgomery?: boolean, stride?: number, infinityFlag?: boolean }) => void;
 // Not in the reference: the scalar buffers of later compute_msm / msmBatch / msmIndexed calls hold Montgomery residues k * 2^256 mod L,
 // decoded on the GPU (any 256-bit value stands for its residue); scalarMul / scalarMulX throw while it is set.
 export declare const setScalarsMontgomery: (flag: boolean) => void;
+// Not in the reference: the engine's option "scalar_record_bytes" for later calls: 0 = the curve's own scalar record (32 bytes here), 32 the
+// same spelled out; 48 is BLS12-377's record, under which every call of this addon that reads scalars rejects (te_msm error -1).
+export declare const setScalarRecordBytes: (n: 0 | 32 | 48) => void;
 export declare const getStats: () => { submittedInEnter: number; submittedInExecute: number; loneRuns: number; boundJobs: number; maxInFlight: number };
 // Not in the reference: opt-in validation of input points (0 none, 1 canonical + on the curve, 2 + prime-order subgroup); a bad
 // point rejects the call's promise (the message names the index and the reason), setBases throws for a bad set.
