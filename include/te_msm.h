@@ -403,6 +403,57 @@ int te_msm_mul_base_device(te_ctx* ctx, te_base* base, const void* d_scalars_le,
 int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uint32_t window, uint32_t first, uint32_t count, void* dst, uint64_t cap,
                          int* entry_bytes);
 
+/* ---- batched group addition and point-set sums ---------------------------------------------------------------------------------
+ * te_msm_add*: out[i] = A_i + B_i for every i -- the reference's bulkAddGroups / addGroups (utils/wasmFunctions.ts:112-119).
+ * te_msm_sum*: ONE point, the sum of all P_i -- the reference's reduceGroups (utils/wasmFunctions.ts:121-125).  With them, results the
+ * engine leaves in device memory are combined there: a Pedersen commitment [v_i] G + [r_i] H is two te_msm_mul_base_device calls and one
+ * te_msm_add_device; an accumulator update acc[i] += new[i] is te_msm_add_device with d_out = d_a.  The curve is option "curve".
+ * flags: TE_MSM_ADD_SUBTRACT out[i] = A_i - B_i; TE_MSM_ADD_SHARED_B b holds ONE point, used for every i.  Any other bit: TE_MSM_EINVAL.
+ *   Negation and doubling are SUBTRACT from the identity and add(a, a).
+ * Points: the wire format above (64 / 96 bytes).  te_msm_add_x / te_msm_sum_x take x-only points in te_msm_points_from_x's format, with
+ *   its recovery and its rules (on the device, no host round trip).  Output: canonical affine x || y exactly as te_msm_mul writes it --
+ *   the Twisted-Edwards identity is (0, 1), the BLS12-377 point at infinity 96 zero bytes.  n = 0: add is a no-op, sum returns the
+ *   identity ((0, 1), or zeros).  n < 2^31, as for te_msm_mul.
+ * Exact for: Twisted-Edwards -- any two points of the curve, cofactor part included (A = B, A = -B, the identity, the points of order 2
+ *   and 4: one complete addition).  BLS12-377 -- inputs in G1, as for te_msm_mul; and because these calls PRODUCE the all-zero record,
+ *   the full-point forms also ACCEPT it as the point at infinity, so add(add(a, b), c) or sum(add(a, b)) never needs a host fix-up.
+ *   te_msm_add_x / te_msm_sum_x keep te_msm_points_from_x's rules and refuse infinity.
+ * Buffers: te_msm_add_device -- a, b (one point under SHARED_B) and out on one device of the context, else TE_MSM_EINVAL; d_out may be
+ *   exactly d_a or exactly d_b (partial overlap is the caller's error and is not detected); returns with d_out complete.  te_msm_add may
+ *   likewise be called with out == a.  te_msm_sum_device: the points on one device of the context; the result goes to HOST memory, as
+ *   an MSM's.  Host forms: contiguous slices over the context's devices, one host thread per device, each slice staged on its device;
+ *   results are copied out only when every slice passed.  te_msm_sum on several devices reduces every slice on its device and adds the
+ *   partial results on the first.  Temporaries are freed before return; the calling thread's current device is left as it was.
+ * Bad points: option "check_points" 1 / 2 applies to both operands of add and to sum's input, before anything is written -- in THESE
+ *   calls the all-zero BLS12-377 record passes both levels.  A failure is TE_MSM_EPOINT with the output untouched; "bad_point_index" /
+ *   "bad_point_reason" hold the LOWEST failing pair index and its reason, and the read-only option "bad_point_operand" which operand
+ *   failed: 0 = a / the sum's input, 1 = b (-1 before any failure; at equal index a is reported before b; a failing shared b is
+ *   reported at index 0).  The _x forms report recovery failures the same way, then apply "check_points" to the recovered points.
+ * Options "points_montgomery", "point_stride" and "point_infinity_flag" are NOT read: these are per-call point paths, like te_msm_mul*.
+ * How it runs (csrc/group_add.hip.hpp): one lane per pair and one complete addition into a projective slot, then
+ *   the affine pass; pieces of TE_MSM_GROUP_ADD_PIECE pairs share one temporary buffer.  The sum runs a grid of at most
+ *   TE_MSM_GROUP_SUM_GRID blocks of 256 lanes, each lane adding points i, i + stride, ..; a block folds to one partial, a second launch
+ *   of one block folds the partials, and one point is normalised.  Both constants are also the read-only options "group_add_piece" /
+ *   "group_sum_grid".
+ * COST (MI355X, device buffers, three alternating rounds, lowest .. highest; tools/group_add_cost.py, profiles/group_add_cost.txt):
+ *   te_msm_add_device at 2^20 pairs: 0.71 .. 0.78 ms (Twisted-Edwards), 1.69 .. 1.74 ms (BLS12-377) a call, of which k_group_add is
+ *   0.10 / 0.29 ms and the affine pass (k_scalar_mul_affine, unchanged) 0.43 / 1.27 ms; the host path it replaces spends 3.5 / 5.3 ms
+ *   on the link alone (both operands down, the result up, pinned memory).  A block-wide batch inversion in the affine pass's place
+ *   (one inversion per 2048 points) measured 0.82 .. 0.85 / 1.69 .. 1.72 ms against 0.78 .. 0.79 / 1.71 .. 1.75 ms in the same rounds:
+ *   not lower in every round on either curve, so it is not in the library.  te_msm_sum_device against te_msm_run_device over
+ *   all-ones scalars: 2^16 points 0.12 against 0.29 ms / 0.41 against 0.63 ms, 2^20 points 0.23 .. 0.24 against 0.56 ms / 0.83 .. 0.86
+ *   against 1.22 .. 1.23 ms, and no scalar buffer to make. */
+#define TE_MSM_ADD_SUBTRACT 1
+#define TE_MSM_ADD_SHARED_B 2
+#define TE_MSM_GROUP_ADD_PIECE (1u << 21)
+#define TE_MSM_GROUP_SUM_GRID 1024u
+int te_msm_add(te_ctx* ctx, const uint8_t* a_xy_le, const uint8_t* b_xy_le, uint64_t n, int flags, uint8_t* out_xy_le);
+int te_msm_add_device(te_ctx* ctx, const void* d_a, const void* d_b, uint64_t n, int flags, void* d_out);
+int te_msm_add_x(te_ctx* ctx, const uint8_t* ax_le, const uint8_t* bx_le, uint64_t n, int flags, uint8_t* out_xy_le);
+int te_msm_sum(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, uint8_t* out_xy_le);
+int te_msm_sum_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, uint8_t* out_xy_le);
+int te_msm_sum_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_xy_le);
+
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "scalars_montgomery" 0 (default) = scalar records hold the integers themselves (the wire format above); 1 = every scalar record holds
  *                   a = k * 2^256 mod m and the MSM uses k = a * 2^-256 mod m, where m is the scalar field of the curve in force:

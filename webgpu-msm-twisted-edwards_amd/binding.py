@@ -22,17 +22,20 @@ EPOINT = -5             # TE_MSM_EPOINT: an input point failed the check of opti
 # why a point failed (TE_MSM_POINT_*): MsmError.reason, the second item of MsmContext.check_points' answer
 POINT_NONCANONICAL, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = 1, 2, 3
 X_BYTES, X_BYTES_BLS12_377 = 32, 48      # TE_MSM_X_BYTES*: one x-only point (points_from_x, bind_points_x, run_x)
+ADD_SUBTRACT, ADD_SHARED_B = 1, 2        # TE_MSM_ADD_*: flags of te_msm_add*
 
 
 class MsmError(RuntimeError):
-    """code: the TE_MSM_E* value.  index / reason: the lowest failing point and TE_MSM_POINT_* when code is EPOINT; index alone: the
-    lowest position of an index outside the bound set (run_scalars_indexed*, code -1); else None."""
+    """code: the TE_MSM_E* value.  index / reason: the lowest failing point and TE_MSM_POINT_* when code is EPOINT, operand: which operand
+    held it (0 = a, or the call's one point buffer; 1 = b of add*); index alone: the lowest position of an index outside the bound set
+    (run_scalars_indexed*, code -1); else None."""
 
-    def __init__(self, code: int, msg: str, index: int | None = None, reason: int | None = None):
+    def __init__(self, code: int, msg: str, index: int | None = None, reason: int | None = None, operand: int | None = None):
         super().__init__(f"te_msm error {code}: {msg}")
         self.code = code
         self.index = index
         self.reason = reason
+        self.operand = operand
 
 
 def library_path() -> str:
@@ -213,6 +216,20 @@ def _lib() -> ctypes.CDLL:
             L.te_msm_mul_base_device.restype = ci
             L.te_msm_base_read.argtypes = [vp, vp, ci, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, u64, ctypes.POINTER(ci)]
             L.te_msm_base_read.restype = ctypes.c_int64
+        # (likewise for an older build named by TE_MSM_LIB: tools/group_add_cost.py times the parent's MSM beside te_msm_sum_device)
+        if not os.environ.get("TE_MSM_LIB") or hasattr(L, "te_msm_add"):
+            L.te_msm_add.argtypes = [vp, vp, vp, u64, ci, vp]
+            L.te_msm_add.restype = ci
+            L.te_msm_add_device.argtypes = [vp, vp, vp, u64, ci, vp]
+            L.te_msm_add_device.restype = ci
+            L.te_msm_add_x.argtypes = [vp, cp, cp, u64, ci, cp]
+            L.te_msm_add_x.restype = ci
+            L.te_msm_sum.argtypes = [vp, cp, u64, cp]
+            L.te_msm_sum.restype = ci
+            L.te_msm_sum_device.argtypes = [vp, vp, u64, cp]
+            L.te_msm_sum_device.restype = ci
+            L.te_msm_sum_x.argtypes = [vp, cp, u64, cp]
+            L.te_msm_sum_x.restype = ci
         _LIB = L
     return _LIB
 
@@ -253,11 +270,16 @@ class MsmContext:
         if rc < 0:
             msg = self._L.te_msm_last_error(self._h).decode()
             if rc == EPOINT:
-                raise MsmError(rc, msg, self.get_option("bad_point_index"), self.get_option("bad_point_reason"))
+                raise MsmError(rc, msg, self.get_option("bad_point_index"), self.get_option("bad_point_reason"), self._bad_operand())
             if rc == -1 and msg.startswith("index at position "):       # an indexed MSM (a call, or the collect of its ticket)
                 raise MsmError(rc, msg, self.get_option("bad_index_position"))
             raise MsmError(rc, msg)
         return rc
+
+    def _bad_operand(self):
+        """option "bad_point_operand" (None from a build without it: TE_MSM_LIB naming an older library)"""
+        v = ctypes.c_int64()
+        return v.value if self._L.te_msm_get_option(self._h, b"bad_point_operand", ctypes.byref(v)) == 0 else None
 
     # ---- input-point validation (include/te_msm.h: option "check_points" makes the calls below check; these run no MSM)
     def _verdict(self, rc: int, bad, why):
@@ -492,6 +514,64 @@ class MsmContext:
         out = ctypes.create_string_buffer(max(1, self._sizes[0] * n))
         self._check(self._L.te_msm_mul_x(self._h, bytes(xs), bytes(scalars), n, int(shared), out))
         return out.raw[:self._sizes[0] * n]
+
+    # ---- batched group addition and point-set sums (include/te_msm.h): out[i] = A_i +- B_i; one point, the sum of all P_i
+    def _add_flags(self, nb_bytes: int, unit: int, n: int, subtract: bool) -> int:
+        """TE_MSM_ADD_*: b of one point (unit bytes) beside n > 1 of a means shared"""
+        if nb_bytes == unit * n:
+            return ADD_SUBTRACT if subtract else 0
+        if nb_bytes != unit:
+            raise MsmError(-1, f"b must be {unit} bytes (one shared point) or {unit}*n bytes")
+        return ADD_SHARED_B | (ADD_SUBTRACT if subtract else 0)
+
+    def add(self, a: bytes, b: bytes, subtract: bool = False) -> bytes:
+        """te_msm_add, bulkAddGroups' counterpart on full points: n points a and n points b (64 / 96 bytes), or ONE point b for all of
+        them -> n points A_i + B_i (A_i - B_i with subtract), canonical affine x || y as mul() writes them.  BLS12-377: the all-zero
+        record is the point at infinity, in and out."""
+        pb = self._sizes[0]
+        if len(a) % pb:
+            raise MsmError(-1, f"points must be {pb}*n bytes")
+        n = len(a) // pb
+        flags = self._add_flags(len(b), pb, n, subtract)
+        out = ctypes.create_string_buffer(max(1, pb * n))
+        self._check(self._L.te_msm_add(self._h, bytes(a), bytes(b), n, flags, out))
+        return out.raw[:pb * n]
+
+    def add_device(self, d_a: int, d_b: int, n: int, d_out: int, subtract: bool = False, shared_b: bool = False):
+        """te_msm_add_device: the same between buffers on one device of the context; d_out may be d_a or d_b; shared_b: d_b holds one point"""
+        flags = (ADD_SUBTRACT if subtract else 0) | (ADD_SHARED_B if shared_b else 0)
+        self._check(self._L.te_msm_add_device(self._h, d_a, d_b, n, flags, d_out))
+
+    def add_x(self, ax: bytes, bx: bytes, subtract: bool = False) -> bytes:
+        """te_msm_add_x, bulkAddGroups' counterpart: n x-only points a and n (or one) b (32 / 48 bytes, points_from_x's format) -> n points x || y"""
+        n = self._x_count(ax)
+        xb = X_BYTES_BLS12_377 if self.curve == CURVE_BLS12_377_G1 else X_BYTES
+        flags = self._add_flags(len(bx), xb, n, subtract)
+        out = ctypes.create_string_buffer(max(1, self._sizes[0] * n))
+        self._check(self._L.te_msm_add_x(self._h, bytes(ax), bytes(bx), n, flags, out))
+        return out.raw[:self._sizes[0] * n]
+
+    def sum(self, points: bytes) -> bytes:
+        """te_msm_sum, reduceGroups' counterpart on full points: n points -> their sum, x || y (64 / 96 bytes; no points: the identity)"""
+        pb = self._sizes[0]
+        if len(points) % pb:
+            raise MsmError(-1, f"points must be {pb}*n bytes")
+        out = ctypes.create_string_buffer(96)
+        self._check(self._L.te_msm_sum(self._h, bytes(points), len(points) // pb, out))
+        return out.raw[:self._sizes[2]]
+
+    def sum_device(self, d_points: int, n: int) -> bytes:
+        """te_msm_sum_device: the same over n points on one device of the context; the result comes to host memory, as an MSM's"""
+        out = ctypes.create_string_buffer(96)
+        self._check(self._L.te_msm_sum_device(self._h, d_points, n, out))
+        return out.raw[:self._sizes[2]]
+
+    def sum_x(self, xs: bytes) -> bytes:
+        """te_msm_sum_x, reduceGroups' counterpart: n x-only points -> their sum, x || y"""
+        n = self._x_count(xs)
+        out = ctypes.create_string_buffer(96)
+        self._check(self._L.te_msm_sum_x(self._h, bytes(xs), n, out))
+        return out.raw[:self._sizes[2]]
 
     # ---- fixed-base batch scalar multiplication (include/te_msm.h): one point bound, [k_i] P for many scalars
     def bind_base(self, point: bytes) -> "Base":

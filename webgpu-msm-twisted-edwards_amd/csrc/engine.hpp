@@ -235,6 +235,7 @@ struct te_ctx {
   int opt_prezero = 1;         // clear a work set's zeroed block behind an MSM's read-back instead of in front of the next MSM's first kernel
   int opt_check_points = 0;    // validate input points before an MSM / a bind: 0 off, 1 form, 2 form + subgroup (include/te_msm.h)
   int64_t bad_point_index = -1; int bad_point_reason = 0;   // the last TE_MSM_EPOINT (get_option "bad_point_index" / "bad_point_reason")
+  int bad_point_operand = -1;       // ... and which operand of te_msm_add* held it: 0 = a (every call with one point buffer), 1 = b; -1 before any failure
   int64_t bad_index_position = -1;  // te_msm_run_scalars_indexed*: lowest position of an index outside the bound set, of the last call that failed on one
   float stage_ms[te_eng::ST_COUNT + 2] = {};
   bool have_stage_ms = false;

@@ -1,12 +1,13 @@
 // points.hip -- what the library does with points beside MSMs: validation (option "check_points", te_msm_check_points*), x-only
 // points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x), batch scalar multiplication (te_msm_mul*) and its fixed-base form
-// over one bound point (te_msm_bind_base, te_msm_mul_base*).  The one unit that includes the kernels of check.hip.hpp, from_x.hip.hpp,
-// scalar_mul.hip.hpp and mul_base.hip.hpp.
+// over one bound point (te_msm_bind_base, te_msm_mul_base*), batched group addition and point-set sums (te_msm_add*, te_msm_sum*).  The
+// one unit that includes the kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp and group_add.hip.hpp.
 #include "engine.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
 #include "scalar_mul.hip.hpp"
 #include "mul_base.hip.hpp"
+#include "group_add.hip.hpp"
 
 using namespace te_eng;
 
@@ -362,6 +363,243 @@ int mul_base_host(te_ctx* ctx, const te_base* b, const uint8_t* scalars_le, uint
   if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
   return te_sched::on_devices(*ctx, D, copy_out);
 }
+
+// ---- batched group addition and point-set sums (te_msm_add*, te_msm_sum*; kernels in group_add.hip.hpp) ------------------------------
+// An addition is mul_on's shape with k_group_add in the chain's place: pieces of kAddPiece pairs into a projective buffer of the call's
+// own, then te_msm_mul's affine pass (k_scalar_mul_affine, unchanged) -- the whole call in one piece up to 2^21 pairs: an addition is
+// two launches of a few hundred microseconds, and pieces of kMulPiece would quadruple them at 2^20 for nothing but a smaller buffer.  A
+// piece's additions have read a and b before its affine pass writes out, and later pieces lie behind it: d_out may be d_a or d_b.  The
+// sum needs the points once: stage 1 over a bounded grid, the same kernel over its partials, one projective point back to the host,
+// normalised there.
+constexpr uint64_t kAddPiece = TE_MSM_GROUP_ADD_PIECE;
+constexpr uint32_t kSumGrid = TE_MSM_GROUP_SUM_GRID;
+
+// the affine pass over m projective slots: te_msm_mul's chains of eight
+void launch_group_affine(bool bls, const uint32_t* proj, uint32_t m, uint32_t* out, hipStream_t st) {
+  const dim3 grid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP)), block(256);
+  if (bls) hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, grid, block, 0, st, proj, m, out, te::kInvExp377);
+  else hipLaunchKernelGGL(te::k_scalar_mul_affine<0>, grid, block, 0, st, proj, m, out, te::kInvExpTe);
+}
+
+// option "check_points" for these calls: n packed points in the memory of devs[di], one launch per level; the all-zero BLS12-377 record passes
+int group_check_on(te_ctx* ctx, size_t di, const void* d_pts, uint64_t n, int level, int64_t* bad, int* reason) {
+  *bad = -1; *reason = 0;
+  if (n == 0 || !level) return 0;
+  gpu_t& d = ctx->devs[di];
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  hipStream_t st = lane.stream();
+  const uint32_t m = (uint32_t)n;
+  const uint4* p4 = static_cast<const uint4*>(d_pts);
+  const dim3 grid((m + 255u) / 256u), block(256);
+  HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
+  if (ctx->opt_curve == TE_MSM_CURVE_BLS12_377_G1) {
+    hipLaunchKernelGGL(te::k_group_check_form<1>, grid, block, 0, st, p4, m, d.chk_word);
+    if (level >= 2) hipLaunchKernelGGL(te::k_group_check_subgroup<1>, grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
+  } else {
+    hipLaunchKernelGGL(te::k_group_check_form<0>, grid, block, 0, st, p4, m, d.chk_word);
+    if (level >= 2) hipLaunchKernelGGL(te::k_group_check_subgroup<0>, grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return lane.verdict(ctx, m, bad, reason);
+}
+
+// the verdict over a pair of operands: the lowest failing index, a before b at equal index
+struct pair_verdict {
+  int64_t bad = -1; int why = 0, operand = 0; bad_kind kind = kBadPoint;
+  void take(int64_t i, int reason, int op, bad_kind k) {
+    if (i < 0 || (bad >= 0 && (bad < i || (bad == i && operand <= op)))) return;
+    bad = i; why = reason; operand = op; kind = k;
+  }
+};
+int note_pair(te_ctx* ctx, const pair_verdict& v, int64_t base) {
+  const int rc = note_bad(ctx, v.kind, base + v.bad, v.why);
+  ctx->bad_point_operand = v.operand;
+  return rc;
+}
+// one step (recovery, or a check level) over both operands in the memory of devs[di]: 0 with v filled in when a point failed
+int check_pair_on(te_ctx* ctx, size_t di, const void* d_a, const void* d_b, uint64_t n, uint64_t nb, pair_verdict& v) {
+  int64_t bad = -1; int why = 0;
+  int rc = group_check_on(ctx, di, d_a, n, ctx->opt_check_points, &bad, &why);
+  if (rc == TE_MSM_EPOINT) v.take(bad, why, 0, kBadPoint); else if (rc) return rc;
+  if (!d_b) return 0;
+  rc = group_check_on(ctx, di, d_b, nb, ctx->opt_check_points, &bad, &why);
+  if (rc == TE_MSM_EPOINT) v.take(bad, why, 1, kBadPoint); else if (rc) return rc;
+  return 0;
+}
+
+// n pairs (memory of devs[di]; shared: d_b holds one point) -> n affine results at d_out, which may be d_a or d_b; returns when they are there
+int add_on(te_ctx* ctx, size_t di, const void* d_a, const void* d_b, uint64_t n, int flags, void* d_out) {
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const int curve = ctx->opt_curve;
+  const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1, shared = (flags & TE_MSM_ADD_SHARED_B) != 0;
+  const int neg = (flags & TE_MSM_ADD_SUBTRACT) ? 1 : 0;
+  const size_t pb = sizes_of(curve).point_in;
+  const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  const uint64_t piece = std::min(n, kAddPiece);
+  dev_tmp proj;
+  if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
+  hipStream_t st = lane.stream();
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint32_t m = (uint32_t)std::min(piece, n - off);
+    const uint4* a4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_a) + off * pb);
+    const uint4* b4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_b) + (shared ? 0 : off * pb));
+    uint4* j4 = static_cast<uint4*>(proj.p);
+    uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
+    const dim3 grid((m + 255u) / 256u), block(256);
+    if (bls && shared) hipLaunchKernelGGL((te::k_group_add<1, true>), grid, block, 0, st, a4, b4, m, neg, j4);
+    else if (bls) hipLaunchKernelGGL((te::k_group_add<1, false>), grid, block, 0, st, a4, b4, m, neg, j4);
+    else if (shared) hipLaunchKernelGGL((te::k_group_add<0, true>), grid, block, 0, st, a4, b4, m, neg, j4);
+    else hipLaunchKernelGGL((te::k_group_add<0, false>), grid, block, 0, st, a4, b4, m, neg, j4);
+    launch_group_affine(bls, static_cast<const uint32_t*>(proj.p), m, o32, st);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+inline size_t partial_bytes_of(int curve) { return 4u * (curve == TE_MSM_CURVE_BLS12_377_G1 ? te::ga_sizes<1>::TW : te::ga_sizes<0>::TW); }
+// count items at d_src (wire points, or -- partials -- projective partials) in the memory of devs[di] -> ONE partial in host memory
+// (h_part: partial_bytes_of).  One temporary holds the stage-1 partials and, behind them, the last one.
+int sum_fold_on(te_ctx* ctx, size_t di, const void* d_src, uint64_t count, bool partials, uint8_t* h_part) {
+  gpu_t& d = ctx->devs[di];
+  const bool bls = ctx->opt_curve == TE_MSM_CURVE_BLS12_377_G1;
+  const size_t tb = partial_bytes_of(ctx->opt_curve);
+  const uint32_t m = (uint32_t)count, blocks = std::min<uint32_t>(kSumGrid, (m + GS_BLOCK - 1u) / GS_BLOCK);
+  dev_tmp tmp;
+  if (int rc = tmp_alloc(ctx, d, tmp, (size_t)(blocks + 1u) * tb)) return rc;
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  hipStream_t st = lane.stream();
+  const uint4 *s4 = static_cast<const uint4*>(d_src), *t4c = static_cast<const uint4*>(tmp.p);
+  uint4 *t4 = static_cast<uint4*>(tmp.p), *o4 = reinterpret_cast<uint4*>(static_cast<uint8_t*>(tmp.p) + (size_t)blocks * tb);
+  const dim3 block(GS_BLOCK);
+  if (bls) {
+    if (partials) hipLaunchKernelGGL((te::k_group_sum<1, true>), dim3(blocks), block, 0, st, s4, m, t4);
+    else hipLaunchKernelGGL((te::k_group_sum<1, false>), dim3(blocks), block, 0, st, s4, m, t4);
+    hipLaunchKernelGGL((te::k_group_sum<1, true>), dim3(1), block, 0, st, t4c, blocks, o4);
+  } else {
+    if (partials) hipLaunchKernelGGL((te::k_group_sum<0, true>), dim3(blocks), block, 0, st, s4, m, t4);
+    else hipLaunchKernelGGL((te::k_group_sum<0, false>), dim3(blocks), block, 0, st, s4, m, t4);
+    hipLaunchKernelGGL((te::k_group_sum<0, true>), dim3(1), block, 0, st, t4c, blocks, o4);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(h_part, o4, tb, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+// the partial (its head is a projective slot) -> canonical x || y: sm_affine_group's code, run by the host for this one point
+void sum_finish(int curve, const uint8_t* h_part, uint8_t* out) {
+  uint32_t w[te::ga_sizes<1>::TW], o[te::sm_sizes<1>::PW];
+  memcpy(w, h_part, partial_bytes_of(curve));
+  if (curve == TE_MSM_CURVE_BLS12_377_G1) te::sm_affine_group<1>(w, 1u, o, te::kInvExp377);
+  else te::sm_affine_group<0>(w, 1u, o, te::kInvExpTe);
+  memcpy(out, o, sizes_of(curve).point_in);
+}
+
+int add_args(te_ctx* ctx, const void* a, const void* b, uint64_t n, int flags, const void* out) {
+  if (flags & ~(TE_MSM_ADD_SUBTRACT | TE_MSM_ADD_SHARED_B)) return set_err(ctx, TE_MSM_EINVAL, "te_msm_add*: unknown flag bits");
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n > 0 && (!a || !b || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  return 0;
+}
+// te_msm_add (x_only = false) and te_msm_add_x (true): host buffers, sliced over the devices; the result of a slice lands in its copy of a
+int add_host(te_ctx* ctx, const uint8_t* a, const uint8_t* b, bool x_only, uint64_t n, int flags, uint8_t* out) {
+  if (int rc = add_args(ctx, a, b, n, flags, out)) return rc;
+  if (n == 0) return 0;
+  const int curve = ctx->opt_curve;
+  const bool shared = (flags & TE_MSM_ADD_SHARED_B) != 0;
+  const size_t pb = sizes_of(curve).point_in, ib = x_only ? x_bytes_of(curve) : pb;
+  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
+  const uint64_t per = (n + D - 1) / D;
+  struct slice_t { dev_tmp a, b; pair_verdict v; };
+  std::vector<slice_t> sl(D);
+  auto stage = [&](size_t i) -> int {                             // upload, recover, check, add: everything but the copy out
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    gpu_t& d = ctx->devs[i];
+    slice_t& s = sl[i];
+    const uint64_t mb = shared ? 1 : m;
+    const uint8_t* bsrc = b + (shared ? 0 : lo * ib);
+    if (int rc = tmp_alloc(ctx, d, s.a, m * pb)) return rc;
+    if (int rc = tmp_alloc(ctx, d, s.b, mb * pb)) return rc;
+    if (x_only) {
+      int64_t bad = -1; int why = 0;
+      int rc = recover_on(ctx, i, a + lo * ib, true, m, s.a.p, nullptr, false, &bad, &why);
+      if (rc == TE_MSM_EPOINT) s.v.take(bad, why, 0, kBadX); else if (rc) return rc;
+      rc = recover_on(ctx, i, bsrc, true, mb, s.b.p, nullptr, false, &bad, &why);
+      if (rc == TE_MSM_EPOINT) s.v.take(bad, why, 1, kBadX); else if (rc) return rc;
+      if (s.v.bad >= 0) return 0;
+    } else {
+      HIP_TRY(ctx, hipMemcpy(s.a.p, a + lo * ib, m * pb, hipMemcpyHostToDevice));
+      HIP_TRY(ctx, hipMemcpy(s.b.p, bsrc, mb * pb, hipMemcpyHostToDevice));
+    }
+    if (int rc = check_pair_on(ctx, i, s.a.p, s.b.p, m, mb, s.v)) return rc;
+    if (s.v.bad >= 0) return 0;
+    return add_on(ctx, i, s.a.p, s.b.p, m, flags, s.a.p);
+  };
+  auto copy_out = [&](size_t i) -> int {
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
+    HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].a.p, m * pb, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
+  for (size_t i = 0; i < D; i++)                                  // slices in order: the first that reports holds the lowest index
+    if (sl[i].v.bad >= 0) return note_pair(ctx, sl[i].v, (int64_t)(per * i));
+  return te_sched::on_devices(*ctx, D, copy_out);
+}
+// te_msm_sum (x_only = false) and te_msm_sum_x (true): every device folds its slice to one partial; the first device adds the partials
+int sum_host(te_ctx* ctx, const uint8_t* src, bool x_only, uint64_t n, uint8_t* out) {
+  if (!out) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  if (int rc = check_n(ctx, n)) return rc;
+  const int curve = ctx->opt_curve;
+  if (n == 0) { write_identity(curve, out); return 0; }
+  if (!src) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  const size_t pb = sizes_of(curve).point_in, ib = x_only ? x_bytes_of(curve) : pb, tb = partial_bytes_of(curve);
+  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
+  const uint64_t per = (n + D - 1) / D;
+  struct slice_t { dev_tmp pts; pair_verdict v; bool have = false; };
+  std::vector<slice_t> sl(D);
+  std::vector<uint8_t> parts(D * tb);
+  auto stage = [&](size_t i) -> int {
+    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    if (m == 0) return 0;
+    gpu_t& d = ctx->devs[i];
+    slice_t& s = sl[i];
+    if (int rc = tmp_alloc(ctx, d, s.pts, m * pb)) return rc;
+    if (x_only) {
+      int64_t bad = -1; int why = 0;
+      const int rc = recover_on(ctx, i, src + lo * ib, true, m, s.pts.p, nullptr, false, &bad, &why);
+      if (rc == TE_MSM_EPOINT) { s.v.take(bad, why, 0, kBadX); return 0; }
+      if (rc) return rc;
+    } else {
+      HIP_TRY(ctx, hipMemcpy(s.pts.p, src + lo * ib, m * pb, hipMemcpyHostToDevice));
+    }
+    if (int rc = check_pair_on(ctx, i, s.pts.p, nullptr, m, 0, s.v)) return rc;
+    if (s.v.bad >= 0) return 0;
+    if (int rc = sum_fold_on(ctx, i, s.pts.p, m, false, &parts[i * tb])) return rc;
+    s.have = true;
+    return 0;
+  };
+  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
+  for (size_t i = 0; i < D; i++)
+    if (sl[i].v.bad >= 0) return note_pair(ctx, sl[i].v, (int64_t)(per * i));
+  if (D > 1) {                                                    // the D partial results are added on the first device
+    size_t have = 0;                                              // (D <= n: every slice holds points; counted all the same)
+    for (size_t i = 0; i < D; i++)
+      if (sl[i].have) { if (have != i) memcpy(&parts[have * tb], &parts[i * tb], tb); have++; }
+    dev_tmp all;
+    if (int rc = tmp_alloc(ctx, ctx->devs[0], all, have * tb)) return rc;
+    HIP_TRY(ctx, hipMemcpy(all.p, parts.data(), have * tb, hipMemcpyHostToDevice));
+    if (int rc = sum_fold_on(ctx, 0, all.p, have, true, parts.data())) return rc;
+  }
+  sum_finish(curve, parts.data(), out);
+  return 0;
+}
 }  // namespace
 
 void free_mul_base(te_ctx* ctx, te_base* b) {
@@ -438,7 +676,7 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
 // A failed check (kBadPoint) or recovery (kBadX, x-only points) as the outcome of a call: the failure is remembered for get_option
 // ("bad_point_index" / "bad_point_reason"), described in the error text and written to the caller's outputs where given.
 int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* first_bad, int* reason_out) {
-  ctx->bad_point_index = index; ctx->bad_point_reason = reason;
+  ctx->bad_point_index = index; ctx->bad_point_reason = reason; ctx->bad_point_operand = 0;      // (te_msm_add* name operand b afterwards: note_pair)
   if (first_bad) *first_bad = index;
   if (reason_out) *reason_out = reason;
   char buf[256];
@@ -616,6 +854,61 @@ int te_msm_mul_base_device(te_ctx* ctx, te_base* base, const void* d_scalars_le,
   const int owner = owner_of(ctx, "te_msm_mul_base_device: the scalars and the output must be resident on one device of the context", {d_scalars_le, d_out_points_xy_le});
   if (owner < 0) return owner;
   return mul_base_on(ctx, (size_t)owner, base, d_scalars_le, n, ctx->opt_scalars_montgomery != 0, d_out_points_xy_le, scalar_bytes_now(ctx));
+}
+
+int te_msm_add(te_ctx* ctx, const uint8_t* a_xy_le, const uint8_t* b_xy_le, uint64_t n, int flags, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  return add_host(ctx, a_xy_le, b_xy_le, false, n, flags, out_xy_le);
+}
+
+int te_msm_add_x(te_ctx* ctx, const uint8_t* ax_le, const uint8_t* bx_le, uint64_t n, int flags, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  return add_host(ctx, ax_le, bx_le, true, n, flags, out_xy_le);
+}
+
+int te_msm_add_device(te_ctx* ctx, const void* d_a, const void* d_b, uint64_t n, int flags, void* d_out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (int rc = add_args(ctx, d_a, d_b, n, flags, d_out)) return rc;
+  if (n == 0) return 0;
+  const int owner = owner_of(ctx, "te_msm_add_device: both operands and the output must be resident on one device of the context", {d_a, d_b, d_out});
+  if (owner < 0) return owner;
+  pair_verdict v;
+  if (int rc = check_pair_on(ctx, (size_t)owner, d_a, d_b, n, (flags & TE_MSM_ADD_SHARED_B) ? 1 : n, v)) return rc;
+  if (v.bad >= 0) return note_pair(ctx, v, 0);
+  return add_on(ctx, (size_t)owner, d_a, d_b, n, flags, d_out);
+}
+
+int te_msm_sum(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  return sum_host(ctx, points_xy_le, false, n, out_xy_le);
+}
+
+int te_msm_sum_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  return sum_host(ctx, x_le, true, n, out_xy_le);
+}
+
+int te_msm_sum_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, uint8_t* out_xy_le) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  if (!out_xy_le) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n == 0) { write_identity(ctx->opt_curve, out_xy_le); return 0; }
+  if (!d_points_xy_le) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  const int owner = owner_of(ctx, "te_msm_sum_device: the points must be resident on a device of the context", {d_points_xy_le});
+  if (owner < 0) return owner;
+  pair_verdict v;
+  if (int rc = check_pair_on(ctx, (size_t)owner, d_points_xy_le, nullptr, n, 0, v)) return rc;
+  if (v.bad >= 0) return note_pair(ctx, v, 0);
+  uint8_t part[4 * te::ga_sizes<1>::TW];
+  if (int rc = sum_fold_on(ctx, (size_t)owner, d_points_xy_le, n, false, part)) return rc;
+  sum_finish(ctx->opt_curve, part, out_xy_le);
+  return 0;
 }
 
 int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uint32_t window, uint32_t first, uint32_t count, void* dst, uint64_t cap,

@@ -441,6 +441,100 @@ napi_value MsmIndexed(napi_env env, napi_callback_info info) {
 napi_value ScalarMul(napi_env env, napi_callback_info info) { return MulCommon(env, info, false); }
 napi_value ScalarMulX(napi_env env, napi_callback_info info) { return MulCommon(env, info, true); }
 
+// groupAdd(a: Buffer, b: Buffer, opts?: {subtract?: boolean}): Buffer -- batched group addition (include/te_msm.h, te_msm_add): n x 64-byte
+// points a and n points b, or ONE 64-byte point b for all of them -> n x 64-byte points A_i + B_i (A_i - B_i with subtract; the identity as
+// (0, 1)).  groupAddX(ax, bx, opts) takes x-only points (pointsFromX's format): bulkAddGroups' counterpart (te_msm_add_x).
+// groupSum(points: Buffer): Buffer and groupSumX(xs: Buffer): Buffer -- 64 bytes x || y, the sum of the points (no points: (0, 1)):
+// reduceGroups' counterpart (te_msm_sum / te_msm_sum_x).  Twisted-Edwards curve only, like the rest of the addon; run like scalarMul.  A bad
+// point (setCheckPoints) or a bad x throws an Error naming the lowest failing index and the reason, also as .index / .reason / .operand
+// (0 = a or the sum's input, 1 = b).
+napi_value GroupThrow(napi_env env, int rc, const std::string& err, int64_t bad, int64_t reason, int64_t operand) {
+  const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+  napi_value msg, errv;
+  napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+  napi_create_error(env, nullptr, msg, &errv);
+  if (rc == TE_MSM_EPOINT) {
+    napi_value iv, rv, ov;
+    napi_create_int64(env, bad, &iv); napi_create_int32(env, (int32_t)reason, &rv); napi_create_int32(env, (int32_t)operand, &ov);
+    napi_set_named_property(env, errv, "index", iv); napi_set_named_property(env, errv, "reason", rv); napi_set_named_property(env, errv, "operand", ov);
+  }
+  napi_throw(env, errv);
+  return nullptr;
+}
+napi_value AddCommon(napi_env env, napi_callback_info info, bool x_only) {
+  const char* const sig = x_only ? "groupAddX(ax: Buffer, bx: Buffer, opts?: {subtract?: boolean})" : "groupAdd(a: Buffer, b: Buffer, opts?: {subtract?: boolean})";
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool b0 = false, b1 = false;
+  if (argc >= 2) { napi_is_buffer(env, argv[0], &b0); napi_is_buffer(env, argv[1], &b1); }
+  if (!b0 || !b1) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  bool subtract = false;
+  if (argc >= 3) {
+    napi_valuetype t = napi_undefined;
+    napi_typeof(env, argv[2], &t);
+    if (t == napi_object) {
+      napi_value v; bool has = false;
+      napi_has_named_property(env, argv[2], "subtract", &has);
+      if (has) { napi_get_named_property(env, argv[2], "subtract", &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &subtract); }
+    } else if (t != napi_undefined && t != napi_null) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  }
+  void *pa = nullptr, *pb = nullptr; size_t al = 0, bl = 0;
+  napi_get_buffer_info(env, argv[0], &pa, &al);
+  napi_get_buffer_info(env, argv[1], &pb, &bl);
+  const size_t in_bytes = x_only ? TE_MSM_X_BYTES : TE_MSM_POINT_BYTES;
+  const uint64_t n = al / in_bytes;
+  if (al % in_bytes != 0 || (bl != in_bytes && bl != n * in_bytes)) {
+    napi_throw_range_error(env, nullptr, x_only ? "groupAddX: ax must be 32*n bytes, bx 32 (shared) or 32*n bytes" : "groupAdd: a must be 64*n bytes, b 64 (shared) or 64*n bytes");
+    return nullptr;
+  }
+  const int flags = (subtract ? TE_MSM_ADD_SUBTRACT : 0) | (bl != n * in_bytes ? TE_MSM_ADD_SHARED_B : 0);
+  std::vector<uint8_t> out((size_t)n * TE_MSM_POINT_BYTES);
+  int64_t bad = -1, reason = 0, operand = -1;
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    const int r = x_only ? te_msm_add_x(c, static_cast<const uint8_t*>(pa), static_cast<const uint8_t*>(pb), n, flags, out.data())
+                         : te_msm_add(c, static_cast<const uint8_t*>(pa), static_cast<const uint8_t*>(pb), n, flags, out.data());
+    if (r == TE_MSM_EPOINT) {
+      (void)te_msm_get_option(c, "bad_point_index", &bad); (void)te_msm_get_option(c, "bad_point_reason", &reason); (void)te_msm_get_option(c, "bad_point_operand", &operand);
+    }
+    return r;
+  }, err);
+  if (rc) return GroupThrow(env, rc, err, bad, reason, operand);
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
+  return buf;
+}
+napi_value SumCommon(napi_env env, napi_callback_info info, bool x_only) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool b0 = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &b0);
+  if (!b0) { napi_throw_type_error(env, nullptr, x_only ? "groupSumX(xs: Buffer)" : "groupSum(points: Buffer)"); return nullptr; }
+  void* p = nullptr; size_t pl = 0;
+  napi_get_buffer_info(env, argv[0], &p, &pl);
+  const size_t in_bytes = x_only ? TE_MSM_X_BYTES : TE_MSM_POINT_BYTES;
+  if (pl % in_bytes != 0) { napi_throw_range_error(env, nullptr, x_only ? "groupSumX: xs must be 32*n bytes" : "groupSum: points must be 64*n bytes"); return nullptr; }
+  const uint64_t n = pl / in_bytes;
+  uint8_t out[TE_MSM_POINT_BYTES];
+  int64_t bad = -1, reason = 0, operand = -1;
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    const int r = x_only ? te_msm_sum_x(c, static_cast<const uint8_t*>(p), n, out) : te_msm_sum(c, static_cast<const uint8_t*>(p), n, out);
+    if (r == TE_MSM_EPOINT) {
+      (void)te_msm_get_option(c, "bad_point_index", &bad); (void)te_msm_get_option(c, "bad_point_reason", &reason); (void)te_msm_get_option(c, "bad_point_operand", &operand);
+    }
+    return r;
+  }, err);
+  if (rc) return GroupThrow(env, rc, err, bad, reason, operand);
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, sizeof out, out, &dst, &buf);
+  return buf;
+}
+napi_value GroupAdd(napi_env env, napi_callback_info info) { return AddCommon(env, info, false); }
+napi_value GroupAddX(napi_env env, napi_callback_info info) { return AddCommon(env, info, true); }
+napi_value GroupSum(napi_env env, napi_callback_info info) { return SumCommon(env, info, false); }
+napi_value GroupSumX(napi_env env, napi_callback_info info) { return SumCommon(env, info, true); }
+
 // setBase(point: Buffer) and scalarMulBase(scalars: Buffer): Buffer -- fixed-base batch scalar multiplication (include/te_msm.h,
 // te_msm_bind_base / te_msm_mul_base): one 64-byte point bound once, then n x 32-byte little-endian scalars -> n x 64-byte points
 // [k_i] P (the identity as (0, 1)).  Twisted-Edwards curve only, like the rest of the addon; run like scalarMul.  The addon keeps the
@@ -594,7 +688,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints}, {"setScalarsMontgomery", SetScalarsMontgomery},
       {"setScalarRecordBytes", SetScalarRecordBytes},
       {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed},
-      {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase}};
+      {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase},
+      {"groupAdd", GroupAdd}, {"groupAddX", GroupAddX}, {"groupSum", GroupSum}, {"groupSumX", GroupSumX}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -80,6 +80,14 @@ const scalarMulX = (xs, scalars) => native.scalarMulX(xs, scalars);
 // replicated, without the doublings.  setScalarsMontgomery applies to these scalars.
 const setBase = (point) => native.setBase(point);
 const scalarMulBase = (scalars) => native.scalarMulBase(scalars);
+// groupAdd(a, b, {subtract}) returns the n points A_i + B_i (A_i - B_i with subtract) as a 64n-byte Buffer, one 64-byte b shared by every
+// a; groupAddX(ax, bx, {subtract}) takes x-only points (bulkAddGroups' counterpart).  groupSum(points) / groupSumX(xs) return the one
+// point sum P_i as 64 bytes x || y (reduceGroups' counterpart; no points: (0, 1)).  A bad point (setCheckPoints) or a bad x throws an
+// Error with .index, .reason and .operand (0 = a or the sum's input, 1 = b).
+const groupAdd = (a, b, opts) => native.groupAdd(a, b, opts);
+const groupAddX = (ax, bx, opts) => native.groupAddX(ax, bx, opts);
+const groupSum = (points) => native.groupSum(points);
+const groupSumX = (xs) => native.groupSumX(xs);
 
 // Outside the reference's interface too: msmBatch(scalarBuffers) runs one MSM per Buffer over the set bound by setBases -- MSM m over
 // its first scalarBuffers[m].length / 32 points (a prover's commitments to polynomials of different degrees against one SRS) -- and
@@ -100,4 +108,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX };

@@ -38,6 +38,13 @@ export declare const scalarMulX: (xs: Buffer, scalars: Buffer) => Buffer;
 // returns [k_i] P for n 32-byte scalars as a 64n-byte points Buffer.  setScalarsMontgomery applies to these scalars.
 export declare const setBase: (point: Buffer) => void;
 export declare const scalarMulBase: (scalars: Buffer) => Buffer;
+// Not in the reference's interface: batched group addition and point-set sums on the device (its bulkAddGroups / reduceGroups run on the
+// CPU).  groupAdd returns the 64n-byte points A_i + B_i (A_i - B_i with subtract); one 64-byte b is shared by every a.  groupAddX /
+// groupSumX take x-only points.  groupSum returns 64 bytes x || y.  A bad point or x throws (error.index / error.reason / error.operand).
+export declare const groupAdd: (a: Buffer, b: Buffer, opts?: { subtract?: boolean }) => Buffer;
+export declare const groupAddX: (ax: Buffer, bx: Buffer, opts?: { subtract?: boolean }) => Buffer;
+export declare const groupSum: (points: Buffer) => Buffer;
+export declare const groupSumX: (xs: Buffer) => Buffer;
 // Not in the reference: batched MSMs over prefixes of the set bound by setBases; MSM m runs over the first scalarBuffers[m].length / 32
 // points.  Results in input order, in compute_msm's form; throws without setBases or for a buffer longer than the set.
 export declare const msmBatch: (scalarBuffers: Buffer[]) => { x: bigint; y: bigint }[];
