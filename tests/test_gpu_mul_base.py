@@ -7,6 +7,7 @@ device."""
 import ctypes
 import json
 import os
+import random
 import shutil
 import subprocess
 
@@ -24,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PB = {0: 64, 1: 96}
 SB = {0: 32, 1: 48}
 EINVAL, EPOINT = -1, -5
+PIECE = 1 << 18                     # a device multiplies in pieces of 2^18 scalars (points.hip, kMulPiece)
 
 
 def _dev(buf):
@@ -166,6 +168,30 @@ def test_equals_te_msm_mul_over_the_point_replicated(pkg, curve):
         got = c.mul_base(base, sc)
         assert got == c.mul(raw * n, sc)
         assert mul_device(c, base, sc, n, curve) == got
+
+
+def test_one_scalar_past_the_piece_boundary(pkg):
+    """te_msm_mul_base_device walks its scalars in pieces: the second turn of that loop, one scalar long"""
+    import torch
+    n = PIECE + 1
+    raw, p = base_of(0)
+    sc = np.random.default_rng(0x9BA5E).integers(0, 256, size=(n, 32), dtype=np.uint8).tobytes()
+    rnd = random.Random(0x9BA5E)
+    idx = sorted(set([0, PIECE - 2, PIECE - 1, PIECE] + rnd.sample(range(n), 40)))
+    with _ctx(pkg, 0) as c:
+        base = c.bind_base(raw)
+        assert base.window == mc.DEFAULT_W
+        got = mul_device(c, base, sc, n, 0)
+        assert len(got) == 64 * n
+        ks = [int.from_bytes(sc[32 * i:32 * i + 32], "little") for i in idx]
+        want = mc.te_expected(p, ks)
+        for j, i in enumerate(idx):
+            assert got[64 * i:64 * i + 64] == want[64 * j:64 * j + 64], i
+        dp, ds = _dev(raw * n), _dev(sc)
+        dout = torch.full((64 * n,), 0xAB, dtype=torch.uint8, device="cuda")
+        _sync()
+        c.mul_device(dp.data_ptr(), ds.data_ptr(), n, dout.data_ptr())
+        assert bytes(dout.cpu().numpy()) == got
 
 
 # ---- the table ---------------------------------------------------------------------------------------------------------------------

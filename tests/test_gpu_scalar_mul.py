@@ -23,6 +23,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOP = (1 << 256) - 1
 SIZES = {0: (64, 32, 32), 1: (96, 48, 48)}          # point, scalar record, x-only bytes
+PIECE = 1 << 18                     # a device multiplies in pieces of 2^18 points (points.hip, kMulPiece)
 
 
 def _dev(buf):
@@ -129,7 +130,7 @@ def test_large_n_sampled(pkg, curve, logn):
     pts, _ = pkg.synth_inputs(0xB16 + logn, n, scalars=False, curve=curve)
     sc = rand_scalars(logn, n, curve)
     rnd = random.Random(logn)
-    idx = sorted(set([0, 1, n // 2, n - 2, n - 1] + rnd.sample(range(n), 507)))
+    idx = sorted(set([0, 1, n // 2, n - 2, n - 1] + rnd.sample(range(n), 507) + ([PIECE - 1, PIECE, PIECE + 1, 2 * PIECE] if logn >= 20 else [])))
     with _ctx(pkg, curve) as c:
         got = c.mul(pts, sc)
         assert len(got) == pb * n

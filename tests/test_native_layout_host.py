@@ -64,7 +64,9 @@ def test_the_replay_restates_the_kernels_as_they_are():
     assert has(t, "prm.sc_stride = (uint32_t)p.sc_bytes / 16u", "(prm.nst + TE_DIG_BLOCK - 1u) / TE_DIG_BLOCK")
     for name in ("scalar_mul.hip.hpp", "mul_base.hip.hpp"):
         assert has(open(os.path.join(CSRC, name)).read(), "sc[(size_t)i * SQ + j]", "int SQ = (CURVE == 1 ? 3 : 2)")
-    assert has(open(os.path.join(CSRC, "points.hip")).read(), "te::k_scalar_mul<1, false, 2>", "(m + 255u) / 256u")
+    # (a 32-byte record reaches the kernels with SQ = 2 on both curves, BLS12-377's own 48-byte record with SQ = 3: with_scalar_quads)
+    assert has(open(os.path.join(CSRC, "points.hip")).read(), "te::k_scalar_mul<C, false, decltype(q)::value>", "te::k_mul_base<C, FORM, decltype(q)::value>",
+               "if (sb != 32) { f(std::integral_constant<int, 3>{}); return; }", "f(std::integral_constant<int, 2>{});", "(m + 255u) / 256u")
 
 
 def digit_reads(n, nst, stride, first=0):

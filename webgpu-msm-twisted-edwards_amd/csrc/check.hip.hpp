@@ -32,6 +32,8 @@ constexpr naf_t kNafTeOrder = {{0x04400200u, 0x020000a0u, 0x04409000u, 0x5294240
 // r = 8444461749428370424248824938781546531375899335154063827935233455917409239041 (253 bits, 88 ones; 69 non-zero digits)
 constexpr naf_t kNaf377Order = {{0x00000001u, 0x0a120000u, 0x10000001u, 0x022a8000u, 0x80400002u, 0x81045120u, 0xa240a800u, 0x14000800u},
                                 {0x00000000u, 0x00008000u, 0x40000000u, 0xa8800901u, 0x24085000u, 0x20500402u, 0x081402aau, 0x0154a2a2u}, 252};
+// ... by the kernels' CURVE parameter (0 Twisted-Edwards BLS12, 1 BLS12-377 G1): what a launch passes beside k_*<CURVE>
+template <int CURVE> constexpr const naf_t& order_naf_of() { return CURVE == 1 ? kNaf377Order : kNafTeOrder; }
 
 // word w of a, w uniform: a chain of selects instead of a dynamically indexed array (which would live in scratch memory)
 TE_HD uint32_t naf_word(const uint32_t (&a)[8], int w) {

@@ -1,13 +1,14 @@
 // engine.hpp -- what the translation units of libtemsm.so share: the context and its work sets, the plan, the requests a launch
 // sequence is asked with, and the functions that more than one unit calls.  No kernel header in here: te_msm.hip alone includes
-// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication kernels (a non-template __global__
-// function may be defined once per library, and every inclusion repeats the device compile).
+// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication / fixed-base / group-addition kernels
+// (a non-template __global__ function may be defined once per library, and every inclusion repeats the device compile).
 //
 // The units:   te_msm.hip   the engine core: plan and buffers, the launch sequences, streams and queue probe, record slabs, uploads
 //              run.hip      te_msm_init / destroy, the lone calls te_msm_run[_device], how a call's status is settled
 //              tickets.hip  te_msm_submit* / ticket_wait / collect
 //              bases.hip    bound point sets: bind, scalars-only, indexed and batched MSMs
-//              points.hip   point checks, x-only points, batch scalar multiplication (per point, and over one bound point)
+//              points.hip   point checks, x-only points, batch scalar multiplication (per point, and over one bound point with its
+//                           fixed-base table), batched group addition and point-set sums
 //              abi.hip      the rest of the C-ABI: options, trim, building blocks, host tails, debug reads
 // Everything in here has hidden visibility; a function only one unit calls is file-local there.  The library exports the C-ABI of
 // include/te_msm.h and nothing else of the engine.

@@ -42,6 +42,8 @@ constexpr exp_t kRootExpTe = {{0x00010a11u, 0x76fed000u, 0xb00159aau, 0x4d1e5c37
 // (t - 1) / 2 with q - 1 = 2^46 t (330 bits)
 constexpr exp_t kRootExp377 = {{0x00010a11u, 0xba886000u, 0x90002e16u, 0xc45f7412u, 0x271e3de6u, 0xb3e601eau, 0x92763445u, 0x0b80d942u,
                                 0x21d58c76u, 0x748c2f8au, 0x0000035cu, 0u}, 329};
+// ... by the kernels' CURVE parameter
+template <int CURVE> constexpr const exp_t& root_exp_of() { return CURVE == 1 ? kRootExp377 : kRootExpTe; }
 TE_HD bool exp_bit(const exp_t& e, int i) {
   uint32_t r = 0;
   const int w = i >> 5;

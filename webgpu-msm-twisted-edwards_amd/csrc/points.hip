@@ -14,6 +14,26 @@ using namespace te_eng;
 namespace te_eng {
 
 namespace {
+// A kernel's template parameters from run-time values, as te_msm.hip's with_scalar_form: f(std::integral_constant<int, CURVE>{}) with the
+// kernels' CURVE (0 Twisted-Edwards BLS12, 1 BLS12-377 G1) of a TE_MSM_CURVE_* value, f(std::true_type / std::false_type{}) of a flag.
+// The per-curve constant of a launch comes by the same parameter: order_naf_of / root_exp_of / inv_exp_of<CURVE>().
+template <typename F> void with_curve(int curve, F&& f) {
+  if (curve == TE_MSM_CURVE_BLS12_377_G1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
+}
+template <typename F> void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+// ... and the 16-byte words of one scalar record (k_scalar_mul's and k_mul_base's SQ) of its bytes: 2, or 3 for BLS12-377's own 48-byte
+// record.  The Twisted-Edwards curve has 32-byte records only: its kernels exist for SQ = 2 alone
+template <int CURVE, typename F> void with_scalar_quads(size_t sb, F&& f) {
+  if constexpr (CURVE == 1) {
+    if (sb != 32) { f(std::integral_constant<int, 3>{}); return; }
+  }
+  f(std::integral_constant<int, 2>{});
+}
+
 // ---- input-point validation (option "check_points", te_msm_check_points*; kernels in check.hip.hpp) ----------------------------
 // Runs on device devs[di] in front of whatever the call does with the points, and waits for its verdict: a point that fails must
 // stop the call before an MSM result exists.  Device-resident points are checked where they lie (one launch per check); host points
@@ -22,8 +42,9 @@ namespace {
 // so the first piece that reports holds the lowest index of the whole buffer.
 constexpr uint64_t kCheckPiece = 1ull << 18;
 
-// The check lane of a device (its stream, report word and pinned host word: check_points_on, recover_on, mul_on), held while this
-// lives: chk_mu locked, the device made current, the three created on first use.  rc: 0, or the HIP error (noted) that left it unusable.
+// The check lane of a device (its stream, report word and pinned host word: check_points_on, recover_on, in_pieces, ...), held while
+// this lives: chk_mu locked, the device made current, the three created on first use.  chk_mu is a plain mutex: whoever holds a lane
+// calls nothing that takes one.  rc: 0, or the HIP error (noted) that left it unusable.
 struct check_lane {
   gpu_t& d;
   std::lock_guard<std::mutex> lk;
@@ -38,6 +59,16 @@ struct check_lane {
     te::check_decode(*d.chk_host, m, bad, reason);
     return TE_MSM_EPOINT;
   }
+  // one check over m points, whatever the kernels (check_points_on's, group_check_on's): the word cleared, form(grid, block) launched,
+  // subgroup(grid, block) behind it when level >= 2, and the verdict waited for
+  template <typename Form, typename Subgroup> int check(te_ctx* ctx, uint32_t m, int level, int64_t* bad, int* reason, Form&& form, Subgroup&& subgroup) {
+    HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), d.chk_stream));
+    const dim3 grid((m + 255u) / 256u), block(256);
+    form(grid, block);
+    if (level >= 2) subgroup(grid, block);
+    HIP_TRY(ctx, hipGetLastError());
+    return verdict(ctx, m, bad, reason);
+  }
  private:
   static int open(te_ctx* ctx, gpu_t& d) {
     HIP_TRY(ctx, hipSetDevice(d.device));
@@ -47,6 +78,23 @@ struct check_lane {
     return 0;
   }
 };
+
+// check_points_on's check of one piece: m points at `at` (device memory), packed or -- lay.stride -- records at a stride
+template <int CURVE, bool MONT> int check_piece(te_ctx* ctx, check_lane& lane, const uint8_t* at, uint32_t m, int level, point_layout lay, int64_t* bad, int* reason) {
+  hipStream_t st = lane.stream();
+  unsigned long long* word = lane.d.chk_word;
+  if (lay.stride) {
+    const uint64_t* p8 = reinterpret_cast<const uint64_t*>(at);
+    const uint32_t sd = lay.stride, fl = lay.flag ? 1u : 0u;
+    return lane.check(ctx, m, level, bad, reason,
+                      [&](dim3 grid, dim3 block) { hipLaunchKernelGGL((te::k_check_form_strided<CURVE, MONT>), grid, block, 0, st, p8, sd, fl, m, word); },
+                      [&](dim3 grid, dim3 block) { hipLaunchKernelGGL((te::k_check_subgroup_strided<CURVE, MONT>), grid, block, 0, st, p8, sd, fl, m, word, te::order_naf_of<CURVE>()); });
+  }
+  const uint4* p4 = reinterpret_cast<const uint4*>(at);
+  return lane.check(ctx, m, level, bad, reason,
+                    [&](dim3 grid, dim3 block) { hipLaunchKernelGGL((te::k_check_form<CURVE, MONT>), grid, block, 0, st, p4, m, word); },
+                    [&](dim3 grid, dim3 block) { hipLaunchKernelGGL((te::k_check_subgroup<CURVE, MONT>), grid, block, 0, st, p4, m, word, te::order_naf_of<CURVE>()); });
+}
 
 // te_msm_run_x and te_msm_mul* read canonical scalars only: with option "scalars_montgomery" set they are refused (a silent canonical
 // reading would be a wrong answer)
@@ -102,8 +150,10 @@ int recover_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64
     const uint4* x4 = reinterpret_cast<const uint4*>(at);
     uint4* o4 = reinterpret_cast<uint4*>(static_cast<uint8_t*>(d_pts) + off * pb);
     const dim3 grid((m + 255u) / 256u), block(256);
-    if (curve == TE_MSM_CURVE_BLS12_377_G1) hipLaunchKernelGGL(te::k_points_from_x<1>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::kRootExp377, te::kNaf377Order);
-    else hipLaunchKernelGGL(te::k_points_from_x<0>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::kRootExpTe, te::kNafTeOrder);
+    with_curve(curve, [&](auto c) {
+      constexpr int C = decltype(c)::value;
+      hipLaunchKernelGGL(te::k_points_from_x<C>, grid, block, 0, st, x4, m, o4, d.chk_word, n, off, te::root_exp_of<C>(), te::order_naf_of<C>());
+    });
     HIP_TRY(ctx, hipGetLastError());
   }
   if (int rc = lane.verdict(ctx, n, bad, reason)) return rc;
@@ -144,11 +194,11 @@ int points_from_x_common(te_ctx* ctx, const void* x, bool on_host, uint64_t n, v
 }
 
 // ---- batch scalar multiplication (te_msm_mul[_device], te_msm_mul_x; kernels in scalar_mul.hip.hpp) ------------------------------
-// Host buffers: contiguous slices over the context's devices, one host thread per device (on_devices), as te_msm_run's point slices.
-// Every slice is staged whole on its device -- points (or x), scalars and results -- checked (recovery, option "check_points"),
-// multiplied, and copied out only when no slice reported a bad point: on a failure `out` is untouched.  The chain writes projective
-// results of a piece of kMulPiece points into a buffer of the call's own; the affine pass turns them into the wire format.  Every
-// temporary is freed before the call returns (dev_tmp).
+// Host buffers: contiguous slices over the context's devices, as te_msm_run's point slices (slice_plan, below).  Every slice is staged
+// whole on its device -- points (or x), scalars and results -- checked (recovery, option "check_points"), multiplied, and copied out only
+// when no slice reported a bad point: on a failure `out` is untouched.  The chain writes projective results of a piece of kMulPiece
+// points into a buffer of the call's own; the affine pass turns them into the wire format (in_pieces).  Every temporary is freed before
+// the call returns (dev_tmp).
 constexpr uint64_t kMulPiece = 1ull << 18;
 // te_msm_mul* as te_msm_run_x: canonical scalars only -- refused under the option instead of a silent canonical reading
 int mul_refused(te_ctx* ctx) { return ctx->opt_scalars_montgomery ? set_err(ctx, TE_MSM_EINVAL, kNoMontgomeryScalars) : 0; }
@@ -158,42 +208,51 @@ inline te::naf_t shared_naf_of(const uint8_t* k32, int curve) {
   memcpy(k, k32, 32);
   return te::sm_shared_naf(k, curve);
 }
-// n points and scalars (memory of devs[di]) -> n affine results at d_out (memory of devs[di]); returns when they are there.
-// sb: bytes of one scalar record -- the call's (scalar_bytes_now), or the curve's own for the records te_msm_bind_base makes itself
-int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t n, bool shared, const te::naf_t& kn, void* d_out, size_t sb) {
+inline size_t proj_bytes_of(int curve) { return 4u * (curve == TE_MSM_CURVE_BLS12_377_G1 ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW); }
+// The piece loop of te_msm_mul*, te_msm_mul_base* and te_msm_add*: n results at d_out (memory of devs[di]) in pieces of at most
+// piece_max, on the device's check lane -- taken here: no caller holds it.  chain(off, m, proj, stream) enqueues the kernel that writes
+// the m projective results of the piece at off into proj, a buffer of the call's own; the affine pass (k_scalar_mul_affine, chains of
+// eight) behind it turns them into the wire format at d_out + off.  One synchronise at the end: returns when the results are there.
+template <typename Chain> int in_pieces(te_ctx* ctx, size_t di, uint64_t n, uint64_t piece_max, void* d_out, Chain&& chain) {
   if (n == 0) return 0;
   gpu_t& d = ctx->devs[di];
   const int curve = ctx->opt_curve;
-  const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1;
   const size_t pb = sizes_of(curve).point_in;
-  const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
   check_lane lane(ctx, d);
   if (lane.rc) return lane.rc;
-  const uint64_t piece = std::min(n, kMulPiece);
+  const uint64_t piece = std::min(n, piece_max);
   dev_tmp proj;
-  if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
+  if (int rc = tmp_alloc(ctx, d, proj, piece * proj_bytes_of(curve))) return rc;
   hipStream_t st = lane.stream();
   for (uint64_t off = 0; off < n; off += piece) {
     const uint32_t m = (uint32_t)std::min(piece, n - off);
-    const uint4* p4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_pts) + off * pb);
-    const uint4* s4 = shared ? nullptr : reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_sc) + off * sb);
-    uint4* j4 = static_cast<uint4*>(proj.p);
     uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
-    const dim3 grid((m + 255u) / 256u), block(256), agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP));
-    if (bls) {
-      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<1, true>), grid, block, 0, st, p4, s4, m, j4, kn);     // (reads no record: the NAF)
-      else if (sb == 32) hipLaunchKernelGGL((te::k_scalar_mul<1, false, 2>), grid, block, 0, st, p4, s4, m, j4, kn);
-      else hipLaunchKernelGGL((te::k_scalar_mul<1, false>), grid, block, 0, st, p4, s4, m, j4, kn);
-      hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExp377);
-    } else {
-      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<0, true>), grid, block, 0, st, p4, s4, m, j4, kn);
-      else hipLaunchKernelGGL((te::k_scalar_mul<0, false>), grid, block, 0, st, p4, s4, m, j4, kn);
-      hipLaunchKernelGGL(te::k_scalar_mul_affine<0>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExpTe);
-    }
+    const dim3 agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP)), block(256);
+    chain(off, m, static_cast<uint4*>(proj.p), st);
+    with_curve(curve, [&](auto c) {
+      constexpr int C = decltype(c)::value;
+      hipLaunchKernelGGL(te::k_scalar_mul_affine<C>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::inv_exp_of<C>());
+    });
     HIP_TRY(ctx, hipGetLastError());
   }
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return 0;
+}
+// n points and scalars (memory of devs[di]) -> n affine results at d_out (memory of devs[di]); returns when they are there.
+// sb: bytes of one scalar record -- the call's (scalar_bytes_now), or the curve's own for the records te_msm_bind_base makes itself
+int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t n, bool shared, const te::naf_t& kn, void* d_out, size_t sb) {
+  const int curve = ctx->opt_curve;
+  const size_t pb = sizes_of(curve).point_in;
+  return in_pieces(ctx, di, n, kMulPiece, d_out, [&](uint64_t off, uint32_t m, uint4* j4, hipStream_t st) {
+    const uint4* p4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_pts) + off * pb);
+    const uint4* s4 = shared ? nullptr : reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_sc) + off * sb);
+    const dim3 grid((m + 255u) / 256u), block(256);
+    with_curve(curve, [&](auto c) {
+      constexpr int C = decltype(c)::value;
+      if (shared) hipLaunchKernelGGL((te::k_scalar_mul<C, true>), grid, block, 0, st, p4, s4, m, j4, kn);     // (reads no record: the NAF)
+      else with_scalar_quads<C>(sb, [&](auto q) { hipLaunchKernelGGL((te::k_scalar_mul<C, false, decltype(q)::value>), grid, block, 0, st, p4, s4, m, j4, kn); });
+    });
+  });
 }
 int mul_args(te_ctx* ctx, const void* pts, const void* sc, uint64_t n, const void* out) {
   if (int rc = check_n(ctx, n)) return rc;
@@ -201,6 +260,63 @@ int mul_args(te_ctx* ctx, const void* pts, const void* sc, uint64_t n, const voi
   if (n > 0 && (!pts || !sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   return 0;
 }
+
+// ---- what the host forms of te_msm_mul*, te_msm_mul_base*, te_msm_add* and te_msm_sum* share ----------------------------------------
+// Contiguous slices over the context's devices, one host thread per device (on_devices).  Every slice is staged whole on its device,
+// worked on there, and copied out only when no slice reported a bad point: stage, then scan, then copy out.
+
+// the slices of n > 0 items: D = min(devices, n) of them, slice i holds count(i) items from lo(i) on (the last ones may hold none)
+struct slice_plan {
+  uint64_t n; size_t D; uint64_t per;
+  slice_plan(const te_ctx* ctx, uint64_t n_) : n(n_), D((size_t)std::min<uint64_t>(ctx->devs.size(), n_)), per((n_ + D - 1) / D) {}
+  uint64_t lo(size_t i) const { return std::min<uint64_t>(n, per * i); }
+  uint64_t count(size_t i) const { return std::min<uint64_t>(n, lo(i) + per) - lo(i); }
+};
+// every slice's result (count(i) points of pb bytes at res(i), memory of devs[i]) -> out + lo(i) * pb
+template <typename Where> int copy_slices_out(te_ctx* ctx, const slice_plan& sp, size_t pb, uint8_t* out, Where&& res) {
+  return te_sched::on_devices(*ctx, sp.D, [&](size_t i) -> int {
+    if (sp.count(i) == 0) return 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
+    HIP_TRY(ctx, hipMemcpy(out + sp.lo(i) * pb, res(i), sp.count(i) * pb, hipMemcpyDeviceToHost));
+    return 0;
+  });
+}
+// the verdict over the operands of a call (te_msm_add*: a = 0, b = 1; every other call: 0): the lowest failing index, a before b at
+// equal index
+struct pair_verdict {
+  int64_t bad = -1; int why = 0, operand = 0; bad_kind kind = kBadPoint;
+  void take(int64_t i, int reason, int op, bad_kind k) {
+    if (i < 0 || (bad >= 0 && (bad < i || (bad == i && operand <= op)))) return;
+    bad = i; why = reason; operand = op; kind = k;
+  }
+};
+int note_pair(te_ctx* ctx, const pair_verdict& v, int64_t base) {
+  const int rc = note_bad(ctx, v.kind, base + v.bad, v.why);
+  ctx->bad_point_operand = v.operand;
+  return rc;
+}
+// slices (each with a pair_verdict v) in order: the first that reports holds the lowest index of the call.  0: none reported
+template <typename Slice> int note_slices(te_ctx* ctx, const slice_plan& sp, const std::vector<Slice>& sl) {
+  for (size_t i = 0; i < sp.D; i++)
+    if (sl[i].v.bad >= 0) return note_pair(ctx, sl[i].v, (int64_t)sp.lo(i));
+  return 0;
+}
+// operand op of a slice onto devs[di]: m points in t (allocated here) of m host points at src (a copy), or -- x_only -- of m host
+// x-coordinates (recovery; an x without a point goes to v as kBadX and the call goes on: 0)
+int stage_operand(te_ctx* ctx, size_t di, const uint8_t* src, bool x_only, uint64_t m, dev_tmp& t, int op, pair_verdict& v) {
+  const size_t pb = sizes_of(ctx->opt_curve).point_in;
+  if (int rc = tmp_alloc(ctx, ctx->devs[di], t, m * pb)) return rc;
+  if (!x_only) {
+    HIP_TRY(ctx, hipMemcpy(t.p, src, m * pb, hipMemcpyHostToDevice));
+    return 0;
+  }
+  int64_t bad = -1; int why = 0;
+  const int rc = recover_on(ctx, di, src, true, m, t.p, nullptr, false, &bad, &why);
+  if (rc != TE_MSM_EPOINT) return rc;
+  v.take(bad, why, op, kBadX);
+  return 0;
+}
+
 // te_msm_mul (x_only = false) and te_msm_mul_x (true): host buffers, sliced over the devices
 int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalars_le, uint64_t n, bool shared, uint8_t* out) {
   if (int rc = mul_args(ctx, src, scalars_le, n, out)) return rc;
@@ -208,55 +324,38 @@ int mul_host(te_ctx* ctx, const uint8_t* src, bool x_only, const uint8_t* scalar
   const int curve = ctx->opt_curve, level = ctx->opt_check_points;
   const size_t pb = sizes_of(curve).point_in, sb = scalar_bytes_now(ctx), ib = x_only ? x_bytes_of(curve) : pb;
   const te::naf_t kn = shared ? shared_naf_of(scalars_le, curve) : te::naf_t{};
-  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
-  const uint64_t per = (n + D - 1) / D;
-  struct slice_t { dev_tmp pts, sc, res; int64_t bad = -1; int why = 0; bool from_x = false; };
-  std::vector<slice_t> sl(D);
+  const slice_plan sp(ctx, n);
+  struct slice_t { dev_tmp pts, sc, res; pair_verdict v; };
+  std::vector<slice_t> sl(sp.D);
   auto stage = [&](size_t i) -> int {                             // upload, recover, check, multiply: everything but the copy out
-    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    const uint64_t lo = sp.lo(i), m = sp.count(i);
     if (m == 0) return 0;
     gpu_t& d = ctx->devs[i];
     slice_t& s = sl[i];
-    if (int rc = tmp_alloc(ctx, d, s.pts, m * pb)) return rc;
     if (int rc = tmp_alloc(ctx, d, s.res, m * pb)) return rc;
     if (!shared) {
       if (int rc = tmp_alloc(ctx, d, s.sc, m * sb)) return rc;
       HIP_TRY(ctx, hipMemcpy(s.sc.p, scalars_le + lo * sb, m * sb, hipMemcpyHostToDevice));
     }
-    if (x_only) {
-      const int rc = recover_on(ctx, i, src + lo * ib, true, m, s.pts.p, nullptr, false, &s.bad, &s.why);
-      if (rc == TE_MSM_EPOINT) { s.from_x = true; return 0; }
-      if (rc) return rc;
-    } else {
-      HIP_TRY(ctx, hipMemcpy(s.pts.p, src + lo * ib, m * pb, hipMemcpyHostToDevice));
-    }
+    if (int rc = stage_operand(ctx, i, src + lo * ib, x_only, m, s.pts, 0, s.v)) return rc;
+    if (s.v.bad >= 0) return 0;                                   // (a bad x is reported before a failed check of a recovered point)
     if (level) {
-      const int rc = check_points_on(ctx, i, s.pts.p, false, m, curve, level, &s.bad, &s.why);
-      if (rc == TE_MSM_EPOINT) return 0;
+      int64_t bad = -1; int why = 0;
+      const int rc = check_points_on(ctx, i, s.pts.p, false, m, curve, level, &bad, &why);
+      if (rc == TE_MSM_EPOINT) { s.v.take(bad, why, 0, kBadPoint); return 0; }
       if (rc) return rc;
     }
     return mul_on(ctx, i, s.pts.p, s.sc.p, m, shared, kn, s.res.p, sb);
   };
-  auto copy_out = [&](size_t i) -> int {
-    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
-    if (m == 0) return 0;
-    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
-    HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].res.p, m * pb, hipMemcpyDeviceToHost));
-    return 0;
-  };
-  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
-  for (size_t i = 0; i < D; i++) {                                // slices in order: the first that reports holds the lowest index
-    if (sl[i].bad < 0) continue;
-    return note_bad(ctx, sl[i].from_x ? kBadX : kBadPoint, (int64_t)(per * i) + sl[i].bad, sl[i].why);
-  }
-  return te_sched::on_devices(*ctx, D, copy_out);
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  if (int rc = note_slices(ctx, sp, sl)) return rc;
+  return copy_slices_out(ctx, sp, pb, out, [&](size_t i) { return sl[i].res.p; });
 }
 
 // ---- fixed-base batch scalar multiplication (te_msm_bind_base, te_msm_mul_base[_device]; kernels in mul_base.hip.hpp) ---------------
 // The bind makes the table's scalars j 2^(W i) mod (4 L | r) on the host and runs te_msm_mul's own chain (mul_on) over the point
-// replicated, on every device; k_mul_base_entries turns the affine results into entries.  A call is mul_on's shape with k_mul_base in the
-// chain's place: pieces of kMulPiece scalars into a projective buffer of the call's own, then the affine pass.  The table is the only
-// memory that outlives a call.
+// replicated, on every device; k_mul_base_entries turns the affine results into entries.  A call is mul_on's piece loop (in_pieces) with
+// k_mul_base as the chain: pieces of kMulPiece scalars.  The table is the only memory that outlives a call.
 const char* const kBadBase = "not a bound point of this context (released, or bound to another context)";
 const char* const kBaseCurve = "the point was bound under another curve than the one selected now (option \"curve\")";
 int check_base(te_ctx* ctx, const te_base* b) {
@@ -267,7 +366,6 @@ int check_base(te_ctx* ctx, const te_base* b) {
 // the table of b on device devs[i]: pts / sc hold the point replicated and the scalar records of its entries (host memory)
 int base_table_on(te_ctx* ctx, te_base* b, size_t i, const uint8_t* pts, const uint8_t* sc, const te::mb_geom& g) {
   gpu_t& d = ctx->devs[i];
-  const bool bls = b->curve == TE_MSM_CURVE_BLS12_377_G1;
   const size_t pb = sizes_of(b->curve).point_in, sb = sizes_of(b->curve).scalar_in;
   HIP_TRY(ctx, hipSetDevice(d.device));
   HIP_TRY(ctx, hipMalloc((void**)&b->tab[i], b->bytes()));                 // (freed by the caller on failure: free_mul_base)
@@ -278,53 +376,30 @@ int base_table_on(te_ctx* ctx, te_base* b, size_t i, const uint8_t* pts, const u
   HIP_TRY(ctx, hipMemcpy(d_pts.p, pts, g.entries * pb, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipMemcpy(d_sc.p, sc, g.entries * sb, hipMemcpyHostToDevice));
   if (int rc = mul_on(ctx, i, d_pts.p, d_sc.p, g.entries, false, te::naf_t{}, d_aff.p, sb)) return rc;
-  check_lane lane(ctx, d);
+  check_lane lane(ctx, d);                                                  // (only now: mul_on takes the lane itself)
   if (lane.rc) return lane.rc;
   const dim3 grid((g.entries + 255u) / 256u), block(256);
   const uint4* a4 = static_cast<const uint4*>(d_aff.p);
   uint4* t4 = reinterpret_cast<uint4*>(b->tab[i]);
-  if (bls) hipLaunchKernelGGL(te::k_mul_base_entries<1>, grid, block, 0, lane.stream(), a4, g.entries, t4);
-  else hipLaunchKernelGGL(te::k_mul_base_entries<0>, grid, block, 0, lane.stream(), a4, g.entries, t4);
+  with_curve(b->curve, [&](auto c) { hipLaunchKernelGGL(te::k_mul_base_entries<decltype(c)::value>, grid, block, 0, lane.stream(), a4, g.entries, t4); });
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(lane.stream()));
   return 0;
 }
 // n scalar records of sb bytes (memory of devs[di]; mont: Montgomery residues) -> n affine results at d_out (memory of devs[di]); returns when they are there
 int mul_base_on(te_ctx* ctx, size_t di, const te_base* b, const void* d_sc, uint64_t n, bool mont, void* d_out, size_t sb) {
-  if (n == 0) return 0;
-  gpu_t& d = ctx->devs[di];
-  const bool bls = b->curve == TE_MSM_CURVE_BLS12_377_G1;
-  const size_t pb = sizes_of(b->curve).point_in;
-  const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
   const te::mb_geom g = te::mb_geometry(b->W);
-  check_lane lane(ctx, d);
-  if (lane.rc) return lane.rc;
-  const uint64_t piece = std::min(n, kMulPiece);
-  dev_tmp proj;
-  if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
-  hipStream_t st = lane.stream();
   const uint4* t4 = reinterpret_cast<const uint4*>(b->tab[di]);
-  for (uint64_t off = 0; off < n; off += piece) {
-    const uint32_t m = (uint32_t)std::min(piece, n - off);
+  return in_pieces(ctx, di, n, kMulPiece, d_out, [&](uint64_t off, uint32_t m, uint4* j4, hipStream_t st) {
     const uint4* s4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_sc) + off * sb);
-    uint4* j4 = static_cast<uint4*>(proj.p);
-    uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
-    const dim3 grid((m + 255u) / 256u), block(256), agrid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP));
-    if (bls) {
-      if (sb == 32 && mont) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_377, 2>), grid, block, 0, st, t4, s4, m, j4, g);
-      else if (sb == 32) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_CANONICAL, 2>), grid, block, 0, st, t4, s4, m, j4, g);
-      else if (mont) hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_377>), grid, block, 0, st, t4, s4, m, j4, g);
-      else hipLaunchKernelGGL((te::k_mul_base<1, te::SCALAR_FORM_CANONICAL>), grid, block, 0, st, t4, s4, m, j4, g);
-      hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExp377);
-    } else {
-      if (mont) hipLaunchKernelGGL((te::k_mul_base<0, te::SCALAR_FORM_TE>), grid, block, 0, st, t4, s4, m, j4, g);
-      else hipLaunchKernelGGL((te::k_mul_base<0, te::SCALAR_FORM_CANONICAL>), grid, block, 0, st, t4, s4, m, j4, g);
-      hipLaunchKernelGGL(te::k_scalar_mul_affine<0>, agrid, block, 0, st, static_cast<const uint32_t*>(proj.p), m, o32, te::kInvExpTe);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return 0;
+    const dim3 grid((m + 255u) / 256u), block(256);
+    with_curve(b->curve, [&](auto c) {
+      with_flag(mont, [&](auto mt) {                                // the records' form: canonical, or the Montgomery residues of the curve's scalar field
+        constexpr int C = decltype(c)::value, FORM = !decltype(mt)::value ? te::SCALAR_FORM_CANONICAL : C == 1 ? te::SCALAR_FORM_377 : te::SCALAR_FORM_TE;
+        with_scalar_quads<C>(sb, [&](auto q) { hipLaunchKernelGGL((te::k_mul_base<C, FORM, decltype(q)::value>), grid, block, 0, st, t4, s4, m, j4, g); });
+      });
+    });
+  });
 }
 // what every te_msm_mul_base* call checks first; *go = false: nothing to do (n = 0)
 int mul_base_args(te_ctx* ctx, const te_base* b, const void* sc, uint64_t n, const void* out, bool* go) {
@@ -340,46 +415,31 @@ int mul_base_args(te_ctx* ctx, const te_base* b, const void* sc, uint64_t n, con
 int mul_base_host(te_ctx* ctx, const te_base* b, const uint8_t* scalars_le, uint64_t n, uint8_t* out) {
   const bool mont = ctx->opt_scalars_montgomery != 0;
   const size_t pb = sizes_of(b->curve).point_in, sb = scalar_bytes_now(ctx);
-  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
-  const uint64_t per = (n + D - 1) / D;
+  const slice_plan sp(ctx, n);
   struct slice_t { dev_tmp sc, res; };
-  std::vector<slice_t> sl(D);
+  std::vector<slice_t> sl(sp.D);
   auto stage = [&](size_t i) -> int {                             // upload and multiply: everything but the copy out
-    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    const uint64_t m = sp.count(i);
     if (m == 0) return 0;
     gpu_t& d = ctx->devs[i];
     if (int rc = tmp_alloc(ctx, d, sl[i].sc, m * sb)) return rc;
     if (int rc = tmp_alloc(ctx, d, sl[i].res, m * pb)) return rc;
-    HIP_TRY(ctx, hipMemcpy(sl[i].sc.p, scalars_le + lo * sb, m * sb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(sl[i].sc.p, scalars_le + sp.lo(i) * sb, m * sb, hipMemcpyHostToDevice));
     return mul_base_on(ctx, i, b, sl[i].sc.p, m, mont, sl[i].res.p, sb);
   };
-  auto copy_out = [&](size_t i) -> int {
-    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
-    if (m == 0) return 0;
-    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
-    HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].res.p, m * pb, hipMemcpyDeviceToHost));
-    return 0;
-  };
-  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
-  return te_sched::on_devices(*ctx, D, copy_out);
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  return copy_slices_out(ctx, sp, pb, out, [&](size_t i) { return sl[i].res.p; });
 }
 
 // ---- batched group addition and point-set sums (te_msm_add*, te_msm_sum*; kernels in group_add.hip.hpp) ------------------------------
-// An addition is mul_on's shape with k_group_add in the chain's place: pieces of kAddPiece pairs into a projective buffer of the call's
-// own, then te_msm_mul's affine pass (k_scalar_mul_affine, unchanged) -- the whole call in one piece up to 2^21 pairs: an addition is
+// An addition is mul_on's piece loop (in_pieces) with k_group_add as the chain, in pieces of kAddPiece pairs, te_msm_mul's affine pass
+// (k_scalar_mul_affine, unchanged) behind each -- the whole call in one piece up to 2^21 pairs: an addition is
 // two launches of a few hundred microseconds, and pieces of kMulPiece would quadruple them at 2^20 for nothing but a smaller buffer.  A
 // piece's additions have read a and b before its affine pass writes out, and later pieces lie behind it: d_out may be d_a or d_b.  The
 // sum needs the points once: stage 1 over a bounded grid, the same kernel over its partials, one projective point back to the host,
 // normalised there.
 constexpr uint64_t kAddPiece = TE_MSM_GROUP_ADD_PIECE;
 constexpr uint32_t kSumGrid = TE_MSM_GROUP_SUM_GRID;
-
-// the affine pass over m projective slots: te_msm_mul's chains of eight
-void launch_group_affine(bool bls, const uint32_t* proj, uint32_t m, uint32_t* out, hipStream_t st) {
-  const dim3 grid((m + 256u * SM_AFF_GROUP - 1u) / (256u * SM_AFF_GROUP)), block(256);
-  if (bls) hipLaunchKernelGGL(te::k_scalar_mul_affine<1>, grid, block, 0, st, proj, m, out, te::kInvExp377);
-  else hipLaunchKernelGGL(te::k_scalar_mul_affine<0>, grid, block, 0, st, proj, m, out, te::kInvExpTe);
-}
 
 // option "check_points" for these calls: n packed points in the memory of devs[di], one launch per level; the all-zero BLS12-377 record passes
 int group_check_on(te_ctx* ctx, size_t di, const void* d_pts, uint64_t n, int level, int64_t* bad, int* reason) {
@@ -391,32 +451,16 @@ int group_check_on(te_ctx* ctx, size_t di, const void* d_pts, uint64_t n, int le
   hipStream_t st = lane.stream();
   const uint32_t m = (uint32_t)n;
   const uint4* p4 = static_cast<const uint4*>(d_pts);
-  const dim3 grid((m + 255u) / 256u), block(256);
-  HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
-  if (ctx->opt_curve == TE_MSM_CURVE_BLS12_377_G1) {
-    hipLaunchKernelGGL(te::k_group_check_form<1>, grid, block, 0, st, p4, m, d.chk_word);
-    if (level >= 2) hipLaunchKernelGGL(te::k_group_check_subgroup<1>, grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
-  } else {
-    hipLaunchKernelGGL(te::k_group_check_form<0>, grid, block, 0, st, p4, m, d.chk_word);
-    if (level >= 2) hipLaunchKernelGGL(te::k_group_check_subgroup<0>, grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  return lane.verdict(ctx, m, bad, reason);
-}
-
-// the verdict over a pair of operands: the lowest failing index, a before b at equal index
-struct pair_verdict {
-  int64_t bad = -1; int why = 0, operand = 0; bad_kind kind = kBadPoint;
-  void take(int64_t i, int reason, int op, bad_kind k) {
-    if (i < 0 || (bad >= 0 && (bad < i || (bad == i && operand <= op)))) return;
-    bad = i; why = reason; operand = op; kind = k;
-  }
-};
-int note_pair(te_ctx* ctx, const pair_verdict& v, int64_t base) {
-  const int rc = note_bad(ctx, v.kind, base + v.bad, v.why);
-  ctx->bad_point_operand = v.operand;
+  int rc = 0;
+  with_curve(ctx->opt_curve, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    rc = lane.check(ctx, m, level, bad, reason,
+                    [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(te::k_group_check_form<C>, grid, block, 0, st, p4, m, d.chk_word); },
+                    [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(te::k_group_check_subgroup<C>, grid, block, 0, st, p4, m, d.chk_word, te::order_naf_of<C>()); });
+  });
   return rc;
 }
+
 // one step (recovery, or a check level) over both operands in the memory of devs[di]: 0 with v filled in when a point failed
 int check_pair_on(te_ctx* ctx, size_t di, const void* d_a, const void* d_b, uint64_t n, uint64_t nb, pair_verdict& v) {
   int64_t bad = -1; int why = 0;
@@ -430,42 +474,24 @@ int check_pair_on(te_ctx* ctx, size_t di, const void* d_a, const void* d_b, uint
 
 // n pairs (memory of devs[di]; shared: d_b holds one point) -> n affine results at d_out, which may be d_a or d_b; returns when they are there
 int add_on(te_ctx* ctx, size_t di, const void* d_a, const void* d_b, uint64_t n, int flags, void* d_out) {
-  if (n == 0) return 0;
-  gpu_t& d = ctx->devs[di];
   const int curve = ctx->opt_curve;
-  const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1, shared = (flags & TE_MSM_ADD_SHARED_B) != 0;
+  const bool shared = (flags & TE_MSM_ADD_SHARED_B) != 0;
   const int neg = (flags & TE_MSM_ADD_SUBTRACT) ? 1 : 0;
   const size_t pb = sizes_of(curve).point_in;
-  const size_t jb = 4u * (bls ? te::sm_sizes<1>::JW : te::sm_sizes<0>::JW);
-  check_lane lane(ctx, d);
-  if (lane.rc) return lane.rc;
-  const uint64_t piece = std::min(n, kAddPiece);
-  dev_tmp proj;
-  if (int rc = tmp_alloc(ctx, d, proj, piece * jb)) return rc;
-  hipStream_t st = lane.stream();
-  for (uint64_t off = 0; off < n; off += piece) {
-    const uint32_t m = (uint32_t)std::min(piece, n - off);
+  return in_pieces(ctx, di, n, kAddPiece, d_out, [&](uint64_t off, uint32_t m, uint4* j4, hipStream_t st) {
     const uint4* a4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_a) + off * pb);
     const uint4* b4 = reinterpret_cast<const uint4*>(static_cast<const uint8_t*>(d_b) + (shared ? 0 : off * pb));
-    uint4* j4 = static_cast<uint4*>(proj.p);
-    uint32_t* o32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + off * pb);
     const dim3 grid((m + 255u) / 256u), block(256);
-    if (bls && shared) hipLaunchKernelGGL((te::k_group_add<1, true>), grid, block, 0, st, a4, b4, m, neg, j4);
-    else if (bls) hipLaunchKernelGGL((te::k_group_add<1, false>), grid, block, 0, st, a4, b4, m, neg, j4);
-    else if (shared) hipLaunchKernelGGL((te::k_group_add<0, true>), grid, block, 0, st, a4, b4, m, neg, j4);
-    else hipLaunchKernelGGL((te::k_group_add<0, false>), grid, block, 0, st, a4, b4, m, neg, j4);
-    launch_group_affine(bls, static_cast<const uint32_t*>(proj.p), m, o32, st);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return 0;
+    with_curve(curve, [&](auto c) {
+      with_flag(shared, [&](auto sh) { hipLaunchKernelGGL((te::k_group_add<decltype(c)::value, decltype(sh)::value>), grid, block, 0, st, a4, b4, m, neg, j4); });
+    });
+  });
 }
 inline size_t partial_bytes_of(int curve) { return 4u * (curve == TE_MSM_CURVE_BLS12_377_G1 ? te::ga_sizes<1>::TW : te::ga_sizes<0>::TW); }
 // count items at d_src (wire points, or -- partials -- projective partials) in the memory of devs[di] -> ONE partial in host memory
 // (h_part: partial_bytes_of).  One temporary holds the stage-1 partials and, behind them, the last one.
 int sum_fold_on(te_ctx* ctx, size_t di, const void* d_src, uint64_t count, bool partials, uint8_t* h_part) {
   gpu_t& d = ctx->devs[di];
-  const bool bls = ctx->opt_curve == TE_MSM_CURVE_BLS12_377_G1;
   const size_t tb = partial_bytes_of(ctx->opt_curve);
   const uint32_t m = (uint32_t)count, blocks = std::min<uint32_t>(kSumGrid, (m + GS_BLOCK - 1u) / GS_BLOCK);
   dev_tmp tmp;
@@ -476,15 +502,11 @@ int sum_fold_on(te_ctx* ctx, size_t di, const void* d_src, uint64_t count, bool 
   const uint4 *s4 = static_cast<const uint4*>(d_src), *t4c = static_cast<const uint4*>(tmp.p);
   uint4 *t4 = static_cast<uint4*>(tmp.p), *o4 = reinterpret_cast<uint4*>(static_cast<uint8_t*>(tmp.p) + (size_t)blocks * tb);
   const dim3 block(GS_BLOCK);
-  if (bls) {
-    if (partials) hipLaunchKernelGGL((te::k_group_sum<1, true>), dim3(blocks), block, 0, st, s4, m, t4);
-    else hipLaunchKernelGGL((te::k_group_sum<1, false>), dim3(blocks), block, 0, st, s4, m, t4);
-    hipLaunchKernelGGL((te::k_group_sum<1, true>), dim3(1), block, 0, st, t4c, blocks, o4);
-  } else {
-    if (partials) hipLaunchKernelGGL((te::k_group_sum<0, true>), dim3(blocks), block, 0, st, s4, m, t4);
-    else hipLaunchKernelGGL((te::k_group_sum<0, false>), dim3(blocks), block, 0, st, s4, m, t4);
-    hipLaunchKernelGGL((te::k_group_sum<0, true>), dim3(1), block, 0, st, t4c, blocks, o4);
-  }
+  with_curve(ctx->opt_curve, [&](auto c) {
+    constexpr int C = decltype(c)::value;
+    with_flag(partials, [&](auto p) { hipLaunchKernelGGL((te::k_group_sum<C, decltype(p)::value>), dim3(blocks), block, 0, st, s4, m, t4); });
+    hipLaunchKernelGGL((te::k_group_sum<C, true>), dim3(1), block, 0, st, t4c, blocks, o4);
+  });
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(h_part, o4, tb, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -494,8 +516,7 @@ int sum_fold_on(te_ctx* ctx, size_t di, const void* d_src, uint64_t count, bool 
 void sum_finish(int curve, const uint8_t* h_part, uint8_t* out) {
   uint32_t w[te::ga_sizes<1>::TW], o[te::sm_sizes<1>::PW];
   memcpy(w, h_part, partial_bytes_of(curve));
-  if (curve == TE_MSM_CURVE_BLS12_377_G1) te::sm_affine_group<1>(w, 1u, o, te::kInvExp377);
-  else te::sm_affine_group<0>(w, 1u, o, te::kInvExpTe);
+  with_curve(curve, [&](auto c) { te::sm_affine_group<decltype(c)::value>(w, 1u, o, te::inv_exp_of<decltype(c)::value>()); });
   memcpy(out, o, sizes_of(curve).point_in);
 }
 
@@ -512,45 +533,24 @@ int add_host(te_ctx* ctx, const uint8_t* a, const uint8_t* b, bool x_only, uint6
   const int curve = ctx->opt_curve;
   const bool shared = (flags & TE_MSM_ADD_SHARED_B) != 0;
   const size_t pb = sizes_of(curve).point_in, ib = x_only ? x_bytes_of(curve) : pb;
-  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
-  const uint64_t per = (n + D - 1) / D;
+  const slice_plan sp(ctx, n);
   struct slice_t { dev_tmp a, b; pair_verdict v; };
-  std::vector<slice_t> sl(D);
+  std::vector<slice_t> sl(sp.D);
   auto stage = [&](size_t i) -> int {                             // upload, recover, check, add: everything but the copy out
-    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    const uint64_t lo = sp.lo(i), m = sp.count(i);
     if (m == 0) return 0;
-    gpu_t& d = ctx->devs[i];
     slice_t& s = sl[i];
     const uint64_t mb = shared ? 1 : m;
-    const uint8_t* bsrc = b + (shared ? 0 : lo * ib);
-    if (int rc = tmp_alloc(ctx, d, s.a, m * pb)) return rc;
-    if (int rc = tmp_alloc(ctx, d, s.b, mb * pb)) return rc;
-    if (x_only) {
-      int64_t bad = -1; int why = 0;
-      int rc = recover_on(ctx, i, a + lo * ib, true, m, s.a.p, nullptr, false, &bad, &why);
-      if (rc == TE_MSM_EPOINT) s.v.take(bad, why, 0, kBadX); else if (rc) return rc;
-      rc = recover_on(ctx, i, bsrc, true, mb, s.b.p, nullptr, false, &bad, &why);
-      if (rc == TE_MSM_EPOINT) s.v.take(bad, why, 1, kBadX); else if (rc) return rc;
-      if (s.v.bad >= 0) return 0;
-    } else {
-      HIP_TRY(ctx, hipMemcpy(s.a.p, a + lo * ib, m * pb, hipMemcpyHostToDevice));
-      HIP_TRY(ctx, hipMemcpy(s.b.p, bsrc, mb * pb, hipMemcpyHostToDevice));
-    }
+    if (int rc = stage_operand(ctx, i, a + lo * ib, x_only, m, s.a, 0, s.v)) return rc;
+    if (int rc = stage_operand(ctx, i, b + (shared ? 0 : lo * ib), x_only, mb, s.b, 1, s.v)) return rc;
+    if (s.v.bad >= 0) return 0;                                   // (after both: b may hold the lower index)
     if (int rc = check_pair_on(ctx, i, s.a.p, s.b.p, m, mb, s.v)) return rc;
     if (s.v.bad >= 0) return 0;
     return add_on(ctx, i, s.a.p, s.b.p, m, flags, s.a.p);
   };
-  auto copy_out = [&](size_t i) -> int {
-    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
-    if (m == 0) return 0;
-    HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
-    HIP_TRY(ctx, hipMemcpy(out + lo * pb, sl[i].a.p, m * pb, hipMemcpyDeviceToHost));
-    return 0;
-  };
-  if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
-  for (size_t i = 0; i < D; i++)                                  // slices in order: the first that reports holds the lowest index
-    if (sl[i].v.bad >= 0) return note_pair(ctx, sl[i].v, (int64_t)(per * i));
-  return te_sched::on_devices(*ctx, D, copy_out);
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  if (int rc = note_slices(ctx, sp, sl)) return rc;
+  return copy_slices_out(ctx, sp, pb, out, [&](size_t i) { return sl[i].a.p; });
 }
 // te_msm_sum (x_only = false) and te_msm_sum_x (true): every device folds its slice to one partial; the first device adds the partials
 int sum_host(te_ctx* ctx, const uint8_t* src, bool x_only, uint64_t n, uint8_t* out) {
@@ -560,25 +560,17 @@ int sum_host(te_ctx* ctx, const uint8_t* src, bool x_only, uint64_t n, uint8_t* 
   if (n == 0) { write_identity(curve, out); return 0; }
   if (!src) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   const size_t pb = sizes_of(curve).point_in, ib = x_only ? x_bytes_of(curve) : pb, tb = partial_bytes_of(curve);
-  const size_t D = (size_t)std::min<uint64_t>(ctx->devs.size(), n);
-  const uint64_t per = (n + D - 1) / D;
+  const slice_plan sp(ctx, n);
+  const size_t D = sp.D;
   struct slice_t { dev_tmp pts; pair_verdict v; bool have = false; };
   std::vector<slice_t> sl(D);
   std::vector<uint8_t> parts(D * tb);
   auto stage = [&](size_t i) -> int {
-    const uint64_t lo = std::min<uint64_t>(n, per * i), m = std::min<uint64_t>(n, lo + per) - lo;
+    const uint64_t m = sp.count(i);
     if (m == 0) return 0;
-    gpu_t& d = ctx->devs[i];
     slice_t& s = sl[i];
-    if (int rc = tmp_alloc(ctx, d, s.pts, m * pb)) return rc;
-    if (x_only) {
-      int64_t bad = -1; int why = 0;
-      const int rc = recover_on(ctx, i, src + lo * ib, true, m, s.pts.p, nullptr, false, &bad, &why);
-      if (rc == TE_MSM_EPOINT) { s.v.take(bad, why, 0, kBadX); return 0; }
-      if (rc) return rc;
-    } else {
-      HIP_TRY(ctx, hipMemcpy(s.pts.p, src + lo * ib, m * pb, hipMemcpyHostToDevice));
-    }
+    if (int rc = stage_operand(ctx, i, src + sp.lo(i) * ib, x_only, m, s.pts, 0, s.v)) return rc;
+    if (s.v.bad >= 0) return 0;
     if (int rc = check_pair_on(ctx, i, s.pts.p, nullptr, m, 0, s.v)) return rc;
     if (s.v.bad >= 0) return 0;
     if (int rc = sum_fold_on(ctx, i, s.pts.p, m, false, &parts[i * tb])) return rc;
@@ -586,8 +578,7 @@ int sum_host(te_ctx* ctx, const uint8_t* src, bool x_only, uint64_t n, uint8_t* 
     return 0;
   };
   if (int rc = te_sched::on_devices(*ctx, D, stage)) return rc;
-  for (size_t i = 0; i < D; i++)
-    if (sl[i].v.bad >= 0) return note_pair(ctx, sl[i].v, (int64_t)(per * i));
+  if (int rc = note_slices(ctx, sp, sl)) return rc;
   if (D > 1) {                                                    // the D partial results are added on the first device
     size_t have = 0;                                              // (D <= n: every slice holds points; counted all the same)
     for (size_t i = 0; i < D; i++)
@@ -635,39 +626,11 @@ int check_points_on(te_ctx* ctx, size_t di, const void* src, bool src_is_host, u
     const uint32_t m = (uint32_t)std::min(piece, n - off);
     const uint8_t* at = static_cast<const uint8_t*>(src) + off * pb;
     if (src_is_host) { HIP_TRY(ctx, hipMemcpyAsync(d.chk_pts, at, (size_t)m * pb, hipMemcpyHostToDevice, st)); at = d.chk_pts; }
-    const uint4* p4 = reinterpret_cast<const uint4*>(at);
-    HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
-    const dim3 grid((m + 255u) / 256u), block(256);
-    if (lay.stride) {
-      const uint64_t* p8 = reinterpret_cast<const uint64_t*>(at);
-      const uint32_t sd = lay.stride, fl = lay.flag ? 1u : 0u;
-      const bool bls = curve == TE_MSM_CURVE_BLS12_377_G1;
-      if (bls && mont) hipLaunchKernelGGL((te::k_check_form_strided<1, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
-      else if (bls) hipLaunchKernelGGL((te::k_check_form_strided<1, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
-      else if (mont) hipLaunchKernelGGL((te::k_check_form_strided<0, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
-      else hipLaunchKernelGGL((te::k_check_form_strided<0, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word);
-      if (level >= 2) {
-        if (bls && mont) hipLaunchKernelGGL((te::k_check_subgroup_strided<1, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNaf377Order);
-        else if (bls) hipLaunchKernelGGL((te::k_check_subgroup_strided<1, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNaf377Order);
-        else if (mont) hipLaunchKernelGGL((te::k_check_subgroup_strided<0, true>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNafTeOrder);
-        else hipLaunchKernelGGL((te::k_check_subgroup_strided<0, false>), grid, block, 0, st, p8, sd, fl, m, d.chk_word, te::kNafTeOrder);
-      }
-    } else if (mont && curve == TE_MSM_CURVE_BLS12_377_G1) {
-      hipLaunchKernelGGL((te::k_check_form<1, true>), grid, block, 0, st, p4, m, d.chk_word);
-      if (level >= 2) hipLaunchKernelGGL((te::k_check_subgroup<1, true>), grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
-    } else if (mont) {
-      hipLaunchKernelGGL((te::k_check_form<0, true>), grid, block, 0, st, p4, m, d.chk_word);
-      if (level >= 2) hipLaunchKernelGGL((te::k_check_subgroup<0, true>), grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
-    } else if (curve == TE_MSM_CURVE_BLS12_377_G1) {
-      hipLaunchKernelGGL(te::k_check_form<1>, grid, block, 0, st, p4, m, d.chk_word);
-      if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<1>, grid, block, 0, st, p4, m, d.chk_word, te::kNaf377Order);
-    } else {
-      hipLaunchKernelGGL(te::k_check_form<0>, grid, block, 0, st, p4, m, d.chk_word);
-      if (level >= 2) hipLaunchKernelGGL(te::k_check_subgroup<0>, grid, block, 0, st, p4, m, d.chk_word, te::kNafTeOrder);
-    }
-    HIP_TRY(ctx, hipGetLastError());
     int64_t i = -1;
-    const int rc = lane.verdict(ctx, m, &i, reason);
+    int rc = 0;
+    with_curve(curve, [&](auto c) {
+      with_flag(mont, [&](auto mt) { rc = check_piece<decltype(c)::value, decltype(mt)::value>(ctx, lane, at, m, level, lay, &i, reason); });
+    });
     if (rc == TE_MSM_EPOINT) *bad = (int64_t)off + i;
     if (rc) return rc;
   }

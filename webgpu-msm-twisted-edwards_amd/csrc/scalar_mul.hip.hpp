@@ -70,6 +70,8 @@ template <int W> TE_HD int sm_digit(const uint32_t (&K)[9], int i) {
 constexpr exp_t kInvExpTe = {{0xffffffffu, 0x0a117fffu, 0xd0000001u, 0x59aa76feu, 0x5c37b001u, 0x60b44d1eu, 0x9a2ca556u, 0x12ab655eu, 0u, 0u, 0u, 0u}, 252};
 constexpr exp_t kInvExp377 = {{0xffffffffu, 0x8508bfffu, 0x30000000u, 0x170b5d44u, 0xba094800u, 0x1ef3622fu, 0x00f5138fu, 0x1a22d9f3u,
                                0x6ca1493bu, 0xc63b05c0u, 0x17c510eau, 0x01ae3a46u}, 376};
+// ... by the kernels' CURVE parameter
+template <int CURVE> constexpr const exp_t& inv_exp_of() { return CURVE == 1 ? kInvExp377 : kInvExpTe; }
 // a^(modulus - 2), e uniform (a square-and-multiply chain over the bits of a kernel argument)
 template <int N> TE_HD fel<N> fe_inv(const fel<N>& a, const exp_t& e) {
   fel<N> r = a;
