@@ -475,7 +475,7 @@ int te_msm_sum_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_xy_l
  *   "scalar_record_bytes" 0 (default) = the curve's own scalar record: 32 bytes on the Twisted-Edwards curve, 48 on BLS12-377 G1.  32 on BLS12-377:
  *                   EVERY scalar buffer of a call is n x 32 bytes little-endian -- where the 48-byte record held a value in bytes 0..31 and
  *                   zeros above, there is now just the value.  48 on BLS12-377 and 32 on the Twisted-Edwards curve are the defaults spelled
- *                   out; any other value is TE_MSM_EINVAL here.  48 on the Twisted-Edwards curve is TE_MSM_EINVAL when a call starts, its
+ *                   out; 8 and 16 are the narrow records described at the end of this entry; any other value is TE_MSM_EINVAL here.  48 on the Twisted-Edwards curve is TE_MSM_EINVAL when a call starts, its
  *                   output untouched (option "curve" may change after this one was set).  Read when a call STARTS, by every entry point
  *                   that reads "scalars_montgomery" (above) and by te_msm_run_x, te_msm_mul[_device], te_msm_mul_x and
  *                   te_msm_mul_base[_device].  It sizes every buffer the call reads: host uploads and their pieces ("host_chunks",
@@ -490,6 +490,29 @@ int te_msm_sum_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_xy_l
  *                   MEASURED (MI355X, n = 2^20 over a bound set, scalars from host memory; profiles/native_layout_cost.txt): the lone
  *                   te_msm_run_scalars call 2.49-2.57 ms with 32-byte records against 2.61-2.67 ms with 48-byte ones, an MSM with four
  *                   tickets in flight 2.10-2.11 against 2.21-2.22 ms.
+ *                   8 and 16, on BOTH curves: the scalars are a native &[u64] / &[u128] -- little-endian integers of that size, no padding --
+ *                   for every entry point above except te_msm_mul* and te_msm_mul_base*, which return TE_MSM_EINVAL with the output
+ *                   untouched.  With 8 the width stands for "scalar_bits" (64; a smaller one may be set, a larger one is TE_MSM_EINVAL when
+ *                   a call starts).  16 is accepted only while "scalar_bits" is set (1..128: set it FIRST, 128 for full u128 values); with
+ *                   "scalar_bits" at 0 the value 16 is TE_MSM_EINVAL here, as it always was, and a call that finds 16 with the width reset to 0
+ *                   is TE_MSM_EINVAL when it starts.  With "scalars_montgomery" = 1 such a call is TE_MSM_EINVAL, output untouched: a residue is 32 bytes.
+ *                   Device pointers of the _device forms must be aligned to the record size, else TE_MSM_EINVAL.  The digit kernels run
+ *                   instantiations of their own (loads of the record's size, a working value of 2 / 4 words, only the windows that width
+ *                   can have); the existing ones keep their code (profiles/narrow_scalars_isa.txt).
+ *   "scalar_bits"   0 (default) = nothing declared; b in 1..256: the caller declares every scalar below 2^b (with "scalars_montgomery": the
+ *                   decoded k), and the plan covers only what b needs.  With c0 the window size the plan would choose anyway
+ *                   ("window_bits", else from n) and g = 2 for signed digits, 0 for unsigned: W = ceil((b + g) / c0) windows of c = c0 bits (the
+ *                   smallest size with that count, max(4, ceil((b + g) / W)), measured 19-56 % slower at n = 2^20: set "window_bits"
+ *                   to run it).  b = 253 signed and b = 256 unsigned give the counts of 0.  te_msm_plan reports the
+ *                   narrow c and W (what te_msm_partial_device* produce and te_msm_finalize* take).  CONTRACT: every scalar below 2^b is
+ *                   accepted and the result is exact; a scalar at or above the exact limit of the plan -- 2^(cW) - sum_{w<W} 2^(cw + c - 1)
+ *                   signed, 2^(cW) unsigned -- is TE_MSM_ESCALAR with the output untouched; anything between is accepted and exact;
+ *                   no scalar ever gives a wrong result.  Read when a call STARTS by every entry point that reads "scalars_montgomery",
+ *                   and by te_msm_run_x; a ticket keeps the width it was submitted with.  te_msm_mul* and te_msm_mul_base* do not read
+ *                   it.  A set bound with "bind_fixed_base" serves such a call from its table 0 with the ordinary windows.  Window shards:
+ *                   on a context whose te_msm_set_window_shard step exceeds W a call is TE_MSM_EINVAL (a shard would hold no window); a
+ *                   lone te_msm_run[_scalars]_device on a context of more devices than W runs whole on the device that holds the inputs.
+ *                   MEASURED: profiles/narrow_scalars_cost.txt.
  *   "point_stride"  0 (default) = packed points; else the bytes from one point record to the next: point i starts at byte i * stride, x and y
  *                   are its first 2 x 32 / 2 x 48 bytes, and the bytes behind the pair (and the flag byte, below) are never interpreted.
  *                   A multiple of 8 from the pair size (64 / 96) up to 128, else TE_MSM_EINVAL here -- 128 because a block stages its 256

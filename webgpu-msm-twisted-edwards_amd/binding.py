@@ -248,7 +248,7 @@ class MsmContext:
         self._L = L
         self._sizes = (64, 32, 64)          # point, scalar, result bytes of the selected curve and scalar record (_resize)
         self.curve = CURVE_TE_BLS12
-        self._scalar_record_bytes = 0       # option "scalar_record_bytes" as set_option left it (0 = the curve's own record)
+        self._scalar_record_bytes = 0       # option "scalar_record_bytes" as set_option left it (0 = the curve's own record; 8 / 16: narrow scalars)
         self._point_stride = 0              # option "point_stride" as set_option left it (0 = packed x || y)
         self._held = {}                     # ticket -> the buffers of an asynchronous submit (alive until collected)
 
@@ -317,7 +317,8 @@ class MsmContext:
 
     def _resize(self):
         """_sizes is the one place that knows the byte sizes: the scalar record is option "scalar_record_bytes" where it is set (32 on
-        BLS12-377: a native prover's records), else the curve's own.  (48 on the Twisted-Edwards curve: the engine refuses the call.)"""
+        BLS12-377: a native prover's records; 8 / 16 on either curve: a native u64 / u128 array, whose width stands for option "scalar_bits"),
+        else the curve's own.  (48 on the Twisted-Edwards curve: the engine refuses the call.)"""
         pb, sb, rb = (96, 48, 96) if self.curve == CURVE_BLS12_377_G1 else (64, 32, 64)
         self._sizes = (pb, self._scalar_record_bytes or sb, rb)
 

@@ -83,7 +83,11 @@ int te_msm_set_option(te_ctx* ctx, const char* key, int64_t value) {
     ctx->opt_point_stride = (int)value; return 0;
   }
   if (!strcmp(key, "point_infinity_flag")) { if (value != 0 && value != 1) return set_err(ctx, TE_MSM_EINVAL, "point_infinity_flag must be 0 or 1"); ctx->opt_point_infinity_flag = (int)value; return 0; }
-  if (!strcmp(key, "scalar_record_bytes")) { if (value != 0 && value != 32 && value != 48) return set_err(ctx, TE_MSM_EINVAL, "scalar_record_bytes must be 0, 32 or 48"); ctx->opt_scalar_record_bytes = (int)value; return 0; }
+  if (!strcmp(key, "scalar_record_bytes")) { if (value != 0 && value != 8 && value != 16 && value != 32 && value != 48) return set_err(ctx, TE_MSM_EINVAL, "scalar_record_bytes must be 0, 8, 16, 32 or 48");
+    // (16 was never a record size: it stays refused, as a slip for 32 or 48 would be, until the caller has declared a width it can hold)
+    if (value == 16 && !ctx->opt_scalar_bits) return set_err(ctx, TE_MSM_EINVAL, "scalar_record_bytes = 16 needs option \"scalar_bits\" set first (1..128)");
+    ctx->opt_scalar_record_bytes = (int)value; return 0; }
+  if (!strcmp(key, "scalar_bits")) { if (value < 0 || value > 256) return set_err(ctx, TE_MSM_EINVAL, "scalar_bits must be 0 or in [1, 256]"); ctx->opt_scalar_bits = (int)value; return 0; }
   if (!strcmp(key, "mul_base_window")) { if (value < 4 || value > 12) return set_err(ctx, TE_MSM_EINVAL, "mul_base_window must be in [4, 12]"); ctx->opt_mul_base_window = (int)value; return 0; }
   if (!strcmp(key, "batch_small_max")) { if (value < 0 || value > (1ll << 31)) return set_err(ctx, TE_MSM_EINVAL, "batch_small_max must be in [0, 2^31]"); ctx->opt_batch_small_max = value; return 0; }
   return set_err(ctx, TE_MSM_EINVAL, "unknown option");
@@ -131,6 +135,7 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "point_stride")) { *value = ctx->opt_point_stride; return 0; }
   if (!strcmp(key, "point_infinity_flag")) { *value = ctx->opt_point_infinity_flag; return 0; }
   if (!strcmp(key, "scalar_record_bytes")) { *value = ctx->opt_scalar_record_bytes; return 0; }
+  if (!strcmp(key, "scalar_bits")) { *value = ctx->opt_scalar_bits; return 0; }
   if (!strcmp(key, "batch_sequences")) { *value = ctx->stat_batch_sequences; return 0; }
   if (!strcmp(key, "bind_fixed_base")) { *value = ctx->opt_bind_fixed_base; return 0; }
   if (!strcmp(key, "fixed_base_fallbacks")) { *value = ctx->stat_fb_fallbacks; return 0; }
@@ -177,7 +182,7 @@ int te_msm_partial_device(te_ctx* ctx, const void* d_points_xy_le, const void* d
   if (ctx->devs.size() != 1) return set_err(ctx, TE_MSM_ESTATE, "te_msm_partial_device needs a single-device context");
   if (ctx->opt_check_points) return set_err(ctx, TE_MSM_EINVAL, kPartialNoCheck);
   if (!d_points_xy_le || !d_scalars_le || !d_partials || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_scalar_record(ctx, d_scalars_le)) return rc;
   gpu_t& d = ctx->devs[0];
   workset_t& ws = d.ws[ctx->opt_workset];
   if (te_sched::slot_ticket(ws.slot)) return set_err(ctx, TE_MSM_ESTATE, "the selected work set holds a submitted MSM that has not been collected");
@@ -196,7 +201,7 @@ int te_msm_partial_device_batch(te_ctx* ctx, const void* const* d_points_xy_le, 
   if (!d_points_xy_le || !d_scalars_le || !d_partials || n == 0 || n >= (1ull << 31) || count < 1 || count > TE_MSM_MAX_BATCH)
     return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
   for (int m = 0; m < count; m++) if (!d_points_xy_le[m] || !d_scalars_le[m]) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
-  if (int rc = check_scalar_record(ctx)) return rc;
+  for (int m = 0; m < count; m++) if (int rc = check_scalar_record(ctx, d_scalars_le[m])) return rc;
   gpu_t& d = ctx->devs[0];
   workset_t& ws = d.ws[ctx->opt_workset];
   if (te_sched::slot_ticket(ws.slot)) return set_err(ctx, TE_MSM_ESTATE, "the selected work set holds a submitted MSM that has not been collected");

@@ -68,7 +68,7 @@ int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_sc
     HIP_TRY(ctx, hipSetDevice(d.device));
     device_inputs in; in.scalars = d_scalars;
     if (must_pull(ctx, d, src_dev)) { if (int rc = pull_inputs(ctx, d, ws, src_dev, n, (size_t)p0.sc_bytes, in, moved[i])) return rc; }
-    partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = ws.stream; r.bases = bases; r.scalar_bytes = p0.sc_bytes;
+    partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = ws.stream; r.bases = bases; r.scalar_bytes = p0.sc_bytes; r.scalar_bits = p0.sc_bits;
     if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
@@ -80,15 +80,18 @@ int run_bound_window_shards(te_ctx* ctx, const te_bases* bases, const void* d_sc
 int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_is_host, uint8_t* out) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   if (int rc = check_bases(ctx, bases)) return rc;
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_scalar_record(ctx, src_is_host ? nullptr : src)) return rc;
   const uint64_t n = bases->n;
   if (n == 0) { write_identity(ctx->opt_curve, out); return 0; }
   if (!src) return set_err(ctx, TE_MSM_EINVAL, "null scalar buffer");
   size_t di = 0;
-  if (ctx->devs.size() > 1) {
-    if (!bases->fb_c) {
+  const bool multi = ctx->devs.size() > 1;
+  const bool fb_set = bases->fb_c && !scalar_bits_now(ctx);      // (a declared width runs the ordinary windows over the set's table 0)
+  if (multi) {
+    if (!fb_set) {
       if (src_is_host) return run_host_sharded(ctx, nullptr, static_cast<const uint8_t*>(src), n, out, bases);
-      return run_bound_window_shards(ctx, bases, src, n, out);
+      // (fewer windows than devices -- a narrow plan: a shard would be left without a window, the call runs whole on the holder, below)
+      if ((size_t)make_plan(ctx, ctx->devs[0], plan_shard(n)).W >= ctx->devs.size()) return run_bound_window_shards(ctx, bases, src, n, out);
     }
     // a fixed-base set has no windows or point slices to shard (one bucket set): the lone call runs on ONE device -- the holder of
     // device-resident scalars, else the first; MSMs in flight (tickets) are how several devices work on such a set
@@ -105,7 +108,7 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
   HIP_TRY(ctx, hipSetDevice(d.device));
   const plan_t p0 = make_plan(ctx, d, plan_shard(n));
   const size_t sb = (size_t)p0.sc_bytes;
-  const bool fb = bases->fb_c && (ctx->devs.size() > 1 || d.w_step == 1);      // (a window-sharded single-device context keeps the ordinary windows)
+  const bool fb = fb_set && (multi || d.w_step == 1);      // (a window-sharded single-device context keeps the ordinary windows)
   if (fb) {
     if (src_is_host) { if (int rc = enqueue_fixed_base_host(ctx, d, ws, bases, static_cast<const uint8_t*>(src), n, true)) return rc; }
     else { if (int rc = enqueue_fixed_base(ctx, d, ws, bases, src, n, 0, ws.stream)) return rc; if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc; }
@@ -122,7 +125,7 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
       if (int rc = upload(ctx, ws, ws.d_in_scalars, static_cast<const uint8_t*>(src), n * sb, ws.stream)) return rc;
       ds = ws.d_in_scalars;
     }
-    partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.bases = bases;
+    partial_req r; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.bases = bases; r.whole = multi;
     if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   }
@@ -136,10 +139,10 @@ int run_scalars_common(te_ctx* ctx, te_bases* bases, const void* src, bool src_i
 
 // ---- MSMs over an indexed subset of a bound point set (include/te_msm.h) ------------------------------------------------------
 // the arguments all four calls share; 0 = go on
-int indexed_args(te_ctx* ctx, const te_bases* bases, const void* idx, const void* scalars, uint64_t m) {
+int indexed_args(te_ctx* ctx, const te_bases* bases, const void* idx, const void* scalars, uint64_t m, bool device = false) {
   if (int rc = check_bases(ctx, bases)) return rc;
   if (int rc = check_n(ctx, m)) return rc;
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_scalar_record(ctx, device ? scalars : nullptr)) return rc;
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_EINVAL, "indexed MSMs are whole MSMs: reset the window shard first");
   if (m > 0 && (!idx || !scalars)) return set_err(ctx, TE_MSM_EINVAL, "null index or scalar buffer");
   if (m > 0 && bases->n == 0) { ctx->bad_index_position = 0; return set_err(ctx, TE_MSM_EINVAL, "the bound point set is empty: no index is below its count"); }
@@ -158,7 +161,7 @@ int settle_indexed(te_ctx* ctx, gpu_t& d, workset_t& ws, uint8_t* out) {
 
 int run_indexed_common(te_ctx* ctx, te_bases* bases, const void* idx, const void* src, bool src_is_host, uint64_t m, uint8_t* out) {
   if (!ctx || !out) return TE_MSM_EINVAL;
-  if (int rc = indexed_args(ctx, bases, idx, src, m)) return rc;
+  if (int rc = indexed_args(ctx, bases, idx, src, m, !src_is_host)) return rc;
   if (m == 0) { write_identity(ctx->opt_curve, out); return 0; }
   const bool multi = ctx->devs.size() > 1;
   if (src_is_host && multi) return run_host_sharded(ctx, nullptr, static_cast<const uint8_t*>(src), m, out, bases, static_cast<const uint32_t*>(idx));
@@ -200,7 +203,7 @@ int run_batch_common(te_ctx* ctx, te_bases* bases, int count, const uint64_t* le
   if (!ctx) return TE_MSM_EINVAL;
   drain_workers(ctx);
   if (int rc = check_bases(ctx, bases)) return rc;
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_scalar_record(ctx, src_is_host ? nullptr : src)) return rc;
   // (the window shards of a multi-device context are the engine's own, for its lone calls: a batch runs whole MSMs on every device)
   if (ctx->devs.size() == 1 && ctx->devs[0].w_step != 1) return set_err(ctx, TE_MSM_EINVAL, "batched MSMs compute whole MSMs: reset the window shard first");
   if (count < 0) return set_err(ctx, TE_MSM_EINVAL, "count must be >= 0");
@@ -348,7 +351,7 @@ int fixed_base_settle(te_ctx* ctx, gpu_t& d, workset_t& ws, const te_bases* base
   ctx->stat_fb_fallbacks++;
   HIP_TRY(ctx, hipSetDevice(d.device));
   partial_req r; r.d_scalars = ws.fb_scalars; r.n = ws.fb_n; r.stream = ws.stream; r.whole = true; r.bases = bases;
-  r.scalar_form = ws.plan.scalar_mont; r.scalar_bytes = ws.plan.sc_bytes;   // (a ticket: the form and size it was submitted with, whatever the options say at its collect)
+  r.scalar_form = ws.plan.scalar_mont; r.scalar_bytes = ws.plan.sc_bytes; r.scalar_bits = 0;   // (a ticket: the form and size it was submitted with, whatever the options say at its collect)
   if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;
   HIP_TRY(ctx, hipEventSynchronize(ws.ev_result));
@@ -413,9 +416,9 @@ int te_msm_submit_scalars(te_ctx* ctx, te_bases* bases, const uint8_t* scalars_l
   // the device the upload hides under THEIR device work, and one piece keeps the sort and the accumulation at full width
   host_slice_req r; r.recs = bases->recs[(size_t)t.di]; r.rec_kind = bases->rec_kind; r.scalars = scalars_le; r.n = n;
   r.c = pf.c; r.K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, n) : 1;
-  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes; r.scalar_bits = pf.sc_bits;
   te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, bases, r]() -> int {
-    return bases->fb_c ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, r.scalars, r.n, false, r.scalar_form) : enqueue_host_pieces(ctx, t.d, t.ws, r);
+    return bases->fb_c && !r.scalar_bits ? enqueue_fixed_base_host(ctx, t.d, t.ws, bases, r.scalars, r.n, false, r.scalar_form) : enqueue_host_pieces(ctx, t.d, t.ws, r);
   });
   hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
@@ -425,7 +428,7 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (int rc = check_bases(ctx, bases)) return rc;
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_scalar_record(ctx, d_scalars_le)) return rc;
   const uint64_t n = bases->n;
   if (!d_scalars_le || n == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty point set has no tickets: te_msm_run_scalars_device returns the identity)");
   const bool multi = ctx->devs.size() > 1;
@@ -436,7 +439,7 @@ int te_msm_submit_scalars_device(te_ctx* ctx, te_bases* bases, const void* d_sca
   const ticket_set& t = *taken;
   device_inputs in; in.scalars = d_scalars_le;
   if (int rc = pull_for_ticket(ctx, t, owner, n, scalar_bytes_now(ctx), in)) return rc;
-  if (bases->fb_c && (multi || t.d.w_step == 1)) { if (int rc = enqueue_fixed_base(ctx, t.d, t.ws, bases, in.scalars, n, 0, t.ws.stream)) return rc; }
+  if (bases->fb_c && !scalar_bits_now(ctx) && (multi || t.d.w_step == 1)) { if (int rc = enqueue_fixed_base(ctx, t.d, t.ws, bases, in.scalars, n, 0, t.ws.stream)) return rc; }
   else {
     partial_req r; r.d_scalars = in.scalars; r.n = n; r.stream = t.ws.stream; r.whole = multi; r.bases = bases;
     if (int rc = enqueue_partial(ctx, t.d, t.ws, r)) return rc;
@@ -469,7 +472,7 @@ int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* 
   // (pieces: the rule of te_msm_submit_scalars -- with other tickets in flight the upload hides under their device work)
   r.c = pf.c; r.K = (ctx->opt_scalar_chunks || t.d.in_flight == 0) ? scalar_pieces(ctx, m) : 1;
   r.idx = idx; r.idx_count = bases->n;
-  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes; r.scalar_bits = pf.sc_bits;
   te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, r]() -> int { return enqueue_host_pieces(ctx, t.d, t.ws, r); });
   hand_out_ticket(ctx, t, ticket, bases, std::move(job));
   return 0;
@@ -478,7 +481,7 @@ int te_msm_submit_scalars_indexed(te_ctx* ctx, te_bases* bases, const uint32_t* 
 int te_msm_submit_scalars_indexed_device(te_ctx* ctx, te_bases* bases, const void* d_idx, const void* d_scalars_le, uint64_t m, uint64_t* ticket) {
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
-  if (int rc = indexed_args(ctx, bases, d_idx, d_scalars_le, m)) return rc;
+  if (int rc = indexed_args(ctx, bases, d_idx, d_scalars_le, m, true)) return rc;
   if (m == 0) return set_err(ctx, TE_MSM_EINVAL, "bad arguments (an empty index list has no tickets: te_msm_run_scalars_indexed_device returns the identity)");
   const int owner = owner_of(ctx, kIndexedResident, {d_idx, d_scalars_le});
   if (owner < 0) return owner;

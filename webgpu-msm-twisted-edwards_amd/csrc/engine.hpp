@@ -80,7 +80,9 @@ struct plan_t {
   uint32_t packed = 0;               // level-1 entries as one 32-bit word (index | key << 23 | sign << 31): n <= 2^23
   int rec_kind = 0;                  // records k_accumulate gathers: 0 = the curve's own, 1 = affine BLS12-377 (bound point sets)
   int scalar_mont = 0;               // the scalar records hold k 2^256 mod (the curve's scalar field): option "scalars_montgomery" as it was when the call started
-  int sc_bytes = 0;                  // bytes of one scalar record, 32 or 48: option "scalar_record_bytes" as it was when the call started (scalar_bytes_now)
+  int sc_bytes = 0;                  // bytes of one scalar record, 8, 16, 32 or 48: option "scalar_record_bytes" as it was when the call started (scalar_bytes_now)
+  int sc_bits = 0;                   // every scalar is below 2^sc_bits, as the caller declared when the call started (scalar_bits_now); 0 = nothing declared.
+                                     // c and W cover this width only (te_plan::windows_for)
   // fixed-base windows (bound point sets with a per-window table, kernels.hip.hpp k_fb_digits): fb_rb > 0 -- the "windows" of this
   // plan are fb_rb + 1 pseudo-windows (rows) of 2^15 buckets over ONE bucket set; fb_c / fb_W: window bits and windows of the real decomposition
   int fb_rb = 0, fb_c = 0, fb_W = 0;
@@ -255,8 +257,10 @@ struct te_ctx {
                                     // starts, on the calling thread -- a ticket keeps the form it was submitted with (plan_t::scalar_mont)
   int opt_points_montgomery = 0;    // te_msm_bind_points[_device]: coordinates are Montgomery residues x 2^256 mod p / x 2^384 mod q; read at bind time
   std::vector<te_base*> mul_bases;  // the bound points of fixed-base scalar multiplication (te_msm_bind_base), freed by te_msm_release_base / te_msm_destroy
-  int opt_scalar_record_bytes = 0;  // bytes of one scalar record: 0 = the curve's own (32 / 48), 32 = BLS12-377 scalars as a native prover holds them; read when a call
-                                    // starts, on the calling thread -- a ticket keeps the size it was submitted with (plan_t::sc_bytes)
+  int opt_scalar_record_bytes = 0;  // bytes of one scalar record: 0 = the curve's own (32 / 48), 32 = BLS12-377 scalars as a native prover holds them, 8 / 16 = a
+                                    // native &[u64] / &[u128]; read when a call starts, on the calling thread -- a ticket keeps the size it was submitted with (plan_t::sc_bytes)
+  int opt_scalar_bits = 0;          // the caller declares every scalar below 2^b (0 = nothing declared; 8-byte records: their width; 16-byte records need it set); read when a call starts, as
+                                    // the record size -- a ticket keeps the width it was submitted with (plan_t::sc_bits)
   int opt_point_stride = 0;         // te_msm_bind_points[_device], te_msm_check_points[_device]: bytes from one point record to the next, 0 = packed x || y; read at bind time
   int opt_point_infinity_flag = 0;  // ... BLS12-377: the byte at offset 96 of every record flags the point at infinity (needs a stride >= 104); read at bind time
   int opt_mul_base_window = 12;     // te_msm_bind_base: window bits W of the table, 4..12 (option "mul_base_window"; 12 measured fastest at every size: DESIGN.md section 17); read at bind time
@@ -303,12 +307,34 @@ inline int set_err(te_ctx* ctx, int code, const char* msg) { std::lock_guard<std
 // Bytes of one scalar record of a call that starts NOW (option "scalar_record_bytes"; 0 = the curve's own record).  Every buffer size and
 // piece offset of the call's scalars, and the stride its kernels read them at, come from this value -- never from sizes_of().scalar_in.
 inline size_t scalar_bytes_now(const te_ctx* ctx) { return ctx->opt_scalar_record_bytes ? (size_t)ctx->opt_scalar_record_bytes : sizes_of(ctx->opt_curve).scalar_in; }
-// ... and what every entry point that reads scalars asks first: the Twisted-Edwards curve has no 48-byte record (the curve option may have
-// changed after this one was set).  0 = go on
-inline int check_scalar_record(te_ctx* ctx) {
-  if (ctx->opt_scalar_record_bytes == 48 && ctx->opt_curve != TE_MSM_CURVE_BLS12_377_G1)
+inline bool narrow_records(int bytes) { return bytes == 8 || bytes == 16; }
+// The width a call that starts NOW declares for its scalars (plan_t::sc_bits): option "scalar_bits", else the width of 8- / 16-byte records,
+// else 0 -- nothing declared, the full-width windows.  A call with a declared width runs the ordinary windows (a fixed-base set serves it
+// from its table 0).
+inline int scalar_bits_now(const te_ctx* ctx) {
+  if (ctx->opt_scalar_bits) return ctx->opt_scalar_bits;
+  return narrow_records(ctx->opt_scalar_record_bytes) ? 8 * ctx->opt_scalar_record_bytes : 0;
+}
+// ... and what every entry point that reads scalars asks first (the options may have changed one after the other): the Twisted-Edwards
+// curve has no 48-byte record; a residue is 32 bytes, so 8- / 16-byte records are never Montgomery forms; a declared width fits the record.
+// d_scalars: the scalars of a _device form, which the kernels load in units of the record (8- / 16-byte records).  0 = go on
+inline int check_scalar_record(te_ctx* ctx, const void* d_scalars = nullptr) {
+  const int rb = ctx->opt_scalar_record_bytes;
+  if (rb == 48 && ctx->opt_curve != TE_MSM_CURVE_BLS12_377_G1)
     return set_err(ctx, TE_MSM_EINVAL, "option \"scalar_record_bytes\" is 48: the Twisted-Edwards curve has 32-byte scalar records only");
+  if (narrow_records(rb)) {
+    if (ctx->opt_scalars_montgomery) return set_err(ctx, TE_MSM_EINVAL, "option \"scalars_montgomery\" needs 32-byte records: a residue does not fit 8 or 16 bytes");
+    if (ctx->opt_scalar_bits > 8 * rb) return set_err(ctx, TE_MSM_EINVAL, "option \"scalar_bits\" is larger than the width of the scalar records");
+    if (rb == 16 && !ctx->opt_scalar_bits) return set_err(ctx, TE_MSM_EINVAL, "16-byte scalar records need a declared width: option \"scalar_bits\" was reset to 0");
+    if (d_scalars && (reinterpret_cast<uintptr_t>(d_scalars) & (uintptr_t)(rb - 1)))
+      return set_err(ctx, TE_MSM_EINVAL, "device scalars must be aligned to the size of their records");
+  }
   return 0;
+}
+// te_msm_mul* / te_msm_mul_base*: 32- / 48-byte records only (they do not read "scalar_bits")
+inline int check_mul_scalar_record(te_ctx* ctx) {
+  if (narrow_records(ctx->opt_scalar_record_bytes)) return set_err(ctx, TE_MSM_EINVAL, "scalar multiplication reads 32- or 48-byte scalar records: reset option \"scalar_record_bytes\"");
+  return check_scalar_record(ctx);
 }
 
 // The engine selects devices with hipSetDevice, which is state of the CALLING thread: every entry point that may do so puts the
@@ -342,6 +368,7 @@ struct plan_req {
   // upload lane and do not read the option, and the second run of a fixed-base ticket; -1 = option "scalars_montgomery" as it is now
   int scalar_form = -1;
   int scalar_bytes = 0;          // ... and their size (plan_t::sc_bytes), fixed by the same callers; 0 = option "scalar_record_bytes" as it is now
+  int scalar_bits = -1;          // ... and their declared width (plan_t::sc_bits), likewise; -1 = as the options have it now (scalar_bits_now)
   int rec_kind = 0;              // records k_accumulate gathers (plan_t::rec_kind): a bound point set's form
   uint64_t idx_count = 0;        // an indexed call: records of the bound set -- the entry form follows the SET (indexed_plan.hpp); 0 = not indexed
 };
@@ -377,6 +404,7 @@ struct partial_req {
   const uint32_t* d_idx = nullptr;    // (with bases) an indexed subset: the n entries gather records d_idx[0 .. n) of the set (device memory of d)
   int scalar_form = -1;               // plan_req's: -1 = option "scalars_montgomery" as it is now
   int scalar_bytes = 0;               // plan_req's: 0 = option "scalar_record_bytes" as it is now
+  int scalar_bits = -1;               // plan_req's: -1 = the declared width as the options have it now
 };
 
 // Device-resident inputs of a call, and the peer pull that brings them from the memory of device src_dev into the staging area of a
@@ -397,6 +425,7 @@ struct host_slice_req {
   const uint32_t* idx = nullptr; uint64_t idx_count = 0, idx_pos = 0;
   int scalar_form = -1;                 // plan_req's (a lane thread passes what its ticket was submitted with)
   int scalar_bytes = 0;                 // plan_req's (likewise)
+  int scalar_bits = -1;                 // plan_req's (likewise)
 };
 
 const char* const kFinalCarry = "final carry is 1: a scalar does not fit the signed window decomposition";

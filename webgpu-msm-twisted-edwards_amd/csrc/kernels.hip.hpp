@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "curve.hpp"
 #include "scalar_form.hpp"
+#include "plan_arith.hpp"
 #include "strided.hip.hpp"
 
 namespace te {
@@ -28,7 +29,8 @@ struct batch_slabs { uint32_t s[TE_BATCH_MAX]; };
 struct digits_params {
   uint32_t half[10];   // signed digits: sum_w 2^(c*w + c-1) over ALL windows of the decomposition, 9 limbs (+1 zero); unsigned: 0
   uint32_t zero_digit; // stored code of digit 0: 2^(c-1) signed, 0 unsigned
-  uint32_t sc_stride;  // scalar record size in 16-byte units: 2 (32 bytes) or 3 (48-byte records, upper 16 bytes must be zero)
+  uint32_t sc_stride;  // scalar record size in 16-byte units: 2 (32 bytes) or 3 (48-byte records, upper 16 bytes must be zero); the narrow
+                       // forms (SCALAR_FORM_U64 / _U128) do not read it: their record size is a template parameter
   uint32_t n, nst;     // points, digit-row stride (n rounded up to a multiple of 8; pad entries hold digit 0)
   int num_windows;     // total windows W of the decomposition
   int w_first, w_step, nw_local;
@@ -230,11 +232,103 @@ __device__ __forceinline__ void digits_block(const uint4* __restrict__ scalars, 
   }
 }
 
+// NARROW RECORDS (option "scalar_record_bytes" = 8 / 16): the scalars are a native &[u64] / &[u128], little-endian, no padding.  The
+// digit kernels' instantiations SCALAR_FORM_U64 / SCALAR_FORM_U128 run this body instead of digits_block: loads of the record's own
+// size (te_plan::loads_of_pair states which; two 8-byte records travel as one 16-byte load where the slice is 16-byte aligned and both
+// exist), a working value of REC / 4 words plus the one that takes the carry of `half`, and a window loop that stops at the
+// ceil((8 REC + 2) / C) windows a plan for this width can have plus the one that catches the carry: s + half < 2^(8 REC) + 2^(c W) and
+// c W < 8 REC + 2 + C, so no bit lies at or above C * WMAX.  Everything else -- digit rows, the level-1 histogram, the error rule (any
+// non-zero bit at or above c * W) -- is digits_block's.
+enum { SCALAR_FORM_U64 = 3, SCALAR_FORM_U128 = 4 };
+template <int FORM> struct narrow_record { static constexpr int bytes = FORM == SCALAR_FORM_U64 ? 8 : FORM == SCALAR_FORM_U128 ? 16 : 0; };
+template <int C, int REC>
+__device__ __forceinline__ void digits_block_narrow(const uint8_t* __restrict__ scalars, const uint32_t n, uint32_t* __restrict__ hist, uint16_t* __restrict__ digits,
+                                                    const digits_params& prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
+  static_assert(REC == 8 || REC == 16, "narrow records");
+  static_assert(TE_DIG_BLOCK == 2u * TE_DIG_THREADS, "one pair per thread");
+  constexpr int NW = REC / 4;                            // words of a record; the working value has NW + 1
+  digits += (size_t)blockIdx.y * prm.nw_local * prm.nst;
+  counts1 += (size_t)blockIdx.y * prm.nw_local * prm.CH * prm.P;
+  const uint32_t hn = (uint32_t)prm.nw_local * prm.P;
+  for (uint32_t j = threadIdx.x; j < hn; j += TE_DIG_THREADS) hist[j] = 0u;
+  __syncthreads();
+  uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(digits);
+  const uint32_t half_stride = prm.nst >> 1;
+  const uint32_t ZERO_DIGIT = prm.zero_digit;
+  bool bad = false;
+  const uint32_t pair = blockIdx.x * TE_DIG_THREADS + threadIdx.x, i0 = 2u * pair;
+  const bool base16 = (reinterpret_cast<uintptr_t>(scalars) & 15u) == 0u;
+  const te_plan::pair_loads L = te_plan::loads_of_pair((uint32_t)REC, i0, n, base16);
+  uint32_t s[2][NW + 1];
+  if constexpr (REC == 8) {
+    if (L.count == 1) {
+      const uint4 v = *reinterpret_cast<const uint4*>(scalars + L.at[0]);
+      s[0][0] = v.x; s[0][1] = v.y; s[1][0] = v.z; s[1][1] = v.w;
+    } else {
+      const uint2 a = *reinterpret_cast<const uint2*>(scalars + L.at[0]), b = *reinterpret_cast<const uint2*>(scalars + L.at[1]);
+      s[0][0] = a.x; s[0][1] = a.y; s[1][0] = b.x; s[1][1] = b.y;
+    }
+  } else {
+    const uint4 a = *reinterpret_cast<const uint4*>(scalars + L.at[0]), b = *reinterpret_cast<const uint4*>(scalars + L.at[1]);
+    s[0][0] = a.x; s[0][1] = a.y; s[0][2] = a.z; s[0][3] = a.w; s[1][0] = b.x; s[1][1] = b.y; s[1][2] = b.z; s[1][3] = b.w;
+  }
+  if (i0 < prm.nst) {
+    if (i0 >= n) {                                       // padding entries: digit 0
+      for (int k = 0; k < prm.nw_local; k++) out[(size_t)k * half_stride + pair] = ZERO_DIGIT | (ZERO_DIGIT << 16);
+    } else {
+      const bool second = i0 + 1u < n;
+#pragma unroll
+      for (int t = 0; t < 2; t++) {
+        s[t][NW] = 0u;
+        uint64_t c = 0;
+#pragma unroll
+        for (int j = 0; j <= NW; j++) { c += (uint64_t)s[t][j] + prm.half[j]; s[t][j] = (uint32_t)c; c >>= 32; }
+      }
+      constexpr int WMAX = (8 * REC + 2 + C - 1) / C + 1;
+      int next = prm.w_first, k = 0;                     // next owned window and its local index
+#pragma unroll
+      for (int w = 0; w < WMAX; w++) {
+        const int bit = w * C;
+        if (bit >= 32 * (NW + 1)) break;
+        const int word = bit >> 5, off = bit & 31;
+        if (w < prm.num_windows && w != next) continue;  // a window of another shard (uniform): nothing to extract
+        uint32_t v[2];
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+          v[t] = s[t][word] >> off;
+          if (off + C > 32 && word + 1 <= NW) v[t] |= s[t][word + 1] << (32 - off);
+          v[t] &= (1u << C) - 1u;
+        }
+        if (!second) v[1] = w < prm.num_windows ? ZERO_DIGIT : 0u;
+        if (w >= prm.num_windows) { bad |= ((v[0] | v[1]) != 0u); continue; }
+        if (k < prm.nw_local) {
+          out[(size_t)k * half_stride + pair] = v[0] | (v[1] << 16);
+#pragma unroll
+          for (int t = 0; t < 2; t++) {
+            uint32_t b, neg;
+            if (digit_bucket(v[t], prm.half_code, b, neg)) atomicAdd(&hist[(uint32_t)k * prm.P + (b >> prm.logS)], 1u);
+          }
+        }
+        k++; next += prm.w_step;
+      }
+    }
+  }
+  if (bad) atomicOr(err, 1u);
+  __syncthreads();
+  const uint32_t ch = (blockIdx.x * TE_DIG_BLOCK) / prm.chunk_len;
+  for (uint32_t j = threadIdx.x; j < hn; j += TE_DIG_THREADS) {
+    const uint32_t v = hist[j];
+    if (v) { const uint32_t k = j / prm.P, p = j - k * prm.P; atomicAdd(&counts1[((size_t)k * prm.CH + ch) * prm.P + p], v); }
+  }
+}
+
 template <int C, int FORM = SCALAR_FORM_CANONICAL>
 __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits(batch_ptrs in, uint16_t* __restrict__ digits,
                                                 digits_params prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
   __shared__ uint32_t hist[4096];                        // [local window][partition]: nw_local * P <= 4096 for every plan
-  digits_block<C, FORM>(in.p[blockIdx.y], prm.n, hist, digits, prm, err, counts1);      // every MSM of the sequence has prm.n scalars
+  // every MSM of the sequence has prm.n scalars
+  if constexpr (narrow_record<FORM>::bytes != 0) digits_block_narrow<C, narrow_record<FORM>::bytes>(reinterpret_cast<const uint8_t*>(in.p[blockIdx.y]), prm.n, hist, digits, prm, err, counts1);
+  else digits_block<C, FORM>(in.p[blockIdx.y], prm.n, hist, digits, prm, err, counts1);
 }
 
 // RAGGED SEQUENCES (te_msm_run_scalars_batch): up to TE_RAGGED_MAX MSMs of DIFFERENT lengths over prefixes of one bound point set.
@@ -249,7 +343,9 @@ __global__ void __launch_bounds__(TE_DIG_THREADS, TE_DIG_WAVES) k_digits_ragged(
                                                        digits_params prm, uint32_t* __restrict__ err, uint32_t* __restrict__ counts1) {
   __shared__ uint32_t hist[4096];
   const uint32_t m = blockIdx.y;
-  digits_block<C, FORM>(scalars + tab.off[m] * prm.sc_stride, tab.len[m], hist, digits, prm, err, counts1);
+  if constexpr (narrow_record<FORM>::bytes != 0)     // (off[m] records of 8 bytes: an odd offset is 8-byte aligned only)
+    digits_block_narrow<C, narrow_record<FORM>::bytes>(reinterpret_cast<const uint8_t*>(scalars) + tab.off[m] * (uint64_t)narrow_record<FORM>::bytes, tab.len[m], hist, digits, prm, err, counts1);
+  else digits_block<C, FORM>(scalars + tab.off[m] * prm.sc_stride, tab.len[m], hist, digits, prm, err, counts1);
 }
 
 // ------------------------------------------------------------------------------------------------

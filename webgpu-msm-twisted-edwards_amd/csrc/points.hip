@@ -256,7 +256,7 @@ int mul_on(te_ctx* ctx, size_t di, const void* d_pts, const void* d_sc, uint64_t
 }
 int mul_args(te_ctx* ctx, const void* pts, const void* sc, uint64_t n, const void* out) {
   if (int rc = check_n(ctx, n)) return rc;
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_mul_scalar_record(ctx)) return rc;
   if (n > 0 && (!pts || !sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   return 0;
 }
@@ -406,7 +406,7 @@ int mul_base_args(te_ctx* ctx, const te_base* b, const void* sc, uint64_t n, con
   *go = false;
   if (int rc = check_base(ctx, b)) return rc;
   if (int rc = check_n(ctx, n)) return rc;
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_mul_scalar_record(ctx)) return rc;
   if (n > 0 && (!sc || !out)) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
   *go = n > 0;
   return 0;

@@ -93,7 +93,7 @@ int run_device_window_shards(te_ctx* ctx, const void* src_points, const void* sr
       }
       dp = ws.d_in_points; ds = ws.d_in_scalars;
     }
-    partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.scalar_bytes = p0.sc_bytes;
+    partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.scalar_bytes = p0.sc_bytes; r.scalar_bits = p0.sc_bits;
     if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
     return fetch_rows(ctx, ws, ws.stream);
   };
@@ -216,7 +216,7 @@ int run_host_sharded(te_ctx* ctx, const uint8_t* src_points, const uint8_t* src_
     gpu_t& d = ctx->devs[i];
     if (hi == lo) return 0;
     workset_t& ws = d.ws[wsel[i]];
-    host_slice_req r; r.scalars = src_scalars + lo * (size_t)p0.sc_bytes; r.n = hi - lo; r.c = p0.c; r.K = K; r.scalar_bytes = p0.sc_bytes;
+    host_slice_req r; r.scalars = src_scalars + lo * (size_t)p0.sc_bytes; r.n = hi - lo; r.c = p0.c; r.K = K; r.scalar_bytes = p0.sc_bytes; r.scalar_bits = p0.sc_bits;
     if (!bases) r.points = src_points + lo * sz.point_in;
     else if (!src_idx) { r.recs = bases->recs[i] + lo * bases->rec_bytes; r.rec_kind = bases->rec_kind; }
     else { r.recs = bases->recs[i]; r.rec_kind = bases->rec_kind; r.idx = src_idx + lo; r.idx_count = bases->n; r.idx_pos = lo; }
@@ -297,7 +297,7 @@ int check_n(te_ctx* ctx, uint64_t n) { return n >= (1ull << 31) ? set_err(ctx, T
 int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, bool src_is_host, uint64_t n, uint8_t out[64], share_mode share) {
   if (!ctx || !out) return TE_MSM_EINVAL;
   if (int rc = check_n(ctx, n)) return rc;
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_scalar_record(ctx, src_is_host ? nullptr : src_scalars)) return rc;
   if (n == 0) { write_identity(ctx->opt_curve, out); return 0; }
   if (!src_points || !src_scalars) return set_err(ctx, TE_MSM_EINVAL, "null input buffer");
   // (device-resident inputs live on the first device: a multi-device call checks them there, before the scatter)
@@ -306,17 +306,20 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
   // several devices: host buffers -> slices of the points, one upload thread per device; device-resident inputs -> window shards
   if (nd > 1) {
     if (src_is_host) return run_host_sharded(ctx, static_cast<const uint8_t*>(src_points), static_cast<const uint8_t*>(src_scalars), n, out);
-    return run_device_window_shards(ctx, src_points, src_scalars, n, out);
+    // (fewer windows than devices -- a narrow plan: a shard would be left without a window, so the call runs whole on the first
+    // device, which holds the inputs, as a lone call over a fixed-base set does)
+    if ((size_t)make_plan(ctx, ctx->devs[0], plan_shard(n)).W >= nd) return run_device_window_shards(ctx, src_points, src_scalars, n, out);
   }
+  const bool whole = nd > 1;
   gpu_t& d = ctx->devs[0];
   if (src_is_host && !ctx->opt_profile && ctx->opt_workset == 0 && d.w_step == 1 && d.in_flight == 0) {
     // no tickets in flight, no stage timing requested: every work set is free for the pieces
     const int K = host_pieces(ctx, n);
     if (K > 1) return run_host_chunked(ctx, static_cast<const uint8_t*>(src_points), static_cast<const uint8_t*>(src_scalars), n, K, out);
   }
-  const int wsel = lone_set(ctx, d, ctx->opt_workset);
+  const int wsel = lone_set(ctx, d, whole ? 0 : ctx->opt_workset);
   if (wsel < 0) return wsel;
-  const plan_t p0 = make_plan(ctx, d, plan_shard(n));
+  const plan_t p0 = make_plan(ctx, d, whole ? plan_whole(n) : plan_shard(n));
   const curve_sizes sz = sizes_of(p0.curve);
   const size_t sb = (size_t)p0.sc_bytes;
   workset_t& ws = d.ws[wsel];
@@ -333,7 +336,7 @@ int run_common(te_ctx* ctx, const void* src_points, const void* src_scalars, boo
     // on the side stream, beside the scalar-only kernels on ws.stream; the conversion to records follows it there
     return upload(ctx, ws, ws.d_in_points, static_cast<const uint8_t*>(src_points), n * sz.point_in, side);
   };
-  partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream;
+  partial_req r; r.d_points = dp; r.d_scalars = ds; r.n = n; r.stream = ws.stream; r.whole = whole;
   if (src_is_host) r.upload_points = &upload_points; else r.share = share;
   if (int rc = enqueue_partial(ctx, d, ws, r)) return rc;
   if (int rc = fetch_rows(ctx, ws, ws.stream)) return rc;

@@ -62,7 +62,8 @@ int auto_window_bits(uint64_t n) {
 // tail block run for nothing at n = 2^16 .. 2^18, where the reduction is ~40 % of the device span.  The error rule stays exact:
 // k_digits flags any bit of s + sum_w 2^(cw + c - 1) at or above c * W, the reference's "final carry is 1"
 // (miscellaneous/utils.ts:80-83) -- with c * W = 255 that is every scalar from 2^254 - 2^240 up (all of them >= 2 p).
-int num_windows_for(int c, int signed_digits) { return ((signed_digits ? 255 : 256) + c - 1) / c; }
+// A declared width (option "scalar_bits", or the width of 8- / 16-byte records) cuts the windows to what it needs and keeps their size:
+// te_plan::windows_for (plan_arith.hpp) is the one statement of the rule.
 }  // namespace
 
 #ifndef TE_SCATTER_BLOCKS
@@ -77,10 +78,11 @@ plan_t make_plan(const te_ctx* ctx, const gpu_t& d, const plan_req& q) {
   p.curve = ctx->opt_curve;
   p.scalar_mont = q.scalar_form >= 0 ? q.scalar_form : ctx->opt_scalars_montgomery;
   p.sc_bytes = q.scalar_bytes ? q.scalar_bytes : (int)scalar_bytes_now(ctx);
+  p.sc_bits = q.scalar_bits >= 0 ? q.scalar_bits : scalar_bits_now(ctx);
   p.rec_kind = q.rec_kind;
-  p.c = q.force_c ? q.force_c : ctx->opt_window_bits ? ctx->opt_window_bits : auto_window_bits(n);
   p.signed_digits = ctx->opt_signed;
-  p.W = num_windows_for(p.c, p.signed_digits);
+  const te_plan::windows win = te_plan::windows_for(q.force_c ? q.force_c : ctx->opt_window_bits ? ctx->opt_window_bits : auto_window_bits(n), p.signed_digits, p.sc_bits);
+  p.c = win.c; p.W = win.W;
   p.w_first = q.whole ? 0 : d.w_first; p.w_step = q.whole ? 1 : d.w_step;
   p.nw = 0;
   for (int w = p.w_first; w < p.W; w += p.w_step) p.nw++;
@@ -182,13 +184,18 @@ template <int C, int FORM> void launch_digits_ragged(const void* sc, const te::r
 }
 static_assert(TE_RAGGED_MAX == TE_BATCH_SEQ_MAX && TE_BATCH_SEQ_MAX == TE_MSM_BATCH_SEQ_MAX, "ragged tables");
 // the instantiation of the digit kernels a plan runs: canonical records, or Montgomery residues modulo the scalar field of the plan's curve
+// -- or 8- / 16-byte records, which are never residues (check_scalar_record refuses the pair when a call starts)
 inline int scalar_form_of(const plan_t& p) {
+  if (p.sc_bytes == 8) return te::SCALAR_FORM_U64;
+  if (p.sc_bytes == 16) return te::SCALAR_FORM_U128;
   return !p.scalar_mont ? te::SCALAR_FORM_CANONICAL : p.curve == TE_MSM_CURVE_BLS12_377_G1 ? te::SCALAR_FORM_377 : te::SCALAR_FORM_TE;
 }
 // f(integral_constant<int, FORM>) for a form of scalar_form_of
 template <typename F> void with_scalar_form(int form, F&& f) {
   if (form == te::SCALAR_FORM_TE) f(std::integral_constant<int, te::SCALAR_FORM_TE>{});
   else if (form == te::SCALAR_FORM_377) f(std::integral_constant<int, te::SCALAR_FORM_377>{});
+  else if (form == te::SCALAR_FORM_U64) f(std::integral_constant<int, te::SCALAR_FORM_U64>{});
+  else if (form == te::SCALAR_FORM_U128) f(std::integral_constant<int, te::SCALAR_FORM_U128>{});
   else f(std::integral_constant<int, te::SCALAR_FORM_CANONICAL>{});
 }
 
@@ -290,7 +297,7 @@ struct msm_launch {
       te::digits_params prm; memset(&prm, 0, sizeof prm);
       if (p.signed_digits) for (int w = 0; w < p.W; w++) { const int bit = w * p.c + p.c - 1; if (bit < 320) prm.half[bit >> 5] |= 1u << (bit & 31); }
       prm.zero_digit = p.signed_digits ? 1u << (p.c - 1) : 0u;
-      prm.sc_stride = (uint32_t)p.sc_bytes / 16u;
+      prm.sc_stride = (uint32_t)p.sc_bytes / 16u;            // (8- and 16-byte records: not read, the instantiation carries the size)
       prm.n = n32; prm.nst = p.nst; prm.num_windows = p.W; prm.w_first = p.w_first; prm.w_step = p.w_step; prm.nw_local = p.nw1;
       prm.half_code = sg.half; prm.logS = p.logS; prm.P = p.P; prm.CH = p.CH; prm.chunk_len = p.chunk_len;
       // one launch over the MSMs of the sequence: MSM m (blockIdx.y) fills digit rows and level-1 counts [m * nw1, (m + 1) * nw1)
@@ -762,10 +769,13 @@ int enqueue_partial(te_ctx* ctx, gpu_t& d, workset_t& ws, const partial_req& r) 
   const void* const d_points = r.d_points; const uint64_t n = r.n; hipStream_t const stream = r.stream;
   const int batch = r.batch; const te_bases* const bases = r.bases; const auto* const upload_points = r.upload_points;
   // (the plan is made for the n entries; only the entry form follows the set's count: indexed_plan.hpp)
-  plan_req q; q.n = n; q.batch = batch; q.whole = r.whole; q.scalar_form = r.scalar_form; q.scalar_bytes = r.scalar_bytes;
+  plan_req q; q.n = n; q.batch = batch; q.whole = r.whole; q.scalar_form = r.scalar_form; q.scalar_bytes = r.scalar_bytes; q.scalar_bits = r.scalar_bits;
   if (bases) q.rec_kind = bases->rec_kind;
   if (r.d_idx) q.idx_count = bases->n;
   const plan_t p = make_plan(ctx, d, q);
+  // (a declared width can leave fewer windows than te_msm_set_window_shard dealt shards: one of them would hold no window)
+  if (p.sc_bits && !q.whole && ctx->devs.size() == 1 && d.w_step > p.W)
+    return set_err(ctx, TE_MSM_EINVAL, "the window shard's step is larger than the windows of the narrow plan: a shard would hold no window");
   // (a batch shares when all its MSMs name ONE point buffer: the batch then holds one conversion anyway -- slab 0 of msm_launch::slabs())
   const void* share_src = d_points;
   if (batch > 1 && d_points) { share_src = static_cast<const void* const*>(d_points)[0]; for (int m = 1; m < batch; m++) if (static_cast<const void* const*>(d_points)[m] != share_src) share_src = nullptr; }
@@ -1092,10 +1102,10 @@ int enqueue_host_pieces(te_ctx* ctx, gpu_t& d, workset_t& ws, const host_slice_r
   const uint64_t n = r.n;
   const bool bound = r.points == nullptr;
   // what the plans of the whole slice and of every piece share; the pieces keep the slice's window bits and scalar form
-  plan_req q = plan_whole(n); q.force_c = r.c; q.scalar_form = r.scalar_form; q.scalar_bytes = r.scalar_bytes;
+  plan_req q = plan_whole(n); q.force_c = r.c; q.scalar_form = r.scalar_form; q.scalar_bytes = r.scalar_bytes; q.scalar_bits = r.scalar_bits;
   if (bound) { q.rec_kind = r.rec_kind; if (r.idx) q.idx_count = r.idx_count; }
   const plan_t pf = make_plan(ctx, d, q);
-  q.force_c = pf.c; q.scalar_form = pf.scalar_mont; q.scalar_bytes = pf.sc_bytes;
+  q.force_c = pf.c; q.scalar_form = pf.scalar_mont; q.scalar_bytes = pf.sc_bytes; q.scalar_bits = pf.sc_bits;
   const curve_sizes sz = sizes_of(pf.curve);
   const size_t sb = (size_t)pf.sc_bytes;                                   // the call's scalar record: every size and piece offset below
   const size_t rec_bytes = rec_bytes_of(pf.curve, pf.rec_kind);
@@ -1218,7 +1228,7 @@ namespace {
 // refusal, `half` and the digit kernel's LDS size)
 te_fb::geometry make_plan_fb(const te_ctx* ctx, const gpu_t& d, uint64_t n, int fb_c, plan_t& p, int scalar_form = -1) {
   const te_fb::geometry g = te_fb::make_geometry(n, fb_c, TE_SCATTER_BLOCKS, TE_SCATTER_MINCHUNK);
-  plan_req q = plan_whole(g.cap); q.force_c = 16; q.scalar_form = scalar_form;
+  plan_req q = plan_whole(g.cap); q.force_c = 16; q.scalar_form = scalar_form; q.scalar_bits = 0;      // (the pseudo-windows are not windows of the scalar: no declared width)
   p = make_plan(ctx, d, q);                                         // curve, scalar form, options for rows of `cap` entries
   p.fb_rb = (int)g.rb; p.fb_c = fb_c; p.fb_W = g.W;
   p.signed_digits = 0; p.c = (int)FB_LOBITS; p.W = (int)g.rows; p.nw = p.nw1 = (int)g.rows; p.batch = 1; p.w_first = 0; p.w_step = 1;

@@ -74,7 +74,7 @@ int submit_host(te_ctx* ctx, const uint8_t* points_xy_le, const uint8_t* scalars
     return 0;
   }
   const int level = ctx->opt_check_points, curve = ctx->opt_curve;
-  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes;
+  r.wait_for_pinned = false; r.scalar_form = pf.scalar_mont; r.scalar_bytes = pf.sc_bytes; r.scalar_bits = pf.sc_bits;
   te_sched::job_ref job = post_to_lane(ctx, t, [ctx, t, r, level, curve]() -> int {
     // on the lane: te_msm_collect finds TE_MSM_EPOINT as the job's status
     if (const int rc = check_ticket(ctx, t.ws, (size_t)t.di, r.points, true, r.n, curve, level)) return rc;
@@ -209,7 +209,7 @@ int te_msm_submit_device(te_ctx* ctx, const void* d_points_xy_le, const void* d_
   device_guard restore_callers_device;
   if (!ctx || !ticket) return TE_MSM_EINVAL;
   if (!d_points_xy_le || !d_scalars_le || n == 0 || n >= (1ull << 31)) return set_err(ctx, TE_MSM_EINVAL, "bad arguments");
-  if (int rc = check_scalar_record(ctx)) return rc;
+  if (int rc = check_scalar_record(ctx, d_scalars_le)) return rc;
   const bool multi = ctx->devs.size() > 1;
   // several devices: the inputs may live on any of them; the ticket goes to the least loaded one and pulls them over xGMI
   const int owner = multi ? owner_of(ctx, "te_msm_submit_device: points and scalars must be resident on one device of the context", {d_points_xy_le, d_scalars_le}) : 0;

@@ -34,6 +34,9 @@ namespace {
 std::atomic<int> g_check_points{0};    // setCheckPoints(level): option "check_points" of every context created from now on
 std::atomic<int> g_scalars_montgomery{0};   // setScalarsMontgomery(flag): option "scalars_montgomery" of every context created from now on
 std::atomic<int> g_scalar_record_bytes{0};  // setScalarRecordBytes(n): option "scalar_record_bytes" of every context created from now on
+std::atomic<int> g_scalar_bits{0};          // setScalarBits(b): option "scalar_bits" of every context created from now on
+// bytes of one scalar record of an MSM call (compute_msm, msmBatch, msmIndexed): 8 or 16 under setScalarRecordBytes, else the curve's 32
+size_t msm_scalar_bytes() { const int n = g_scalar_record_bytes.load(); return n == 8 || n == 16 ? (size_t)n : (size_t)TE_MSM_SCALAR_BYTES; }
 // what setBases bound: the Buffer, kept alive so that its address cannot become another object's, and the form of its coordinates
 // ({montgomery: true}: option "points_montgomery" for every bind of that buffer; a pool thread binds it again on a new context;
 // {stride, infinityFlag}: options "point_stride" / "point_infinity_flag", remembered and applied in the same way)
@@ -67,6 +70,10 @@ struct EngineApi {
     }
     if (rc == 0 && g_scalars_montgomery.load()) {
       const int orc = te_msm_set_option(*out, "scalars_montgomery", 1);
+      if (orc) { te_msm_destroy(*out); *out = nullptr; return orc; }
+    }
+    if (rc == 0 && g_scalar_bits.load()) {               // (before the record size: 16-byte records need a declared width)
+      const int orc = te_msm_set_option(*out, "scalar_bits", g_scalar_bits.load());
       if (orc) { te_msm_destroy(*out); *out = nullptr; return orc; }
     }
     if (rc == 0 && g_scalar_record_bytes.load()) {
@@ -146,16 +153,17 @@ napi_value MsmNative(napi_env env, napi_callback_info info) {
   napi_get_buffer_info(env, argv[1], &s, &sl);
   // (the buffer setBases bound at a stride is stride*n bytes: it is recognised by identity and its points are not read again)
   bool bound_at_stride = false;
-  if (g_bases.ref && g_bases.stride.load() && pl == (size_t)g_bases.stride.load() * (sl / 32)) {
+  const size_t sb = msm_scalar_bytes();
+  if (g_bases.ref && g_bases.stride.load() && pl == (size_t)g_bases.stride.load() * (sl / sb)) {
     napi_value bound = nullptr;
     if (napi_get_reference_value(env, g_bases.ref, &bound) == napi_ok && bound) napi_strict_equals(env, bound, argv[0], &bound_at_stride);
   }
-  if (sl % 32 != 0 || (pl != 2 * sl && !bound_at_stride)) {
-    napi_throw_range_error(env, nullptr, "points must be 64*n bytes and scalars 32*n bytes");
+  if (sl % sb != 0 || (pl != TE_MSM_POINT_BYTES * (sl / sb) && !bound_at_stride)) {
+    napi_throw_range_error(env, nullptr, "points must be 64*n bytes and scalars 32*n bytes (8*n / 16*n under setScalarRecordBytes)");
     return nullptr;
   }
   Job* j = new Job();
-  j->j.points = static_cast<const uint8_t*>(p); j->j.scalars = static_cast<const uint8_t*>(s); j->j.n = sl / 32;
+  j->j.points = static_cast<const uint8_t*>(p); j->j.scalars = static_cast<const uint8_t*>(s); j->j.n = sl / sb;
   napi_create_reference(env, argv[0], 1, &j->points_ref);
   napi_create_reference(env, argv[1], 1, &j->scalars_ref);
   napi_value promise, name;
@@ -379,8 +387,8 @@ napi_value MsmBatch(napi_env env, napi_callback_info info) {
     if (!is_buf) { napi_throw_type_error(env, nullptr, "msmBatch(scalarBuffers: Buffer[])"); return nullptr; }
     void* p = nullptr; size_t pl = 0;
     napi_get_buffer_info(env, e, &p, &pl);
-    if (pl % TE_MSM_SCALAR_BYTES != 0) { napi_throw_range_error(env, nullptr, "msmBatch: every scalar buffer must be 32*n bytes"); return nullptr; }
-    lens[m] = pl / TE_MSM_SCALAR_BYTES;
+    if (pl % msm_scalar_bytes() != 0) { napi_throw_range_error(env, nullptr, "msmBatch: every scalar buffer must be 32*n bytes (8*n / 16*n under setScalarRecordBytes)"); return nullptr; }
+    lens[m] = pl / msm_scalar_bytes();
     packed.insert(packed.end(), static_cast<const uint8_t*>(p), static_cast<const uint8_t*>(p) + pl);
   }
   std::vector<uint8_t> out((size_t)count * TE_MSM_POINT_BYTES);
@@ -415,7 +423,7 @@ napi_value MsmIndexed(napi_env env, napi_callback_info info) {
   if (tt != napi_uint32_array) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
   void* s = nullptr; size_t sl = 0;
   napi_get_buffer_info(env, argv[1], &s, &sl);
-  if (sl != m * TE_MSM_SCALAR_BYTES) { napi_throw_range_error(env, nullptr, "msmIndexed: scalars must be 32 bytes per index"); return nullptr; }
+  if (sl != m * msm_scalar_bytes()) { napi_throw_range_error(env, nullptr, "msmIndexed: scalars must be 32 bytes per index (8 / 16 under setScalarRecordBytes)"); return nullptr; }
   uint8_t out[TE_MSM_POINT_BYTES];
   int64_t bad = -1;
   std::string err;
@@ -648,18 +656,35 @@ napi_value SetScalarsMontgomery(napi_env env, napi_callback_info info) {
 }
 
 // setScalarRecordBytes(n): option "scalar_record_bytes" (include/te_msm.h) for the next call, like setScalarsMontgomery: 0 = the curve's own
-// record, 32 or 48 spelled out.  The addon runs the Twisted-Edwards curve, whose one record is 32 bytes: 0 and 32 change nothing, and under
-// 48 every call that reads scalars rejects with the engine's TE_MSM_EINVAL -- the switch is here so that the addon names every input option.
+// record, 32 or 48 spelled out, 8 / 16 = the scalar buffers of compute_msm, msmBatch and msmIndexed are a native u64 / u128 array (little-endian,
+// n * 8 / n * 16 bytes; scalarMul* reject under them).  The addon runs the Twisted-Edwards curve, whose own record is 32 bytes: 0 and 32 change
+// nothing, and under 48 every call that reads scalars rejects with the engine's TE_MSM_EINVAL.
 napi_value SetScalarRecordBytes(napi_env env, napi_callback_info info) {
   size_t argc = 1; napi_value argv[1];
   napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
   int32_t n = -1;
-  if (argc < 1 || napi_get_value_int32(env, argv[0], &n) != napi_ok || (n != 0 && n != 32 && n != 48)) {
-    napi_throw_type_error(env, nullptr, "setScalarRecordBytes(n: 0 | 32 | 48)");
+  if (argc < 1 || napi_get_value_int32(env, argv[0], &n) != napi_ok || (n != 0 && n != 8 && n != 16 && n != 32 && n != 48)) {
+    napi_throw_type_error(env, nullptr, "setScalarRecordBytes(n: 0 | 8 | 16 | 32 | 48)");
     return nullptr;
   }
   g_proto.reset();
   g_scalar_record_bytes.store(n);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
+// setScalarBits(b): option "scalar_bits" (include/te_msm.h) for the next call, like setScalarRecordBytes: the caller declares every scalar of
+// later MSM calls below 2^b (0 = nothing declared), and the engine runs only the windows that width needs; a scalar that does not fit
+// the plan rejects with TE_MSM_ESCALAR, never a wrong result.
+napi_value SetScalarBits(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  int32_t b = -1;
+  if (argc < 1 || napi_get_value_int32(env, argv[0], &b) != napi_ok || b < 0 || b > 256) {
+    napi_throw_type_error(env, nullptr, "setScalarBits(b: 0..256)");
+    return nullptr;
+  }
+  g_proto.reset();
+  g_scalar_bits.store(b);
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
@@ -686,7 +711,7 @@ napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"msmNative", MsmNative}, {"resetContext", ResetContext}, {"setDevices", SetDevices}, {"getDevices", GetDevices},
       {"setBases", SetBases}, {"getStats", GetStats}, {"setCheckPoints", SetCheckPoints}, {"setScalarsMontgomery", SetScalarsMontgomery},
-      {"setScalarRecordBytes", SetScalarRecordBytes},
+      {"setScalarRecordBytes", SetScalarRecordBytes}, {"setScalarBits", SetScalarBits},
       {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed},
       {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase},
       {"groupAdd", GroupAdd}, {"groupAddX", GroupAddX}, {"groupSum", GroupSum}, {"groupSumX", GroupSumX}};

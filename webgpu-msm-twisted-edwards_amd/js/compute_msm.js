@@ -60,7 +60,10 @@ const setBases = (bufferPoints, options) => native.setBases(bufferPoints === und
 const setScalarsMontgomery = (flag) => native.setScalarsMontgomery(!!flag);
 // setScalarRecordBytes(n): the engine's option "scalar_record_bytes" for later calls (0 = the curve's own record; 32 and 48 spelled out).
 // On the Twisted-Edwards curve the addon runs, 0 and 32 are the same thing and 48 makes every call that reads scalars reject.
+// 8 / 16: the scalar buffers of compute_msm, msmBatch and msmIndexed are native u64 / u128 arrays (n * 8 / n * 16 bytes, little-endian).
 const setScalarRecordBytes = (n) => native.setScalarRecordBytes(n);
+// setScalarBits(b): the engine's option "scalar_bits" for later calls -- every scalar is below 2^b (0 = nothing declared): fewer windows.
+const setScalarBits = (b) => native.setScalarBits(b);
 const getStats = () => native.getStats();
 // Opt-in as well: setCheckPoints(level) validates the input points of later calls (0 = none, default; 1 = canonical and on the
 // curve; 2 = also in the prime-order subgroup, costly -- best paired with setBases, which then checks the set once).  A call with
@@ -108,4 +111,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX };

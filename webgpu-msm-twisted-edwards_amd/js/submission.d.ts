@@ -22,7 +22,10 @@ export declare const setBases: (bufferPoints: Buffer | null, options?: { montgom
 export declare const setScalarsMontgomery: (flag: boolean) => void;
 // Not in the reference: the engine's option "scalar_record_bytes" for later calls: 0 = the curve's own scalar record (32 bytes here), 32 the
 // same spelled out; 48 is BLS12-377's record, under which every call of this addon that reads scalars rejects (te_msm error -1).
-export declare const setScalarRecordBytes: (n: 0 | 32 | 48) => void;
+export declare const setScalarRecordBytes: (n: 0 | 8 | 16 | 32 | 48) => void;
+// Not in the reference: the engine's option "scalar_bits" for later calls: every scalar is below 2^b (0 = nothing declared).  With 8 / 16 above
+// the scalar buffers of compute_msm, msmBatch and msmIndexed are native u64 / u128 arrays; 8 stands for b = 64, 16 needs setScalarBits(1..128).
+export declare const setScalarBits: (b: number) => void;
 export declare const getStats: () => { submittedInEnter: number; submittedInExecute: number; loneRuns: number; boundJobs: number; maxInFlight: number };
 // Not in the reference: opt-in validation of input points (0 none, 1 canonical + on the curve, 2 + prime-order subgroup); a bad
 // point rejects the call's promise (the message names the index and the reason), setBases throws for a bad set.
