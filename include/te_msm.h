@@ -53,6 +53,7 @@ typedef struct te_ctx te_ctx;
                                      (submission/miscellaneous/utils.ts:80-83) */
 #define TE_MSM_ESTATE      (-4)   /* call order / capacity */
 #define TE_MSM_EPOINT      (-5)   /* an input point failed the check selected by option `check_points` */
+#define TE_MSM_EFIELD      (-6)   /* a field element has no result (te_msm_field_op*): see "bad_field_index" / "bad_field_reason" */
 
 /* Why a point failed (option "bad_point_reason", te_msm_check_points*):  */
 #define TE_MSM_POINT_NONCANONICAL     1   /* a coordinate >= p (Twisted-Edwards) / q (BLS12-377) */
@@ -453,6 +454,76 @@ int te_msm_add_x(te_ctx* ctx, const uint8_t* ax_le, const uint8_t* bx_le, uint64
 int te_msm_sum(te_ctx* ctx, const uint8_t* points_xy_le, uint64_t n, uint8_t* out_xy_le);
 int te_msm_sum_device(te_ctx* ctx, const void* d_points_xy_le, uint64_t n, uint8_t* out_xy_le);
 int te_msm_sum_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_xy_le);
+
+/* ---- batched field arithmetic ---------------------------------------------------------------------------------------------------
+ * te_msm_field_op*: out[i] = a_i op b_i for every i -- the reference's bulkAddFields, bulkSubFields, bulkMulFields, bulkDoubleFields,
+ * bulkInvertFields, bulkPowFields, bulkPowFields17 and bulkSqrtFields (utils/wasmFunctions.ts), so that a vector of field elements in
+ * device memory stays there between the calls that use it.  Aleo's `field` is the integers mod p, the base field of the Twisted-Edwards
+ * curve -- and the same p is BLS12-377's scalar field: a vector of Aleo fields on the device is also the &[Fr] a BLS12-377 prover hands
+ * to te_msm_run_scalars_device / te_msm_submit_scalars_device (option "scalars_montgomery" for its native residues).
+ * field: TE_MSM_FIELD_P    p = 8444461749428370424248824938781546531375899335154063827935233455917409239041, 32-byte elements
+ *        TE_MSM_FIELD_Q377 q, BLS12-377's base field (the modulus of the 48-byte coordinates above), 48-byte elements
+ *   The field is an argument, not option "curve": p serves both curves.
+ * op:    TE_MSM_FIELD_ADD a + b, SUB a - b, MUL a b, POW a^b read b;  DOUBLE 2 a, NEG -a, SQUARE a^2, INV 1 / a, SQRT take a alone:
+ *   b must be NULL and TE_MSM_FIELD_SHARED_B clear, else TE_MSM_EINVAL.
+ * flags: TE_MSM_FIELD_SHARED_B    b holds ONE record, used for every i (the addend, the factor, the exponent: bulkPowFields17 is POW
+ *                                 with the shared exponent 17)
+ *        TE_MSM_FIELD_MONTGOMERY  a, b (not an exponent) and out hold v * 2^256 mod p / v * 2^384 mod q: a native prover's residues
+ *        TE_MSM_FIELD_ZERO_OK     INV only: the inverse of 0 is 0 (arkworks' batch_inversion) instead of a failure
+ *   Any other bit, an unknown op or field, or ZERO_OK on another op: TE_MSM_EINVAL, the output untouched.
+ * Values: little-endian, 32 / 48 bytes.  ANY 256- / 384-bit value is accepted and stands for its residue (the reference does the
+ *   same: its add_fields(p, 1) is 1); outputs are canonical (< p, < q).  Under MONTGOMERY a stored value likewise stands for its
+ *   residue, and the output is the canonical residue of result * 2^256 / result * 2^384.  An exponent is ALWAYS a plain 256-bit
+ *   integer in a 32-byte record, on both fields and under MONTGOMERY, used as that integer without reduction; 0^0 = 1, as the
+ *   reference has it.  sqrt(0) = 0.  n = 0: a no-op.  n < 2^31, as for te_msm_mul.
+ * WHICH SQUARE ROOT: the numerically smaller one, r <= (m - 1) / 2 (under MONTGOMERY: of the value r, not of its residue form).  The
+ *   reference returns whichever root its Tonelli-Shanks lands on (sqrt(4) = p - 2, sqrt(3) the small root): no rule to reproduce.
+ * Failures: INV of 0 without ZERO_OK and SQRT of a non-square are TE_MSM_EFIELD (the reference's WASM traps on both) with the output
+ *   untouched and the context usable.  The read-only options "bad_field_index" (-1 before any failure) and "bad_field_reason"
+ *   (0 before any; TE_MSM_FIELD_ZERO, TE_MSM_FIELD_NOT_SQUARE) hold the LOWEST failing index into the caller's whole buffer and its reason.
+ * Buffers: te_msm_field_op_device -- a, b (one record under SHARED_B) and out on one device of the context, else TE_MSM_EINVAL; d_out
+ *   may be exactly d_a or exactly d_b (partial overlap is the caller's error and is not detected; POW on TE_MSM_FIELD_Q377 refuses
+ *   d_out == d_b, whose records differ in size, with TE_MSM_EINVAL); returns with d_out complete.  te_msm_field_op: contiguous slices
+ *   over the context's devices, one host thread per device, each slice staged on its device; results are copied out only when every
+ *   slice passed; out may be a.  Temporaries are freed before return; the calling thread's current device is left as it was.
+ * How it runs (csrc/field_ops.hip.hpp): one lane per element, 256-lane blocks.  add / sub / double / neg are one
+ *   or two field products on the raw limbs and a conditional subtraction, the same code in both forms; mul / square two products.
+ *   INV without ZERO_OK first runs a scan for zero residues (one product and compares per element) and waits for its verdict; the
+ *   inversion is Montgomery's trick, one Fermat chain per TE_MSM_FIELD_INV_GROUP elements of a lane (read-only option
+ *   "field_inv_group"), the prefix products in a slab of the call's own (48 / 64 bytes an element, pieces of 2^20).  POW with
+ *   per-element exponents is 384 products in fixed 2-bit windows; a shared exponent runs square-and-multiply from its top bit (17: five
+ *   products).  SQRT is the x-recovery's root (te_msm_points_from_x) and writes into a temporary of n elements, copied on success.
+ * COST (MI355X, device buffers, three alternating rounds, lowest .. highest; tools/field_ops_cost.py, profiles/field_ops_cost.txt):
+ *   n = 2^20 elements, p / q: add 0.029 .. 0.032 / 0.038 .. 0.041 ms, sub 0.034 .. 0.037 / 0.048 .. 0.053, mul 0.035 .. 0.037 / 0.048 .. 0.053 (the
+ *   same under MONTGOMERY), double, neg and square between add and mul; INV 0.49 .. 0.53 / 1.19 .. 1.33 ms (with ZERO_OK, no scan:
+ *   0.46 .. 0.50 / 1.17 .. 1.24); POW per element 2.70 .. 2.82 / 6.33 .. 6.41 ms, with the shared exponent 17 0.071 .. 0.072 / 0.115 ..
+ *   0.120; SQRT 8.52 .. 8.65 / 21.7 .. 21.9 ms.  At 2^16: the map ops 0.015 .. 0.020 ms (a launch), INV 0.47 .. 0.48 / 1.20 .. 1.21 ms --
+ *   as long as at 2^20: an inversion is the latency of one lane's chain until the device is full -- POW 0.24 / 0.65, SQRT 0.77 .. 0.95 /
+ *   2.69 .. 2.76 ms.  Chains of 1, 8, 16, 32, 64 elements at 2^20 (ZERO_OK, the candidates alternating): p 2.74 .. 2.84, 0.63 .. 0.67,
+ *   0.49 .. 0.52, 0.52 .. 0.57, 0.61 .. 0.66 ms; q 7.90 .. 8.10, 1.26 .. 1.30, 1.15 .. 1.24, 1.28 .. 1.34, 1.59 .. 1.64 ms -- 16 is the
+ *   lowest in every round on both fields, and the trick buys 5.6x / 6.8x over n independent chains.  The floor, a device copy of the
+ *   same bytes: 0.022 / 0.025 ms at 2^20 -- add is within 1.5x of it, an inversion 23x / 47x above.  Host form at 2^20 (pageable
+ *   memory, through the Python method): MUL 17.4 .. 20.5 / 25.1 .. 27.2 ms, INV 19.4 .. 22.9 / 25.0 .. 37.0 ms, against 1.8 / 2.7 and
+ *   1.2 / 1.8 ms for the same bytes over the link from pinned memory: the host form is the staging copies, not the arithmetic. */
+#define TE_MSM_FIELD_P 0
+#define TE_MSM_FIELD_Q377 1
+#define TE_MSM_FIELD_ADD 0
+#define TE_MSM_FIELD_SUB 1
+#define TE_MSM_FIELD_MUL 2
+#define TE_MSM_FIELD_DOUBLE 3
+#define TE_MSM_FIELD_NEG 4
+#define TE_MSM_FIELD_SQUARE 5
+#define TE_MSM_FIELD_INV 6
+#define TE_MSM_FIELD_POW 7
+#define TE_MSM_FIELD_SQRT 8
+#define TE_MSM_FIELD_SHARED_B 1
+#define TE_MSM_FIELD_MONTGOMERY 2
+#define TE_MSM_FIELD_ZERO_OK 4
+#define TE_MSM_FIELD_ZERO 1
+#define TE_MSM_FIELD_NOT_SQUARE 2
+#define TE_MSM_FIELD_INV_GROUP 16u
+int te_msm_field_op(te_ctx* ctx, int field, int op, const uint8_t* a, const uint8_t* b, uint64_t n, int flags, uint8_t* out);
+int te_msm_field_op_device(te_ctx* ctx, int field, int op, const void* d_a, const void* d_b, uint64_t n, int flags, void* d_out);
 
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "scalars_montgomery" 0 (default) = scalar records hold the integers themselves (the wire format above); 1 = every scalar record holds

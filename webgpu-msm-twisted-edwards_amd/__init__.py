@@ -39,5 +39,22 @@ from .binding import (  # noqa: F401
     POINT_NOT_IN_SUBGROUP,
     X_BYTES,
     X_BYTES_BLS12_377,
+    EFIELD,
+    FIELD_P,
+    FIELD_Q377,
+    FIELD_ADD,
+    FIELD_SUB,
+    FIELD_MUL,
+    FIELD_DOUBLE,
+    FIELD_NEG,
+    FIELD_SQUARE,
+    FIELD_INV,
+    FIELD_POW,
+    FIELD_SQRT,
+    FIELD_SHARED_B,
+    FIELD_MONTGOMERY,
+    FIELD_ZERO_OK,
+    FIELD_ZERO,
+    FIELD_NOT_SQUARE,
 )
 from .sharding import ShardedPipeline, compute_msm_sharded, distribute_inputs, exchange_partials, merge_partials, rows_of_batched_msm, window_shard_for_rank  # noqa: F401

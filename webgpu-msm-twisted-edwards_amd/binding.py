@@ -23,12 +23,18 @@ EPOINT = -5             # TE_MSM_EPOINT: an input point failed the check of opti
 POINT_NONCANONICAL, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = 1, 2, 3
 X_BYTES, X_BYTES_BLS12_377 = 32, 48      # TE_MSM_X_BYTES*: one x-only point (points_from_x, bind_points_x, run_x)
 ADD_SUBTRACT, ADD_SHARED_B = 1, 2        # TE_MSM_ADD_*: flags of te_msm_add*
+EFIELD = -6             # TE_MSM_EFIELD: a field element has no result (field_op*): MsmError.index / .reason
+FIELD_P, FIELD_Q377 = 0, 1               # TE_MSM_FIELD_P / _Q377: 32-byte elements mod p (Aleo `field`, BLS12-377 Fr), 48-byte elements mod q
+FIELD_ADD, FIELD_SUB, FIELD_MUL, FIELD_DOUBLE, FIELD_NEG, FIELD_SQUARE, FIELD_INV, FIELD_POW, FIELD_SQRT = range(9)     # TE_MSM_FIELD_<op>
+FIELD_SHARED_B, FIELD_MONTGOMERY, FIELD_ZERO_OK = 1, 2, 4      # flags of te_msm_field_op*
+FIELD_ZERO, FIELD_NOT_SQUARE = 1, 2      # why an element has no result (MsmError.reason)
 
 
 class MsmError(RuntimeError):
     """code: the TE_MSM_E* value.  index / reason: the lowest failing point and TE_MSM_POINT_* when code is EPOINT, operand: which operand
     held it (0 = a, or the call's one point buffer; 1 = b of add*); index alone: the lowest position of an index outside the bound set
-    (run_scalars_indexed*, code -1); else None."""
+    (run_scalars_indexed*, code -1); index / reason: the lowest failing element and FIELD_ZERO / FIELD_NOT_SQUARE when code is EFIELD
+    (field_op*); else None."""
 
     def __init__(self, code: int, msg: str, index: int | None = None, reason: int | None = None, operand: int | None = None):
         super().__init__(f"te_msm error {code}: {msg}")
@@ -230,6 +236,11 @@ def _lib() -> ctypes.CDLL:
             L.te_msm_sum_device.restype = ci
             L.te_msm_sum_x.argtypes = [vp, cp, u64, cp]
             L.te_msm_sum_x.restype = ci
+        if not os.environ.get("TE_MSM_LIB") or hasattr(L, "te_msm_field_op"):
+            L.te_msm_field_op.argtypes = [vp, ci, ci, vp, vp, u64, ci, vp]
+            L.te_msm_field_op.restype = ci
+            L.te_msm_field_op_device.argtypes = [vp, ci, ci, vp, vp, u64, ci, vp]
+            L.te_msm_field_op_device.restype = ci
         _LIB = L
     return _LIB
 
@@ -271,6 +282,8 @@ class MsmContext:
             msg = self._L.te_msm_last_error(self._h).decode()
             if rc == EPOINT:
                 raise MsmError(rc, msg, self.get_option("bad_point_index"), self.get_option("bad_point_reason"), self._bad_operand())
+            if rc == EFIELD:
+                raise MsmError(rc, msg, self.get_option("bad_field_index"), self.get_option("bad_field_reason"))
             if rc == -1 and msg.startswith("index at position "):       # an indexed MSM (a call, or the collect of its ticket)
                 raise MsmError(rc, msg, self.get_option("bad_index_position"))
             raise MsmError(rc, msg)
@@ -542,6 +555,34 @@ class MsmContext:
         """te_msm_add_device: the same between buffers on one device of the context; d_out may be d_a or d_b; shared_b: d_b holds one point"""
         flags = (ADD_SUBTRACT if subtract else 0) | (ADD_SHARED_B if shared_b else 0)
         self._check(self._L.te_msm_add_device(self._h, d_a, d_b, n, flags, d_out))
+
+    # ---- batched field arithmetic (include/te_msm.h "batched field arithmetic"): the reference's bulk*Fields
+    @staticmethod
+    def _field_flags(shared_b: bool, montgomery: bool, zero_ok: bool) -> int:
+        return (FIELD_SHARED_B if shared_b else 0) | (FIELD_MONTGOMERY if montgomery else 0) | (FIELD_ZERO_OK if zero_ok else 0)
+
+    def field_op(self, op: int, a: bytes, b: bytes | None = None, *, field: int = FIELD_P, shared_b: bool = False, montgomery: bool = False,
+                 zero_ok: bool = False) -> bytes:
+        """te_msm_field_op: out[i] = a_i op b_i over n elements of 32 (FIELD_P) or 48 (FIELD_Q377) bytes; b for FIELD_ADD / SUB / MUL / POW
+        (an exponent is a 32-byte integer on both fields), one record of it with shared_b.  Inverting 0 without zero_ok and the root of a
+        non-square raise MsmError(EFIELD) with .index / .reason."""
+        eb = 48 if field == FIELD_Q377 else 32
+        if len(a) % eb:
+            raise MsmError(-1, f"a must be {eb}*n bytes")
+        n = len(a) // eb
+        if b is not None:
+            bb = 32 if op == FIELD_POW else eb
+            if len(b) != (bb if shared_b else bb * n):
+                raise MsmError(-1, f"b must be {bb} bytes for every element, or one record of them with shared_b")
+        out = ctypes.create_string_buffer(max(1, eb * n))
+        self._check(self._L.te_msm_field_op(self._h, field, op, bytes(a), None if b is None else bytes(b), n,
+                                            self._field_flags(shared_b, montgomery, zero_ok), out))
+        return out.raw[:eb * n]
+
+    def field_op_device(self, op: int, d_a: int, d_b: int | None, n: int, d_out: int, *, field: int = FIELD_P, shared_b: bool = False,
+                        montgomery: bool = False, zero_ok: bool = False):
+        """te_msm_field_op_device: the same between buffers on one device of the context; d_out may be d_a or d_b; d_b None for the ops of one operand"""
+        self._check(self._L.te_msm_field_op_device(self._h, field, op, d_a, d_b, n, self._field_flags(shared_b, montgomery, zero_ok), d_out))
 
     def add_x(self, ax: bytes, bx: bytes, subtract: bool = False) -> bytes:
         """te_msm_add_x, bulkAddGroups' counterpart: n x-only points a and n (or one) b (32 / 48 bytes, points_from_x's format) -> n points x || y"""

@@ -117,6 +117,9 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "bad_point_operand")) { *value = ctx->bad_point_operand; return 0; }
   if (!strcmp(key, "group_add_piece")) { *value = (int64_t)TE_MSM_GROUP_ADD_PIECE; return 0; }
   if (!strcmp(key, "group_sum_grid")) { *value = (int64_t)TE_MSM_GROUP_SUM_GRID; return 0; }
+  if (!strcmp(key, "bad_field_index")) { *value = ctx->bad_field_index; return 0; }
+  if (!strcmp(key, "bad_field_reason")) { *value = ctx->bad_field_reason; return 0; }
+  if (!strcmp(key, "field_inv_group")) { *value = (int64_t)TE_MSM_FIELD_INV_GROUP; return 0; }
   if (!strcmp(key, "bad_index_position")) { *value = ctx->bad_index_position; return 0; }
   if (!strcmp(key, "host_chunks")) { *value = ctx->opt_host_chunks; return 0; }
   if (!strcmp(key, "host_shard_min")) { *value = ctx->opt_host_shard_min; return 0; }

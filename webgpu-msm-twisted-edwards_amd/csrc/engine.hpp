@@ -1,6 +1,6 @@
 // engine.hpp -- what the translation units of libtemsm.so share: the context and its work sets, the plan, the requests a launch
 // sequence is asked with, and the functions that more than one unit calls.  No kernel header in here: te_msm.hip alone includes
-// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication / fixed-base / group-addition kernels
+// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication / fixed-base / group-addition / field-arithmetic kernels
 // (a non-template __global__ function may be defined once per library, and every inclusion repeats the device compile).
 //
 // The units:   te_msm.hip   the engine core: plan and buffers, the launch sequences, streams and queue probe, record slabs, uploads
@@ -8,7 +8,7 @@
 //              tickets.hip  te_msm_submit* / ticket_wait / collect
 //              bases.hip    bound point sets: bind, scalars-only, indexed and batched MSMs
 //              points.hip   point checks, x-only points, batch scalar multiplication (per point, and over one bound point with its
-//                           fixed-base table), batched group addition and point-set sums
+//                           fixed-base table), batched group addition and point-set sums, batched field arithmetic
 //              abi.hip      the rest of the C-ABI: options, trim, building blocks, host tails, debug reads
 // Everything in here has hidden visibility; a function only one unit calls is file-local there.  The library exports the C-ABI of
 // include/te_msm.h and nothing else of the engine.
@@ -239,6 +239,7 @@ struct te_ctx {
   int opt_check_points = 0;    // validate input points before an MSM / a bind: 0 off, 1 form, 2 form + subgroup (include/te_msm.h)
   int64_t bad_point_index = -1; int bad_point_reason = 0;   // the last TE_MSM_EPOINT (get_option "bad_point_index" / "bad_point_reason")
   int bad_point_operand = -1;       // ... and which operand of te_msm_add* held it: 0 = a (every call with one point buffer), 1 = b; -1 before any failure
+  int64_t bad_field_index = -1; int bad_field_reason = 0;   // the last TE_MSM_EFIELD (get_option "bad_field_index" / "bad_field_reason")
   int64_t bad_index_position = -1;  // te_msm_run_scalars_indexed*: lowest position of an index outside the bound set, of the last call that failed on one
   float stage_ms[te_eng::ST_COUNT + 2] = {};
   bool have_stage_ms = false;

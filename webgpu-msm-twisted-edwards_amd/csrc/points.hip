@@ -1,13 +1,15 @@
 // points.hip -- what the library does with points beside MSMs: validation (option "check_points", te_msm_check_points*), x-only
 // points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x), batch scalar multiplication (te_msm_mul*) and its fixed-base form
-// over one bound point (te_msm_bind_base, te_msm_mul_base*), batched group addition and point-set sums (te_msm_add*, te_msm_sum*).  The
-// one unit that includes the kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp and group_add.hip.hpp.
+// over one bound point (te_msm_bind_base, te_msm_mul_base*), batched group addition and point-set sums (te_msm_add*, te_msm_sum*), and
+// batched arithmetic in the two base fields (te_msm_field_op*).  The one unit that includes the kernels of check.hip.hpp,
+// from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp, group_add.hip.hpp and field_ops.hip.hpp.
 #include "engine.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
 #include "scalar_mul.hip.hpp"
 #include "mul_base.hip.hpp"
 #include "group_add.hip.hpp"
+#include "field_ops.hip.hpp"
 
 using namespace te_eng;
 
@@ -591,6 +593,168 @@ int sum_host(te_ctx* ctx, const uint8_t* src, bool x_only, uint64_t n, uint8_t* 
   sum_finish(curve, parts.data(), out);
   return 0;
 }
+// ---- batched field arithmetic (te_msm_field_op*; kernels in field_ops.hip.hpp) ------------------------------------------------------
+// One launch over the n elements on the device's check lane, except: a strict inversion runs k_field_zero_scan in front and waits for
+// its verdict; an inversion runs in pieces of kFieldInvPiece elements that share one slab; a square root of the device form writes into
+// a temporary of the call's own and is copied to d_out when no element was reported.  A failure is the check lane's report word
+// (check_code / check_decode): reason 1 zero, 2 not a square.  SHARED_B: the one record (or exponent) is a kernel argument, read to
+// the host first -- no lane reads b, so d_out == d_b needs no care there.
+constexpr uint64_t kFieldInvPiece = 1ull << 20;
+struct field_req { int field = 0, op = 0, flags = 0; te::fo_rec shared = {}; uint32_t group = FO_INV_GROUP_DEFAULT; };
+inline size_t field_bytes_of(int field) { return field == TE_MSM_FIELD_Q377 ? 48 : 32; }
+inline bool field_op_binary(int op) { return op == TE_MSM_FIELD_ADD || op == TE_MSM_FIELD_SUB || op == TE_MSM_FIELD_MUL || op == TE_MSM_FIELD_POW; }
+// bytes of one record of b: an exponent is 32 bytes on both fields
+inline size_t field_b_bytes_of(const field_req& q) { return q.op == TE_MSM_FIELD_POW ? 32 : field_bytes_of(q.field); }
+// elements of one inversion chain: FO_INV_GROUP_DEFAULT (measured; read-only option "field_inv_group"), or what TE_MSM_FIELD_INV_GROUP
+// names (1 .. FO_INV_GROUP_MAX: tools/field_ops_cost.py measures the candidates with it)
+uint32_t field_inv_group() {
+  const char* e = getenv("TE_MSM_FIELD_INV_GROUP");
+  const long v = e ? atol(e) : 0;
+  return v >= 1 && v <= (long)FO_INV_GROUP_MAX ? (uint32_t)v : FO_INV_GROUP_DEFAULT;
+}
+template <typename F> void with_limbs(int field, F&& f) {
+  if (field == TE_MSM_FIELD_Q377) f(std::integral_constant<int, 14>{});
+  else f(std::integral_constant<int, 9>{});
+}
+// k_field_map for add, sub, mul, double, neg, square: MONT is a template parameter of the products alone (field_ops.hip.hpp)
+template <int N> void launch_field_map(const field_req& q, dim3 grid, hipStream_t st, const uint4* a, const uint4* b, uint32_t m, uint4* o) {
+  const bool shared = (q.flags & TE_MSM_FIELD_SHARED_B) != 0, mont = (q.flags & TE_MSM_FIELD_MONTGOMERY) != 0;
+  auto go = [&](auto op, auto mt, auto bs) {
+    hipLaunchKernelGGL((te::k_field_map<N, decltype(op)::value, decltype(mt)::value, decltype(bs)::value>), grid, dim3(256), 0, st, a, b, q.shared, m, o);
+  };
+  using std::integral_constant;
+  const integral_constant<int, te::FO_B_ARRAY> arr; const integral_constant<int, te::FO_B_SHARED> sh; const integral_constant<int, te::FO_B_IS_A> same;
+  const integral_constant<int, te::FO_ADD> add; const integral_constant<int, te::FO_SUB> sub; const integral_constant<int, te::FO_MUL> mul; const integral_constant<int, te::FO_NEG> neg;
+  const std::false_type plain; const std::true_type mg;
+  switch (q.op) {
+    case TE_MSM_FIELD_ADD: if (shared) go(add, plain, sh); else go(add, plain, arr); break;
+    case TE_MSM_FIELD_DOUBLE: go(add, plain, same); break;
+    case TE_MSM_FIELD_SUB: if (shared) go(sub, plain, sh); else go(sub, plain, arr); break;
+    case TE_MSM_FIELD_NEG: go(neg, plain, same); break;
+    case TE_MSM_FIELD_MUL:
+      if (mont) { if (shared) go(mul, mg, sh); else go(mul, mg, arr); }
+      else { if (shared) go(mul, plain, sh); else go(mul, plain, arr); }
+      break;
+    default: if (mont) go(mul, mg, same); else go(mul, plain, same); break;   // TE_MSM_FIELD_SQUARE
+  }
+}
+// n elements a (and b) in the memory of devs[di] -> d_out, which may be d_a or d_b; returns when they are there.  TE_MSM_EFIELD: *bad /
+// *why hold the lowest failing index and its reason, and d_out is as it was -- unless out_is_scratch (the host form's staged copy), which
+// a failed square root leaves undefined
+int field_on(te_ctx* ctx, size_t di, const field_req& q, const void* d_a, const void* d_b, uint64_t n, void* d_out, bool out_is_scratch, int64_t* bad, int* why) {
+  *bad = -1; *why = 0;
+  if (n == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const size_t eb = field_bytes_of(q.field);
+  const bool mont = (q.flags & TE_MSM_FIELD_MONTGOMERY) != 0, shared = (q.flags & TE_MSM_FIELD_SHARED_B) != 0;
+  const uint32_t m = (uint32_t)n;
+  dev_tmp tmp;                                                      // the slab of an inversion's piece, or a square root's results
+  const uint64_t piece = std::min(n, kFieldInvPiece);
+  if (q.op == TE_MSM_FIELD_INV) { if (int rc = tmp_alloc(ctx, d, tmp, piece * (q.field == TE_MSM_FIELD_Q377 ? 64 : 48))) return rc; }
+  if (q.op == TE_MSM_FIELD_SQRT && !out_is_scratch) { if (int rc = tmp_alloc(ctx, d, tmp, n * eb)) return rc; }
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  hipStream_t st = lane.stream();
+  const uint4 *a4 = static_cast<const uint4*>(d_a), *b4 = static_cast<const uint4*>(d_b);
+  uint4* o4 = static_cast<uint4*>(d_out);
+  const dim3 grid((m + 255u) / 256u), block(256);
+  int rc = 0;
+  with_limbs(q.field, [&](auto nl) {
+    constexpr int N = decltype(nl)::value;
+    with_flag(mont, [&](auto mt) {
+      constexpr bool M = decltype(mt)::value;
+      if (q.op == TE_MSM_FIELD_INV) {
+        if (!(q.flags & TE_MSM_FIELD_ZERO_OK)) {
+          rc = [&]() -> int {
+            HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
+            hipLaunchKernelGGL(te::k_field_zero_scan<N>, grid, block, 0, st, a4, m, d.chk_word, n, (uint64_t)0);
+            HIP_TRY(ctx, hipGetLastError());
+            return lane.verdict(ctx, n, bad, why);
+          }();
+          if (rc) return;
+        }
+        for (uint64_t off = 0; off < n; off += piece) {
+          const uint32_t pm = (uint32_t)std::min(piece, n - off);
+          const dim3 igrid((pm + 256u * q.group - 1u) / (256u * q.group));
+          hipLaunchKernelGGL((te::k_field_inv<N, M>), igrid, block, 0, st, a4 + off * (eb / 16), pm, q.group, static_cast<uint4*>(tmp.p), (uint32_t)piece,
+                             o4 + off * (eb / 16), N == 9 ? te::kInvExpTe : te::kInvExp377);
+        }
+      } else if (q.op == TE_MSM_FIELD_POW) {
+        with_flag(shared, [&](auto sh) { hipLaunchKernelGGL((te::k_field_pow<N, M, decltype(sh)::value>), grid, block, 0, st, a4, b4, q.shared, m, o4); });
+      } else if (q.op == TE_MSM_FIELD_SQRT) {
+        uint4* r4 = out_is_scratch ? o4 : static_cast<uint4*>(tmp.p);
+        rc = [&]() -> int {
+          HIP_TRY(ctx, hipMemsetAsync(d.chk_word, 0, sizeof(unsigned long long), st));
+          hipLaunchKernelGGL((te::k_field_sqrt<N, M>), grid, block, 0, st, a4, m, r4, d.chk_word, n, (uint64_t)0, N == 9 ? te::kRootExpTe : te::kRootExp377);
+          HIP_TRY(ctx, hipGetLastError());
+          if (int v = lane.verdict(ctx, n, bad, why)) return v;
+          if (!out_is_scratch) HIP_TRY(ctx, hipMemcpyAsync(d_out, tmp.p, n * eb, hipMemcpyDeviceToDevice, st));
+          return 0;
+        }();
+      } else {
+        launch_field_map<N>(q, grid, st, a4, b4, m, o4);            // (reads the flag itself: only a product has two forms)
+      }
+    });
+  });
+  if (rc == TE_MSM_EPOINT) return TE_MSM_EFIELD;                    // (the lane's verdict: an element was reported)
+  if (rc) return rc;
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+// a failed element as the outcome of a call: remembered for get_option ("bad_field_index" / "bad_field_reason"), described in the error text
+int note_bad_field(te_ctx* ctx, int64_t index, int reason) {
+  ctx->bad_field_index = index; ctx->bad_field_reason = reason;
+  char buf[160];
+  snprintf(buf, sizeof buf, "field element %lld has no result (reason %d): %s", (long long)index, reason,
+           reason == TE_MSM_FIELD_ZERO ? "the inverse of 0 (TE_MSM_FIELD_ZERO_OK writes 0 instead)" : "not a square");
+  return set_err(ctx, TE_MSM_EFIELD, buf);
+}
+// what every te_msm_field_op* call checks first; q: the request, its shared record still empty
+int field_args(te_ctx* ctx, int field, int op, const void* a, const void* b, uint64_t n, int flags, const void* out, field_req& q) {
+  if (field != TE_MSM_FIELD_P && field != TE_MSM_FIELD_Q377) return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_op*: unknown field");
+  if (op < TE_MSM_FIELD_ADD || op > TE_MSM_FIELD_SQRT) return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_op*: unknown op");
+  if (flags & ~(TE_MSM_FIELD_SHARED_B | TE_MSM_FIELD_MONTGOMERY | TE_MSM_FIELD_ZERO_OK)) return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_op*: unknown flag bits");
+  if ((flags & TE_MSM_FIELD_ZERO_OK) && op != TE_MSM_FIELD_INV) return set_err(ctx, TE_MSM_EINVAL, "TE_MSM_FIELD_ZERO_OK belongs to TE_MSM_FIELD_INV alone");
+  if (!field_op_binary(op) && (b || (flags & TE_MSM_FIELD_SHARED_B))) return set_err(ctx, TE_MSM_EINVAL, "this op takes one operand: b must be NULL, without TE_MSM_FIELD_SHARED_B");
+  if (int rc = check_n(ctx, n)) return rc;
+  if (n > 0 && (!a || !out || (field_op_binary(op) && !b))) return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  q.field = field; q.op = op; q.flags = flags; q.group = field_inv_group();
+  return 0;
+}
+// the one record of b under SHARED_B (host memory) into the request
+void field_take_shared(field_req& q, const uint8_t* rec) {
+  memcpy(q.shared.w, rec, field_b_bytes_of(q));
+  uint32_t e[8];
+  memcpy(e, q.shared.w, 32);
+  q.shared.top = te::fo_exp_top(e);
+}
+// te_msm_field_op: host buffers, sliced over the devices; the result of a slice lands in its copy of a
+int field_host(te_ctx* ctx, field_req& q, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) {
+  const bool shared = (q.flags & TE_MSM_FIELD_SHARED_B) != 0, binary = field_op_binary(q.op);
+  const size_t eb = field_bytes_of(q.field), bb = field_b_bytes_of(q);
+  if (shared) field_take_shared(q, b);
+  const slice_plan sp(ctx, n);
+  struct slice_t { dev_tmp a, b; int64_t bad = -1; int why = 0; };
+  std::vector<slice_t> sl(sp.D);
+  auto stage = [&](size_t i) -> int {                             // upload and compute: everything but the copy out
+    const uint64_t lo = sp.lo(i), m = sp.count(i);
+    if (m == 0) return 0;
+    slice_t& s = sl[i];
+    if (int rc = tmp_alloc(ctx, ctx->devs[i], s.a, m * eb)) return rc;
+    HIP_TRY(ctx, hipMemcpy(s.a.p, a + lo * eb, m * eb, hipMemcpyHostToDevice));
+    if (binary && !shared) {
+      if (int rc = tmp_alloc(ctx, ctx->devs[i], s.b, m * bb)) return rc;
+      HIP_TRY(ctx, hipMemcpy(s.b.p, b + lo * bb, m * bb, hipMemcpyHostToDevice));
+    }
+    const int rc = field_on(ctx, i, q, s.a.p, s.b.p, m, s.a.p, true, &s.bad, &s.why);
+    return rc == TE_MSM_EFIELD ? 0 : rc;
+  };
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  for (size_t i = 0; i < sp.D; i++)                               // slices in order: the first that reports holds the lowest index
+    if (sl[i].bad >= 0) return note_bad_field(ctx, (int64_t)sp.lo(i) + sl[i].bad, sl[i].why);
+  return copy_slices_out(ctx, sp, eb, out, [&](size_t i) { return sl[i].a.p; });
+}
 }  // namespace
 
 void free_mul_base(te_ctx* ctx, te_base* b) {
@@ -888,6 +1052,36 @@ int64_t te_msm_base_read(te_ctx* ctx, const te_base* base, int device_index, uin
   HIP_TRY(ctx, hipSetDevice(ctx->devs[(size_t)device_index].device));
   HIP_TRY(ctx, hipMemcpy(dst, base->tab[(size_t)device_index] + ((size_t)window * base->per + first) * 128, bytes, hipMemcpyDeviceToHost));
   return (int64_t)bytes;
+}
+
+int te_msm_field_op(te_ctx* ctx, int field, int op, const uint8_t* a, const uint8_t* b, uint64_t n, int flags, uint8_t* out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  field_req q;
+  if (int rc = field_args(ctx, field, op, a, b, n, flags, out, q)) return rc;
+  return n ? field_host(ctx, q, a, b, n, out) : 0;
+}
+
+int te_msm_field_op_device(te_ctx* ctx, int field, int op, const void* d_a, const void* d_b, uint64_t n, int flags, void* d_out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  field_req q;
+  if (int rc = field_args(ctx, field, op, d_a, d_b, n, flags, d_out, q)) return rc;
+  if (n == 0) return 0;
+  const char* const where = "te_msm_field_op_device: the operands and the output must be resident on one device of the context";
+  const int owner = d_b ? owner_of(ctx, where, {d_a, d_b, d_out}) : owner_of(ctx, where, {d_a, d_out});
+  if (owner < 0) return owner;
+  if (op == TE_MSM_FIELD_POW && field == TE_MSM_FIELD_Q377 && d_out == d_b && !(flags & TE_MSM_FIELD_SHARED_B))
+    return set_err(ctx, TE_MSM_EINVAL, "TE_MSM_FIELD_POW on TE_MSM_FIELD_Q377: d_out may not be d_b (32-byte exponents, 48-byte results)");
+  if (flags & TE_MSM_FIELD_SHARED_B) {                              // the one record comes back: it is a kernel argument
+    uint8_t rec[48];
+    HIP_TRY(ctx, hipSetDevice(ctx->devs[(size_t)owner].device));
+    HIP_TRY(ctx, hipMemcpy(rec, d_b, field_b_bytes_of(q), hipMemcpyDeviceToHost));
+    field_take_shared(q, rec);
+  }
+  int64_t bad = -1; int why = 0;
+  const int rc = field_on(ctx, (size_t)owner, q, d_a, d_b, n, d_out, false, &bad, &why);
+  return rc == TE_MSM_EFIELD ? note_bad_field(ctx, bad, why) : rc;
 }
 
 }  // extern "C"

@@ -543,6 +543,74 @@ napi_value GroupAddX(napi_env env, napi_callback_info info) { return AddCommon(e
 napi_value GroupSum(napi_env env, napi_callback_info info) { return SumCommon(env, info, false); }
 napi_value GroupSumX(napi_env env, napi_callback_info info) { return SumCommon(env, info, true); }
 
+// fieldOp(op: number, a: Buffer, b: Buffer | null, opts?: {field?: 0 | 1, sharedB?: boolean, montgomery?: boolean, zeroOk?: boolean}): Buffer --
+// batched field arithmetic (include/te_msm.h, te_msm_field_op): n elements a of 32 (field 0: p, Aleo's `field`) or 48 bytes (field 1: q of
+// BLS12-377) and, for TE_MSM_FIELD_ADD / SUB / MUL / POW, n records b (an exponent is 32 bytes on both fields) or ONE with sharedB ->
+// n elements a_i op b_i; b null for the ops of one operand.  The counterpart of the reference's bulk*Fields; run like groupAdd.  The inverse
+// of 0 without zeroOk and the root of a non-square throw an Error naming the lowest failing index, also as .index / .reason (1 zero, 2 not
+// a square); compute_msm.js wraps the call into a promise, which then rejects with that Error.
+napi_value FieldOp(napi_env env, napi_callback_info info) {
+  const char* const sig = "fieldOp(op: number, a: Buffer, b: Buffer | null, opts?: {field?: 0 | 1, sharedB?: boolean, montgomery?: boolean, zeroOk?: boolean})";
+  size_t argc = 4; napi_value argv[4];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool a_buf = false, b_buf = false;
+  napi_valuetype t_op = napi_undefined, t_b = napi_undefined, t_opts = napi_undefined;
+  if (argc >= 1) napi_typeof(env, argv[0], &t_op);
+  if (argc >= 2) napi_is_buffer(env, argv[1], &a_buf);
+  if (argc >= 3) { napi_typeof(env, argv[2], &t_b); napi_is_buffer(env, argv[2], &b_buf); }
+  if (argc >= 4) napi_typeof(env, argv[3], &t_opts);
+  const bool b_none = t_b == napi_undefined || t_b == napi_null, opts_none = t_opts == napi_undefined || t_opts == napi_null;
+  if (t_op != napi_number || !a_buf || (!b_buf && !b_none) || (t_opts != napi_object && !opts_none)) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  int32_t op = -1, field = TE_MSM_FIELD_P;
+  napi_get_value_int32(env, argv[0], &op);
+  int flags = 0;
+  if (t_opts == napi_object) {
+    const struct { const char* name; int bit; } bits[] = {{"sharedB", TE_MSM_FIELD_SHARED_B}, {"montgomery", TE_MSM_FIELD_MONTGOMERY}, {"zeroOk", TE_MSM_FIELD_ZERO_OK}};
+    for (const auto& f : bits) {
+      napi_value v; bool has = false, on = false;
+      napi_has_named_property(env, argv[3], f.name, &has);
+      if (has) { napi_get_named_property(env, argv[3], f.name, &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &on); }
+      if (on) flags |= f.bit;
+    }
+    napi_value v; bool has = false;
+    napi_has_named_property(env, argv[3], "field", &has);
+    if (has) { napi_get_named_property(env, argv[3], "field", &v); if (napi_get_value_int32(env, v, &field) != napi_ok) { napi_throw_type_error(env, nullptr, sig); return nullptr; } }
+  }
+  void *pa = nullptr, *pb = nullptr; size_t al = 0, bl = 0;
+  napi_get_buffer_info(env, argv[1], &pa, &al);
+  if (b_buf) napi_get_buffer_info(env, argv[2], &pb, &bl);
+  const size_t eb = field == TE_MSM_FIELD_Q377 ? 48 : 32, bb = op == TE_MSM_FIELD_POW ? 32 : eb;
+  const uint64_t n = al / eb;
+  if (al % eb != 0 || (b_buf && bl != ((flags & TE_MSM_FIELD_SHARED_B) ? bb : n * bb))) {
+    napi_throw_range_error(env, nullptr, "fieldOp: a must be 32*n (48*n on field 1) bytes, b one record per element (32 bytes for an exponent) or one record with sharedB");
+    return nullptr;
+  }
+  std::vector<uint8_t> out((size_t)n * eb);
+  int64_t bad = -1, reason = 0;
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    const int r = te_msm_field_op(c, field, op, static_cast<const uint8_t*>(pa), b_buf ? static_cast<const uint8_t*>(pb) : nullptr, n, flags, out.data());
+    if (r == TE_MSM_EFIELD) { (void)te_msm_get_option(c, "bad_field_index", &bad); (void)te_msm_get_option(c, "bad_field_reason", &reason); }
+    return r;
+  }, err);
+  if (rc) {
+    const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_value msg, errv;
+    napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+    napi_create_error(env, nullptr, msg, &errv);
+    if (rc == TE_MSM_EFIELD) {
+      napi_value iv, rv;
+      napi_create_int64(env, bad, &iv); napi_create_int32(env, (int32_t)reason, &rv);
+      napi_set_named_property(env, errv, "index", iv); napi_set_named_property(env, errv, "reason", rv);
+    }
+    napi_throw(env, errv);
+    return nullptr;
+  }
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
+  return buf;
+}
+
 // setBase(point: Buffer) and scalarMulBase(scalars: Buffer): Buffer -- fixed-base batch scalar multiplication (include/te_msm.h,
 // te_msm_bind_base / te_msm_mul_base): one 64-byte point bound once, then n x 32-byte little-endian scalars -> n x 64-byte points
 // [k_i] P (the identity as (0, 1)).  Twisted-Edwards curve only, like the rest of the addon; run like scalarMul.  The addon keeps the
@@ -714,7 +782,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"setScalarRecordBytes", SetScalarRecordBytes}, {"setScalarBits", SetScalarBits},
       {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed},
       {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase},
-      {"groupAdd", GroupAdd}, {"groupAddX", GroupAddX}, {"groupSum", GroupSum}, {"groupSumX", GroupSumX}};
+      {"groupAdd", GroupAdd}, {"groupAddX", GroupAddX}, {"groupSum", GroupSum}, {"groupSumX", GroupSumX},
+      {"fieldOp", FieldOp}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

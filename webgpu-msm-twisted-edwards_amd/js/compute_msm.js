@@ -91,6 +91,14 @@ const groupAdd = (a, b, opts) => native.groupAdd(a, b, opts);
 const groupAddX = (ax, bx, opts) => native.groupAddX(ax, bx, opts);
 const groupSum = (points) => native.groupSum(points);
 const groupSumX = (xs) => native.groupSumX(xs);
+// fieldOp(op, a, b, {field, sharedB, montgomery, zeroOk}): batched field arithmetic on the device, the counterpart of the reference's
+// bulkAddFields / bulkSubFields / bulkMulFields / bulkDoubleFields / bulkInvertFields / bulkPowFields / bulkPowFields17 / bulkSqrtFields.
+// op: FIELD_OPS.add ..; a: n elements of 32 bytes (field 0: p, Aleo's `field`) or 48 (field 1: BLS12-377's q); b: n records, one with
+// sharedB, or null for double / neg / square / inv / sqrt; an exponent is a 32-byte integer.  Resolves to the n results as a Buffer
+// (canonical; the smaller square root).  Rejects for the inverse of 0 without zeroOk and for the root of a non-square: the Error has
+// .index (the lowest failing element) and .reason (1 zero, 2 not a square).
+const FIELD_OPS = { add: 0, sub: 1, mul: 2, double: 3, neg: 4, square: 5, inv: 6, pow: 7, sqrt: 8 };
+const fieldOp = async (op, a, b, opts) => native.fieldOp(op, a, b === undefined ? null : b, opts);
 
 // Outside the reference's interface too: msmBatch(scalarBuffers) runs one MSM per Buffer over the set bound by setBases -- MSM m over
 // its first scalarBuffers[m].length / 32 points (a prover's commitments to polynomials of different degrees against one SRS) -- and
@@ -111,4 +119,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS };

@@ -48,6 +48,14 @@ export declare const groupAdd: (a: Buffer, b: Buffer, opts?: { subtract?: boolea
 export declare const groupAddX: (ax: Buffer, bx: Buffer, opts?: { subtract?: boolean }) => Buffer;
 export declare const groupSum: (points: Buffer) => Buffer;
 export declare const groupSumX: (xs: Buffer) => Buffer;
+// Not in the reference's interface: batched field arithmetic on the device (its bulk*Fields run on the CPU, one WASM call per element).
+// a: n elements of 32 bytes (field 0: p, Aleo's `field`) or 48 (field 1: BLS12-377's base field); b: n records, ONE with sharedB, or null
+// for double / neg / square / inv / sqrt; an exponent is a 32-byte integer (bulkPowFields17: pow, sharedB, b = 17).  montgomery: inputs
+// and outputs are residues v * 2^256 mod p / v * 2^384 mod q.  Resolves to the n canonical results (sqrt: the smaller root).  The inverse
+// of 0 without zeroOk and the root of a non-square reject with an Error whose .index is the lowest failing element and .reason 1 / 2.
+export declare const FIELD_OPS: { add: 0, sub: 1, mul: 2, double: 3, neg: 4, square: 5, inv: 6, pow: 7, sqrt: 8 };
+export declare const fieldOp: (op: number, a: Buffer, b?: Buffer | null,
+  opts?: { field?: 0 | 1, sharedB?: boolean, montgomery?: boolean, zeroOk?: boolean }) => Promise<Buffer>;
 // Not in the reference: batched MSMs over prefixes of the set bound by setBases; MSM m runs over the first scalarBuffers[m].length / 32
 // points.  Results in input order, in compute_msm's form; throws without setBases or for a buffer longer than the set.
 export declare const msmBatch: (scalarBuffers: Buffer[]) => { x: bigint; y: bigint }[];
