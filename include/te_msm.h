@@ -525,6 +525,48 @@ int te_msm_sum_x(te_ctx* ctx, const uint8_t* x_le, uint64_t n, uint8_t* out_xy_l
 int te_msm_field_op(te_ctx* ctx, int field, int op, const uint8_t* a, const uint8_t* b, uint64_t n, int flags, uint8_t* out);
 int te_msm_field_op_device(te_ctx* ctx, int field, int op, const void* d_a, const void* d_b, uint64_t n, int flags, void* d_out);
 
+/* ---- batched NTTs ---------------------------------------------------------------------------------------------------------------
+ * te_msm_ntt*: `count` number-theoretic transforms of n = 2^log_n elements each over p (TE_MSM_FIELD_P: Aleo's `field`, BLS12-377's
+ * Fr), the radix-2 domains of arkworks / snarkVM (Radix2EvaluationDomain): the step of a Marlin / KZG prover between its pointwise
+ * arithmetic (te_msm_field_op_device) and its commitments (te_msm_run_scalars_device), so that the vector stays on the device.
+ * a holds the count transforms back to back, 32-byte little-endian records, natural order in and out.
+ *   W = 22^((p - 1) / 2^47) mod p = 8065159656716812877374967518403273466521432693661810619979959746626482506078 (order 2^47: arkworks'
+ *   TWO_ADIC_ROOT_OF_UNITY), w = W^(2^(47 - log_n)), s = the shift (1 when `shift` is NULL):
+ *     forward                       out[j] = sum_i a_i s^i w^(i j)                     (coset_fft with generator s)
+ *     TE_MSM_NTT_INVERSE            out[i] = s^-i n^-1 sum_j a_j w^(-i j)              (coset_ifft: undoes the forward with the same s)
+ * shift: a HOST pointer to one 32-byte record in both forms, or NULL.
+ * flags: TE_MSM_NTT_INVERSE; TE_MSM_NTT_MONTGOMERY -- a, s and out hold v * 2^256 mod p (a native prover's residues).  Any other bit:
+ *   TE_MSM_EINVAL.
+ * Values: as te_msm_field_op -- ANY 256-bit value stands for its residue, outputs are canonical.  log_n = 0 is the reduced copy.
+ *   count = 0 succeeds and touches nothing.
+ * Refusals, all TE_MSM_EINVAL with the output untouched and the context usable: log_n > TE_MSM_NTT_MAX_LOG_N; an unknown flag bit;
+ *   s = 0 mod p (s = p included), in either direction; NULL a / out with count > 0; count * n * 32 beyond 64 bits; te_msm_ntt_device:
+ *   d_a and d_out not on one device of the context.
+ * Buffers: out may be exactly a (partial overlap is the caller's error).  te_msm_ntt_device returns with d_out complete.  te_msm_ntt
+ *   slices WHOLE transforms over the context's devices, one host thread per device, each slice staged on its device (one transform
+ *   runs on one device).  Every element and byte offset is 64 bits wide: count * n * 32 may pass 2^32.  A shift's tables (384 KB) and the
+ *   host form's staged copies are freed before return; the buffer between the passes of a multi-pass size (the records of the call's
+ *   transforms, at most 2^24 elements: 512 MB) is the device's, grown on use and kept until te_msm_trim / te_msm_destroy -- allocating
+ *   32 MB per call cost more than the three passes over it.  The calling thread's device is left as it was.
+ * How it runs (csrc/ntt_plan.hpp, csrc/ntt.hip.hpp): one kernel; a 256-lane block stages a tile of 2^10 elements
+ *   in LDS as 9 x 29-bit limbs and runs up to 10 radix-2 stages on it, one field product a butterfly.  n <= 2^10: one launch, 2^(10 -
+ *   log_n) transforms a block.  n <= 2^16: two passes, above: three (2^24 = 8 + 8 + 8), over a buffer of the call's own; the last pass
+ *   writes natural order (no bit-reversal pass).  Twiddles: w^e = hi[e >> 12] lo[e & 4095] from two tables of 4096 powers of a root of
+ *   order 2^24 (384 KB a device, built on the device at the first transform, kept until te_msm_trim / te_msm_destroy; the inverse
+ *   reads them at the negated index).  Read-only options: "ntt_max_log_n"; "ntt_table_bytes" and "ntt_scratch_bytes" (what the context's devices hold now
+ *   of tables, and of the buffer between passes).
+ * COST (MI355X, device form, in place, three alternating rounds, lowest .. highest; tools/ntt_cost.py, profiles/ntt_cost.txt), forward /
+ *   inverse: 1024 x 2^10 0.095 .. 0.103 / 0.101 .. 0.107 ms; 16 x 2^16 0.145 .. 0.159 / 0.154 .. 0.158; 2^20 0.193 .. 0.210 / 0.199 ..
+ *   0.208 (with a shift 0.225 .. 0.242); 2^24 2.70 .. 3.08 / 2.53 .. 2.67 ms.  Beside them, in the same rounds: a device copy of the same
+ *   bytes times the passes 0.021, 0.030, 0.040, 0.61 ms; te_msm_field_op_device(MUL) over n log_n / 2 elements a transform 0.102, 0.151 ..
+ *   0.156, 0.186 .. 0.193, 3.76 .. 3.84 ms -- the products bind everywhere, and a transform costs 0.72x .. 1.04x of that yardstick.
+ *   The link alone of the host round trip the device form replaces: 1.19 ms for 2^20 elements, 18.7 ms for 2^24. */
+#define TE_MSM_NTT_INVERSE 1
+#define TE_MSM_NTT_MONTGOMERY 2
+#define TE_MSM_NTT_MAX_LOG_N 24u
+int te_msm_ntt(te_ctx* ctx, const uint8_t* a, uint32_t log_n, uint64_t count, int flags, const uint8_t* shift, uint8_t* out);
+int te_msm_ntt_device(te_ctx* ctx, const void* d_a, uint32_t log_n, uint64_t count, int flags, const uint8_t* shift, void* d_out);
+
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "scalars_montgomery" 0 (default) = scalar records hold the integers themselves (the wire format above); 1 = every scalar record holds
  *                   a = k * 2^256 mod m and the MSM uses k = a * 2^-256 mod m, where m is the scalar field of the curve in force:

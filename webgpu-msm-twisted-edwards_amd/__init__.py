@@ -56,5 +56,8 @@ from .binding import (  # noqa: F401
     FIELD_ZERO_OK,
     FIELD_ZERO,
     FIELD_NOT_SQUARE,
+    NTT_INVERSE,
+    NTT_MONTGOMERY,
+    NTT_MAX_LOG_N,
 )
 from .sharding import ShardedPipeline, compute_msm_sharded, distribute_inputs, exchange_partials, merge_partials, rows_of_batched_msm, window_shard_for_rank  # noqa: F401

@@ -27,6 +27,8 @@ EFIELD = -6             # TE_MSM_EFIELD: a field element has no result (field_op
 FIELD_P, FIELD_Q377 = 0, 1               # TE_MSM_FIELD_P / _Q377: 32-byte elements mod p (Aleo `field`, BLS12-377 Fr), 48-byte elements mod q
 FIELD_ADD, FIELD_SUB, FIELD_MUL, FIELD_DOUBLE, FIELD_NEG, FIELD_SQUARE, FIELD_INV, FIELD_POW, FIELD_SQRT = range(9)     # TE_MSM_FIELD_<op>
 FIELD_SHARED_B, FIELD_MONTGOMERY, FIELD_ZERO_OK = 1, 2, 4      # flags of te_msm_field_op*
+NTT_INVERSE, NTT_MONTGOMERY = 1, 2                              # flags of te_msm_ntt*
+NTT_MAX_LOG_N = 24
 FIELD_ZERO, FIELD_NOT_SQUARE = 1, 2      # why an element has no result (MsmError.reason)
 
 
@@ -241,6 +243,11 @@ def _lib() -> ctypes.CDLL:
             L.te_msm_field_op.restype = ci
             L.te_msm_field_op_device.argtypes = [vp, ci, ci, vp, vp, u64, ci, vp]
             L.te_msm_field_op_device.restype = ci
+        if not os.environ.get("TE_MSM_LIB") or hasattr(L, "te_msm_ntt"):
+            L.te_msm_ntt.argtypes = [vp, vp, ctypes.c_uint32, u64, ci, vp, vp]
+            L.te_msm_ntt.restype = ci
+            L.te_msm_ntt_device.argtypes = [vp, vp, ctypes.c_uint32, u64, ci, vp, vp]
+            L.te_msm_ntt_device.restype = ci
         _LIB = L
     return _LIB
 
@@ -583,6 +590,32 @@ class MsmContext:
                         montgomery: bool = False, zero_ok: bool = False):
         """te_msm_field_op_device: the same between buffers on one device of the context; d_out may be d_a or d_b; d_b None for the ops of one operand"""
         self._check(self._L.te_msm_field_op_device(self._h, field, op, d_a, d_b, n, self._field_flags(shared_b, montgomery, zero_ok), d_out))
+
+    # ---- batched NTTs over p (include/te_msm.h "batched NTTs"): arkworks' radix-2 domains of BLS12-377's scalar field
+    @staticmethod
+    def _ntt_args(inverse: bool, montgomery: bool, shift):
+        flags = (NTT_INVERSE if inverse else 0) | (NTT_MONTGOMERY if montgomery else 0)
+        if shift is None:
+            return flags, None
+        rec = int(shift).to_bytes(32, "little") if isinstance(shift, int) else bytes(shift)
+        if len(rec) != 32:
+            raise MsmError(-1, "shift must be one 32-byte record (or an integer below 2^256)")
+        return flags, rec
+
+    def ntt(self, a: bytes, log_n: int, *, count: int = 1, inverse: bool = False, montgomery: bool = False, shift=None) -> bytes:
+        """te_msm_ntt: `count` transforms of 2^log_n 32-byte elements of p each, natural order in and out; shift: the coset generator s
+        (an integer or a 32-byte record; in the Montgomery form with `montgomery`), None for s = 1.  inverse undoes the forward with the same s."""
+        if log_n < 0 or count < 0 or len(a) != (32 * count) << min(log_n, 40):
+            raise MsmError(-1, "a must be count * 2^log_n * 32 bytes")
+        flags, rec = self._ntt_args(inverse, montgomery, shift)
+        out = ctypes.create_string_buffer(max(1, len(a)))
+        self._check(self._L.te_msm_ntt(self._h, bytes(a), log_n, count, flags, rec, out))
+        return out.raw[:len(a)]
+
+    def ntt_device(self, d_a: int, log_n: int, count: int, d_out: int, *, inverse: bool = False, montgomery: bool = False, shift=None):
+        """te_msm_ntt_device: the same between buffers on one device of the context; d_out may be d_a.  shift stays a host value"""
+        flags, rec = self._ntt_args(inverse, montgomery, shift)
+        self._check(self._L.te_msm_ntt_device(self._h, d_a, log_n, count, flags, rec, d_out))
 
     def add_x(self, ax: bytes, bx: bytes, subtract: bool = False) -> bytes:
         """te_msm_add_x, bulkAddGroups' counterpart: n x-only points a and n (or one) b (32 / 48 bytes, points_from_x's format) -> n points x || y"""

@@ -40,6 +40,7 @@ int te_msm_trim(te_ctx* ctx, int keep_worksets) {
       free_workset_buffers(ws);
       freed++;
     }
+    { std::lock_guard<std::mutex> lk(*d.chk_mu); d.ntt_tab.release(); d.ntt_tmp.release(); }      // the NTT twiddle tables and scratch: made again by the next transform (none runs: it holds chk_mu)
     for (auto& sl : d.slabs) if (sl.users == 0 && sl.d) {                    // idle shared record slabs
       if (int rc = settle_slab(ctx, sl, nullptr, true)) return rc;
       for (workset_t& ws : d.ws) if (ws.recs_last == sl.d) ws.recs_last = nullptr;
@@ -120,6 +121,17 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "bad_field_index")) { *value = ctx->bad_field_index; return 0; }
   if (!strcmp(key, "bad_field_reason")) { *value = ctx->bad_field_reason; return 0; }
   if (!strcmp(key, "field_inv_group")) { *value = (int64_t)TE_MSM_FIELD_INV_GROUP; return 0; }
+  if (!strcmp(key, "ntt_max_log_n")) { *value = (int64_t)TE_MSM_NTT_MAX_LOG_N; return 0; }
+  if (!strcmp(key, "ntt_table_bytes")) {                               // twiddle tables the context holds, over its devices
+    *value = 0;
+    for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.ntt_tab.p ? (int64_t)d.ntt_tab.cap : 0; }
+    return 0;
+  }
+  if (!strcmp(key, "ntt_scratch_bytes")) {                             // ... and the buffer between the passes of multi-pass transforms
+    *value = 0;
+    for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.ntt_tmp.p ? (int64_t)d.ntt_tmp.cap : 0; }
+    return 0;
+  }
   if (!strcmp(key, "bad_index_position")) { *value = ctx->bad_index_position; return 0; }
   if (!strcmp(key, "host_chunks")) { *value = ctx->opt_host_chunks; return 0; }
   if (!strcmp(key, "host_shard_min")) { *value = ctx->opt_host_shard_min; return 0; }

@@ -1,6 +1,6 @@
 // engine.hpp -- what the translation units of libtemsm.so share: the context and its work sets, the plan, the requests a launch
 // sequence is asked with, and the functions that more than one unit calls.  No kernel header in here: te_msm.hip alone includes
-// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication / fixed-base / group-addition / field-arithmetic kernels
+// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication / fixed-base / group-addition / field-arithmetic / NTT kernels
 // (a non-template __global__ function may be defined once per library, and every inclusion repeats the device compile).
 //
 // The units:   te_msm.hip   the engine core: plan and buffers, the launch sequences, streams and queue probe, record slabs, uploads
@@ -8,7 +8,7 @@
 //              tickets.hip  te_msm_submit* / ticket_wait / collect
 //              bases.hip    bound point sets: bind, scalars-only, indexed and batched MSMs
 //              points.hip   point checks, x-only points, batch scalar multiplication (per point, and over one bound point with its
-//                           fixed-base table), batched group addition and point-set sums, batched field arithmetic
+//                           fixed-base table), batched group addition and point-set sums, batched field arithmetic, batched NTTs
 //              abi.hip      the rest of the C-ABI: options, trim, building blocks, host tails, debug reads
 // Everything in here has hidden visibility; a function only one unit calls is file-local there.  The library exports the C-ABI of
 // include/te_msm.h and nothing else of the engine.
@@ -36,6 +36,7 @@
 #include "indexed_plan.hpp"
 #include "plan_arith.hpp"
 #include "fb_plan.hpp"
+#include "ntt_plan.hpp"
 
 #pragma GCC visibility push(hidden)
 #include "host_sched.hpp"
@@ -202,6 +203,10 @@ struct gpu_t {
   bool streams_exported = false;         // te_msm_workset_stream handed a handle out: te_msm_destroy parks the streams instead of destroying them
   bool streams_final = false;            // ... and the work sets' streams will not be re-dealt any more
   uint8_t* h_batch_rows = nullptr; size_t h_batch_cap = 0;   // te_msm_run_scalars_batch: pinned landing area of every sequence's rows (grown on use)
+  dev_buf<uint32_t> ntt_tab;             // te_msm_ntt*: the twiddle tables hi | lo (ntt_plan.hpp), built at the first transform on the device under chk_mu;
+                                         // te_msm_trim / destroy free them (get_option "ntt_table_bytes")
+  dev_buf<uint8_t> ntt_tmp;              // ... and the buffer between the passes of a multi-pass transform (ntt_plan.hpp, tmp_records_for: at most 512 MB), grown on
+                                         // use under chk_mu, freed with the tables (get_option "ntt_scratch_bytes")
 };
 
 }  // namespace te_eng

@@ -1,8 +1,8 @@
 // points.hip -- what the library does with points beside MSMs: validation (option "check_points", te_msm_check_points*), x-only
 // points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x), batch scalar multiplication (te_msm_mul*) and its fixed-base form
 // over one bound point (te_msm_bind_base, te_msm_mul_base*), batched group addition and point-set sums (te_msm_add*, te_msm_sum*), and
-// batched arithmetic in the two base fields (te_msm_field_op*).  The one unit that includes the kernels of check.hip.hpp,
-// from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp, group_add.hip.hpp and field_ops.hip.hpp.
+// batched arithmetic in the two base fields (te_msm_field_op*) and batched NTTs over p (te_msm_ntt*).  The one unit that includes the
+// kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp, group_add.hip.hpp, field_ops.hip.hpp and ntt.hip.hpp.
 #include "engine.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
@@ -10,6 +10,7 @@
 #include "mul_base.hip.hpp"
 #include "group_add.hip.hpp"
 #include "field_ops.hip.hpp"
+#include "ntt.hip.hpp"
 
 using namespace te_eng;
 
@@ -755,6 +756,104 @@ int field_host(te_ctx* ctx, field_req& q, const uint8_t* a, const uint8_t* b, ui
     if (sl[i].bad >= 0) return note_bad_field(ctx, (int64_t)sp.lo(i) + sl[i].bad, sl[i].why);
   return copy_slices_out(ctx, sp, eb, out, [&](size_t i) { return sl[i].a.p; });
 }
+
+// ---- batched NTTs over p (te_msm_ntt*; kernels in ntt.hip.hpp, plan in ntt_plan.hpp) -------------------------------------------------
+// `count` transforms on the device's check lane, in pieces of the plan's piece_transforms; a piece runs the plan's passes back to back:
+// a -> out (one pass), or a -> tmp (-> tmp) -> out, tmp the device's scratch buffer (grown on use, held like the tables; the lane's mutex
+// serialises its users).  The twiddle tables of the device are built by the
+// first call (k_ntt_table from Omega = W^(2^23) and Omega^4096, computed here with the host build of the field) and stay until
+// te_msm_trim / destroy; a call with a shift builds its two tables of powers of s (forward) or 1 / s (inverse) the same way, with
+// the decoding / encoding constant folded into the hi table.  1 / s and 1 / n are one fe_inv each, here.
+using te::ntt_req;
+// entries of one table on st: g^j, times pre as a plain factor when with_pre (k_ntt_table)
+void ntt_table_launch(hipStream_t st, const te::fel<9>& g, const te::fel<9>& pre, bool with_pre, uint32_t* out) {
+  hipLaunchKernelGGL(te::k_ntt_table, dim3(te_ntt::kTabEntries / 256u), dim3(256), 0, st, g, pre, with_pre ? 1 : 0, out);
+}
+// the twiddle tables of d, built on st (the lane's stream, held by the caller)
+int ntt_tables_on(te_ctx* ctx, gpu_t& d, hipStream_t st) {
+  if (d.ntt_tab.p) return 0;
+  if (int rc = make_room(ctx, d.ntt_tab, 2 * te_ntt::kTabBytes / sizeof(uint32_t))) return rc;
+  te::fel<9> hi, lo;
+  te::ntt_twiddle_gens(hi, lo);
+  ntt_table_launch(st, hi, hi, false, d.ntt_tab.p);
+  ntt_table_launch(st, lo, lo, false, d.ntt_tab.p + te_ntt::kTabEntries * te_ntt::kTabWords);
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+int ntt_on(te_ctx* ctx, size_t di, const ntt_req& q, const void* d_a, uint64_t count, void* d_out) {
+  if (count == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  const te_ntt::plan P = te_ntt::make_plan(q.log_n);
+  dev_tmp sh;
+  if (q.shifted) { if (int rc = tmp_alloc(ctx, d, sh, 2 * te_ntt::kTabBytes)) return rc; }
+  const te::ntt_consts k = te::ntt_consts_of(q);
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  hipStream_t st = lane.stream();
+  if (int rc = ntt_tables_on(ctx, d, st)) return rc;
+  // tmp is the device's own, grown on use and kept (allocating and freeing 32 MB a call cost more than the three passes over it)
+  if (P.passes > 1) { if (int rc = make_room(ctx, d.ntt_tmp, (size_t)te_ntt::tmp_records_for(P, count) * 32)) return rc; }
+  uint8_t* const tmp = d.ntt_tmp.p;
+  te::ntt_tabs tb;
+  tb.hi = d.ntt_tab.p; tb.lo = d.ntt_tab.p + te_ntt::kTabEntries * te_ntt::kTabWords;
+  tb.sh_hi = tb.sh_lo = nullptr;
+  if (q.shifted) {
+    uint32_t* t = static_cast<uint32_t*>(sh.p);
+    te::fel<9> hi, lo;
+    te::ntt_shift_gens(q, hi, lo);
+    ntt_table_launch(st, hi, q.inverse ? k.enc : k.dec, true, t);
+    ntt_table_launch(st, lo, lo, false, t + te_ntt::kTabEntries * te_ntt::kTabWords);
+    tb.sh_hi = t; tb.sh_lo = t + te_ntt::kTabEntries * te_ntt::kTabWords;
+  }
+  const size_t rec4 = (size_t)2 << q.log_n;                          // 16-byte words of one transform
+  for (uint64_t off = 0; off < count; off += P.piece_transforms) {
+    const uint64_t m = std::min(P.piece_transforms, count - off);
+    const uint4* a4 = static_cast<const uint4*>(d_a) + off * rec4;
+    uint4* o4 = static_cast<uint4*>(d_out) + off * rec4;
+    for (uint32_t p = 0; p < P.passes; p++) {
+      const te_ntt::pass& ps = P.p[p];
+      const uint4* src = p == 0 ? a4 : reinterpret_cast<const uint4*>(tmp);
+      uint4* dst = p + 1 == P.passes ? o4 : reinterpret_cast<uint4*>(tmp);
+      const dim3 grid((uint32_t)te_ntt::tiles_of(ps, m)), block(te_ntt::kLanes);
+      const uint64_t lines = te_ntt::lines_of(ps, m);
+      with_flag(q.inverse, [&](auto inv) {
+        with_flag(q.shifted, [&](auto shf) {
+          hipLaunchKernelGGL((te::k_ntt_pass<decltype(inv)::value, decltype(shf)::value>), grid, block, 0, st, src, dst, ps, lines, k, tb);
+        });
+      });
+    }
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+// what every te_msm_ntt* call checks first (te::ntt_check); q: the request
+int ntt_args(te_ctx* ctx, const void* a, uint32_t log_n, uint64_t count, int flags, const uint8_t* shift, const void* out, ntt_req& q) {
+  switch (te::ntt_check(a, log_n, count, flags, shift, out, q)) {
+    case te::NTT_OK: return 0;
+    case te::NTT_BAD_LOG_N: return set_err(ctx, TE_MSM_EINVAL, "te_msm_ntt*: log_n is above TE_MSM_NTT_MAX_LOG_N");
+    case te::NTT_BAD_FLAGS: return set_err(ctx, TE_MSM_EINVAL, "te_msm_ntt*: unknown flag bits");
+    case te::NTT_TOO_LARGE: return set_err(ctx, TE_MSM_EINVAL, "te_msm_ntt*: count x n x 32 does not fit 64 bits");
+    case te::NTT_NULL: return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+    default: return set_err(ctx, TE_MSM_EINVAL, "te_msm_ntt*: the shift is 0 mod p");
+  }
+}
+// te_msm_ntt: host buffers, whole transforms sliced over the devices; a slice is transformed in place in its staged copy
+int ntt_host(te_ctx* ctx, const ntt_req& q, const uint8_t* a, uint64_t count, uint8_t* out) {
+  const size_t tb = (size_t)32 << q.log_n;
+  const slice_plan sp(ctx, count);
+  struct slice_t { dev_tmp a; };
+  std::vector<slice_t> sl(sp.D);
+  auto stage = [&](size_t i) -> int {
+    const uint64_t lo = sp.lo(i), m = sp.count(i);
+    if (m == 0) return 0;
+    if (int rc = tmp_alloc(ctx, ctx->devs[i], sl[i].a, m * tb)) return rc;
+    HIP_TRY(ctx, hipMemcpy(sl[i].a.p, a + lo * tb, m * tb, hipMemcpyHostToDevice));
+    return ntt_on(ctx, i, q, sl[i].a.p, m, sl[i].a.p);
+  };
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  return copy_slices_out(ctx, sp, tb, out, [&](size_t i) { return sl[i].a.p; });
+}
 }  // namespace
 
 void free_mul_base(te_ctx* ctx, te_base* b) {
@@ -1082,6 +1181,25 @@ int te_msm_field_op_device(te_ctx* ctx, int field, int op, const void* d_a, cons
   int64_t bad = -1; int why = 0;
   const int rc = field_on(ctx, (size_t)owner, q, d_a, d_b, n, d_out, false, &bad, &why);
   return rc == TE_MSM_EFIELD ? note_bad_field(ctx, bad, why) : rc;
+}
+
+int te_msm_ntt(te_ctx* ctx, const uint8_t* a, uint32_t log_n, uint64_t count, int flags, const uint8_t* shift, uint8_t* out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  ntt_req q;
+  if (int rc = ntt_args(ctx, a, log_n, count, flags, shift, out, q)) return rc;
+  return count ? ntt_host(ctx, q, a, count, out) : 0;
+}
+
+int te_msm_ntt_device(te_ctx* ctx, const void* d_a, uint32_t log_n, uint64_t count, int flags, const uint8_t* shift, void* d_out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  ntt_req q;
+  if (int rc = ntt_args(ctx, d_a, log_n, count, flags, shift, d_out, q)) return rc;
+  if (count == 0) return 0;
+  const int owner = owner_of(ctx, "te_msm_ntt_device: the input and the output must be resident on one device of the context", {d_a, d_out});
+  if (owner < 0) return owner;
+  return ntt_on(ctx, (size_t)owner, q, d_a, count, d_out);
 }
 
 }  // extern "C"

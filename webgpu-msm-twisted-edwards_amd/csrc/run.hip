@@ -116,6 +116,8 @@ void free_dev(gpu_t& d) {
   d.slabs.clear();
   if (d.chk_stream) (void)hipStreamDestroy(d.chk_stream);
   d.chk_pts.release();
+  d.ntt_tab.release();
+  d.ntt_tmp.release();
   if (d.chk_word) (void)hipFree(d.chk_word);
   if (d.chk_host) (void)hipHostFree(d.chk_host);
   d.chk_stream = nullptr; d.chk_word = d.chk_host = nullptr;

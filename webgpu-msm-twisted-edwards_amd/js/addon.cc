@@ -611,6 +611,68 @@ napi_value FieldOp(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+// ntt(a: Buffer, logN: number, opts?: {count?: number, inverse?: boolean, montgomery?: boolean, shift?: Buffer}): Buffer -- batched NTTs over p
+// (include/te_msm.h, te_msm_ntt): `count` (default 1) transforms of 2^logN 32-byte elements each, natural order in and out, the radix-2
+// domains of arkworks / snarkVM; shift: one 32-byte record, the coset generator.  Run like fieldOp; a refusal (logN above 24, a shift
+// that is 0 mod p) throws; compute_msm.js wraps the call into a promise, which then rejects with that Error.
+napi_value Ntt(napi_env env, napi_callback_info info) {
+  const char* const sig = "ntt(a: Buffer, logN: number, opts?: {count?: number, inverse?: boolean, montgomery?: boolean, shift?: Buffer})";
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool a_buf = false;
+  napi_valuetype t_log = napi_undefined, t_opts = napi_undefined;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &a_buf);
+  if (argc >= 2) napi_typeof(env, argv[1], &t_log);
+  if (argc >= 3) napi_typeof(env, argv[2], &t_opts);
+  const bool opts_none = t_opts == napi_undefined || t_opts == napi_null;
+  if (!a_buf || t_log != napi_number || (t_opts != napi_object && !opts_none)) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  uint32_t log_n = 0;
+  napi_get_value_uint32(env, argv[1], &log_n);
+  int flags = 0;
+  int64_t count = 1;
+  void* ps = nullptr; size_t sl = 0; bool s_buf = false;
+  if (t_opts == napi_object) {
+    const struct { const char* name; int bit; } bits[] = {{"inverse", TE_MSM_NTT_INVERSE}, {"montgomery", TE_MSM_NTT_MONTGOMERY}};
+    for (const auto& f : bits) {
+      napi_value v; bool has = false, on = false;
+      napi_has_named_property(env, argv[2], f.name, &has);
+      if (has) { napi_get_named_property(env, argv[2], f.name, &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &on); }
+      if (on) flags |= f.bit;
+    }
+    napi_value v; bool has = false;
+    napi_has_named_property(env, argv[2], "count", &has);
+    if (has) { napi_get_named_property(env, argv[2], "count", &v); if (napi_get_value_int64(env, v, &count) != napi_ok || count < 0) { napi_throw_type_error(env, nullptr, sig); return nullptr; } }
+    napi_has_named_property(env, argv[2], "shift", &has);
+    if (has) {
+      napi_valuetype t_s = napi_undefined;
+      napi_get_named_property(env, argv[2], "shift", &v);
+      napi_typeof(env, v, &t_s);
+      napi_is_buffer(env, v, &s_buf);
+      if (!s_buf && t_s != napi_undefined && t_s != napi_null) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+      if (s_buf) napi_get_buffer_info(env, v, &ps, &sl);
+    }
+  }
+  void* pa = nullptr; size_t al = 0;
+  napi_get_buffer_info(env, argv[0], &pa, &al);
+  if ((s_buf && sl != 32) || (log_n <= TE_MSM_NTT_MAX_LOG_N && al != (((size_t)count * 32) << log_n))) {
+    napi_throw_range_error(env, nullptr, "ntt: a must be count * 2^logN * 32 bytes, shift one record of 32");
+    return nullptr;
+  }
+  std::vector<uint8_t> out(al);
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    return te_msm_ntt(c, static_cast<const uint8_t*>(pa), log_n, (uint64_t)count, flags, s_buf ? static_cast<const uint8_t*>(ps) : nullptr, out.data());
+  }, err);
+  if (rc) {
+    const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_throw_error(env, nullptr, m.c_str());
+    return nullptr;
+  }
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size(), out.data(), &dst, &buf);
+  return buf;
+}
+
 // setBase(point: Buffer) and scalarMulBase(scalars: Buffer): Buffer -- fixed-base batch scalar multiplication (include/te_msm.h,
 // te_msm_bind_base / te_msm_mul_base): one 64-byte point bound once, then n x 32-byte little-endian scalars -> n x 64-byte points
 // [k_i] P (the identity as (0, 1)).  Twisted-Edwards curve only, like the rest of the addon; run like scalarMul.  The addon keeps the
@@ -783,7 +845,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"pointsFromX", PointsFromX}, {"scalarMul", ScalarMul}, {"scalarMulX", ScalarMulX}, {"msmBatch", MsmBatch}, {"msmIndexed", MsmIndexed},
       {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase},
       {"groupAdd", GroupAdd}, {"groupAddX", GroupAddX}, {"groupSum", GroupSum}, {"groupSumX", GroupSumX},
-      {"fieldOp", FieldOp}};
+      {"fieldOp", FieldOp},
+      {"ntt", Ntt}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -99,6 +99,11 @@ const groupSumX = (xs) => native.groupSumX(xs);
 // .index (the lowest failing element) and .reason (1 zero, 2 not a square).
 const FIELD_OPS = { add: 0, sub: 1, mul: 2, double: 3, neg: 4, square: 5, inv: 6, pow: 7, sqrt: 8 };
 const fieldOp = async (op, a, b, opts) => native.fieldOp(op, a, b === undefined ? null : b, opts);
+// ntt(a, logN, {count, inverse, montgomery, shift}): `count` (default 1) number-theoretic transforms of 2^logN 32-byte elements of p each,
+// natural order in and out -- arkworks' / snarkVM's radix-2 domains of BLS12-377's scalar field (te_msm_ntt).  shift: a 32-byte Buffer, the
+// coset generator s; inverse undoes the forward with the same s; montgomery: a, s and the result are residues v * 2^256 mod p.  Resolves
+// to the results as a Buffer (canonical); rejects for logN above 24 and for a shift that is 0 mod p.
+const ntt = async (a, logN, opts) => native.ntt(a, logN, opts);
 
 // Outside the reference's interface too: msmBatch(scalarBuffers) runs one MSM per Buffer over the set bound by setBases -- MSM m over
 // its first scalarBuffers[m].length / 32 points (a prover's commitments to polynomials of different degrees against one SRS) -- and
@@ -119,4 +124,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS, ntt };

@@ -56,6 +56,11 @@ export declare const groupSumX: (xs: Buffer) => Buffer;
 export declare const FIELD_OPS: { add: 0, sub: 1, mul: 2, double: 3, neg: 4, square: 5, inv: 6, pow: 7, sqrt: 8 };
 export declare const fieldOp: (op: number, a: Buffer, b?: Buffer | null,
   opts?: { field?: 0 | 1, sharedB?: boolean, montgomery?: boolean, zeroOk?: boolean }) => Promise<Buffer>;
+// Not in the reference: batched NTTs over p on the device -- `count` (default 1) transforms of 2^logN 32-byte elements each, natural order
+// in and out, the radix-2 domains of arkworks / snarkVM over BLS12-377's scalar field.  shift: one 32-byte record, the coset generator;
+// inverse undoes the forward with the same shift; montgomery as for fieldOp.  Rejects for logN above 24 and a shift that is 0 mod p.
+export declare const ntt: (a: Buffer, logN: number,
+  opts?: { count?: number, inverse?: boolean, montgomery?: boolean, shift?: Buffer }) => Promise<Buffer>;
 // Not in the reference: batched MSMs over prefixes of the set bound by setBases; MSM m runs over the first scalarBuffers[m].length / 32
 // points.  Results in input order, in compute_msm's form; throws without setBases or for a buffer longer than the set.
 export declare const msmBatch: (scalarBuffers: Buffer[]) => { x: bigint; y: bigint }[];
