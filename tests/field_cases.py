@@ -212,6 +212,44 @@ def pow_operands(field):
     return pack([x for x, _ in pairs], nbytes(field)), pack([e for _, e in pairs], 32)
 
 
+# ---- the piece loops of points.hip (tests/test_gpu_piece_loops.py, pinned on the host by tests/test_piece_cases_host.py) ---------------
+def piece_constant(name):
+    """a `constexpr uint64_t <name> = 1ull << N;` of points.hip as an integer; a line that is gone is an error, never a default"""
+    import re
+    src = open(os.path.join(ROOT, "webgpu-msm-twisted-edwards_amd", "csrc", "points.hip")).read()
+    found = re.findall(r"^constexpr uint64_t %s = 1ull << (\d+);" % re.escape(name), src, re.M)
+    assert len(found) == 1, "points.hip: %d lines define %s" % (len(found), name)
+    return 1 << int(found[0])
+
+
+TILE = 4099                                                        # prime: a pattern of this period lines up with no tile, chain or piece
+
+
+@functools.lru_cache(maxsize=None)
+def tile_set(field, zeros=True):
+    """TILE raw values: the extremes, 2 m, and random full-width integers; without `zeros`, 1 stands where a residue would be 0"""
+    p, bits = modulus(field), 8 * nbytes(field)
+    rnd = random.Random(0x4099 + field)
+    v = list(extremes(field)) + [2 * p]
+    v += [rnd.randrange(1 << bits) for _ in range(TILE - len(v))]
+    rnd.shuffle(v)
+    assert sum(1 for x in v if x % p == 0) >= 3
+    return tuple(v if zeros else [x if x % p else 1 for x in v])
+
+
+@functools.lru_cache(maxsize=None)
+def tile_inverses(field, flags, zeros=True):
+    """what te_msm_field_op(INV) makes of tile_set: TILE integers, 0 for a zero residue.  MONTGOMERY: x = a A -> (1 / a) A = A^2 / x"""
+    p, A = modulus(field), 1 << (8 * nbytes(field))
+    k = A * A % p if flags & MONTGOMERY else 1
+    return tuple(pow(x, -1, p) * k % p if x % p else 0 for x in tile_set(field, zeros))
+
+
+def tiled(table, n):
+    """v[i] = table[i % TILE], as bytes: the host's form of the index_select the GPU tests do on the device"""
+    return b"".join(table[i % TILE] for i in range(n))
+
+
 def inv_sizes(group):
     t = 256 * group
     return (1, 255, 256, 257, t - 1, t, t + 1, 2 * t + 300)

@@ -175,6 +175,98 @@ def values(n, seed=0):
     return pack(v, 32)
 
 
+# ---- closed forms for the sizes and batches no textbook transform reaches in a test's time (tests/test_gpu_piece_loops.py; each is pinned
+# to model() at small sizes by tests/test_piece_cases_host.py).  Inputs and outputs are wire integers: encode()d under MONTGOMERY ------------
+def shift_value(flags, shift):
+    """the s a call multiplies by: 1 without a shift, else the shift record decoded as the elements are"""
+    return 1 if shift is None else decode([shift], flags)[0]
+
+
+def const_forward(log_n, c):
+    """forward of the all-c input, canonical form, no shift: n c delta_0 -- small enough to need no reduction"""
+    n = 1 << log_n
+    assert 0 < c and n * c < 1 << 40
+    return [n * c] + [0] * (n - 1)
+
+
+def delta0_inverse(log_n, c):
+    """inverse of c delta_0, canonical form, no shift: c / n at every place -- this one integer"""
+    return c * pow(1 << log_n, -1, P) % P
+
+
+def delta_place(log_n, t):
+    """where transform t of a batch of deltas has its one: odd multiples of a large odd constant, so every digit of the plan moves"""
+    return 2654435761 * (t + 1) % (1 << log_n)
+
+
+def terms_input(log_n, terms, flags=0):
+    """the sum of c delta_k over terms = [(k, c), ..] as n wire integers"""
+    a = [0] * (1 << log_n)
+    for k, c in terms:
+        a[k] = encode([c], flags)[0]
+    return a
+
+
+def terms_forward(log_n, terms, j, flags=0, shift=None):
+    """output j of the forward transform of terms_input: sum of c s^k w^(j k)"""
+    n, w, s = 1 << log_n, omega(log_n), shift_value(flags, shift)
+    return encode([sum(c * pow(s, k, P) * pow(w, j * k % n, P) for k, c in terms) % P], flags)[0]
+
+
+def geometric_input(log_n, g):
+    """a_i = g^i, canonical"""
+    a, t = [], 1
+    for _ in range(1 << log_n):
+        a.append(t)
+        t = t * g % P
+    return a
+
+
+def geometric_forward(log_n, g, j):
+    """output j of the forward transform of geometric_input: (g^n - 1) / (g w^j - 1); g^n != 1 keeps every denominator away from 0"""
+    n = 1 << log_n
+    top = (pow(g, n, P) - 1) % P
+    assert top
+    return top * pow(g * pow(omega(log_n), j, P) - 1, -1, P) % P
+
+
+def plan_digits(r, k):
+    """the digits of an input index as the plan cuts it: the first pass's on top (csrc/ntt_plan.hpp)"""
+    out, low = [], sum(r)
+    for width in r:
+        low -= width
+        out.append((k >> low) & ((1 << width) - 1))
+    return out
+
+
+def distinct_digit_places(log_n, r):
+    """three input indices whose plan digits are all non-zero and pairwise different; the first is odd and near n"""
+    n = 1 << log_n
+
+    def ok(k):
+        d = plan_digits(r, k)
+        return all(d) and len(set(d)) == len(d)
+    out = []
+    for start, step in ((n - 12345, -2), (n // 3, 1), (0x9E3779B1 % (n // 2), 1)):
+        k = start
+        while not ok(k) or k in out:
+            k += step
+        assert 0 < k < n
+        out.append(k)
+    assert out[0] & 1 and out[0] > n - (n >> 4)
+    return out
+
+
+def sample_places(L, log_n, seed, want=4096):
+    """about `want` output indices: the tile corners of every pass, 0, 1, n / 2, n - 1 and random ones (all of a small transform)"""
+    n = 1 << log_n
+    if n <= want:
+        return list(range(n))
+    rnd = random.Random(seed)
+    js = set(tile_corners(L, log_n)) | {0, 1 % n, n // 2, n - 1} | {rnd.randrange(n) for _ in range(want)}
+    return sorted(js)
+
+
 def batch_counts(per_tile):
     """transforms of a one-pass launch that leave the last block partly filled, fill it, and pass it"""
     return sorted({1, 2, 3, max(1, per_tile - 1), per_tile, per_tile + 1, 1000})
