@@ -567,6 +567,49 @@ int te_msm_field_op_device(te_ctx* ctx, int field, int op, const void* d_a, cons
 int te_msm_ntt(te_ctx* ctx, const uint8_t* a, uint32_t log_n, uint64_t count, int flags, const uint8_t* shift, uint8_t* out);
 int te_msm_ntt_device(te_ctx* ctx, const void* d_a, uint32_t log_n, uint64_t count, int flags, const uint8_t* shift, void* d_out);
 
+/* ---- polynomial openings --------------------------------------------------------------------------------------------------------
+ * te_msm_poly_divide*: evaluate `count` polynomials over p (TE_MSM_FIELD_P, the records of te_msm_ntt) at a point each and divide them
+ * by X - z: the opening of a KZG / Marlin / Varuna round, between the inverse transform (te_msm_ntt_device) and the opening's MSM
+ * (te_msm_run_scalars_device), so that the coefficients stay on the device.  Polynomial k is a[k n .. k n + n - 1], 32-byte
+ * little-endian records, lowest coefficient first; n is ANY length from 1 to TE_MSM_POLY_MAX_N.  Its point z_k is record k of z, or
+ * record 0 under TE_MSM_POLY_SHARED_Z.  With h_(n-1) = a_(n-1) and h_i = a_i + z h_(i+1):
+ *     evals[k]       = h_0 = a(z)
+ *     q[k n + i]     = h_(i+1), i < n - 1      the witness polynomial (a(X) - a(z)) / (X - z)
+ *     q[k n + n - 1] = 0
+ * The quotient keeps the stride n: q may be exactly a, and te_msm_run_scalars_batch_device takes it with the lengths n - 1.
+ * z and evals are HOST pointers in both forms (a challenge comes from the host's transcript, an evaluation goes back into it).  Either
+ *   evals or q may be NULL: with q NULL the call only evaluates -- it reads a once and writes nothing on the device but its scratch.
+ * flags: TE_MSM_POLY_MONTGOMERY -- a, z, evals and q hold v * 2^256 mod p; TE_MSM_POLY_SHARED_Z.  Any other bit: TE_MSM_EINVAL.
+ * Values: as te_msm_field_op -- ANY 256-bit coefficient or point stands for its residue (z = 0 and z = p are one point), outputs are
+ *   canonical.  count = 0 succeeds and touches nothing.
+ * Refusals, all TE_MSM_EINVAL with every output untouched and the context usable: n = 0 or n > TE_MSM_POLY_MAX_N; an unknown flag bit;
+ *   evals and q both NULL; NULL a or z with count > 0; count * n * 32 beyond 64 bits (or more than 2^31 - 1 tiles in one launch);
+ *   te_msm_poly_divide_device: d_a and d_q not on one device of the context.  evals is written only when the call succeeds.
+ * Buffers: te_msm_poly_divide_device returns with d_q complete.  te_msm_poly_divide slices WHOLE polynomials over the context's devices,
+ *   one host thread per device, each slice staged on its device.  Every element and byte offset is 64 bits wide.  The tile sums, the
+ *   carries and the powers of the points live in a buffer of the device's (about count * n / T records), grown on use and kept until
+ *   te_msm_trim / te_msm_destroy.  The calling thread's device is left as it was.
+ * How it runs (csrc/poly_plan.hpp, csrc/poly.hip.hpp): a 256-lane block owns a tile of T = 256 chunk coefficients
+ *   of one polynomial.  k_poly_sums leaves S_b = sum_k a_(bT+k) z^k for every tile; the carries h_(bT) are the quotient of S(X) by
+ *   X - z^T -- the same call on ceil(n / T) coefficients, recursed until one tile is left, whose sum is a(z); k_poly_apply takes a
+ *   tile's carry, scans its lanes and writes h_(i+1) at i (skipped when q is NULL).  z is in Montgomery form, coefficients never are:
+ *   a step is one product and one normalised sum, and both forms run the same code.  chunk: TE_MSM_POLY_CHUNK (measured), or what the
+ *   environment variable TE_MSM_POLY_CHUNK names (1 .. 16), read by every call -- and never more than one tile needs to cover n, so that
+ *   a batch of short polynomials (1024 x 2^10) fills its blocks.  Read-only options: "poly_chunk" (the chunk in force),
+ *   "poly_scratch_bytes" (what the context's devices hold now of that buffer).
+ * COST (MI355X, device form, in place, one shared point, three alternating rounds, lowest .. highest; tools/poly_cost.py,
+ *   profiles/poly_cost.txt), with the quotient / evaluation only: 1024 x 2^10 0.124 .. 0.132 / 0.061 .. 0.066 ms; 16 x 2^16 0.139 .. 0.143 /
+ *   0.070 .. 0.071; 2^20 0.136 / 0.065 .. 0.067; 2^24 0.96 .. 1.05 / 0.28 .. 0.40 ms.  Beside them, in the same rounds: a device copy of the
+ *   bytes the call moves (two reads and a write / one read) 0.026 / 0.019 ms at 2^20 elements and 0.31 / 0.11 ms at 2^24;
+ *   te_msm_field_op_device(MUL) over n elements 0.035 and 0.28 .. 0.29 ms; the pinned link time of 32 n bytes down and up -- what the call
+ *   replaces -- 1.19 ms and 18.7 ms.  Chunk 8 was the lowest of 4, 8 and 16 in every round at 2^20 and 16 x 2^16 (32 does not fit LDS). */
+#define TE_MSM_POLY_MONTGOMERY 1   /* a, z, evals, q hold v * 2^256 mod p */
+#define TE_MSM_POLY_SHARED_Z 2     /* z is ONE record, used for every polynomial */
+#define TE_MSM_POLY_MAX_N (1ull << 30)
+#define TE_MSM_POLY_CHUNK 8u
+int te_msm_poly_divide(te_ctx* ctx, const uint8_t* a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, uint8_t* q);
+int te_msm_poly_divide_device(te_ctx* ctx, const void* d_a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, void* d_q);
+
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "scalars_montgomery" 0 (default) = scalar records hold the integers themselves (the wire format above); 1 = every scalar record holds
  *                   a = k * 2^256 mod m and the MSM uses k = a * 2^-256 mod m, where m is the scalar field of the curve in force:

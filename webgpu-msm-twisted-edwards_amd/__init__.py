@@ -59,5 +59,8 @@ from .binding import (  # noqa: F401
     NTT_INVERSE,
     NTT_MONTGOMERY,
     NTT_MAX_LOG_N,
+    POLY_MONTGOMERY,
+    POLY_SHARED_Z,
+    POLY_MAX_N,
 )
 from .sharding import ShardedPipeline, compute_msm_sharded, distribute_inputs, exchange_partials, merge_partials, rows_of_batched_msm, window_shard_for_rank  # noqa: F401

@@ -29,6 +29,8 @@ FIELD_ADD, FIELD_SUB, FIELD_MUL, FIELD_DOUBLE, FIELD_NEG, FIELD_SQUARE, FIELD_IN
 FIELD_SHARED_B, FIELD_MONTGOMERY, FIELD_ZERO_OK = 1, 2, 4      # flags of te_msm_field_op*
 NTT_INVERSE, NTT_MONTGOMERY = 1, 2                              # flags of te_msm_ntt*
 NTT_MAX_LOG_N = 24
+POLY_MONTGOMERY, POLY_SHARED_Z = 1, 2                            # flags of te_msm_poly_divide*
+POLY_MAX_N = 1 << 30
 FIELD_ZERO, FIELD_NOT_SQUARE = 1, 2      # why an element has no result (MsmError.reason)
 
 
@@ -248,6 +250,11 @@ def _lib() -> ctypes.CDLL:
             L.te_msm_ntt.restype = ci
             L.te_msm_ntt_device.argtypes = [vp, vp, ctypes.c_uint32, u64, ci, vp, vp]
             L.te_msm_ntt_device.restype = ci
+        if not os.environ.get("TE_MSM_LIB") or hasattr(L, "te_msm_poly_divide"):
+            L.te_msm_poly_divide.argtypes = [vp, vp, u64, u64, vp, ci, vp, vp]
+            L.te_msm_poly_divide.restype = ci
+            L.te_msm_poly_divide_device.argtypes = [vp, vp, u64, u64, vp, ci, vp, vp]
+            L.te_msm_poly_divide_device.restype = ci
         _LIB = L
     return _LIB
 
@@ -616,6 +623,37 @@ class MsmContext:
         """te_msm_ntt_device: the same between buffers on one device of the context; d_out may be d_a.  shift stays a host value"""
         flags, rec = self._ntt_args(inverse, montgomery, shift)
         self._check(self._L.te_msm_ntt_device(self._h, d_a, log_n, count, flags, rec, d_out))
+
+    # ---- polynomial openings (include/te_msm.h "polynomial openings"): a(z) and the quotient by X - z, the witness of a KZG opening
+    @staticmethod
+    def _poly_args(z, count: int, montgomery: bool, shared_z: bool):
+        flags = (POLY_MONTGOMERY if montgomery else 0) | (POLY_SHARED_Z if shared_z else 0)
+        if isinstance(z, int):
+            z = [z]
+        rec = bytes(z) if isinstance(z, (bytes, bytearray, memoryview)) else b"".join(int(v).to_bytes(32, "little") for v in z)
+        if len(rec) != 32 * (1 if shared_z else count):
+            raise MsmError(-1, "z must be one 32-byte record a polynomial (one in all with shared_z): bytes, or integers below 2^256")
+        return flags, rec
+
+    def poly_divide(self, a: bytes, n: int, z, *, count: int = 1, montgomery: bool = False, shared_z: bool = False, quotient: bool = True):
+        """te_msm_poly_divide: `count` polynomials of n 32-byte coefficients of p each, lowest first, and their points z (bytes, or integers)
+        -> (evals, q): a(z) of each, and the coefficients of (a(X) - a(z)) / (X - z) at the stride n (the last one 0); q is None without
+        `quotient` (the call then only evaluates)."""
+        if n < 0 or count < 0 or len(a) != 32 * count * n:
+            raise MsmError(-1, "a must be count * n * 32 bytes")
+        flags, rec = self._poly_args(z, count, montgomery, shared_z)
+        evals = ctypes.create_string_buffer(max(1, 32 * count))
+        q = ctypes.create_string_buffer(max(1, len(a))) if quotient else None
+        self._check(self._L.te_msm_poly_divide(self._h, bytes(a), n, count, rec, flags, evals, q))
+        return evals.raw[:32 * count], q.raw[:len(a)] if quotient else None
+
+    def poly_divide_device(self, d_a: int, n: int, count: int, z, d_q, *, montgomery: bool = False, shared_z: bool = False, evals: bool = True):
+        """te_msm_poly_divide_device: the same from a buffer on one device of the context into d_q, which may be d_a, or None to evaluate
+        only.  z stays a host value; returns the evaluations (None without `evals`)."""
+        flags, rec = self._poly_args(z, count, montgomery, shared_z)
+        ev = ctypes.create_string_buffer(max(1, 32 * count)) if evals else None
+        self._check(self._L.te_msm_poly_divide_device(self._h, d_a, n, count, rec, flags, ev, d_q))
+        return ev.raw[:32 * count] if evals else None
 
     def add_x(self, ax: bytes, bx: bytes, subtract: bool = False) -> bytes:
         """te_msm_add_x, bulkAddGroups' counterpart: n x-only points a and n (or one) b (32 / 48 bytes, points_from_x's format) -> n points x || y"""

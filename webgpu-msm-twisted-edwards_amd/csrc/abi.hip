@@ -40,7 +40,7 @@ int te_msm_trim(te_ctx* ctx, int keep_worksets) {
       free_workset_buffers(ws);
       freed++;
     }
-    { std::lock_guard<std::mutex> lk(*d.chk_mu); d.ntt_tab.release(); d.ntt_tmp.release(); }      // the NTT twiddle tables and scratch: made again by the next transform (none runs: it holds chk_mu)
+    { std::lock_guard<std::mutex> lk(*d.chk_mu); d.ntt_tab.release(); d.ntt_tmp.release(); d.poly_tmp.release(); }      // the NTT twiddle tables and scratch: made again by the next transform (none runs: it holds chk_mu)
     for (auto& sl : d.slabs) if (sl.users == 0 && sl.d) {                    // idle shared record slabs
       if (int rc = settle_slab(ctx, sl, nullptr, true)) return rc;
       for (workset_t& ws : d.ws) if (ws.recs_last == sl.d) ws.recs_last = nullptr;
@@ -130,6 +130,12 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "ntt_scratch_bytes")) {                             // ... and the buffer between the passes of multi-pass transforms
     *value = 0;
     for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.ntt_tmp.p ? (int64_t)d.ntt_tmp.cap : 0; }
+    return 0;
+  }
+  if (!strcmp(key, "poly_chunk")) { *value = (int64_t)te_poly::chunk_in_force(); return 0; }   // TE_MSM_POLY_CHUNK, or what the environment names
+  if (!strcmp(key, "poly_scratch_bytes")) {                            // the sums, carries and powers of te_msm_poly_divide*
+    *value = 0;
+    for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.poly_tmp.p ? (int64_t)d.poly_tmp.cap : 0; }
     return 0;
   }
   if (!strcmp(key, "bad_index_position")) { *value = ctx->bad_index_position; return 0; }

@@ -37,6 +37,7 @@
 #include "plan_arith.hpp"
 #include "fb_plan.hpp"
 #include "ntt_plan.hpp"
+#include "poly_plan.hpp"
 
 #pragma GCC visibility push(hidden)
 #include "host_sched.hpp"
@@ -207,6 +208,8 @@ struct gpu_t {
                                          // te_msm_trim / destroy free them (get_option "ntt_table_bytes")
   dev_buf<uint8_t> ntt_tmp;              // ... and the buffer between the passes of a multi-pass transform (ntt_plan.hpp, tmp_records_for: at most 512 MB), grown on
                                          // use under chk_mu, freed with the tables (get_option "ntt_scratch_bytes")
+  dev_buf<uint8_t> poly_tmp;             // te_msm_poly_divide*: the tile sums, carries and powers of a call (poly_plan.hpp, scratch_bytes: about count * n / T records),
+                                         // grown on use under chk_mu, freed by te_msm_trim / destroy (get_option "poly_scratch_bytes")
 };
 
 }  // namespace te_eng

@@ -1,8 +1,9 @@
 // points.hip -- what the library does with points beside MSMs: validation (option "check_points", te_msm_check_points*), x-only
 // points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x), batch scalar multiplication (te_msm_mul*) and its fixed-base form
 // over one bound point (te_msm_bind_base, te_msm_mul_base*), batched group addition and point-set sums (te_msm_add*, te_msm_sum*), and
-// batched arithmetic in the two base fields (te_msm_field_op*) and batched NTTs over p (te_msm_ntt*).  The one unit that includes the
-// kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp, group_add.hip.hpp, field_ops.hip.hpp and ntt.hip.hpp.
+// batched arithmetic in the two base fields (te_msm_field_op*), batched NTTs over p (te_msm_ntt*) and polynomial openings
+// (te_msm_poly_divide*).  The one unit that includes the kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp,
+// group_add.hip.hpp, field_ops.hip.hpp, ntt.hip.hpp and poly.hip.hpp.
 #include "engine.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
@@ -11,6 +12,7 @@
 #include "group_add.hip.hpp"
 #include "field_ops.hip.hpp"
 #include "ntt.hip.hpp"
+#include "poly.hip.hpp"
 
 using namespace te_eng;
 
@@ -854,6 +856,88 @@ int ntt_host(te_ctx* ctx, const ntt_req& q, const uint8_t* a, uint64_t count, ui
   if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
   return copy_slices_out(ctx, sp, tb, out, [&](size_t i) { return sl[i].a.p; });
 }
+
+// ---- polynomial openings (te_msm_poly_divide*; kernels in poly.hip.hpp, plan in poly_plan.hpp) ---------------------------------------
+// `count` polynomials on the device's check lane: the powers of the points (computed here with the host build of the field: 25 products
+// a point and level) go up behind the regions of the device's scratch buffer (grown on use, held like ntt_tmp; the lane's mutex
+// serialises its users); k_poly_sums runs level by level upwards -- the one record a polynomial of the last region is a(z) -- and
+// k_poly_apply level by level downwards, each level's quotient over its sums, the last launch a -> q.  No piece loop: the buffer is about
+// count n / T records.
+static_assert(TE_MSM_POLY_CHUNK == te_poly::kChunkDefault && TE_MSM_POLY_MAX_N == te_poly::kMaxN, "include/te_msm.h and poly_plan.hpp disagree");
+using te::poly_req;
+// z: the points on the host (count records, or one); evals: where the count evaluations go on the host once everything succeeded, or
+// nullptr; d_q: nullptr evaluates only
+int poly_on(te_ctx* ctx, size_t di, const poly_req& r, const void* d_a, uint64_t count, const uint8_t* z, uint8_t* evals, void* d_q) {
+  if (count == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  te_poly::plan P;
+  if (!te_poly::make_plan(r.n, count, r.chunk, r.shared, P)) return set_err(ctx, TE_MSM_EINVAL, "te_msm_poly_divide*: more tiles than one launch holds");
+  std::vector<uint32_t> pows((size_t)P.pow_words);
+  te::poly_pow_table(P, z, r.mont, pows.data());
+  std::vector<uint8_t> ev(evals ? (size_t)count * 32 : 0);
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  hipStream_t st = lane.stream();
+  if (int rc = make_room(ctx, d.poly_tmp, (size_t)P.scratch_bytes)) return rc;
+  uint4* const reg = reinterpret_cast<uint4*>(d.poly_tmp.p);
+  uint32_t* const d_pows = reinterpret_cast<uint32_t*>(d.poly_tmp.p + P.records * 32u);
+  HIP_TRY(ctx, hipMemcpyAsync(d_pows, pows.data(), pows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  const uint64_t pow_stride = P.points == 1u ? 0 : te_poly::pow_word(P, 1, 0, 0);
+  const dim3 block(te_poly::kLanes);
+  for (uint32_t l = 0; l < P.levels; l++) {
+    const te_poly::level& v = P.lv[l];
+    const uint4* src = l ? reg + v.src * 2 : static_cast<const uint4*>(d_a);
+    hipLaunchKernelGGL(te::k_poly_sums, dim3((uint32_t)(count * v.tiles)), block, 0, st, src, reg + v.dst * 2, v, P.chunk, d_pows + te_poly::pow_word(P, 0, l, 0), pow_stride);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  if (evals) HIP_TRY(ctx, hipMemcpyAsync(ev.data(), reg + P.lv[P.levels - 1].dst * 2, ev.size(), hipMemcpyDeviceToHost, st));
+  if (d_q) {
+    const size_t lds = te_poly::lds_bytes_apply(P.chunk);
+    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&te::k_poly_apply), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (uint32_t l = P.levels; l-- > 0u;) {
+      const te_poly::level& v = P.lv[l];
+      const uint4* src = l ? reg + v.src * 2 : static_cast<const uint4*>(d_a);
+      uint4* dst = l ? reg + v.src * 2 : static_cast<uint4*>(d_q);
+      const uint4* carries = l + 1u < P.levels ? reg + v.dst * 2 : nullptr;
+      hipLaunchKernelGGL(te::k_poly_apply, dim3((uint32_t)(count * v.tiles)), block, lds, st, src, dst, carries, v, P.chunk, d_pows + te_poly::pow_word(P, 0, l, 0), pow_stride);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (evals) memcpy(evals, ev.data(), ev.size());
+  return 0;
+}
+// what every te_msm_poly_divide* call checks first (te::poly_check); r: the request
+int poly_args(te_ctx* ctx, const void* a, uint64_t n, uint64_t count, const uint8_t* z, int flags, const void* evals, const void* q, poly_req& r) {
+  switch (te::poly_check(a, n, count, z, flags, evals, q, r)) {
+    case te::POLY_OK: r.chunk = te_poly::chunk_for(n, te_poly::chunk_in_force()); return 0;
+    case te::POLY_BAD_N: return set_err(ctx, TE_MSM_EINVAL, "te_msm_poly_divide*: n must be in [1, TE_MSM_POLY_MAX_N]");
+    case te::POLY_BAD_FLAGS: return set_err(ctx, TE_MSM_EINVAL, "te_msm_poly_divide*: unknown flag bits");
+    case te::POLY_NO_OUTPUT: return set_err(ctx, TE_MSM_EINVAL, "te_msm_poly_divide*: evals and q are both NULL");
+    case te::POLY_TOO_LARGE: return set_err(ctx, TE_MSM_EINVAL, "te_msm_poly_divide*: count x n x 32 does not fit 64 bits");
+    default: return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  }
+}
+// te_msm_poly_divide: host buffers, whole polynomials sliced over the devices; a slice is divided in place in its staged copy, and the
+// outputs are written once every slice succeeded
+int poly_host(te_ctx* ctx, const poly_req& r, const uint8_t* a, uint64_t count, const uint8_t* z, uint8_t* evals, uint8_t* q) {
+  const size_t pb = (size_t)r.n * 32;
+  const slice_plan sp(ctx, count);
+  struct slice_t { dev_tmp a; };
+  std::vector<slice_t> sl(sp.D);
+  std::vector<uint8_t> ev(evals ? (size_t)count * 32 : 0);
+  auto stage = [&](size_t i) -> int {
+    const uint64_t lo = sp.lo(i), m = sp.count(i);
+    if (m == 0) return 0;
+    if (int rc = tmp_alloc(ctx, ctx->devs[i], sl[i].a, m * pb)) return rc;
+    HIP_TRY(ctx, hipMemcpy(sl[i].a.p, a + lo * pb, m * pb, hipMemcpyHostToDevice));
+    return poly_on(ctx, i, r, sl[i].a.p, m, r.shared ? z : z + lo * 32, evals ? ev.data() + lo * 32 : nullptr, q ? sl[i].a.p : nullptr);
+  };
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  if (q) { if (int rc = copy_slices_out(ctx, sp, pb, q, [&](size_t i) { return sl[i].a.p; })) return rc; }
+  if (evals) memcpy(evals, ev.data(), ev.size());
+  return 0;
+}
 }  // namespace
 
 void free_mul_base(te_ctx* ctx, te_base* b) {
@@ -1200,6 +1284,26 @@ int te_msm_ntt_device(te_ctx* ctx, const void* d_a, uint32_t log_n, uint64_t cou
   const int owner = owner_of(ctx, "te_msm_ntt_device: the input and the output must be resident on one device of the context", {d_a, d_out});
   if (owner < 0) return owner;
   return ntt_on(ctx, (size_t)owner, q, d_a, count, d_out);
+}
+
+int te_msm_poly_divide(te_ctx* ctx, const uint8_t* a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, uint8_t* q) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  poly_req r;
+  if (int rc = poly_args(ctx, a, n, count, z, flags, evals, q, r)) return rc;
+  return count ? poly_host(ctx, r, a, count, z, evals, q) : 0;
+}
+
+int te_msm_poly_divide_device(te_ctx* ctx, const void* d_a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, void* d_q) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  poly_req r;
+  if (int rc = poly_args(ctx, d_a, n, count, z, flags, evals, d_q, r)) return rc;
+  if (count == 0) return 0;
+  const char* const where = "te_msm_poly_divide_device: the coefficients and the quotient must be resident on one device of the context";
+  const int owner = d_q ? owner_of(ctx, where, {d_a, d_q}) : owner_of(ctx, where, {d_a});
+  if (owner < 0) return owner;
+  return poly_on(ctx, (size_t)owner, r, d_a, count, z, evals, d_q);
 }
 
 }  // extern "C"

@@ -118,6 +118,7 @@ void free_dev(gpu_t& d) {
   d.chk_pts.release();
   d.ntt_tab.release();
   d.ntt_tmp.release();
+  d.poly_tmp.release();
   if (d.chk_word) (void)hipFree(d.chk_word);
   if (d.chk_host) (void)hipHostFree(d.chk_host);
   d.chk_stream = nullptr; d.chk_word = d.chk_host = nullptr;

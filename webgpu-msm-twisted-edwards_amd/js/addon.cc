@@ -673,6 +673,68 @@ napi_value Ntt(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+// polyDivide(a: Buffer, n: number, z: Buffer, opts?: {count?: number, montgomery?: boolean, sharedZ?: boolean, quotient?: boolean}):
+// {evals: Buffer, quotient: Buffer | null} -- polynomial openings over p (include/te_msm.h, te_msm_poly_divide): `count` (default 1)
+// polynomials of n 32-byte coefficients each, lowest first; z one 32-byte record a polynomial, or one in all with sharedZ.  evals: a(z) of
+// each; quotient: the coefficients of (a(X) - a(z)) / (X - z) at the stride n, or null with quotient: false (the call then only
+// evaluates).  Run like ntt; a refusal (n = 0, n above 2^30) throws.
+napi_value PolyDivide(napi_env env, napi_callback_info info) {
+  const char* const sig = "polyDivide(a: Buffer, n: number, z: Buffer, opts?: {count?: number, montgomery?: boolean, sharedZ?: boolean, quotient?: boolean})";
+  size_t argc = 4; napi_value argv[4];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool a_buf = false, z_buf = false;
+  napi_valuetype t_n = napi_undefined, t_opts = napi_undefined;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &a_buf);
+  if (argc >= 2) napi_typeof(env, argv[1], &t_n);
+  if (argc >= 3) napi_is_buffer(env, argv[2], &z_buf);
+  if (argc >= 4) napi_typeof(env, argv[3], &t_opts);
+  const bool opts_none = t_opts == napi_undefined || t_opts == napi_null;
+  if (!a_buf || !z_buf || t_n != napi_number || (t_opts != napi_object && !opts_none)) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  int64_t n = 0, count = 1;
+  if (napi_get_value_int64(env, argv[1], &n) != napi_ok || n < 0) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  int flags = 0;
+  bool want_q = true;
+  if (t_opts == napi_object) {
+    const struct { const char* name; int bit; } bits[] = {{"montgomery", TE_MSM_POLY_MONTGOMERY}, {"sharedZ", TE_MSM_POLY_SHARED_Z}};
+    for (const auto& f : bits) {
+      napi_value v; bool has = false, on = false;
+      napi_has_named_property(env, argv[3], f.name, &has);
+      if (has) { napi_get_named_property(env, argv[3], f.name, &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &on); }
+      if (on) flags |= f.bit;
+    }
+    napi_value v; bool has = false;
+    napi_has_named_property(env, argv[3], "count", &has);
+    if (has) { napi_get_named_property(env, argv[3], "count", &v); if (napi_get_value_int64(env, v, &count) != napi_ok || count < 0) { napi_throw_type_error(env, nullptr, sig); return nullptr; } }
+    napi_has_named_property(env, argv[3], "quotient", &has);
+    if (has) { napi_get_named_property(env, argv[3], "quotient", &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &want_q); }
+  }
+  void *pa = nullptr, *pz = nullptr; size_t al = 0, zl = 0;
+  napi_get_buffer_info(env, argv[0], &pa, &al);
+  napi_get_buffer_info(env, argv[2], &pz, &zl);
+  const bool n_ok = n >= 1 && (uint64_t)n <= TE_MSM_POLY_MAX_N;      // (the library refuses the others itself: any a is then passed through)
+  if (zl != 32u * (size_t)((flags & TE_MSM_POLY_SHARED_Z) ? 1 : count) || (n_ok && (count > (int64_t)(SIZE_MAX >> 36) || al != (size_t)count * (size_t)n * 32u))) {
+    napi_throw_range_error(env, nullptr, "polyDivide: a must be count * n * 32 bytes, z one record of 32 a polynomial (one in all with sharedZ)");
+    return nullptr;
+  }
+  std::vector<uint8_t> evals((size_t)count * 32 + 1), q(want_q ? al + 1 : 0);      // (never empty: an output the call is given is not NULL)
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    return te_msm_poly_divide(c, static_cast<const uint8_t*>(pa), (uint64_t)n, (uint64_t)count, static_cast<const uint8_t*>(pz), flags, evals.data(), want_q ? q.data() : nullptr);
+  }, err);
+  if (rc) {
+    const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_throw_error(env, nullptr, m.c_str());
+    return nullptr;
+  }
+  napi_value res, be, bq; void* dst = nullptr;
+  napi_create_object(env, &res);
+  napi_create_buffer_copy(env, (size_t)count * 32, evals.data(), &dst, &be);
+  if (want_q) napi_create_buffer_copy(env, al, q.data(), &dst, &bq); else napi_get_null(env, &bq);
+  napi_set_named_property(env, res, "evals", be);
+  napi_set_named_property(env, res, "quotient", bq);
+  return res;
+}
+
 // setBase(point: Buffer) and scalarMulBase(scalars: Buffer): Buffer -- fixed-base batch scalar multiplication (include/te_msm.h,
 // te_msm_bind_base / te_msm_mul_base): one 64-byte point bound once, then n x 32-byte little-endian scalars -> n x 64-byte points
 // [k_i] P (the identity as (0, 1)).  Twisted-Edwards curve only, like the rest of the addon; run like scalarMul.  The addon keeps the
@@ -846,7 +908,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"setBase", SetBase}, {"scalarMulBase", ScalarMulBase},
       {"groupAdd", GroupAdd}, {"groupAddX", GroupAddX}, {"groupSum", GroupSum}, {"groupSumX", GroupSumX},
       {"fieldOp", FieldOp},
-      {"ntt", Ntt}};
+      {"ntt", Ntt},
+      {"polyDivide", PolyDivide}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -105,6 +105,12 @@ const fieldOp = async (op, a, b, opts) => native.fieldOp(op, a, b === undefined 
 // to the results as a Buffer (canonical); rejects for logN above 24 and for a shift that is 0 mod p.
 const ntt = async (a, logN, opts) => native.ntt(a, logN, opts);
 
+// polyDivide(a, n, z, {count, montgomery, sharedZ, quotient}): `count` (default 1) polynomials of n 32-byte coefficients of p each, lowest
+// first, evaluated at their points z (one 32-byte record each, or one in all with sharedZ) and divided by X - z (te_msm_poly_divide):
+// resolves to {evals, quotient} -- a(z) of each, and the coefficients of (a(X) - a(z)) / (X - z) at the stride n, the witness polynomial
+// of a KZG opening (null with quotient: false).  montgomery: every record holds v * 2^256 mod p.  A refusal rejects.
+const polyDivide = async (a, n, z, opts) => native.polyDivide(a, n, z, opts);
+
 // Outside the reference's interface too: msmBatch(scalarBuffers) runs one MSM per Buffer over the set bound by setBases -- MSM m over
 // its first scalarBuffers[m].length / 32 points (a prover's commitments to polynomials of different degrees against one SRS) -- and
 // returns their results as [{x, y}, ...] in compute_msm's form, in input order.  Small MSMs share launch sequences on the GPU.
@@ -124,4 +130,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS, ntt };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS, ntt, polyDivide };

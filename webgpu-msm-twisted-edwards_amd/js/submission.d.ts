@@ -61,6 +61,12 @@ export declare const fieldOp: (op: number, a: Buffer, b?: Buffer | null,
 // inverse undoes the forward with the same shift; montgomery as for fieldOp.  Rejects for logN above 24 and a shift that is 0 mod p.
 export declare const ntt: (a: Buffer, logN: number,
   opts?: { count?: number, inverse?: boolean, montgomery?: boolean, shift?: Buffer }) => Promise<Buffer>;
+// Not in the reference: polynomial openings over p on the device -- `count` (default 1) polynomials of n 32-byte coefficients each, lowest
+// first, evaluated at their points z (one 32-byte record each, or one in all with sharedZ) and divided by X - z.  evals: a(z) of each;
+// quotient: the coefficients of (a(X) - a(z)) / (X - z) at the stride n (the last one 0), the witness polynomial of a KZG opening, or null
+// with quotient: false.  montgomery as for fieldOp.  Rejects for n = 0 and n above 2^30.
+export declare const polyDivide: (a: Buffer, n: number, z: Buffer,
+  opts?: { count?: number, montgomery?: boolean, sharedZ?: boolean, quotient?: boolean }) => Promise<{ evals: Buffer, quotient: Buffer | null }>;
 // Not in the reference: batched MSMs over prefixes of the set bound by setBases; MSM m runs over the first scalarBuffers[m].length / 32
 // points.  Results in input order, in compute_msm's form; throws without setBases or for a buffer longer than the set.
 export declare const msmBatch: (scalarBuffers: Buffer[]) => { x: bigint; y: bigint }[];
