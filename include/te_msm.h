@@ -610,6 +610,49 @@ int te_msm_ntt_device(te_ctx* ctx, const void* d_a, uint32_t log_n, uint64_t cou
 int te_msm_poly_divide(te_ctx* ctx, const uint8_t* a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, uint8_t* q);
 int te_msm_poly_divide_device(te_ctx* ctx, const void* d_a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, void* d_q);
 
+/* ---- sparse matrices --------------------------------------------------------------------------------------------------------------
+ * te_msm_bind_matrix / te_msm_spmv*: products of a sparse matrix over p (TE_MSM_FIELD_P, the records of te_msm_ntt) with `count`
+ * vectors -- the Az, Bz, Cz every R1CS prover (Groth16, Marlin, Varuna) starts with, and Varuna's products with the transposed matrices.
+ * The matrices are fixed per circuit and the assignment changes per proof: bind once, as te_msm_bind_points binds the bases, then move
+ * only the vector -- or leave it on the device, where te_msm_ntt_device takes the result.
+ * Matrix: CSR from HOST memory, bound on EVERY device of the context.  row_ptr has rows + 1 entries, row_ptr[0] = 0, nnz = row_ptr[rows];
+ *   row r holds the entries row_ptr[r] .. row_ptr[r + 1] - 1: column col_idx[e] (any order inside a row; a repeated column is summed;
+ *   empty rows are allowed) and the 32-byte little-endian value vals[32 e ..].  The arrays are not read after the bind returns.
+ * Result:  out[k * rows + r] = sum_e vals[e] * x[k * cols + col_idx[e]] mod p  over the entries e of row r, for k < count.
+ *   Under TE_MSM_SPMV_TRANSPOSE the same for the transposed matrix: x is count x rows, out is count x cols.  A call may ask for it only
+ *   if the bind kept the transpose (TE_MSM_MATRIX_TRANSPOSE: twice the device memory).
+ * Montgomery forms: TE_MSM_MATRIX_MONTGOMERY -- vals hold v * 2^256 mod p; TE_MSM_SPMV_MONTGOMERY -- x and out do.  Independent of
+ *   each other: the product is linear in x, the bind stores every value once in the engine's own form, and one code path serves both.
+ * Values: as te_msm_field_op -- ANY 256-bit record stands for its residue, outputs are canonical.  count = 0 succeeds and touches nothing.
+ * Refusals, all TE_MSM_EINVAL with every output untouched and the context usable.  Bind: rows or cols 0 or above 2^31; row_ptr[0] != 0 or
+ *   a row_ptr that is not monotone; a column index >= cols (its lowest position: read-only option "bad_index_position"); a NULL array
+ *   with nnz > 0 (row_ptr: always); an unknown flag bit; more than 2^40 entries.  Call: an unknown flag bit; TRANSPOSE on a matrix bound
+ *   without it; a matrix that is not bound to this context; NULL x or out; out == x (the kernel gathers from x: never in place); byte
+ *   counts beyond 64 bits (or more than 2^31 - 1 blocks in one launch); te_msm_spmv_device: d_x and d_out not on one device of the context.
+ * Buffers: te_msm_spmv_device returns with d_out complete -- EVERY record written, empty rows as 0, whatever d_out held.  te_msm_spmv
+ *   slices WHOLE vectors over the context's devices, one host thread per device.  Every element and byte offset is 64 bits wide.  The
+ *   fragments of rows that span tiles (two records a tile and vector) live in a buffer of the device's, grown on use and kept until
+ *   te_msm_trim / te_msm_destroy.  te_msm_destroy frees matrices left bound.  The calling thread's device is left as it was.
+ * How it runs (csrc/spmv_plan.hpp, csrc/spmv.hip.hpp): a 256-lane block owns a tile of T = 256 chunk consecutive
+ *   ENTRIES, cut by position, never by row -- a row of 2^20 entries (the constant column's row of a transpose) is 1024 tiles like any
+ *   others.  k_spmv_tile forms the products, sums runs of equal row inside a lane and across the lanes with a segmented scan, and writes
+ *   the rows that lie inside the tile; k_spmv_rows writes the empty rows and sums the fragments of rows that span tiles.  No atomics:
+ *   the result is the same bytes every time.  chunk: TE_MSM_SPMV_CHUNK, or what the environment variable TE_MSM_SPMV_CHUNK names
+ *   (1 .. 16), read by every call.  Read-only options: "spmv_chunk" (the chunk in force), "matrix_bytes" (what the context's devices
+ *   hold of bound matrices: 0 once all are released), "spmv_scratch_bytes" (what they hold now of the fragment buffer).
+ * COST: DESIGN.md section 24, profiles/spmv_cost.txt (tools/spmv_cost.py). */
+typedef struct te_matrix te_matrix;
+#define TE_MSM_MATRIX_MONTGOMERY 1   /* vals hold v * 2^256 mod p */
+#define TE_MSM_MATRIX_TRANSPOSE 2    /* keep the transpose too: calls may then pass TE_MSM_SPMV_TRANSPOSE */
+#define TE_MSM_SPMV_MONTGOMERY 1     /* x and out hold v * 2^256 mod p */
+#define TE_MSM_SPMV_TRANSPOSE 2      /* multiply by the transposed matrix */
+#define TE_MSM_SPMV_CHUNK 4u
+int te_msm_bind_matrix(te_ctx* ctx, uint64_t rows, uint64_t cols, const uint64_t* row_ptr, const uint32_t* col_idx, const uint8_t* vals, int flags, te_matrix** out);
+int te_msm_release_matrix(te_ctx* ctx, te_matrix* matrix);
+int te_msm_matrix_shape(const te_matrix* matrix, uint64_t* rows, uint64_t* cols, uint64_t* nnz);
+int te_msm_spmv(te_ctx* ctx, te_matrix* matrix, const uint8_t* x, uint64_t count, int flags, uint8_t* out);
+int te_msm_spmv_device(te_ctx* ctx, te_matrix* matrix, const void* d_x, uint64_t count, int flags, void* d_out);
+
 /* Options (the reference hard-codes these: chunk_size submission.ts:80, dispatch table :109-142).
  *   "scalars_montgomery" 0 (default) = scalar records hold the integers themselves (the wire format above); 1 = every scalar record holds
  *                   a = k * 2^256 mod m and the MSM uses k = a * 2^-256 mod m, where m is the scalar field of the curve in force:

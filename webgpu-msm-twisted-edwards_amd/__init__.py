@@ -62,5 +62,10 @@ from .binding import (  # noqa: F401
     POLY_MONTGOMERY,
     POLY_SHARED_Z,
     POLY_MAX_N,
+    MATRIX_MONTGOMERY,
+    MATRIX_TRANSPOSE,
+    SPMV_MONTGOMERY,
+    SPMV_TRANSPOSE,
+    Matrix,
 )
 from .sharding import ShardedPipeline, compute_msm_sharded, distribute_inputs, exchange_partials, merge_partials, rows_of_batched_msm, window_shard_for_rank  # noqa: F401

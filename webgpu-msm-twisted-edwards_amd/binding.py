@@ -31,6 +31,8 @@ NTT_INVERSE, NTT_MONTGOMERY = 1, 2                              # flags of te_ms
 NTT_MAX_LOG_N = 24
 POLY_MONTGOMERY, POLY_SHARED_Z = 1, 2                            # flags of te_msm_poly_divide*
 POLY_MAX_N = 1 << 30
+MATRIX_MONTGOMERY, MATRIX_TRANSPOSE = 1, 2                        # flags of te_msm_bind_matrix
+SPMV_MONTGOMERY, SPMV_TRANSPOSE = 1, 2                            # flags of te_msm_spmv*
 FIELD_ZERO, FIELD_NOT_SQUARE = 1, 2      # why an element has no result (MsmError.reason)
 
 
@@ -255,6 +257,17 @@ def _lib() -> ctypes.CDLL:
             L.te_msm_poly_divide.restype = ci
             L.te_msm_poly_divide_device.argtypes = [vp, vp, u64, u64, vp, ci, vp, vp]
             L.te_msm_poly_divide_device.restype = ci
+        if not os.environ.get("TE_MSM_LIB") or hasattr(L, "te_msm_bind_matrix"):
+            L.te_msm_bind_matrix.argtypes = [vp, u64, u64, vp, vp, vp, ci, ctypes.POINTER(vp)]
+            L.te_msm_bind_matrix.restype = ci
+            L.te_msm_release_matrix.argtypes = [vp, vp]
+            L.te_msm_release_matrix.restype = ci
+            L.te_msm_matrix_shape.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+            L.te_msm_matrix_shape.restype = ci
+            L.te_msm_spmv.argtypes = [vp, vp, vp, u64, ci, vp]
+            L.te_msm_spmv.restype = ci
+            L.te_msm_spmv_device.argtypes = [vp, vp, vp, u64, ci, vp]
+            L.te_msm_spmv_device.restype = ci
         _LIB = L
     return _LIB
 
@@ -655,6 +668,44 @@ class MsmContext:
         self._check(self._L.te_msm_poly_divide_device(self._h, d_a, n, count, rec, flags, ev, d_q))
         return ev.raw[:32 * count] if evals else None
 
+    # ---- sparse matrices (include/te_msm.h "sparse matrices"): a CSR matrix over p bound once, products with many vectors
+    def bind_matrix(self, rows: int, cols: int, row_ptr, col_idx, vals, *, montgomery: bool = False, transpose: bool = False) -> "Matrix":
+        """te_msm_bind_matrix: row_ptr (rows + 1 offsets) and col_idx as sequences of integers or packed little-endian bytes (8 / 4 bytes
+        each), vals as 32-byte records (bytes) or integers below 2^256 (Montgomery residues with `montgomery`).  transpose: keep the
+        transpose too, so that spmv(..., transpose=True) may be asked.  Bound on every device of the context."""
+        def packed(v, width):
+            return bytes(v) if isinstance(v, (bytes, bytearray, memoryview)) else b"".join(int(x).to_bytes(width, "little") for x in v)
+        ptr, col, val = packed(row_ptr, 8), packed(col_idx, 4), packed(vals, 32)
+        if rows < 0 or cols < 0 or len(ptr) != 8 * (rows + 1):
+            raise MsmError(-1, "row_ptr must hold rows + 1 offsets")
+        nnz = int.from_bytes(ptr[-8:], "little")
+        if len(col) < 4 * nnz or len(val) < 32 * nnz:
+            raise MsmError(-1, "col_idx and vals must hold row_ptr[rows] entries")
+        flags = (MATRIX_MONTGOMERY if montgomery else 0) | (MATRIX_TRANSPOSE if transpose else 0)
+        h = ctypes.c_void_p()
+        self._check(self._L.te_msm_bind_matrix(self._h, rows, cols, ptr, col or None, val or None, flags, ctypes.byref(h)))
+        return Matrix(self, h, rows, cols, nnz, transpose)
+
+    def release_matrix(self, matrix: "Matrix"):
+        self._check(self._L.te_msm_release_matrix(self._h, matrix._h))
+        matrix._h = None
+
+    def spmv(self, matrix: "Matrix", x: bytes, *, count: int = 1, montgomery: bool = False, transpose: bool = False) -> bytes:
+        """te_msm_spmv: `count` vectors of cols 32-byte records each (rows with `transpose`) -> count x rows records (count x cols):
+        out[k rows + r] = sum over the entries of row r of vals[e] x[k cols + col_idx[e]] mod p, canonical"""
+        n_in, n_out = (matrix.rows, matrix.cols) if transpose else (matrix.cols, matrix.rows)
+        if count < 0 or len(x) != 32 * count * n_in:
+            raise MsmError(-1, "x must be count * cols * 32 bytes (count * rows with transpose)")
+        flags = (SPMV_MONTGOMERY if montgomery else 0) | (SPMV_TRANSPOSE if transpose else 0)
+        out = ctypes.create_string_buffer(max(1, 32 * count * n_out))
+        self._check(self._L.te_msm_spmv(self._h, matrix._h, bytes(x) or None, count, flags, out))
+        return out.raw[:32 * count * n_out]
+
+    def spmv_device(self, matrix: "Matrix", d_x: int, count: int, d_out: int, *, montgomery: bool = False, transpose: bool = False):
+        """te_msm_spmv_device: the same between buffers on one device of the context; d_out must not be d_x"""
+        flags = (SPMV_MONTGOMERY if montgomery else 0) | (SPMV_TRANSPOSE if transpose else 0)
+        self._check(self._L.te_msm_spmv_device(self._h, matrix._h, d_x, count, flags, d_out))
+
     def add_x(self, ax: bytes, bx: bytes, subtract: bool = False) -> bytes:
         """te_msm_add_x, bulkAddGroups' counterpart: n x-only points a and n (or one) b (32 / 48 bytes, points_from_x's format) -> n points x || y"""
         n = self._x_count(ax)
@@ -930,6 +981,18 @@ class Base:
     def release(self):
         if self._h is not None and getattr(self._ctx, "_h", None):
             self._ctx.release_base(self)
+        self._h = None
+
+
+class Matrix:
+    """A bound sparse matrix of one MsmContext (te_matrix): its CSR arrays, and its transpose's when asked, on every device of the context."""
+
+    def __init__(self, ctx: MsmContext, handle, rows: int, cols: int, nnz: int, transpose: bool):
+        self._ctx, self._h, self.rows, self.cols, self.nnz, self.transpose = ctx, handle, rows, cols, nnz, transpose
+
+    def release(self):
+        if self._h is not None and getattr(self._ctx, "_h", None):
+            self._ctx.release_matrix(self)
         self._h = None
 
 

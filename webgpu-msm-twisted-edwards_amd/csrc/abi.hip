@@ -40,7 +40,7 @@ int te_msm_trim(te_ctx* ctx, int keep_worksets) {
       free_workset_buffers(ws);
       freed++;
     }
-    { std::lock_guard<std::mutex> lk(*d.chk_mu); d.ntt_tab.release(); d.ntt_tmp.release(); d.poly_tmp.release(); }      // the NTT twiddle tables and scratch: made again by the next transform (none runs: it holds chk_mu)
+    { std::lock_guard<std::mutex> lk(*d.chk_mu); d.ntt_tab.release(); d.ntt_tmp.release(); d.poly_tmp.release(); d.spmv_tmp.release(); }      // the NTT twiddle tables and scratch: made again by the next transform (none runs: it holds chk_mu)
     for (auto& sl : d.slabs) if (sl.users == 0 && sl.d) {                    // idle shared record slabs
       if (int rc = settle_slab(ctx, sl, nullptr, true)) return rc;
       for (workset_t& ws : d.ws) if (ws.recs_last == sl.d) ws.recs_last = nullptr;
@@ -136,6 +136,18 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "poly_scratch_bytes")) {                            // the sums, carries and powers of te_msm_poly_divide*
     *value = 0;
     for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.poly_tmp.p ? (int64_t)d.poly_tmp.cap : 0; }
+    return 0;
+  }
+  if (!strcmp(key, "spmv_chunk")) { *value = (int64_t)te_spmv::chunk_in_force(); return 0; }   // TE_MSM_SPMV_CHUNK, or what the environment names
+  if (!strcmp(key, "spmv_scratch_bytes")) {                            // the fragments of te_msm_spmv*
+    *value = 0;
+    for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.spmv_tmp.p ? (int64_t)d.spmv_tmp.cap : 0; }
+    return 0;
+  }
+  if (!strcmp(key, "matrix_bytes")) {                                  // the bound matrices, over all devices
+    int64_t t = 0;
+    for (const te_matrix* m : ctx->matrices) for (const uint8_t* s : m->side) if (s) t += (int64_t)m->bytes();
+    *value = t;
     return 0;
   }
   if (!strcmp(key, "bad_index_position")) { *value = ctx->bad_index_position; return 0; }

@@ -1,6 +1,6 @@
 // engine.hpp -- what the translation units of libtemsm.so share: the context and its work sets, the plan, the requests a launch
 // sequence is asked with, and the functions that more than one unit calls.  No kernel header in here: te_msm.hip alone includes
-// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication / fixed-base / group-addition / field-arithmetic / NTT kernels
+// kernels.hip.hpp and probe.hip.hpp, points.hip the check / x-recovery / scalar-multiplication / fixed-base / group-addition / field-arithmetic / NTT / polynomial / sparse-matrix kernels
 // (a non-template __global__ function may be defined once per library, and every inclusion repeats the device compile).
 //
 // The units:   te_msm.hip   the engine core: plan and buffers, the launch sequences, streams and queue probe, record slabs, uploads
@@ -8,7 +8,8 @@
 //              tickets.hip  te_msm_submit* / ticket_wait / collect
 //              bases.hip    bound point sets: bind, scalars-only, indexed and batched MSMs
 //              points.hip   point checks, x-only points, batch scalar multiplication (per point, and over one bound point with its
-//                           fixed-base table), batched group addition and point-set sums, batched field arithmetic, batched NTTs
+//                           fixed-base table), batched group addition and point-set sums, batched field arithmetic, batched NTTs,
+//                           polynomial openings, bound sparse matrices and their products
 //              abi.hip      the rest of the C-ABI: options, trim, building blocks, host tails, debug reads
 // Everything in here has hidden visibility; a function only one unit calls is file-local there.  The library exports the C-ABI of
 // include/te_msm.h and nothing else of the engine.
@@ -38,6 +39,7 @@
 #include "fb_plan.hpp"
 #include "ntt_plan.hpp"
 #include "poly_plan.hpp"
+#include "spmv_plan.hpp"
 
 #pragma GCC visibility push(hidden)
 #include "host_sched.hpp"
@@ -210,6 +212,8 @@ struct gpu_t {
                                          // use under chk_mu, freed with the tables (get_option "ntt_scratch_bytes")
   dev_buf<uint8_t> poly_tmp;             // te_msm_poly_divide*: the tile sums, carries and powers of a call (poly_plan.hpp, scratch_bytes: about count * n / T records),
                                          // grown on use under chk_mu, freed by te_msm_trim / destroy (get_option "poly_scratch_bytes")
+  dev_buf<uint8_t> spmv_tmp;             // te_msm_spmv*: the fragments of rows that span tiles (spmv_plan.hpp, scratch_bytes: two records a tile and vector),
+                                         // grown on use under chk_mu, freed by te_msm_trim / destroy (get_option "spmv_scratch_bytes")
 };
 
 }  // namespace te_eng
@@ -266,6 +270,7 @@ struct te_ctx {
                                     // starts, on the calling thread -- a ticket keeps the form it was submitted with (plan_t::scalar_mont)
   int opt_points_montgomery = 0;    // te_msm_bind_points[_device]: coordinates are Montgomery residues x 2^256 mod p / x 2^384 mod q; read at bind time
   std::vector<te_base*> mul_bases;  // the bound points of fixed-base scalar multiplication (te_msm_bind_base), freed by te_msm_release_base / te_msm_destroy
+  std::vector<te_matrix*> matrices; // the bound sparse matrices (te_msm_bind_matrix), freed by te_msm_release_matrix / te_msm_destroy
   int opt_scalar_record_bytes = 0;  // bytes of one scalar record: 0 = the curve's own (32 / 48), 32 = BLS12-377 scalars as a native prover holds them, 8 / 16 = a
                                     // native &[u64] / &[u128]; read when a call starts, on the calling thread -- a ticket keeps the size it was submitted with (plan_t::sc_bytes)
   int opt_scalar_bits = 0;          // the caller declares every scalar below 2^b (0 = nothing declared; 8-byte records: their width; 16-byte records need it set); read when a call starts, as
@@ -296,6 +301,16 @@ struct te_base {
   uint32_t per = 0;              // entries of a window: 2^(W-1) + 1
   std::vector<uint8_t*> tab;     // tab[i]: M * per entries in the memory of ctx->devs[i]
   size_t bytes() const { return (size_t)M * per * 128; }
+};
+
+// A bound sparse matrix (include/te_msm.h, te_msm_bind_matrix; csrc/spmv_plan.hpp): its CSR arrays on EVERY device of its context, the
+// values converted once; with_t: the same for its transpose, a CSR matrix of cols rows.
+struct te_matrix {
+  te_ctx* ctx = nullptr;
+  uint64_t rows = 0, cols = 0, nnz = 0;
+  bool with_t = false;
+  std::vector<uint8_t*> side, side_t;    // side[i] / side_t[i]: one allocation of te_spmv::layout_of in the memory of ctx->devs[i]
+  size_t bytes() const { return (size_t)(te_spmv::layout_of(rows, nnz).bytes + (with_t ? te_spmv::layout_of(cols, nnz).bytes : 0)); }
 };
 
 namespace te_eng {
@@ -524,6 +539,7 @@ int note_bad(te_ctx* ctx, bad_kind kind, int64_t index, int reason, int64_t* fir
 int check_call(te_ctx* ctx, size_t di, const void* src, bool src_is_host, uint64_t n, bool mont = false, point_layout lay = {});
 int tmp_alloc(te_ctx* ctx, gpu_t& d, dev_tmp& t, size_t bytes);
 void free_mul_base(te_ctx* ctx, te_base* b);
+void free_matrix(te_ctx* ctx, te_matrix* m);
 
 // An asynchronous ticket: `enqueue` (the upload and the launches of one whole MSM; 0 or an error already noted) runs on an upload lane
 // of the ticket's device, and the call returns at once -- D of them keep D links busy.  The job's status, and the error text of a failure,

@@ -2,8 +2,9 @@
 // points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x), batch scalar multiplication (te_msm_mul*) and its fixed-base form
 // over one bound point (te_msm_bind_base, te_msm_mul_base*), batched group addition and point-set sums (te_msm_add*, te_msm_sum*), and
 // batched arithmetic in the two base fields (te_msm_field_op*), batched NTTs over p (te_msm_ntt*) and polynomial openings
-// (te_msm_poly_divide*).  The one unit that includes the kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp,
-// group_add.hip.hpp, field_ops.hip.hpp, ntt.hip.hpp and poly.hip.hpp.
+// (te_msm_poly_divide*), bound sparse matrices and their products (te_msm_bind_matrix, te_msm_spmv*).  The one unit that includes the
+// kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp, group_add.hip.hpp, field_ops.hip.hpp, ntt.hip.hpp,
+// poly.hip.hpp and spmv.hip.hpp.
 #include "engine.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
@@ -13,6 +14,7 @@
 #include "field_ops.hip.hpp"
 #include "ntt.hip.hpp"
 #include "poly.hip.hpp"
+#include "spmv.hip.hpp"
 
 using namespace te_eng;
 
@@ -938,11 +940,98 @@ int poly_host(te_ctx* ctx, const poly_req& r, const uint8_t* a, uint64_t count, 
   if (evals) memcpy(evals, ev.data(), ev.size());
   return 0;
 }
+
+// ---- sparse matrices (te_msm_bind_matrix, te_msm_spmv*; kernels in spmv.hip.hpp, plan in spmv_plan.hpp) --------------------------------
+// A bind converts the values on the host (one product an entry with the host build of the field), fills the row ids, builds the
+// transpose when asked, and copies one allocation a side to every device.  A call runs on the device's check lane: k_spmv_tile over
+// count x tiles blocks (none for a matrix without entries), k_spmv_rows behind it; the fragments live in the device's spmv_tmp, grown on
+// use like poly_tmp.  No piece loop: x and out are the caller's.
+static_assert(TE_MSM_SPMV_CHUNK == te_spmv::kChunkDefault, "include/te_msm.h and spmv_plan.hpp disagree");
+const char* const kBadMatrix = "not a bound matrix of this context (released, or bound to another context)";
+// one side as the host holds it before the upload: te_spmv::layout_of(rows, nnz) in one buffer
+struct matrix_image {
+  te_spmv::layout lay; std::vector<uint8_t> bytes;
+  matrix_image(uint64_t rows, uint64_t nnz) : lay(te_spmv::layout_of(rows, nnz)), bytes((size_t)lay.bytes) {}
+  uint8_t* vals() { return bytes.data() + lay.vals; }
+  uint64_t* ptr() { return reinterpret_cast<uint64_t*>(bytes.data() + lay.ptr); }
+  uint32_t* col() { return reinterpret_cast<uint32_t*>(bytes.data() + lay.col); }
+  uint32_t* row() { return reinterpret_cast<uint32_t*>(bytes.data() + lay.row); }
+};
+int matrix_upload(te_ctx* ctx, size_t i, const matrix_image& img, uint8_t** where) {
+  HIP_TRY(ctx, hipSetDevice(ctx->devs[i].device));
+  HIP_TRY(ctx, hipMalloc((void**)where, img.bytes.size()));                 // (freed by the caller on failure: free_matrix)
+  HIP_TRY(ctx, hipMemcpy(*where, img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+te::spmv_side side_at(const uint8_t* base, uint64_t rows, uint64_t nnz) {
+  const te_spmv::layout l = te_spmv::layout_of(rows, nnz);
+  return te::spmv_side{reinterpret_cast<const uint4*>(base + l.vals), reinterpret_cast<const uint64_t*>(base + l.ptr), reinterpret_cast<const uint32_t*>(base + l.col),
+                       reinterpret_cast<const uint32_t*>(base + l.row)};
+}
+// `count` vectors at d_x (memory of devs[di]) -> d_out; tr: by the transpose.  Returns when d_out is complete
+int spmv_on(te_ctx* ctx, size_t di, const te_matrix* M, bool tr, uint32_t chunk, const void* d_x, uint64_t count, void* d_out) {
+  if (count == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  te_spmv::plan P;
+  if (!te_spmv::make_plan(tr ? M->cols : M->rows, tr ? M->rows : M->cols, M->nnz, count, chunk, P))
+    return set_err(ctx, TE_MSM_EINVAL, "te_msm_spmv*: count x rows x 32 does not fit 64 bits, or more blocks than one launch holds");
+  const te::spmv_side side = side_at(tr ? M->side_t[di] : M->side[di], P.rows, P.nnz);
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  hipStream_t st = lane.stream();
+  if (P.scratch_bytes) { if (int rc = make_room(ctx, d.spmv_tmp, (size_t)P.scratch_bytes)) return rc; }
+  uint4* const frag = reinterpret_cast<uint4*>(d.spmv_tmp.p);
+  const dim3 block(te_spmv::kLanes);
+  if (P.tiles > 0) {
+    const size_t lds = te_spmv::lds_bytes(P.chunk);
+    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&te::k_spmv_tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(te::k_spmv_tile, dim3((uint32_t)(count * P.tiles)), block, lds, st, side, P, static_cast<const uint4*>(d_x), static_cast<uint4*>(d_out), frag);
+  }
+  hipLaunchKernelGGL(te::k_spmv_rows, dim3((uint32_t)(count * P.per)), block, 0, st, side, P, static_cast<uint4*>(d_out), frag);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return 0;
+}
+// what every te_msm_spmv* call checks first (te::spmv_check_call); go: there is something to run
+int spmv_args(te_ctx* ctx, const te_matrix* M, const void* x, uint64_t count, int flags, const void* out, bool* go) {
+  *go = false;
+  if (!M || std::find(ctx->matrices.begin(), ctx->matrices.end(), M) == ctx->matrices.end()) return set_err(ctx, TE_MSM_EINVAL, kBadMatrix);
+  switch (te::spmv_check_call(M->with_t, M->rows, M->cols, x, count, flags, out)) {
+    case te::SPMV_OK: *go = count > 0; return 0;
+    case te::SPMV_BAD_FLAGS: return set_err(ctx, TE_MSM_EINVAL, "te_msm_spmv*: unknown flag bits");
+    case te::SPMV_NO_TRANSPOSE: return set_err(ctx, TE_MSM_EINVAL, "te_msm_spmv*: the matrix was bound without TE_MSM_MATRIX_TRANSPOSE");
+    case te::SPMV_IN_PLACE: return set_err(ctx, TE_MSM_EINVAL, "te_msm_spmv*: out must not be x (the product gathers from x)");
+    case te::SPMV_TOO_LARGE: return set_err(ctx, TE_MSM_EINVAL, "te_msm_spmv*: count x rows x 32 does not fit 64 bits");
+    default: return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  }
+}
+// te_msm_spmv: host buffers, whole vectors sliced over the devices; out is written once every slice succeeded
+int spmv_host(te_ctx* ctx, const te_matrix* M, bool tr, uint32_t chunk, const uint8_t* x, uint64_t count, uint8_t* out) {
+  const size_t xb = (size_t)(tr ? M->rows : M->cols) * 32, ob = (size_t)(tr ? M->cols : M->rows) * 32;
+  const slice_plan sp(ctx, count);
+  struct slice_t { dev_tmp x, out; };
+  std::vector<slice_t> sl(sp.D);
+  auto stage = [&](size_t i) -> int {
+    const uint64_t lo = sp.lo(i), m = sp.count(i);
+    if (m == 0) return 0;
+    if (int rc = tmp_alloc(ctx, ctx->devs[i], sl[i].x, m * xb)) return rc;
+    if (int rc = tmp_alloc(ctx, ctx->devs[i], sl[i].out, m * ob)) return rc;
+    HIP_TRY(ctx, hipMemcpy(sl[i].x.p, x + lo * xb, m * xb, hipMemcpyHostToDevice));
+    return spmv_on(ctx, i, M, tr, chunk, sl[i].x.p, m, sl[i].out.p);
+  };
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  return copy_slices_out(ctx, sp, ob, out, [&](size_t i) { return sl[i].out.p; });
+}
 }  // namespace
 
 void free_mul_base(te_ctx* ctx, te_base* b) {
   for (size_t i = 0; i < b->tab.size() && i < ctx->devs.size(); i++)
     if (b->tab[i]) { (void)hipSetDevice(ctx->devs[i].device); (void)hipFree(b->tab[i]); b->tab[i] = nullptr; }
+}
+void free_matrix(te_ctx* ctx, te_matrix* m) {
+  for (std::vector<uint8_t*>* v : {&m->side, &m->side_t})
+    for (size_t i = 0; i < v->size() && i < ctx->devs.size(); i++)
+      if ((*v)[i]) { (void)hipSetDevice(ctx->devs[i].device); (void)hipFree((*v)[i]); (*v)[i] = nullptr; }
 }
 
 // mont: the coordinates are Montgomery residues (option "points_montgomery": te_msm_bind_points*, te_msm_check_points*); every per-call
@@ -1304,6 +1393,91 @@ int te_msm_poly_divide_device(te_ctx* ctx, const void* d_a, uint64_t n, uint64_t
   const int owner = d_q ? owner_of(ctx, where, {d_a, d_q}) : owner_of(ctx, where, {d_a});
   if (owner < 0) return owner;
   return poly_on(ctx, (size_t)owner, r, d_a, count, z, evals, d_q);
+}
+
+int te_msm_bind_matrix(te_ctx* ctx, uint64_t rows, uint64_t cols, const uint64_t* row_ptr, const uint32_t* col_idx, const uint8_t* vals, int flags, te_matrix** out) {
+  device_guard restore_callers_device;
+  if (!ctx || !out) return TE_MSM_EINVAL;
+  *out = nullptr;
+  int64_t bad = -1;
+  switch (te::spmv_check_bind(rows, cols, row_ptr, col_idx, vals, flags, &bad)) {
+    case te::SPMV_OK: break;
+    case te::SPMV_BAD_DIMS: return set_err(ctx, TE_MSM_EINVAL, "te_msm_bind_matrix: rows and cols must be in [1, 2^31]");
+    case te::SPMV_BAD_FLAGS: return set_err(ctx, TE_MSM_EINVAL, "te_msm_bind_matrix: unknown flag bits");
+    case te::SPMV_BAD_PTR: return set_err(ctx, TE_MSM_EINVAL, "te_msm_bind_matrix: row_ptr must start at 0 and never decrease");
+    case te::SPMV_TOO_LARGE: return set_err(ctx, TE_MSM_EINVAL, "te_msm_bind_matrix: more than 2^40 entries");
+    case te::SPMV_BAD_INDEX: {
+      ctx->bad_index_position = bad;
+      char buf[160];
+      snprintf(buf, sizeof buf, "te_msm_bind_matrix: the column index at position %lld is not below cols", (long long)bad);
+      return set_err(ctx, TE_MSM_EINVAL, buf);
+    }
+    default: return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  }
+  const uint64_t nnz = row_ptr[rows];
+  const bool mont = (flags & TE_MSM_MATRIX_MONTGOMERY) != 0, with_t = (flags & TE_MSM_MATRIX_TRANSPOSE) != 0;
+  te_matrix* m = new te_matrix;
+  m->ctx = ctx; m->rows = rows; m->cols = cols; m->nnz = nnz; m->with_t = with_t;
+  const size_t nd = ctx->devs.size();
+  m->side.assign(nd, nullptr);
+  m->side_t.assign(with_t ? nd : 0, nullptr);
+  int rc = 0;
+  {
+    matrix_image img(rows, nnz);
+    for (uint64_t e = 0; e < nnz; e++) te::spmv_value(vals + e * 32, mont, img.vals() + e * 32);
+    memcpy(img.ptr(), row_ptr, (size_t)(rows + 1) * sizeof(uint64_t));
+    if (nnz) memcpy(img.col(), col_idx, (size_t)nnz * sizeof(uint32_t));
+    te_spmv::fill_rows(row_ptr, rows, img.row());
+    rc = te_sched::on_devices(*ctx, nd, [&](size_t i) { return matrix_upload(ctx, i, img, &m->side[i]); });
+    if (!rc && with_t) {
+      matrix_image tr(cols, nnz);
+      te_spmv::transpose(rows, cols, row_ptr, col_idx, img.vals(), tr.ptr(), tr.col(), tr.vals());
+      te_spmv::fill_rows(tr.ptr(), cols, tr.row());
+      rc = te_sched::on_devices(*ctx, nd, [&](size_t i) { return matrix_upload(ctx, i, tr, &m->side_t[i]); });
+    }
+  }
+  if (rc) { free_matrix(ctx, m); delete m; return rc; }
+  ctx->matrices.push_back(m);
+  *out = m;
+  return 0;
+}
+
+int te_msm_release_matrix(te_ctx* ctx, te_matrix* matrix) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  const auto at = std::find(ctx->matrices.begin(), ctx->matrices.end(), matrix);
+  if (!matrix || at == ctx->matrices.end()) return set_err(ctx, TE_MSM_EINVAL, kBadMatrix);
+  free_matrix(ctx, matrix);                                         // (every call over it has returned: they are synchronous)
+  ctx->matrices.erase(at);
+  delete matrix;
+  return 0;
+}
+
+int te_msm_matrix_shape(const te_matrix* matrix, uint64_t* rows, uint64_t* cols, uint64_t* nnz) {
+  if (!matrix) return TE_MSM_EINVAL;
+  if (rows) *rows = matrix->rows;
+  if (cols) *cols = matrix->cols;
+  if (nnz) *nnz = matrix->nnz;
+  return 0;
+}
+
+int te_msm_spmv(te_ctx* ctx, te_matrix* matrix, const uint8_t* x, uint64_t count, int flags, uint8_t* out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  bool go = false;
+  if (int rc = spmv_args(ctx, matrix, x, count, flags, out, &go)) return rc;
+  return go ? spmv_host(ctx, matrix, (flags & TE_MSM_SPMV_TRANSPOSE) != 0, te_spmv::chunk_in_force(), x, count, out) : 0;
+}
+
+int te_msm_spmv_device(te_ctx* ctx, te_matrix* matrix, const void* d_x, uint64_t count, int flags, void* d_out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  bool go = false;
+  if (int rc = spmv_args(ctx, matrix, d_x, count, flags, d_out, &go)) return rc;
+  if (!go) return 0;
+  const int owner = owner_of(ctx, "te_msm_spmv_device: the vectors and the output must be resident on one device of the context", {d_x, d_out});
+  if (owner < 0) return owner;
+  return spmv_on(ctx, (size_t)owner, matrix, (flags & TE_MSM_SPMV_TRANSPOSE) != 0, te_spmv::chunk_in_force(), d_x, count, d_out);
 }
 
 }  // extern "C"

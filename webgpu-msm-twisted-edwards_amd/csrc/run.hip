@@ -119,6 +119,7 @@ void free_dev(gpu_t& d) {
   d.ntt_tab.release();
   d.ntt_tmp.release();
   d.poly_tmp.release();
+  d.spmv_tmp.release();
   if (d.chk_word) (void)hipFree(d.chk_word);
   if (d.chk_host) (void)hipHostFree(d.chk_host);
   d.chk_stream = nullptr; d.chk_word = d.chk_host = nullptr;
@@ -426,6 +427,7 @@ void te_msm_destroy(te_ctx* ctx) {
     delete b;
   }
   for (te_base* b : ctx->mul_bases) { free_mul_base(ctx, b); delete b; }   // ... and the bound points of te_msm_bind_base
+  for (te_matrix* m : ctx->matrices) { free_matrix(ctx, m); delete m; }    // ... and the matrices of te_msm_bind_matrix
   delete ctx;
 }
 

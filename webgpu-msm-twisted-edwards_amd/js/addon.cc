@@ -25,6 +25,7 @@
 #include <atomic>
 #include <string>
 #include <vector>
+#include <memory>
 
 #include "../../include/te_msm.h"
 #include "promise_protocol.hpp"
@@ -812,6 +813,128 @@ napi_value ScalarMulBase(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+// bindMatrix(rows, cols, rowPtr: Buffer, colIdx: Buffer, vals: Buffer, opts?: {montgomery?: boolean, transpose?: boolean}): number,
+// spmv(id, x: Buffer, opts?: {count?: number, montgomery?: boolean, transpose?: boolean}): Buffer and releaseMatrix(id) -- sparse matrices
+// over p (include/te_msm.h "sparse matrices", te_msm_bind_matrix / te_msm_spmv): a CSR matrix -- rows + 1 offsets of 8 bytes, nnz column
+// indices of 4 bytes and nnz values of 32 bytes, all little-endian -- bound once, then `count` (default 1) vectors of cols records each
+// (rows with transpose, which the bind must have kept) -> count x rows records (count x cols).  Run like ntt; a refusal throws.  The addon
+// keeps the arrays, as setBase keeps its point: a context that replaces the cached one binds the matrix again at the next spmv (a fresh
+// context holds no matrix: read-only option "matrix_bytes" = 0).
+struct BoundMatrix {
+  uint64_t rows = 0, cols = 0; int flags = 0;
+  std::vector<uint64_t> ptr; std::vector<uint32_t> col; std::vector<uint8_t> vals;
+  te_ctx* owner = nullptr; te_matrix* handle = nullptr;      // stale once `owner` is gone: see bound_matrix
+};
+std::vector<std::unique_ptr<BoundMatrix>> g_matrices;          // id = index + 1; a released slot is empty
+int bound_matrix(te_ctx* c, BoundMatrix& m) {
+  int64_t held = 0;
+  (void)te_msm_get_option(c, "matrix_bytes", &held);
+  if (m.owner == c && held > 0 && m.handle) return 0;
+  if (held == 0) for (auto& o : g_matrices) if (o) { o->owner = nullptr; o->handle = nullptr; }     // a fresh context: every handle is stale
+  m.handle = nullptr;
+  const int rc = te_msm_bind_matrix(c, m.rows, m.cols, m.ptr.data(), m.col.data(), m.vals.data(), m.flags, &m.handle);
+  m.owner = rc ? nullptr : c;
+  return rc;
+}
+bool flag_of(napi_env env, napi_value opts, const char* name) {
+  napi_value v; bool has = false, on = false;
+  napi_has_named_property(env, opts, name, &has);
+  if (has) { napi_get_named_property(env, opts, name, &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &on); }
+  return on;
+}
+napi_value BindMatrix(napi_env env, napi_callback_info info) {
+  const char* const sig = "bindMatrix(rows: number, cols: number, rowPtr: Buffer, colIdx: Buffer, vals: Buffer, opts?: {montgomery?: boolean, transpose?: boolean})";
+  size_t argc = 6; napi_value argv[6];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool b2 = false, b3 = false, b4 = false;
+  napi_valuetype t_opts = napi_undefined;
+  int64_t rows = -1, cols = -1;
+  if (argc >= 5) { napi_is_buffer(env, argv[2], &b2); napi_is_buffer(env, argv[3], &b3); napi_is_buffer(env, argv[4], &b4); }
+  if (argc >= 6) napi_typeof(env, argv[5], &t_opts);
+  const bool opts_none = t_opts == napi_undefined || t_opts == napi_null;
+  if (!b2 || !b3 || !b4 || napi_get_value_int64(env, argv[0], &rows) != napi_ok || napi_get_value_int64(env, argv[1], &cols) != napi_ok || rows < 0 || cols < 0 ||
+      (t_opts != napi_object && !opts_none)) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  auto m = std::make_unique<BoundMatrix>();
+  m->rows = (uint64_t)rows; m->cols = (uint64_t)cols;
+  if (t_opts == napi_object) m->flags = (flag_of(env, argv[5], "montgomery") ? TE_MSM_MATRIX_MONTGOMERY : 0) | (flag_of(env, argv[5], "transpose") ? TE_MSM_MATRIX_TRANSPOSE : 0);
+  void *pp = nullptr, *pc = nullptr, *pv = nullptr; size_t lp = 0, lc = 0, lv = 0;
+  napi_get_buffer_info(env, argv[2], &pp, &lp);
+  napi_get_buffer_info(env, argv[3], &pc, &lc);
+  napi_get_buffer_info(env, argv[4], &pv, &lv);
+  if ((uint64_t)rows >= (1ull << 32) || lp != 8u * ((size_t)rows + 1u)) { napi_throw_range_error(env, nullptr, "bindMatrix: rowPtr must be (rows + 1) * 8 bytes"); return nullptr; }
+  m->ptr.resize((size_t)rows + 1u);
+  memcpy(m->ptr.data(), pp, lp);
+  const uint64_t nnz = m->ptr.back();
+  if (lc / 4u < nnz || lv / 32u < nnz) { napi_throw_range_error(env, nullptr, "bindMatrix: colIdx and vals must hold rowPtr[rows] entries of 4 and 32 bytes"); return nullptr; }
+  m->col.resize((size_t)nnz + 1u); m->vals.resize((size_t)nnz * 32u + 1u);      // (never empty: an array the bind is given is not NULL)
+  if (nnz) { memcpy(m->col.data(), pc, (size_t)nnz * 4u); memcpy(m->vals.data(), pv, (size_t)nnz * 32u); }
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) { return bound_matrix(c, *m); }, err);
+  if (rc) return throw_te_error(env, rc, err, -1, 0);
+  g_matrices.push_back(std::move(m));
+  napi_value id; napi_create_int64(env, (int64_t)g_matrices.size(), &id);
+  return id;
+}
+BoundMatrix* matrix_by_id(napi_env env, napi_value v) {
+  int64_t id = 0;
+  if (napi_get_value_int64(env, v, &id) != napi_ok || id < 1 || (size_t)id > g_matrices.size() || !g_matrices[(size_t)id - 1]) return nullptr;
+  return g_matrices[(size_t)id - 1].get();
+}
+napi_value Spmv(napi_env env, napi_callback_info info) {
+  const char* const sig = "spmv(id: number, x: Buffer, opts?: {count?: number, montgomery?: boolean, transpose?: boolean})";
+  size_t argc = 3; napi_value argv[3];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool x_buf = false;
+  napi_valuetype t_opts = napi_undefined;
+  if (argc >= 2) napi_is_buffer(env, argv[1], &x_buf);
+  if (argc >= 3) napi_typeof(env, argv[2], &t_opts);
+  const bool opts_none = t_opts == napi_undefined || t_opts == napi_null;
+  if (!x_buf || (t_opts != napi_object && !opts_none)) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  BoundMatrix* m = matrix_by_id(env, argv[0]);
+  if (!m) { napi_throw_error(env, nullptr, "spmv: no such matrix (bindMatrix; released?)"); return nullptr; }
+  int64_t count = 1; int flags = 0;
+  if (t_opts == napi_object) {
+    flags = (flag_of(env, argv[2], "montgomery") ? TE_MSM_SPMV_MONTGOMERY : 0) | (flag_of(env, argv[2], "transpose") ? TE_MSM_SPMV_TRANSPOSE : 0);
+    napi_value v; bool has = false;
+    napi_has_named_property(env, argv[2], "count", &has);
+    if (has) { napi_get_named_property(env, argv[2], "count", &v); if (napi_get_value_int64(env, v, &count) != napi_ok || count < 0) { napi_throw_type_error(env, nullptr, sig); return nullptr; } }
+  }
+  const bool tr = (flags & TE_MSM_SPMV_TRANSPOSE) != 0;
+  const uint64_t n_in = tr ? m->rows : m->cols, n_out = tr ? m->cols : m->rows;
+  void* px = nullptr; size_t xl = 0;
+  napi_get_buffer_info(env, argv[1], &px, &xl);
+  if (count > (int64_t)(SIZE_MAX >> 38) || xl != (size_t)count * (size_t)n_in * 32u) {
+    napi_throw_range_error(env, nullptr, "spmv: x must be count * cols * 32 bytes (count * rows with transpose)");
+    return nullptr;
+  }
+  std::vector<uint8_t> out((size_t)count * (size_t)n_out * 32u + 1u);
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    int r = bound_matrix(c, *m);
+    if (!r) r = te_msm_spmv(c, m->handle, static_cast<const uint8_t*>(px), (uint64_t)count, flags, out.data());
+    return r;
+  }, err);
+  if (rc) return throw_te_error(env, rc, err, -1, 0);
+  napi_value buf; void* dst = nullptr;
+  napi_create_buffer_copy(env, out.size() - 1u, out.data(), &dst, &buf);
+  return buf;
+}
+napi_value ReleaseMatrix(napi_env env, napi_callback_info info) {
+  size_t argc = 1; napi_value argv[1];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  BoundMatrix* m = argc >= 1 ? matrix_by_id(env, argv[0]) : nullptr;
+  if (!m) { napi_throw_error(env, nullptr, "releaseMatrix: no such matrix"); return nullptr; }
+  std::string err;
+  (void)g_proto.with_context([&](te_ctx* c) {
+    int64_t held = 0;
+    (void)te_msm_get_option(c, "matrix_bytes", &held);
+    return m->owner == c && held > 0 && m->handle ? te_msm_release_matrix(c, m->handle) : 0;
+  }, err);
+  int64_t id = 0; napi_get_value_int64(env, argv[0], &id);
+  g_matrices[(size_t)id - 1].reset();
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
 // setCheckPoints(level): opt-in validation of the input points (include/te_msm.h, option "check_points"): 0 = none (default),
 // 1 = canonical and on the curve, 2 = also in the prime-order subgroup (costly: about 3 000 field products per point).  A call whose
 // points fail rejects its promise with an Error that names the lowest failing index and the reason; setBases then throws for a bad
@@ -909,7 +1032,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"groupAdd", GroupAdd}, {"groupAddX", GroupAddX}, {"groupSum", GroupSum}, {"groupSumX", GroupSumX},
       {"fieldOp", FieldOp},
       {"ntt", Ntt},
-      {"polyDivide", PolyDivide}};
+      {"polyDivide", PolyDivide},
+      {"bindMatrix", BindMatrix}, {"spmv", Spmv}, {"releaseMatrix", ReleaseMatrix}};
   for (const auto& f : fns) {
     napi_value v;
     napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v);

@@ -111,6 +111,15 @@ const ntt = async (a, logN, opts) => native.ntt(a, logN, opts);
 // of a KZG opening (null with quotient: false).  montgomery: every record holds v * 2^256 mod p.  A refusal rejects.
 const polyDivide = async (a, n, z, opts) => native.polyDivide(a, n, z, opts);
 
+// bindMatrix(rows, cols, rowPtr, colIdx, vals, {montgomery, transpose}) binds a sparse matrix over p in CSR form -- rows + 1 offsets of 8
+// bytes, nnz column indices of 4 bytes, nnz values of 32 bytes, little-endian Buffers -- and resolves to its id (te_msm_bind_matrix);
+// spmv(id, x, {count, montgomery, transpose}) resolves to the products with `count` (default 1) vectors of cols 32-byte records each as a
+// Buffer of count x rows canonical records (te_msm_spmv): the Az, Bz, Cz of an R1CS prover.  transpose multiplies by the transposed
+// matrix (x: count x rows records) and needs a bind with transpose: true.  releaseMatrix(id) gives the matrix back.  A refusal rejects.
+const bindMatrix = async (rows, cols, rowPtr, colIdx, vals, opts) => native.bindMatrix(rows, cols, rowPtr, colIdx, vals, opts);
+const spmv = async (id, x, opts) => native.spmv(id, x, opts);
+const releaseMatrix = (id) => native.releaseMatrix(id);
+
 // Outside the reference's interface too: msmBatch(scalarBuffers) runs one MSM per Buffer over the set bound by setBases -- MSM m over
 // its first scalarBuffers[m].length / 32 points (a prover's commitments to polynomials of different degrees against one SRS) -- and
 // returns their results as [{x, y}, ...] in compute_msm's form, in input order.  Small MSMs share launch sequences on the GPU.
@@ -130,4 +139,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS, ntt, polyDivide };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS, ntt, polyDivide, bindMatrix, spmv, releaseMatrix };

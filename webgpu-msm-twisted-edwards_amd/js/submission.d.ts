@@ -67,6 +67,14 @@ export declare const ntt: (a: Buffer, logN: number,
 // with quotient: false.  montgomery as for fieldOp.  Rejects for n = 0 and n above 2^30.
 export declare const polyDivide: (a: Buffer, n: number, z: Buffer,
   opts?: { count?: number, montgomery?: boolean, sharedZ?: boolean, quotient?: boolean }) => Promise<{ evals: Buffer, quotient: Buffer | null }>;
+// Not in the reference: sparse matrices over p bound once in CSR form (rowPtr: rows + 1 offsets of 8 bytes, colIdx: nnz indices of 4 bytes,
+// vals: nnz records of 32 bytes, little-endian), and their products with `count` (default 1) vectors of cols records each: count x rows
+// canonical records.  transpose multiplies by the transposed matrix and needs a bind with transpose: true; montgomery as for fieldOp (on the
+// bind: the values; on spmv: x and the result).  Rejects for rows or cols 0, a column index >= cols, and a released id.
+export declare const bindMatrix: (rows: number, cols: number, rowPtr: Buffer, colIdx: Buffer, vals: Buffer,
+  opts?: { montgomery?: boolean, transpose?: boolean }) => Promise<number>;
+export declare const spmv: (id: number, x: Buffer, opts?: { count?: number, montgomery?: boolean, transpose?: boolean }) => Promise<Buffer>;
+export declare const releaseMatrix: (id: number) => void;
 // Not in the reference: batched MSMs over prefixes of the set bound by setBases; MSM m runs over the first scalarBuffers[m].length / 32
 // points.  Results in input order, in compute_msm's form; throws without setBases or for a buffer longer than the set.
 export declare const msmBatch: (scalarBuffers: Buffer[]) => { x: bigint; y: bigint }[];
