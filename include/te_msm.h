@@ -610,6 +610,48 @@ int te_msm_ntt_device(te_ctx* ctx, const void* d_a, uint32_t log_n, uint64_t cou
 int te_msm_poly_divide(te_ctx* ctx, const uint8_t* a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, uint8_t* q);
 int te_msm_poly_divide_device(te_ctx* ctx, const void* d_a, uint64_t n, uint64_t count, const uint8_t* z, int flags, uint8_t* evals, void* d_q);
 
+/* ---- prefix sums and products ---------------------------------------------------------------------------------------------------
+ * te_msm_field_scan*: the running sum or running product of `count` vectors over p (TE_MSM_FIELD_P, the records of te_msm_ntt), each
+ * from a seed: the grand product z_(i+1) = z_i num_i / den_i of a permutation or lookup argument (num / den from te_msm_field_op_device),
+ * the running sums of logUp, the powers s g^i of one record (into te_msm_mul_base_device: an SRS), and the total of a vector -- so that
+ * these vectors stay on the device.  Vector k is a[k n .. k n + n - 1], 32-byte little-endian records; n is ANY length from 1 to
+ * TE_MSM_SCAN_MAX_N.  op: TE_MSM_SCAN_SUM or TE_MSM_SCAN_PRODUCT; write o for + or * mod p and e_k for record k of init:
+ *     out[k n + i] = e_k o a_0 o .. o a_i          inclusive
+ *     out[k n + i] = e_k o a_0 o .. o a_(i-1)      TE_MSM_SCAN_EXCLUSIVE: out[k n] = e_k
+ *     totals[k]    = e_k o a_0 o .. o a_(n-1)      in both modes
+ * init and totals are HOST pointers in both forms, `count` records each (a seed comes from the caller's previous call -- a scan continues
+ *   across calls with it -- or from the transcript, and a total goes back there).  init is not modified; NULL stands for the identity (0
+ *   for the sum, 1 for the product).  Either totals or out may be NULL: with out NULL the call reads a once and writes nothing on the
+ *   device but its scratch.  totals is written only when the call succeeds.
+ * flags: TE_MSM_SCAN_MONTGOMERY -- a, init, totals and out hold v * 2^256 mod p; TE_MSM_SCAN_EXCLUSIVE; TE_MSM_SCAN_SHARED_A -- a holds
+ *   `count` records, and vector k is record k repeated n times (init * g^i, init + i g).  Any other bit: TE_MSM_EINVAL.
+ * Values: as te_msm_field_op -- ANY 256-bit record stands for its residue, outputs are canonical.  A zero among the factors of a product
+ *   is an ordinary value: nothing inverts.  count = 0 succeeds and touches nothing.  The result is the same bytes every time.
+ * Aliasing: out may be exactly a, except under TE_MSM_SCAN_SHARED_A (the two have different sizes).
+ * Refusals, all TE_MSM_EINVAL with every output untouched and the context usable: an unknown op or flag bit; n = 0 or
+ *   n > TE_MSM_SCAN_MAX_N; totals and out both NULL; NULL a with count > 0; count * n * 32 beyond 64 bits (or more than 2^31 - 1 tiles in
+ *   one launch); out = a under TE_MSM_SCAN_SHARED_A; te_msm_field_scan_device: d_a and d_out not on one device of the context.
+ * Buffers: te_msm_field_scan_device returns with d_out complete.  te_msm_field_scan slices WHOLE vectors over the context's devices, one
+ *   host thread per device, each slice staged on its device.  Every element and byte offset is 64 bits wide.  The tile totals, the
+ *   carries and the seeds live in a buffer of the device's (about count * n / T records), grown on use and kept until te_msm_trim /
+ *   te_msm_destroy.  The calling thread's device is left as it was.
+ * How it runs (csrc/scan_plan.hpp, csrc/scan.hip.hpp): a 256-lane block owns a tile of T = 256 chunk elements of
+ *   one vector.  k_scan_totals leaves every tile's total; the carries are the exclusive scan of the totals -- the same call on
+ *   ceil(n / T) records, recursed until one tile is left, whose carry is the seed; k_scan_apply takes a tile's carry, scans its lanes and
+ *   writes the values (skipped when out is NULL).  chunk: TE_MSM_SCAN_CHUNK, or what the environment variable TE_MSM_SCAN_CHUNK names
+ *   (1 .. 16), read by every call -- and never more than one tile needs to cover n.  Read-only options: "scan_chunk" (the chunk in
+ *   force), "scan_scratch_bytes" (what the context's devices hold now of that buffer).
+ * COST: DESIGN.md section 25, profiles/scan_cost.txt (tools/scan_cost.py). */
+#define TE_MSM_SCAN_SUM 0
+#define TE_MSM_SCAN_PRODUCT 1
+#define TE_MSM_SCAN_MONTGOMERY 1   /* a, init, totals, out hold v * 2^256 mod p */
+#define TE_MSM_SCAN_EXCLUSIVE 2    /* out[i] leaves a_i out: out[0] = init */
+#define TE_MSM_SCAN_SHARED_A 4     /* vector k is ONE record a[k], used for every i: init * g^i, init + i g */
+#define TE_MSM_SCAN_MAX_N (1ull << 30)
+#define TE_MSM_SCAN_CHUNK 8u
+int te_msm_field_scan(te_ctx* ctx, int op, const uint8_t* a, uint64_t n, uint64_t count, int flags, const uint8_t* init, uint8_t* totals, uint8_t* out);
+int te_msm_field_scan_device(te_ctx* ctx, int op, const void* d_a, uint64_t n, uint64_t count, int flags, const uint8_t* init, uint8_t* totals, void* d_out);
+
 /* ---- sparse matrices --------------------------------------------------------------------------------------------------------------
  * te_msm_bind_matrix / te_msm_spmv*: products of a sparse matrix over p (TE_MSM_FIELD_P, the records of te_msm_ntt) with `count`
  * vectors -- the Az, Bz, Cz every R1CS prover (Groth16, Marlin, Varuna) starts with, and Varuna's products with the transposed matrices.

@@ -62,6 +62,12 @@ from .binding import (  # noqa: F401
     POLY_MONTGOMERY,
     POLY_SHARED_Z,
     POLY_MAX_N,
+    SCAN_SUM,
+    SCAN_PRODUCT,
+    SCAN_MONTGOMERY,
+    SCAN_EXCLUSIVE,
+    SCAN_SHARED_A,
+    SCAN_MAX_N,
     MATRIX_MONTGOMERY,
     MATRIX_TRANSPOSE,
     SPMV_MONTGOMERY,

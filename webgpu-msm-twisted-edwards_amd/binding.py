@@ -31,6 +31,9 @@ NTT_INVERSE, NTT_MONTGOMERY = 1, 2                              # flags of te_ms
 NTT_MAX_LOG_N = 24
 POLY_MONTGOMERY, POLY_SHARED_Z = 1, 2                            # flags of te_msm_poly_divide*
 POLY_MAX_N = 1 << 30
+SCAN_SUM, SCAN_PRODUCT = 0, 1                                    # ops of te_msm_field_scan*
+SCAN_MONTGOMERY, SCAN_EXCLUSIVE, SCAN_SHARED_A = 1, 2, 4         # ... and its flags
+SCAN_MAX_N = 1 << 30
 MATRIX_MONTGOMERY, MATRIX_TRANSPOSE = 1, 2                        # flags of te_msm_bind_matrix
 SPMV_MONTGOMERY, SPMV_TRANSPOSE = 1, 2                            # flags of te_msm_spmv*
 FIELD_ZERO, FIELD_NOT_SQUARE = 1, 2      # why an element has no result (MsmError.reason)
@@ -268,6 +271,11 @@ def _lib() -> ctypes.CDLL:
             L.te_msm_spmv.restype = ci
             L.te_msm_spmv_device.argtypes = [vp, vp, vp, u64, ci, vp]
             L.te_msm_spmv_device.restype = ci
+        if not os.environ.get("TE_MSM_LIB") or hasattr(L, "te_msm_field_scan"):
+            L.te_msm_field_scan.argtypes = [vp, ci, vp, u64, u64, ci, vp, vp, vp]
+            L.te_msm_field_scan.restype = ci
+            L.te_msm_field_scan_device.argtypes = [vp, ci, vp, u64, u64, ci, vp, vp, vp]
+            L.te_msm_field_scan_device.restype = ci
         _LIB = L
     return _LIB
 
@@ -705,6 +713,41 @@ class MsmContext:
         """te_msm_spmv_device: the same between buffers on one device of the context; d_out must not be d_x"""
         flags = (SPMV_MONTGOMERY if montgomery else 0) | (SPMV_TRANSPOSE if transpose else 0)
         self._check(self._L.te_msm_spmv_device(self._h, matrix._h, d_x, count, flags, d_out))
+
+    # ---- prefix sums and products (include/te_msm.h "prefix sums and products"): running sums, grand products, powers of a record
+    @staticmethod
+    def _scan_args(op: int, count: int, montgomery: bool, exclusive: bool, shared_a: bool, init):
+        flags = (SCAN_MONTGOMERY if montgomery else 0) | (SCAN_EXCLUSIVE if exclusive else 0) | (SCAN_SHARED_A if shared_a else 0)
+        if init is None:
+            return flags, None
+        if isinstance(init, int):
+            init = [init]
+        rec = bytes(init) if isinstance(init, (bytes, bytearray, memoryview)) else b"".join(int(v).to_bytes(32, "little") for v in init)
+        if len(rec) != 32 * count:
+            raise MsmError(-1, "init must be one 32-byte record a vector: bytes, or integers below 2^256 (None: the identity)")
+        return flags, rec
+
+    def field_scan(self, op: int, a: bytes, n: int, *, count: int = 1, init=None, montgomery: bool = False, exclusive: bool = False, shared_a: bool = False,
+                   out: bool = True, totals: bool = True):
+        """te_msm_field_scan: `count` vectors of n 32-byte records of p each (shared_a: ONE record each) and their seeds (bytes, integers, or
+        None for the identity) -> (out, totals): the running sums (SCAN_SUM) or products (SCAN_PRODUCT) from the seed, inclusive or
+        exclusive, and seed o a_0 o .. o a_(n-1) of each vector; either is None when it was not asked for."""
+        if n < 0 or count < 0 or len(a) != 32 * count * (1 if shared_a else n):
+            raise MsmError(-1, "a must be count * n * 32 bytes (count * 32 with shared_a)")
+        flags, rec = self._scan_args(op, count, montgomery, exclusive, shared_a, init)
+        tot = ctypes.create_string_buffer(max(1, 32 * count)) if totals else None
+        o = ctypes.create_string_buffer(max(1, 32 * count * n)) if out else None
+        self._check(self._L.te_msm_field_scan(self._h, op, bytes(a), n, count, flags, rec, tot, o))
+        return o.raw[:32 * count * n] if out else None, tot.raw[:32 * count] if totals else None
+
+    def field_scan_device(self, op: int, d_a: int, n: int, count: int, d_out, *, init=None, montgomery: bool = False, exclusive: bool = False, shared_a: bool = False,
+                          totals: bool = True):
+        """te_msm_field_scan_device: the same from a buffer on one device of the context into d_out, which may be d_a (not with shared_a), or
+        None for the totals alone.  init stays a host value; returns (d_out, totals) -- totals None when not asked for."""
+        flags, rec = self._scan_args(op, count, montgomery, exclusive, shared_a, init)
+        tot = ctypes.create_string_buffer(max(1, 32 * count)) if totals else None
+        self._check(self._L.te_msm_field_scan_device(self._h, op, d_a, n, count, flags, rec, tot, d_out))
+        return d_out, tot.raw[:32 * count] if totals else None
 
     def add_x(self, ax: bytes, bx: bytes, subtract: bool = False) -> bytes:
         """te_msm_add_x, bulkAddGroups' counterpart: n x-only points a and n (or one) b (32 / 48 bytes, points_from_x's format) -> n points x || y"""

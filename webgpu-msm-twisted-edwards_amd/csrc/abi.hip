@@ -40,7 +40,7 @@ int te_msm_trim(te_ctx* ctx, int keep_worksets) {
       free_workset_buffers(ws);
       freed++;
     }
-    { std::lock_guard<std::mutex> lk(*d.chk_mu); d.ntt_tab.release(); d.ntt_tmp.release(); d.poly_tmp.release(); d.spmv_tmp.release(); }      // the NTT twiddle tables and scratch: made again by the next transform (none runs: it holds chk_mu)
+    { std::lock_guard<std::mutex> lk(*d.chk_mu); d.ntt_tab.release(); d.ntt_tmp.release(); d.poly_tmp.release(); d.spmv_tmp.release(); d.scan_tmp.release(); }      // the NTT twiddle tables and scratch: made again by the next transform (none runs: it holds chk_mu)
     for (auto& sl : d.slabs) if (sl.users == 0 && sl.d) {                    // idle shared record slabs
       if (int rc = settle_slab(ctx, sl, nullptr, true)) return rc;
       for (workset_t& ws : d.ws) if (ws.recs_last == sl.d) ws.recs_last = nullptr;
@@ -142,6 +142,12 @@ int te_msm_get_option(te_ctx* ctx, const char* key, int64_t* value) {
   if (!strcmp(key, "spmv_scratch_bytes")) {                            // the fragments of te_msm_spmv*
     *value = 0;
     for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.spmv_tmp.p ? (int64_t)d.spmv_tmp.cap : 0; }
+    return 0;
+  }
+  if (!strcmp(key, "scan_chunk")) { *value = (int64_t)te_scan::chunk_in_force(); return 0; }   // TE_MSM_SCAN_CHUNK, or what the environment names
+  if (!strcmp(key, "scan_scratch_bytes")) {                            // the totals, carries and seeds of te_msm_field_scan*
+    *value = 0;
+    for (gpu_t& d : ctx->devs) { std::lock_guard<std::mutex> lk(*d.chk_mu); *value += d.scan_tmp.p ? (int64_t)d.scan_tmp.cap : 0; }
     return 0;
   }
   if (!strcmp(key, "matrix_bytes")) {                                  // the bound matrices, over all devices

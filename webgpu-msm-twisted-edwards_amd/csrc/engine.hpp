@@ -39,6 +39,7 @@
 #include "fb_plan.hpp"
 #include "ntt_plan.hpp"
 #include "poly_plan.hpp"
+#include "scan_plan.hpp"
 #include "spmv_plan.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -212,6 +213,8 @@ struct gpu_t {
                                          // use under chk_mu, freed with the tables (get_option "ntt_scratch_bytes")
   dev_buf<uint8_t> poly_tmp;             // te_msm_poly_divide*: the tile sums, carries and powers of a call (poly_plan.hpp, scratch_bytes: about count * n / T records),
                                          // grown on use under chk_mu, freed by te_msm_trim / destroy (get_option "poly_scratch_bytes")
+  dev_buf<uint8_t> scan_tmp;             // te_msm_field_scan*: the tile totals, carries and seeds of a call (scan_plan.hpp, scratch_bytes: about count * n / T records),
+                                         // grown on use under chk_mu, freed by te_msm_trim / destroy (get_option "scan_scratch_bytes")
   dev_buf<uint8_t> spmv_tmp;             // te_msm_spmv*: the fragments of rows that span tiles (spmv_plan.hpp, scratch_bytes: two records a tile and vector),
                                          // grown on use under chk_mu, freed by te_msm_trim / destroy (get_option "spmv_scratch_bytes")
 };

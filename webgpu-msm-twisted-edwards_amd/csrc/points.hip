@@ -2,9 +2,9 @@
 // points (te_msm_points_from_x*, te_msm_bind_points_x, te_msm_run_x), batch scalar multiplication (te_msm_mul*) and its fixed-base form
 // over one bound point (te_msm_bind_base, te_msm_mul_base*), batched group addition and point-set sums (te_msm_add*, te_msm_sum*), and
 // batched arithmetic in the two base fields (te_msm_field_op*), batched NTTs over p (te_msm_ntt*) and polynomial openings
-// (te_msm_poly_divide*), bound sparse matrices and their products (te_msm_bind_matrix, te_msm_spmv*).  The one unit that includes the
-// kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp, group_add.hip.hpp, field_ops.hip.hpp, ntt.hip.hpp,
-// poly.hip.hpp and spmv.hip.hpp.
+// (te_msm_poly_divide*), bound sparse matrices and their products (te_msm_bind_matrix, te_msm_spmv*), prefix sums and products
+// (te_msm_field_scan*).  The one unit that includes the kernels of check.hip.hpp, from_x.hip.hpp, scalar_mul.hip.hpp, mul_base.hip.hpp,
+// group_add.hip.hpp, field_ops.hip.hpp, ntt.hip.hpp, poly.hip.hpp, spmv.hip.hpp and scan.hip.hpp.
 #include "engine.hpp"
 #include "check.hip.hpp"
 #include "from_x.hip.hpp"
@@ -15,6 +15,7 @@
 #include "ntt.hip.hpp"
 #include "poly.hip.hpp"
 #include "spmv.hip.hpp"
+#include "scan.hip.hpp"
 
 using namespace te_eng;
 
@@ -1022,6 +1023,100 @@ int spmv_host(te_ctx* ctx, const te_matrix* M, bool tr, uint32_t chunk, const ui
   if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
   return copy_slices_out(ctx, sp, ob, out, [&](size_t i) { return sl[i].out.p; });
 }
+// ---- prefix sums and products (te_msm_field_scan*; kernels in scan.hip.hpp, plan in scan_plan.hpp) ------------------------------------
+// `count` vectors on the device's check lane: the seeds (put into the internal form here with the host build of the field: one product a
+// vector) go up behind the regions of the device's scratch buffer (grown on use, held like poly_tmp; the lane's mutex serialises its
+// users); k_scan_totals runs level by level upwards -- the one record a vector of the last region is the total, seed included -- and
+// k_scan_apply level by level downwards, each level's exclusive scan over its elements, the last launch a -> out.  No piece loop: the
+// buffer is about count n / T records.
+static_assert(TE_MSM_SCAN_CHUNK == te_scan::kChunkDefault && TE_MSM_SCAN_MAX_N == te_scan::kMaxN && TE_MSM_SCAN_SUM == te_scan::kSum && TE_MSM_SCAN_PRODUCT == te_scan::kProduct,
+              "include/te_msm.h and scan_plan.hpp disagree");
+using te::scan_req;
+template <int OP> int scan_launches(te_ctx* ctx, hipStream_t st, const scan_req& r, const te_scan::plan& P, uint4* reg, const void* d_a, bool want_totals, void* d_out) {
+  const dim3 block(te_scan::kLanes);
+  const uint4* const seeds = reg + P.seeds * 2;
+  const uint32_t caller = te::scan_caller_form(r);
+  for (uint32_t l = 0; l < P.levels; l++) {
+    const te_scan::level& v = P.lv[l];
+    const bool last = l + 1u == P.levels;
+    if (last && !want_totals) break;
+    const uint4* src = l ? reg + v.src * 2 : static_cast<const uint4*>(d_a);
+    hipLaunchKernelGGL(te::k_scan_totals<OP>, dim3((uint32_t)(P.count * v.tiles)), block, 0, st, src, reg + v.dst * 2, last ? seeds : nullptr, v, P.chunk,
+                       l ? (uint32_t)te_scan::kInternal : caller, last ? caller : (uint32_t)te_scan::kInternal, l == 0u && r.shared ? 1u : 0u);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  if (!d_out) return 0;
+  const size_t lds = te_scan::lds_bytes_apply(P.chunk);
+  HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&te::k_scan_apply<OP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (uint32_t l = P.levels; l-- > 0u;) {
+    const te_scan::level& v = P.lv[l];
+    const uint4* src = l ? reg + v.src * 2 : static_cast<const uint4*>(d_a);
+    uint4* dst = l ? reg + v.src * 2 : static_cast<uint4*>(d_out);
+    const uint4* carries = l + 1u < P.levels ? reg + v.dst * 2 : seeds;
+    hipLaunchKernelGGL(te::k_scan_apply<OP>, dim3((uint32_t)(P.count * v.tiles)), block, lds, st, src, dst, carries, v, P.chunk, l ? (uint32_t)te_scan::kInternal : caller,
+                       l ? (uint32_t)te_scan::kInternal : caller, l || r.exclusive ? 1u : 0u, l == 0u && r.shared ? 1u : 0u);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+// init: the seeds on the host (count records) or nullptr; totals: where the count totals go on the host once everything succeeded, or
+// nullptr; d_out: nullptr leaves the device's buffers alone
+int scan_on(te_ctx* ctx, size_t di, const scan_req& q, const void* d_a, uint64_t count, const uint8_t* init, uint8_t* totals, void* d_out) {
+  if (count == 0) return 0;
+  gpu_t& d = ctx->devs[di];
+  scan_req r = q;
+  r.count = count;
+  te_scan::plan P;
+  if (!te_scan::make_plan(r.n, count, r.chunk, P)) return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_scan*: more tiles than one launch holds");
+  std::vector<uint8_t> seeds((size_t)count * 32), tot(totals ? (size_t)count * 32 : 0);
+  te::scan_seeds(r, init, seeds.data());
+  check_lane lane(ctx, d);
+  if (lane.rc) return lane.rc;
+  hipStream_t st = lane.stream();
+  if (int rc = make_room(ctx, d.scan_tmp, (size_t)P.scratch_bytes)) return rc;
+  uint4* const reg = reinterpret_cast<uint4*>(d.scan_tmp.p);
+  HIP_TRY(ctx, hipMemcpyAsync(reg + P.seeds * 2, seeds.data(), seeds.size(), hipMemcpyHostToDevice, st));
+  if (int rc = r.op == TE_MSM_SCAN_SUM ? scan_launches<te_scan::kSum>(ctx, st, r, P, reg, d_a, totals != nullptr, d_out)
+                                       : scan_launches<te_scan::kProduct>(ctx, st, r, P, reg, d_a, totals != nullptr, d_out)) return rc;
+  if (totals) HIP_TRY(ctx, hipMemcpyAsync(tot.data(), reg + P.lv[P.levels - 1].dst * 2, tot.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (totals) memcpy(totals, tot.data(), tot.size());
+  return 0;
+}
+// what every te_msm_field_scan* call checks first (te::scan_check); r: the request
+int scan_args(te_ctx* ctx, int op, const void* a, uint64_t n, uint64_t count, int flags, const void* totals, const void* out, scan_req& r) {
+  switch (te::scan_check(op, a, n, count, flags, totals, out, r)) {
+    case te::SCAN_OK: r.chunk = te_scan::chunk_for(n, te_scan::chunk_in_force()); return 0;
+    case te::SCAN_BAD_OP: return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_scan*: op must be TE_MSM_SCAN_SUM or TE_MSM_SCAN_PRODUCT");
+    case te::SCAN_BAD_N: return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_scan*: n must be in [1, TE_MSM_SCAN_MAX_N]");
+    case te::SCAN_BAD_FLAGS: return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_scan*: unknown flag bits");
+    case te::SCAN_NO_OUTPUT: return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_scan*: totals and out are both NULL");
+    case te::SCAN_TOO_LARGE: return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_scan*: count x n x 32 does not fit 64 bits");
+    case te::SCAN_ALIAS: return set_err(ctx, TE_MSM_EINVAL, "te_msm_field_scan*: out may not be a under TE_MSM_SCAN_SHARED_A");
+    default: return set_err(ctx, TE_MSM_EINVAL, "null buffer");
+  }
+}
+// te_msm_field_scan: host buffers, whole vectors sliced over the devices; a slice is scanned in place in its staged copy (SHARED_A: into a
+// buffer of its own), and the outputs are written once every slice succeeded
+int scan_host(te_ctx* ctx, const scan_req& r, const uint8_t* a, uint64_t count, const uint8_t* init, uint8_t* totals, uint8_t* out) {
+  const size_t ob = (size_t)r.n * 32, ab = r.shared ? 32 : ob;
+  const slice_plan sp(ctx, count);
+  struct slice_t { dev_tmp a, out; };
+  std::vector<slice_t> sl(sp.D);
+  std::vector<uint8_t> tot(totals ? (size_t)count * 32 : 0);
+  auto stage = [&](size_t i) -> int {
+    const uint64_t lo = sp.lo(i), m = sp.count(i);
+    if (m == 0) return 0;
+    if (int rc = tmp_alloc(ctx, ctx->devs[i], sl[i].a, m * ab)) return rc;
+    if (r.shared && out) { if (int rc = tmp_alloc(ctx, ctx->devs[i], sl[i].out, m * ob)) return rc; }
+    HIP_TRY(ctx, hipMemcpy(sl[i].a.p, a + lo * ab, m * ab, hipMemcpyHostToDevice));
+    return scan_on(ctx, i, r, sl[i].a.p, m, init ? init + lo * 32 : nullptr, totals ? tot.data() + lo * 32 : nullptr, !out ? nullptr : r.shared ? sl[i].out.p : sl[i].a.p);
+  };
+  if (int rc = te_sched::on_devices(*ctx, sp.D, stage)) return rc;
+  if (out) { if (int rc = copy_slices_out(ctx, sp, ob, out, [&](size_t i) { return r.shared ? sl[i].out.p : sl[i].a.p; })) return rc; }
+  if (totals) memcpy(totals, tot.data(), tot.size());
+  return 0;
+}
 }  // namespace
 
 void free_mul_base(te_ctx* ctx, te_base* b) {
@@ -1478,6 +1573,26 @@ int te_msm_spmv_device(te_ctx* ctx, te_matrix* matrix, const void* d_x, uint64_t
   const int owner = owner_of(ctx, "te_msm_spmv_device: the vectors and the output must be resident on one device of the context", {d_x, d_out});
   if (owner < 0) return owner;
   return spmv_on(ctx, (size_t)owner, matrix, (flags & TE_MSM_SPMV_TRANSPOSE) != 0, te_spmv::chunk_in_force(), d_x, count, d_out);
+}
+
+int te_msm_field_scan(te_ctx* ctx, int op, const uint8_t* a, uint64_t n, uint64_t count, int flags, const uint8_t* init, uint8_t* totals, uint8_t* out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  scan_req r;
+  if (int rc = scan_args(ctx, op, a, n, count, flags, totals, out, r)) return rc;
+  return count ? scan_host(ctx, r, a, count, init, totals, out) : 0;
+}
+
+int te_msm_field_scan_device(te_ctx* ctx, int op, const void* d_a, uint64_t n, uint64_t count, int flags, const uint8_t* init, uint8_t* totals, void* d_out) {
+  device_guard restore_callers_device;
+  if (!ctx) return TE_MSM_EINVAL;
+  scan_req r;
+  if (int rc = scan_args(ctx, op, d_a, n, count, flags, totals, d_out, r)) return rc;
+  if (count == 0) return 0;
+  const char* const where = "te_msm_field_scan_device: the vectors and the output must be resident on one device of the context";
+  const int owner = d_out ? owner_of(ctx, where, {d_a, d_out}) : owner_of(ctx, where, {d_a});
+  if (owner < 0) return owner;
+  return scan_on(ctx, (size_t)owner, r, d_a, count, init, totals, d_out);
 }
 
 }  // extern "C"

@@ -119,6 +119,7 @@ void free_dev(gpu_t& d) {
   d.ntt_tab.release();
   d.ntt_tmp.release();
   d.poly_tmp.release();
+  d.scan_tmp.release();
   d.spmv_tmp.release();
   if (d.chk_word) (void)hipFree(d.chk_word);
   if (d.chk_host) (void)hipHostFree(d.chk_host);

@@ -736,6 +736,88 @@ napi_value PolyDivide(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// fieldScan(op: number, a: Buffer, n: number, opts?: {count?: number, init?: Buffer, montgomery?: boolean, exclusive?: boolean, sharedA?: boolean,
+// out?: boolean, totals?: boolean}): {out: Buffer | null, totals: Buffer | null} -- prefix sums (op 0) and products (op 1) over p
+// (include/te_msm.h, te_msm_field_scan): `count` (default 1) vectors of n 32-byte records each -- ONE record each with sharedA -- from
+// their seeds init (one 32-byte record a vector; absent: the identity).  out: the running values at the stride n, inclusive or exclusive;
+// totals: seed o a_0 o .. o a_(n-1) of each vector; either is null when its option is false.  Run like ntt; a refusal throws.
+napi_value FieldScan(napi_env env, napi_callback_info info) {
+  const char* const sig = "fieldScan(op: number, a: Buffer, n: number, opts?: {count?: number, init?: Buffer, montgomery?: boolean, exclusive?: boolean, sharedA?: boolean, "
+                          "out?: boolean, totals?: boolean})";
+  size_t argc = 4; napi_value argv[4];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool a_buf = false;
+  napi_valuetype t_op = napi_undefined, t_n = napi_undefined, t_opts = napi_undefined;
+  if (argc >= 1) napi_typeof(env, argv[0], &t_op);
+  if (argc >= 2) napi_is_buffer(env, argv[1], &a_buf);
+  if (argc >= 3) napi_typeof(env, argv[2], &t_n);
+  if (argc >= 4) napi_typeof(env, argv[3], &t_opts);
+  const bool opts_none = t_opts == napi_undefined || t_opts == napi_null;
+  if (!a_buf || t_op != napi_number || t_n != napi_number || (t_opts != napi_object && !opts_none)) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  int32_t op = 0;
+  int64_t n = 0, count = 1;
+  if (napi_get_value_int32(env, argv[0], &op) != napi_ok || napi_get_value_int64(env, argv[2], &n) != napi_ok || n < 0) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+  int flags = 0;
+  bool want_out = true, want_totals = true;
+  void* pi = nullptr; size_t il = 0;
+  if (t_opts == napi_object) {
+    const struct { const char* name; int bit; } bits[] = {{"montgomery", TE_MSM_SCAN_MONTGOMERY}, {"exclusive", TE_MSM_SCAN_EXCLUSIVE}, {"sharedA", TE_MSM_SCAN_SHARED_A}};
+    for (const auto& f : bits) {
+      napi_value v; bool has = false, on = false;
+      napi_has_named_property(env, argv[3], f.name, &has);
+      if (has) { napi_get_named_property(env, argv[3], f.name, &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &on); }
+      if (on) flags |= f.bit;
+    }
+    napi_value v; bool has = false;
+    napi_has_named_property(env, argv[3], "count", &has);
+    if (has) { napi_get_named_property(env, argv[3], "count", &v); if (napi_get_value_int64(env, v, &count) != napi_ok || count < 0) { napi_throw_type_error(env, nullptr, sig); return nullptr; } }
+    napi_has_named_property(env, argv[3], "out", &has);
+    if (has) { napi_get_named_property(env, argv[3], "out", &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &want_out); }
+    napi_has_named_property(env, argv[3], "totals", &has);
+    if (has) { napi_get_named_property(env, argv[3], "totals", &v); napi_coerce_to_bool(env, v, &v); napi_get_value_bool(env, v, &want_totals); }
+    napi_has_named_property(env, argv[3], "init", &has);
+    if (has) {
+      napi_valuetype t_init = napi_undefined; bool init_buf = false;
+      napi_get_named_property(env, argv[3], "init", &v);
+      napi_typeof(env, v, &t_init);
+      if (t_init != napi_undefined && t_init != napi_null) {
+        napi_is_buffer(env, v, &init_buf);
+        if (!init_buf) { napi_throw_type_error(env, nullptr, sig); return nullptr; }
+        napi_get_buffer_info(env, v, &pi, &il);
+        if (il != 32u * (size_t)count) { napi_throw_range_error(env, nullptr, "fieldScan: init must be one record of 32 bytes a vector"); return nullptr; }
+        if (!pi) pi = &il;                                            // (count = 0: an empty Buffer; any non-NULL pointer)
+      }
+    }
+  }
+  void* pa = nullptr; size_t al = 0;
+  napi_get_buffer_info(env, argv[1], &pa, &al);
+  const bool n_ok = n >= 1 && (uint64_t)n <= TE_MSM_SCAN_MAX_N;      // (the library refuses the others itself: any a is then passed through)
+  const bool shared = (flags & TE_MSM_SCAN_SHARED_A) != 0;
+  if (n_ok && (count > (int64_t)(SIZE_MAX >> 36) || (uint64_t)count * (uint64_t)n > (SIZE_MAX >> 6) || al != (size_t)count * (shared ? 1u : (size_t)n) * 32u)) {
+    napi_throw_range_error(env, nullptr, "fieldScan: a must be count * n * 32 bytes (count * 32 with sharedA)");
+    return nullptr;
+  }
+  const size_t ol = n_ok ? (size_t)count * (size_t)n * 32u : 0;
+  std::vector<uint8_t> totals(want_totals ? (size_t)count * 32 + 1 : 0), out(want_out ? ol + 1 : 0);      // (never empty: an output the call is given is not NULL)
+  std::string err;
+  const int rc = g_proto.with_context([&](te_ctx* c) {
+    return te_msm_field_scan(c, op, static_cast<const uint8_t*>(pa), (uint64_t)n, (uint64_t)count, flags, static_cast<const uint8_t*>(pi), want_totals ? totals.data() : nullptr,
+                             want_out ? out.data() : nullptr);
+  }, err);
+  if (rc) {
+    const std::string m = "te_msm error " + std::to_string(rc) + ": " + err;
+    napi_throw_error(env, nullptr, m.c_str());
+    return nullptr;
+  }
+  napi_value res, bo, bt; void* dst = nullptr;
+  napi_create_object(env, &res);
+  if (want_out) napi_create_buffer_copy(env, ol, out.data(), &dst, &bo); else napi_get_null(env, &bo);
+  if (want_totals) napi_create_buffer_copy(env, (size_t)count * 32, totals.data(), &dst, &bt); else napi_get_null(env, &bt);
+  napi_set_named_property(env, res, "out", bo);
+  napi_set_named_property(env, res, "totals", bt);
+  return res;
+}
+
 // setBase(point: Buffer) and scalarMulBase(scalars: Buffer): Buffer -- fixed-base batch scalar multiplication (include/te_msm.h,
 // te_msm_bind_base / te_msm_mul_base): one 64-byte point bound once, then n x 32-byte little-endian scalars -> n x 64-byte points
 // [k_i] P (the identity as (0, 1)).  Twisted-Edwards curve only, like the rest of the addon; run like scalarMul.  The addon keeps the
@@ -1033,6 +1115,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"fieldOp", FieldOp},
       {"ntt", Ntt},
       {"polyDivide", PolyDivide},
+      {"fieldScan", FieldScan},
       {"bindMatrix", BindMatrix}, {"spmv", Spmv}, {"releaseMatrix", ReleaseMatrix}};
   for (const auto& f : fns) {
     napi_value v;

@@ -111,6 +111,18 @@ const ntt = async (a, logN, opts) => native.ntt(a, logN, opts);
 // of a KZG opening (null with quotient: false).  montgomery: every record holds v * 2^256 mod p.  A refusal rejects.
 const polyDivide = async (a, n, z, opts) => native.polyDivide(a, n, z, opts);
 
+// fieldScan(op, a, n, {count, init, montgomery, exclusive, sharedA, out, totals}): the running sums (op 'sum') or products ('product') of
+// `count` (default 1) vectors of n 32-byte records of p each -- one record each with sharedA: init * g^i, init + i g -- from their seeds
+// init (one 32-byte record a vector; absent: 0 for the sum, 1 for the product) (te_msm_field_scan).  Resolves to {out, totals}: the running
+// values at the stride n, a_i left out of value i with exclusive, and seed o a_0 o .. o a_(n-1) of each vector -- the closing value of a
+// grand product; either is null when its option is false.  montgomery: every record holds v * 2^256 mod p.  A refusal rejects.
+const SCAN_OPS = { sum: 0, product: 1 };
+const fieldScan = async (op, a, n, opts) => {
+  const code = typeof op === 'number' ? op : SCAN_OPS[op];
+  if (code === undefined) throw new TypeError("fieldScan: op must be 'sum' or 'product'");
+  return native.fieldScan(code, a, n, opts);
+};
+
 // bindMatrix(rows, cols, rowPtr, colIdx, vals, {montgomery, transpose}) binds a sparse matrix over p in CSR form -- rows + 1 offsets of 8
 // bytes, nnz column indices of 4 bytes, nnz values of 32 bytes, little-endian Buffers -- and resolves to its id (te_msm_bind_matrix);
 // spmv(id, x, {count, montgomery, transpose}) resolves to the products with `count` (default 1) vectors of cols 32-byte records each as a
@@ -139,4 +151,4 @@ const msmIndexed = async (indices, scalars) => {
   return { x: fromLE32(out, 0), y: fromLE32(out, 32) };
 };
 
-module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS, ntt, polyDivide, bindMatrix, spmv, releaseMatrix };
+module.exports = { compute_msm, setDevices, getDevices, setBases, getStats, setCheckPoints, setScalarsMontgomery, setScalarRecordBytes, setScalarBits, pointsFromX, scalarMul, scalarMulX, msmBatch, msmIndexed, setBase, scalarMulBase, groupAdd, groupAddX, groupSum, groupSumX, fieldOp, FIELD_OPS, ntt, polyDivide, bindMatrix, spmv, releaseMatrix, fieldScan, SCAN_OPS };

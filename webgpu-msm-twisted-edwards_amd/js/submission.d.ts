@@ -67,6 +67,13 @@ export declare const ntt: (a: Buffer, logN: number,
 // with quotient: false.  montgomery as for fieldOp.  Rejects for n = 0 and n above 2^30.
 export declare const polyDivide: (a: Buffer, n: number, z: Buffer,
   opts?: { count?: number, montgomery?: boolean, sharedZ?: boolean, quotient?: boolean }) => Promise<{ evals: Buffer, quotient: Buffer | null }>;
+// Not in the reference: prefix sums ('sum') and products ('product') over p on the device -- `count` (default 1) vectors of n 32-byte
+// records each (one record each with sharedA) from their seeds init (one record a vector; absent: the identity).  out: the running values at
+// the stride n (exclusive leaves a_i out of value i); totals: seed o a_0 o .. o a_(n-1) of each vector; either is null when its option is
+// false.  montgomery as for fieldOp.  Rejects for an unknown op, n = 0 and n above 2^30.
+export declare const SCAN_OPS: { sum: 0, product: 1 };
+export declare const fieldScan: (op: 'sum' | 'product' | number, a: Buffer, n: number,
+  opts?: { count?: number, init?: Buffer, montgomery?: boolean, exclusive?: boolean, sharedA?: boolean, out?: boolean, totals?: boolean }) => Promise<{ out: Buffer | null, totals: Buffer | null }>;
 // Not in the reference: sparse matrices over p bound once in CSR form (rowPtr: rows + 1 offsets of 8 bytes, colIdx: nnz indices of 4 bytes,
 // vals: nnz records of 32 bytes, little-endian), and their products with `count` (default 1) vectors of cols records each: count x rows
 // canonical records.  transpose multiplies by the transposed matrix and needs a bind with transpose: true; montgomery as for fieldOp (on the
